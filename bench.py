@@ -7,10 +7,19 @@ retarget the tracking cost, primal and dual shift_fill, warm-started solve;
 random_linear_problem.jl:121-161).  Every input of the timed region (long reference
 trajectories, noise samples, dynamics) is resident in HBM before the clock starts.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 N > 1 is launched by the driver with torch.distributed.run, one rank per GPU; instances are
 sharded over ranks (weak scaling: 8192 per GPU), there is no data-path collective, and the
 only RCCL traffic is one all_gather of the first controls after the timed region.
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds
+the CPU baseline, the repeated K-step regions and the secondary configs to that line.
+--dump-outputs DIR writes what the last timed step left in the solver as DIR/<name>.npy.
+The inputs cover the steps that run: W + K, or W + K x repeats with --full.  One handle's
+reference track holds fewer than 4096 knots at batch 8192 (the library's 4 GiB limit); when
+K > SEGMENT_STEPS or the steps do not fit it, every timed region runs as segments of at most
+SEGMENT_STEPS steps, each on a fresh solver restarting the same closed loops (untimed set-up
+and warm-up), and the segments' timed brackets are summed.
 """
 import argparse
 import json
@@ -295,7 +304,7 @@ def _capped(mp, altro, cap, K, W, B):
 def secondary_configs(which, K, W, emit=None, state_dims=(8, 16, 32, 48, 64), grp=None, device=0):
     """BASELINE configs[2..4] at their per-GPU sizes.  `--config <name>` prints them as lines of their own (under
     torch.distributed.run every rank owns a shard of the config's instances: configs[3] "65536 sharded over 8" and
-    configs[4] "16384 over 8" are 8192 and 2048 instances per GPU); the default run carries short single-GPU versions
+    configs[4] "16384 over 8" are 8192 and 2048 instances per GPU); a --full run carries short single-GPU versions
     (<= 10 steps) inside the headline line's `secondary` list."""
     import altro_amd_loader  # noqa: F401
     import altro_mpc_icra2021_amd as altro
@@ -372,16 +381,58 @@ def secondary_configs(which, K, W, emit=None, state_dims=(8, 16, 32, 48, 64), gr
     return lines
 
 
+SEGMENT_STEPS = 2048
+"""longest segment of a region whose steps do not fit one reference track: keeps the inputs' generation on the host short"""
+
+
+def track_steps(batch, N):
+    """MPC steps one handle's reference track can cover.  The library packs the track as Nt knots x the batch rounded up
+    to 4 instances x 16 lanes of doubles and addresses it with 32-bit offsets (below 4 GiB, altro_batch.hip
+    set_ref_common); a loop of S steps needs Nt = N + S + 1 knots."""
+    bp = (batch + 3) // 4 * 4
+    return ((1 << 32) - 1) // (bp * 16 * 8) - N - 1
+
+
+DUMP_LIMIT_BYTES = 64_000_000 - 64 * 1024
+"""--dump-outputs: at most 64 MB in all (the margin covers the .npy headers)"""
+
+
+def dump_outputs(path, mp, altro, st):
+    """What a caller of the timed path receives after its last MPC step, as float64 DIR/<name>.npy: the solver's
+    trajectories, the plant state the last solve started from and its statistics, one row per instance.  If the
+    whole batch exceeds DUMP_LIMIT_BYTES, a fixed seeded sample of instances is written (same rows in every run),
+    with their indices in instance_index.npy."""
+    arrays = {"states": altro.states(mp.solver), "controls": altro.controls(mp.solver), "initial_state": mp.x0(),
+              "cost": st.cost, "c_max": st.c_max, "iterations": st.iterations, "iterations_outer": st.iterations_outer,
+              "status": st.status}
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    B = arrays["states"].shape[0]
+    per_instance = sum(v[0].nbytes for v in arrays.values())
+    if B * per_instance > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(B, DUMP_LIMIT_BYTES // (per_instance + 8), replace=False))
+        arrays = {k: v[rows] for k, v in arrays.items()}
+        arrays["instance_index"] = rows.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(v))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=BATCH_PER_GPU, help="instances per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="headline only (the profiling scripts use this)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline, the repeated K-step regions and the secondary configs (a plain run times "
+                         "the headline region only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed region, write what its last step computed as DIR/<name>.npy (float64, <= 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: leave out the secondary configs")
     ap.add_argument("--repeats", type=int, default=5,
-                    help="K-step regions timed back to back; `value` is the FIRST (W warm-up steps, then exactly K steps), the others are reported beside it")
+                    help="K-step regions timed back to back with --full; `value` is the FIRST (W warm-up steps, then exactly K "
+                         "steps), the others are reported beside it.  The inputs cover all of them with or without --full")
     ap.add_argument("--config", default="headline", choices=["headline", "rocket", "state_dim", "quadruped", "all"],
                     help="headline (BASELINE configs[1], the driver's line) or a secondary config: extra JSON lines, 1 GPU only")
     ap.add_argument("--preheat-ms", type=float, default=300.0,
@@ -411,7 +462,7 @@ def main():
         return
 
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         cpu = cpu_baseline()
 
     import torch
@@ -425,28 +476,65 @@ def main():
     assert (grp.rank, grp.world) == (rank, world)
 
     B, K, W, R = a.batch, a.steps, a.warmup, max(1, a.repeats)
-    pb = altro.problems.gen_random_linear_batch(B, n=N_STATE, m=N_CTRL, N=N_KNOT, steps=W + K * R, seed=1,
-                                                first_instance=altro.parallel.shard_first_instance(rank, B))
-    mp = altro.mpc.BatchMPC(pb, device=local_rank)
-    mp.initial_solve()
-    for i in range(W):
-        mp.step(i)
-    altro.timing_reset(mp.solver)
+    R_run = R if a.full else 1         # regions timed: the later ones are --full figures
+    # The inputs cover the steps that run and no more: W + K in a plain run, W + K x R with --full.  One closed loop runs
+    # all the timed regions back to back when K <= SEGMENT_STEPS and its reference track fits one handle.  Otherwise
+    # every region is split into segments of at most `seg` steps, each on a fresh solver that restarts the same closed
+    # loops, and the inputs cover W + seg steps.
+    cap = track_steps(B, N_KNOT)
+    contiguous = K <= SEGMENT_STEPS and W + K * R_run <= cap
+    seg = K if contiguous else min(K, cap - W, SEGMENT_STEPS)
+    assert seg >= 1, "batch %d leaves no room in the reference track for %d warm-up steps" % (B, W)
+    segs = [seg] * (K // seg) + ([K % seg] if K % seg else [])
+    pb = altro.problems.gen_random_linear_batch(B, n=N_STATE, m=N_CTRL, N=N_KNOT, steps=W + K * R_run if contiguous else W + seg,
+                                                seed=1, first_instance=altro.parallel.shard_first_instance(rank, B))
+
+    def start_loop():
+        """a solver on the batch, its initial solve and the W warm-up steps (all before any clock starts)"""
+        mp_ = altro.mpc.BatchMPC(pb, device=local_rank)
+        mp_.initial_solve()
+        for i in range(W):
+            mp_.step(i)
+        return mp_
+
+    mp = start_loop()
+    fresh = True                       # mp has run no timed step yet
 
     spl = a.steps_per_launch if a.steps_per_launch > 0 else K
-    launches_per_region = (K + spl - 1) // spl
-    assert launches_per_region * R <= 1024, "more launches than the library's timing ring holds (launch_ring.h CAP)"
+    launches_per_region = sum((s + spl - 1) // spl for s in segs)
+    assert (seg + spl - 1) // spl <= 1024, "more launches than the library's timing ring holds (launch_ring.h CAP)"
 
-    def region(first):
-        """exactly K MPC steps of every instance, bracketed by barrier + synchronize on both sides; max over ranks"""
-        def run():
-            i = first
-            while i < first + K:
-                n = min(spl, first + K - i)
-                mp.run_async(n, first=i)   # n consecutive MPC steps of every instance in one launch
-                i += n
-            mp.synchronize()
-        return grp.timed(run)
+    def region(r):
+        """exactly K MPC steps of every instance, each segment bracketed by barrier + synchronize on both sides (max over
+        ranks); returns the summed wall time, the kernel time of every launch and the pass counters summed over segments"""
+        nonlocal mp, fresh
+        wall, ms_, cnt = 0.0, [], None
+        for k, n in enumerate(segs):
+            if contiguous:
+                first = W + r * K
+            else:
+                if not fresh:
+                    mp.solver.close()
+                    mp = start_loop()
+                if r > 0 or k > 0:
+                    preheat(a.preheat_ms)    # the restart's warm-up launches leave the clocks as the first region's do
+                first = W
+            fresh = False
+            altro.timing_reset(mp.solver)    # synchronises the library's stream
+
+            def run():
+                i = first
+                while i < first + n:
+                    nl = min(spl, first + n - i)
+                    mp.run_async(nl, first=i)   # nl consecutive MPC steps of every instance in one launch
+                    i += nl
+                mp.synchronize()
+            wall += grp.timed(run)
+            ms_.append(altro.timing_get(mp.solver))
+            c = (altro.work_counters(mp.solver) + altro.solve_counters(mp.solver) +
+                 (altro.confirm_counter(mp.solver), altro.reuse_counter(mp.solver)))
+            cnt = c if cnt is None else tuple(x + y for x, y in zip(cnt, c))
+        return wall, np.concatenate(ms_), cnt
 
     def preheat(ms_):
         """keep the GPU busy for ms_ milliseconds with work that touches nothing of the solver"""
@@ -462,15 +550,11 @@ def main():
         del x
 
     preheat(a.preheat_ms)
-    dt = region(W)                     # THE timed region: W warm-up steps have run, now exactly K steps
+    dt, ms, counters = region(0)       # THE timed region: W warm-up steps have run, now exactly K steps
 
     st = altro.stats(mp.solver)
-    ms = altro.timing_get(mp.solver)
     assert len(ms) == launches_per_region, (len(ms), launches_per_region)
-    nb, nr, ntr = altro.work_counters(mp.solver)
-    nsol, nit, nok = altro.solve_counters(mp.solver)
-    ngc = altro.confirm_counter(mp.solver)
-    nfo = altro.reuse_counter(mp.solver)
+    nb, nr, ntr, nsol, nit, nok, ngc, nfo = counters
     assert int(nsol.sum()) == B * K, (int(nsol.sum()), B * K)
     assert int(nb.sum() + nfo.sum() + ngc.sum()) == int(nit.sum())    # every iteration is exactly one of the three kinds
     ok = int(nok.sum())
@@ -481,17 +565,20 @@ def main():
     allU, allS = grp.gather_checked(U1, st.status)   # asserts that rank r's shard sits at rows [r B, (r + 1) B)
     assert allU.shape == (world * B, N_CTRL)
     ok = grp.sum_over_ranks(ok)
+    if a.dump_outputs and rank == 0:   # rank 0's shard: global instances [0, B)
+        dump_outputs(a.dump_outputs, mp, altro, st)
 
-    # the same K-step region R - 1 more times, back to back (later steps of the same closed loops): the spread of the number
-    rep_wall = [dt]
-    for r in range(1, R):
-        rep_wall.append(region(W + r * K))
-    ms_all = altro.timing_get(mp.solver)
-    assert len(ms_all) == launches_per_region * R, (len(ms_all), launches_per_region, R)
-    rep_kernel = [float(ms_all[r * launches_per_region:(r + 1) * launches_per_region].sum()) for r in range(R)]
+    # the same K-step region R - 1 more times, back to back (later steps of the same closed loops, or the same segments
+    # once more on restarted loops): the spread of the number
+    rep_wall, rep_kernel = [dt], [float(ms.sum())]
+    for r in range(1, R_run):
+        w_r, ms_r, _ = region(r)
+        assert len(ms_r) == launches_per_region, (len(ms_r), launches_per_region)
+        rep_wall.append(w_r)
+        rep_kernel.append(float(ms_r.sum()))
 
     secondary = None
-    if rank == 0 and world == 1 and not a.no_secondary:
+    if a.full and rank == 0 and world == 1 and not a.no_secondary:
         mp.solver.close()
         secondary = secondary_configs("all", min(K, 10), min(W, 3), state_dims=(8, 16, 32, 48, 64), device=local_rank)
 
@@ -549,12 +636,20 @@ def main():
                          "hbm_algorithmic_GBps": bytes_launch / (avg_ms * 1e-3) / 1e9,
                          "hbm_frac": bytes_launch / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS},
             "cpu_baseline": cpu,
-            "repeats": {"regions": R, "steps_each": K, "wall_ms": [1e3 * w for w in rep_wall], "kernel_ms": rep_kernel,
+            "full": a.full,
+            "repeats": {"regions": R_run, "steps_each": K, "wall_ms": [1e3 * w for w in rep_wall], "kernel_ms": rep_kernel,
                         "solves_per_s_median": rep_rate[len(rep_rate) // 2], "solves_per_s_min": rep_rate[0],
                         "solves_per_s_max": rep_rate[-1],
-                        "note": "`value` is region 0 (W warm-up steps, then exactly K steps); regions 1.. are the next K steps of the "
-                                "same closed loops, each bracketed the same way"},
+                        "note": "`value` is region 0 (W warm-up steps, then exactly K steps); " + (
+                            "regions 1.. are the next K steps of the same closed loops, each bracketed the same way" if contiguous else
+                            "regions 1.. run the same segments once more on restarted solvers, each bracketed the same way")}
+                       if a.full else None,
             "steps_per_launch": spl,
+            "segments": None if contiguous else {
+                "steps": segs, "note": "K > %d, or the W + K x regions steps do not fit one reference track (%d steps at this "
+                                       "batch): each segment restarts the same closed loops on a fresh solver (initial solve, W "
+                                       "warm-up steps, preheat; all untimed), and `value` sums the segments' timed brackets"
+                                       % (SEGMENT_STEPS, cap)},
             "solve_succeeded_frac": ok / (world * B * K),
             "iterations_mean": float(nit.sum() / (B * K)),
             "iterations_hist_last_step": np.bincount(st.iterations).tolist(),
