@@ -36,7 +36,8 @@ EXPORTS = [
     "altro_mpc_step_async", "altro_batch_get_initial_state", "altro_batch_get_stream",
     "altro_mpc_prepare_async", "altro_batch_benchmark_solve", "altro_mpc_set_dynamics_track",
     "altro_batch_get_confirm_counter", "altro_batch_get_reuse_counter", "altro_batch_get_polish_stats",
-    "altro_debug_set", "altro_batch_get_polish_dual_residuals",
+    "altro_debug_set", "altro_batch_get_polish_dual_residuals", "altro_batch_set_tracking_cost_per_instance",
+    "altro_batch_set_bounds",
 ]
 """every symbol include/altro_batch.h declares"""
 
@@ -122,6 +123,10 @@ def lib():
     L.altro_last_error.restype = C.c_char_p
     L.altro_batch_set_dynamics.argtypes = [H, dp, dp, dp, C.c_int32, C.c_int32]
     L.altro_batch_set_tracking_cost.argtypes = [H, dp, dp, dp, C.c_double]
+    # (an older build given through ALTRO_HIP_LIB -- the A/B tools -- may lack the newest exports; build() checks them all)
+    if hasattr(L, "altro_batch_set_tracking_cost_per_instance"):
+        L.altro_batch_set_tracking_cost_per_instance.argtypes = [H, dp, dp, dp, C.c_double]
+        L.altro_batch_set_bounds.argtypes = [H, C.c_int32, dp, dp, C.c_int32]
     L.altro_batch_add_constraint.argtypes = [H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                              dp, dp, dp, dp, C.c_int32, ip]
     L.altro_batch_update_constraint_data.argtypes = [H, C.c_int32, dp, dp]
@@ -164,7 +169,7 @@ def lib():
     L.altro_debug_set.argtypes = [H, C.c_char_p, C.c_int32]
     L.altro_batch_get_polish_dual_residuals.argtypes = [H, dp, dp, ip]
     for name in EXPORTS:
-        if name != "altro_last_error":
+        if name != "altro_last_error" and hasattr(L, name):
             getattr(L, name).restype = C.c_int32
     _lib = L
     return L

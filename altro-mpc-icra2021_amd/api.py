@@ -68,9 +68,29 @@ class LinearModel:
     per_knot: bool = False
 
 
+def _rows(arrs, B):
+    """Shared or per-instance data: every array 1-D -> (False, the arrays as (k,)); any of them (B, k) -> (True, all of them as
+    (B, k), the 1-D ones broadcast).  A 2-D array whose leading dimension is not B raises AltroError(ERR_INVALID_ARG)."""
+    arrs = [np.asarray(a, dtype=np.float64) for a in arrs]
+    for a in arrs:
+        if a.ndim not in (1, 2) or (a.ndim == 2 and a.shape[0] != B):
+            raise AltroError(_lib.ERR_INVALID_ARG, f"expected ({B}, k) or (k,) per-instance data, got shape {a.shape}")
+    if all(a.ndim == 1 for a in arrs):
+        return False, [_c(a) for a in arrs]
+    return True, [_c(np.broadcast_to(a, (B, a.shape[-1]))) for a in arrs]
+
+
+def cost_rows(Q, R, Qf, B):
+    """(per_instance, Q, R, Qf) as the C-ABI takes them: (n,), (m,), (n,) for altro_batch_set_tracking_cost, or (B, n),
+    (B, m), (B, n) for altro_batch_set_tracking_cost_per_instance when any of them is given per instance."""
+    pi, (q, r, qf) = _rows((Q, R, Qf), B)
+    return pi, q, r, qf
+
+
 @dataclass
 class TrackingObjective:
-    """Diagonal tracking cost about (Xref, Uref); stage costs are scaled by dt."""
+    """Diagonal tracking cost about (Xref, Uref); stage costs are scaled by dt.  Q, R, Qf are (n,), (m,), (n,) for the
+    whole batch or (B, n), (B, m), (B, n) per instance (random_linear_problem.jl:11-13 draws them per problem)."""
     Q: np.ndarray
     R: np.ndarray
     Qf: np.ndarray
@@ -80,6 +100,8 @@ class TrackingObjective:
 
 @dataclass
 class BoundConstraint:
+    """Each field: None (unbounded), a scalar, (k,) for the whole batch, or (B, k) per instance (which elements are bounded
+    must then be the same in every row: altro_batch_set_bounds)."""
     n: int
     m: int
     x_min: Optional[np.ndarray] = None
@@ -87,13 +109,26 @@ class BoundConstraint:
     u_min: Optional[np.ndarray] = None
     u_max: Optional[np.ndarray] = None
 
-    def zbounds(self):
+    def per_instance(self):
+        return any(v is not None and np.ndim(v) == 2 for v in (self.x_min, self.x_max, self.u_min, self.u_max))
+
+    def zbounds(self, B=None):
+        """(zmin, zmax): (n+m,) each, or (B, n+m) each when a field is given per instance (B: the batch, checked)."""
+        pi = self.per_instance()
+        rows = None
+        if pi:
+            rows = B if B is not None else next(np.shape(v)[0] for v in (self.x_min, self.x_max, self.u_min, self.u_max)
+                                                if v is not None and np.ndim(v) == 2)
+
         def full(v, k, fill):
             if v is None:
-                return np.full(k, fill)
-            return np.broadcast_to(np.asarray(v, dtype=np.float64), (k,)).copy()
-        zmin = np.r_[full(self.x_min, self.n, -np.inf), full(self.u_min, self.m, -np.inf)]
-        zmax = np.r_[full(self.x_max, self.n, np.inf), full(self.u_max, self.m, np.inf)]
+                v = fill
+            v = np.asarray(v, dtype=np.float64)
+            if v.ndim == 2 and (v.shape[0] != rows or v.shape[1] != k):
+                raise AltroError(_lib.ERR_INVALID_ARG, f"bound of shape {v.shape}: expected ({rows}, {k}) or ({k},)")
+            return np.broadcast_to(v, (rows, k) if pi else (k,)).copy()
+        zmin = np.concatenate([full(self.x_min, self.n, -np.inf), full(self.u_min, self.m, -np.inf)], axis=-1)
+        zmax = np.concatenate([full(self.x_max, self.n, np.inf), full(self.u_max, self.m, np.inf)], axis=-1)
         return zmin, zmax
 
 
@@ -171,14 +206,19 @@ class ALTROSolver:
         self.con_ids = []
         mdl = prob.model
         set_dynamics(self, mdl)
-        self._chk(L.altro_batch_set_tracking_cost(h, _p(_c(prob.obj.Q)), _p(_c(prob.obj.R)), _p(_c(prob.obj.Qf)), mdl.dt))
+        set_tracking_cost(self, prob.obj.Q, prob.obj.R, prob.obj.Qf, mdl.dt)
         for con, first, last in prob.constraints.items:
             if isinstance(con, BoundConstraint):
-                zmin, zmax = con.zbounds()
+                zmin, zmax = con.zbounds(B)
                 cid = C.c_int32(-1)
+                # per-instance bounds: the BOX is added with instance 0's row (it fixes the pattern of finite sides), then
+                # every instance gets its own
                 self._chk(L.altro_batch_add_constraint(h, _lib.CON_BOX, _lib.SENSE_INEQ, first - 1, last - 1, 0,
-                                                       None, None, _p(_c(zmin)), _p(_c(zmax)), 0, C.byref(cid)))
+                                                       None, None, _p(_c(zmin.reshape(-1, n + m)[0])),
+                                                       _p(_c(zmax.reshape(-1, n + m)[0])), 0, C.byref(cid)))
                 self.con_ids.append(cid.value)
+                if zmin.ndim == 2:
+                    self._chk(L.altro_batch_set_bounds(h, cid.value, _p(_c(zmin)), _p(_c(zmax)), 1))
             elif isinstance(con, (LinearConstraint, NormConstraint)):
                 A, b = _c(con.A), _c(con.b)
                 per_inst = bool(getattr(con, "per_instance", False))
@@ -245,9 +285,19 @@ def set_dynamics_track(solver, A, B, d=None, step_stride=1):
 
 
 def set_tracking_cost(solver, Q, R, Qf, dt=None):
-    """Replace the diagonal weights of the tracking objective (TO.TrackingObjective(Q, R, Z; Qf), mpc.jl:26-29)."""
+    """Replace the diagonal weights of the tracking objective (TO.TrackingObjective(Q, R, Z; Qf), mpc.jl:26-29).  Q, R, Qf
+    are (n,), (m,), (n,) for the batch or (B, n), (B, m), (B, n) per instance (any 2-D one makes the call per instance)."""
     dt = solver.prob.model.dt if dt is None else dt
-    solver._chk(solver._L.altro_batch_set_tracking_cost(solver.h, _p(_c(Q)), _p(_c(R)), _p(_c(Qf)), dt))
+    pi, q, r, qf = cost_rows(Q, R, Qf, solver.B)
+    fn = solver._L.altro_batch_set_tracking_cost_per_instance if pi else solver._L.altro_batch_set_tracking_cost
+    solver._chk(fn(solver.h, _p(q), _p(r), _p(qf), dt))
+
+
+def set_bounds(solver, con, zmin, zmax):
+    """New bounds of the BOX constraint `con` (index into the problem's constraint list), in place: (n+m,) each for the
+    batch or (B, n+m) each per instance; the finite sides must be those the BOX was added with (altro_batch_set_bounds)."""
+    pi, (lo, hi) = _rows((zmin, zmax), solver.B)
+    solver._chk(solver._L.altro_batch_set_bounds(solver.h, solver.con_ids[con], _p(lo), _p(hi), int(pi)))
 
 
 def set_options(solver, **kw):

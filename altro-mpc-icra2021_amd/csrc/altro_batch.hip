@@ -60,7 +60,12 @@ struct altro_handle {
   int* dzero = nullptr;  // [Bp] the last iteration of the last solve was costate-confirmed: its d is zero
   // problem data (device)
   double *Gcol = nullptr, *Grow = nullptr, *fvec = nullptr;
-  double *wd = nullptr, *wf = nullptr, *zmin = nullptr, *zmax = nullptr;
+  double *wd = nullptr, *wf = nullptr, *zmin = nullptr, *zmax = nullptr;  // [16] each, or [Bp][16] (tab_rows)
+  // host copies of the cost weights and bounds: [rows][16] each, rows = 1 (shared by the batch) or batch (per instance)
+  std::vector<double> wd_h, wf_h, zmin_h, zmax_h;
+  bool cost_pi = false, bnd_pi = false;  // per-instance cost weights / bounds: the device tables then hold Bp rows (imask)
+  int tab_cap = 1;                       // rows the device tables have room for
+  bool box_lo_fin[LW] = {}, box_hi_fin[LW] = {};  // finite sides of the BOX as it was added (altro_batch_set_bounds)
   double *x0 = nullptr, *Zref = nullptr, *Z = nullptr, *Lb = nullptr, *mu = nullptr,
          *KD = nullptr, *Qz = nullptr, *Dff = nullptr, *kmu = nullptr;
   altro::ASet* ahash = nullptr;  // [Bp][16] active set of the backward pass behind the gains in KD (gain reuse, solve_dpp16.h)
@@ -357,7 +362,7 @@ __global__ void k_plane_copy(double* __restrict__ Zp, double* __restrict__ Zs, c
 // wave (tests: instance results do not depend on the batch; lone-row == four-row pass bit for bit).
 // one 16-lane row per instance (lane j = element j of z: coalesced 128-byte reads), 16 instances per block
 __global__ void k_group_score(const double* __restrict__ Zref, const double* __restrict__ zmin, const double* __restrict__ zmax,
-                              int* __restrict__ score, int Bp, int Nt, int first, int nsteps, int k0, int k1, int nz) {
+                              unsigned imask, int* __restrict__ score, int Bp, int Nt, int first, int nsteps, int k0, int k1, int nz) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   const int b = t / LW, j = t % LW;
   const bool live = b < Bp;
@@ -366,7 +371,8 @@ __global__ void k_group_score(const double* __restrict__ Zref, const double* __r
   const int a0 = first + 1 + k0;             // first absolute knot touched by the launch's windows
   const int na = nsteps + W - 1;             // absolute knots touched
   if (na > 256 || W < 1) { if (live && j == 0) score[b] = 0; return; }
-  const double lo = zmin[j], hi = zmax[j];
+  const unsigned bo = ((unsigned)bb * LW + j) & imask;   // the instance's row of per-instance bounds (SolveParams::imask)
+  const double lo = zmin[bo], hi = zmax[bo];
   const bool fl = (j < nz) && lo > -1e300, fh = (j < nz) && hi < 1e300;
   const double m = 0.02 * ((fl && fh) ? 0.5 * (hi - lo) : fmax(1.0, fabs(fh ? hi : lo)));
   unsigned long long bits[4] = {0ull, 0ull, 0ull, 0ull};
@@ -462,6 +468,37 @@ static bool supported_dims(int n, int m) {
   return (n == 12 && m == 4) || (n == 6 && m == 3) || (n == 6 && m == 6) || (n == 8 && m == 4) || (n == 12 && m == 3);
 }
 
+// Cost weights and bounds: one row [16] each for the batch (imask 15, the kernels read element j), or -- once either is
+// given per instance -- [Bp][16] each (imask ~0u: element inst * 16 + j), the padded instances repeating the last row.
+static unsigned tab_imask(const altro_handle* h) { return (h->cost_pi || h->bnd_pi) ? ~0u : 15u; }
+
+static int upload_tables(altro_handle* h) {
+  const bool pi = h->cost_pi || h->bnd_pi;
+  const size_t rows = pi ? (size_t)h->Bp : 1;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if ((int)rows > h->tab_cap) {
+    double** tabs[] = {&h->wd, &h->wf, &h->zmin, &h->zmax};
+    for (double** t : tabs) {
+      HIPCHK(h, hipFree(*t));
+      *t = nullptr;
+    }
+    for (double** t : tabs) HIPCHK(h, hipMalloc(t, rows * LW * sizeof(double)));
+    h->tab_cap = (int)rows;
+  }
+  const std::vector<double>* src[] = {&h->wd_h, &h->wf_h, &h->zmin_h, &h->zmax_h};
+  double* dst[] = {h->wd, h->wf, h->zmin, h->zmax};
+  std::vector<double> img(rows * LW);
+  for (int t = 0; t < 4; ++t) {
+    const bool own = t < 2 ? h->cost_pi : h->bnd_pi;   // this table has one host row per instance
+    for (size_t r = 0; r < rows; ++r) {
+      const size_t sr = own ? (r < (size_t)h->d.batch ? r : (size_t)h->d.batch - 1) : 0;
+      std::memcpy(&img[r * LW], &(*src[t])[sr * LW], LW * sizeof(double));
+    }
+    HIPCHK(h, hipMemcpy(dst[t], img.data(), rows * LW * sizeof(double), hipMemcpyHostToDevice));
+  }
+  return ALTRO_OK;
+}
+
 static int launch_solve(altro_handle* h, int first_step, int nsteps, int prepare_only = 0) {
   altro::SolveParams p{};
   p.prepare_only = prepare_only;
@@ -471,7 +508,7 @@ static int launch_solve(altro_handle* h, int first_step, int nsteps, int prepare
   p.noise = h->noise; p.noise_w = h->noise_w; p.noise_grp = h->noise_grp; p.noise_mode = h->noise_mode; p.mpc_shift = h->mpc_shift;
   p.box_k0 = h->box_k0; p.box_k1 = h->box_k1;
   p.Gcol = h->Gcol; p.Grow = h->Grow; p.fvec = h->fvec;
-  p.wd = h->wd; p.wf = h->wf; p.zmin = h->zmin; p.zmax = h->zmax;
+  p.wd = h->wd; p.wf = h->wf; p.zmin = h->zmin; p.zmax = h->zmax; p.imask = tab_imask(h);
   p.x0 = h->x0; p.Zref = h->Zref; p.Z = h->Z; p.cur = h->cur;
   p.Lb = h->Lb; p.bslot = h->bslot; p.nbp = h->nbp; p.mu = h->mu; p.lone = h->lone; p.useqz = h->useqz; p.shadow = h->shadow; p.reuse = h->reuse; p.resync = h->resync; p.dbg_wave = h->dbg_wave;
   p.Dff = h->Dff; p.ahash = h->ahash; p.kmu = h->kmu; p.n_fo = h->n_fo;
@@ -496,7 +533,7 @@ static int launch_solve(altro_handle* h, int first_step, int nsteps, int prepare
   //  instances and clustering the pass-heavy rows -- they are also the ones with the hard solves -- lengthens the tail:
   //  measured 20 steps +2 %, 100 steps -3 %, tools/gpu_ab.py)
   if (h->group && h->reuse && !h->o.strict && nsteps >= 4 && nsteps <= h->group_max_steps && !prepare_only && h->ncrows == 0 && h->box_k1 >= h->box_k0 && h->Bp <= 32768) {
-    hipLaunchKernelGGL(k_group_score, grid_for((size_t)h->Bp * LW), dim3(256), 0, h->stream, h->Zref, h->zmin, h->zmax, h->gscore, h->Bp, h->Nt,
+    hipLaunchKernelGGL(k_group_score, grid_for((size_t)h->Bp * LW), dim3(256), 0, h->stream, h->Zref, h->zmin, h->zmax, tab_imask(h), h->gscore, h->Bp, h->Nt,
                        first_step, nsteps, h->box_k0, h->box_k1, h->d.n + h->d.m);
     hipLaunchKernelGGL(k_group_rank, dim3(1), dim3(256), 0, h->stream, h->gscore, h->perm, h->Bp, h->group);
     p.perm = h->perm;
@@ -862,6 +899,8 @@ int32_t altro_batch_create(const altro_dims* dims, const altro_opts* opts, int32
     {
       // no bounds until a BOX constraint is added
       std::vector<double> lo(LW, -INFINITY), hi(LW, INFINITY);
+      h->zmin_h = lo; h->zmax_h = hi;
+      h->wd_h.assign(LW, 0.0); h->wf_h.assign(LW, 0.0);
       CCHK(hipMemcpyAsync(h->zmin, lo.data(), LW * sizeof(double), hipMemcpyHostToDevice, h->stream));
       CCHK(hipMemcpyAsync(h->zmax, hi.data(), LW * sizeof(double), hipMemcpyHostToDevice, h->stream));
       CCHK(hipStreamSynchronize(h->stream));
@@ -987,22 +1026,41 @@ int32_t altro_batch_set_dynamics(altro_handle* h, const double* A, const double*
   });
 }
 
+// altro_batch_set_tracking_cost(_per_instance): Qd [rows][n], Rd [rows][m], Qfd [rows][n], rows = 1 or batch
+static int set_cost_rows(altro_handle* h, const double* Qd, const double* Rd, const double* Qfd, double dt, bool per_instance) {
+  HIPCHK(h, hipSetDevice(h->device));
+  const int n = h->d.n, m = h->d.m;
+  const size_t rows = per_instance ? (size_t)h->d.batch : 1;
+  std::vector<double> wd(rows * LW, 0.0), wf(rows * LW, 0.0);
+  for (size_t r = 0; r < rows; ++r) {
+    for (int j = 0; j < n; ++j) { wd[r * LW + j] = dt * Qd[r * n + j]; wf[r * LW + j] = Qfd[r * n + j]; }
+    for (int j = 0; j < m; ++j) wd[r * LW + n + j] = dt * Rd[r * m + j];
+  }
+  h->wd_h.swap(wd);
+  h->wf_h.swap(wf);
+  h->cost_pi = per_instance;
+  if (int rc = upload_tables(h)) return rc;
+  if (int rcd = drop_gains(h)) return rcd;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->dt = dt;
+  h->have_cost = true;
+  return ALTRO_OK;
+}
+
 int32_t altro_batch_set_tracking_cost(altro_handle* h, const double* Qd, const double* Rd, const double* Qfd, double dt) {
   return guard(h, [&]() -> int32_t {
     WIDE_FWD(h, set_tracking_cost(Qd, Rd, Qfd, dt));
     if (!h || !Qd || !Rd || !Qfd || !(dt > 0)) return ALTRO_ERR_INVALID_ARG;
-    HIPCHK(h, hipSetDevice(h->device));
-    const int n = h->d.n, m = h->d.m;
-    std::vector<double> wd(LW, 0.0), wf(LW, 0.0);
-    for (int j = 0; j < n; ++j) { wd[j] = dt * Qd[j]; wf[j] = Qfd[j]; }
-    for (int j = 0; j < m; ++j) wd[n + j] = dt * Rd[j];
-    HIPCHK(h, hipMemcpyAsync(h->wd, wd.data(), LW * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->wf, wf.data(), LW * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    if (int rcd = drop_gains(h)) return rcd;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->dt = dt;
-    h->have_cost = true;
-    return ALTRO_OK;
+    return set_cost_rows(h, Qd, Rd, Qfd, dt, false);
+  });
+}
+
+int32_t altro_batch_set_tracking_cost_per_instance(altro_handle* h, const double* Qd, const double* Rd, const double* Qfd,
+                                                   double dt) {
+  return guard(h, [&]() -> int32_t {
+    WIDE_FWD(h, set_tracking_cost_per_instance(Qd, Rd, Qfd, dt));
+    if (!h || !Qd || !Rd || !Qfd || !(dt > 0)) return ALTRO_ERR_INVALID_ARG;
+    return set_cost_rows(h, Qd, Rd, Qfd, dt, true);
   });
 }
 
@@ -1159,8 +1217,16 @@ int32_t altro_batch_add_constraint(altro_handle* h, int32_t kind, int32_t sense,
     if (!zmin || !zmax) return ALTRO_ERR_INVALID_ARG;
     std::vector<double> lo(LW, -INFINITY), hi(LW, INFINITY);
     for (int j = 0; j < nz; ++j) { lo[j] = zmin[j]; hi[j] = zmax[j]; }
-    HIPCHK(h, hipMemcpyAsync(h->zmin, lo.data(), LW * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->zmax, hi.data(), LW * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    for (int j = 0; j < LW; ++j) { h->box_lo_fin[j] = j < nz && lo[j] > -1e300; h->box_hi_fin[j] = j < nz && hi[j] < 1e300; }
+    h->zmin_h = lo;
+    h->zmax_h = hi;
+    h->bnd_pi = false;
+    if (h->cost_pi) {   // the tables hold one row per instance: the BOX's row goes to every one of them
+      if (int rc = upload_tables(h)) return rc;
+    } else {
+      HIPCHK(h, hipMemcpyAsync(h->zmin, lo.data(), LW * sizeof(double), hipMemcpyHostToDevice, h->stream));
+      HIPCHK(h, hipMemcpyAsync(h->zmax, hi.data(), LW * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    }
     // compact dual rows: one slot per element with at least one finite bound
     int nb = 0;
     for (int j = 0; j < LW; ++j) h->bslot_h[j] = (j < nz && (std::isfinite(lo[j]) || std::isfinite(hi[j]))) ? nb++ : -1;
@@ -1202,6 +1268,29 @@ int32_t altro_batch_update_constraint_data(altro_handle* h, int32_t con_id, cons
       return pack_constraints(h);
     }
     FAIL(h, ALTRO_ERR_INVALID_ARG, "unknown or non-affine constraint id");
+  });
+}
+
+int32_t altro_batch_set_bounds(altro_handle* h, int32_t con_id, const double* zmin, const double* zmax, int32_t per_instance) {
+  return guard(h, [&]() -> int32_t {
+    WIDE_FWD(h, set_bounds(con_id, zmin, zmax, per_instance));
+    if (!h) return ALTRO_ERR_INVALID_ARG;
+    if (h->box_id < 0 || con_id != h->box_id) FAIL(h, ALTRO_ERR_INVALID_ARG, "altro_batch_set_bounds: con_id is not a BOX constraint");
+    if (!zmin || !zmax) return ALTRO_ERR_INVALID_ARG;
+    const int nz = h->d.n + h->d.m;
+    const size_t rows = per_instance ? (size_t)h->d.batch : 1;
+    if (const char* e = altro_wide::check_bound_rows(zmin, zmax, rows, nz, h->box_lo_fin, h->box_hi_fin)) FAIL(h, ALTRO_ERR_INVALID_ARG, e);
+    HIPCHK(h, hipSetDevice(h->device));
+    std::vector<double> lo(rows * LW, -INFINITY), hi(rows * LW, INFINITY);
+    for (size_t r = 0; r < rows; ++r)
+      for (int j = 0; j < nz; ++j) { lo[r * LW + j] = zmin[r * nz + j]; hi[r * LW + j] = zmax[r * nz + j]; }
+    h->zmin_h.swap(lo);
+    h->zmax_h.swap(hi);
+    h->bnd_pi = per_instance != 0;
+    if (int rc = upload_tables(h)) return rc;
+    if (int rcd = drop_gains(h)) return rcd;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return ALTRO_OK;
   });
 }
 
@@ -1352,6 +1441,7 @@ static int launch_polish(altro_handle* h) {
   q.box_k0 = h->box_k0; q.box_k1 = h->box_k1; q.ncrows = h->ncrows;
   q.con_istride = h->con_per_instance ? (unsigned)(h->d.N * LW * LW) : 0u;
   q.Grow = h->Grow; q.fvec = h->fvec; q.wd = h->wd; q.wf = h->wf; q.zmin = h->zmin; q.zmax = h->zmax; q.x0 = h->x0;
+  q.wstride = q.bstride = tab_imask(h) == 15u ? 0u : (unsigned)LW;
   q.Acon = h->Acon; q.bcon = h->bcon; q.cmeta = h->cmeta;
   q.Z = h->Z; q.Zref = h->Zref; q.kref = h->kref; q.cur = h->cur; q.status = h->status; q.cost = h->cost; q.cmax = h->cmax;
   q.pn_ran = h->pn_ran; q.pn_failed = h->pn_failed; q.pn_res = h->pn_res;

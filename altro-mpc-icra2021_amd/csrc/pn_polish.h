@@ -32,6 +32,7 @@ struct PnParams {
   int box_k0, box_k1, ncrows;
   unsigned con_istride;   // as SolveParams
   const double *Grow, *fvec, *wd, *wf, *zmin, *zmax, *x0;
+  unsigned wstride, bstride;  // rows of wd / wf and of zmin / zmax: 0 (one row [16] for the batch) or 16 ([Bp][16] per instance)
   const double *Acon, *bcon;
   const int* cmeta;
   double* Z;              // [Bp][2 N + 1][16] (two planes of N rows + trash row per instance): plane cur is polished, plane cur^1 is the trial buffer
@@ -64,6 +65,7 @@ struct Pn {
   const PnParams& P;
   int inst, tid, N, n, m, nz, bm;
   double *E, *dv, *Ld, *Lo, *lam, *res, *cor, *Sv, *dtr, *spare, *tz, *gz, *rz;
+  const double *wd_, *wf_, *zmin_, *zmax_;  // this instance's row of the cost weights and of the bounds
   bool unit = false;   // the metric H = I of the multiplier projection (D D' instead of D H^-1 D')
   int *nb, *nst, *rinfo;
   double* Lc;  // LDS: current block [bm][bm+1]
@@ -75,6 +77,8 @@ struct Pn {
     tid = threadIdx.x;
     N = P.N; n = P.n; m = P.m; nz = n + m; bm = P.bm;
     const size_t i = (size_t)inst;
+    wd_ = P.wd + i * P.wstride; wf_ = P.wf + i * P.wstride;
+    zmin_ = P.zmin + i * P.bstride; zmax_ = P.zmax + i * P.bstride;
     E = P.E + i * N * bm * LW;
     dv = P.dv + i * N * bm;
     Ld = P.Ld + i * N * bm * bm;
@@ -99,7 +103,7 @@ struct Pn {
   }
   __device__ __forceinline__ double hinv(int k, int j) const {
     if (unit) return 1.0;
-    const double h = (k < N - 1) ? P.wd[j] : (j < n ? P.wf[j] : 0.0);
+    const double h = (k < N - 1) ? wd_[j] : (j < n ? wf_[j] : 0.0);
     return 1.0 / (h + P.o.rho_primal);
   }
   __device__ __forceinline__ double G(int i, int c) const { return P.Grow[((size_t)inst * LW + c) * LW + i]; }  // [A B][i][c]
@@ -112,9 +116,9 @@ struct Pn {
     if (Erow) for (int j = 0; j < LW; ++j) Erow[j] = 0.0;
     if (code < 32) {
       const int j = code & 15;
-      if (code < 16) { if (Erow) Erow[j] = 1.0; return z[j] - P.zmax[j]; }
+      if (code < 16) { if (Erow) Erow[j] = 1.0; return z[j] - zmax_[j]; }
       if (Erow) Erow[j] = -1.0;
-      return P.zmin[j] - z[j];
+      return zmin_[j] - z[j];
     }
     const int lane = code - 64;
     const int* cm = P.cmeta + ((size_t)k * LW + lane) * 4;
@@ -166,7 +170,7 @@ struct Pn {
       const int lim = (k == N - 1) ? n : nz;
       for (int side = 0; side < 2; ++side)
         for (int j = 0; j < lim; ++j) {
-          const bool has = side == 0 ? (P.zmax[j] < 1e300) : (P.zmin[j] > -1e300);
+          const bool has = side == 0 ? (zmax_[j] < 1e300) : (zmin_[j] > -1e300);
           if (!has) continue;
           const int code = side * 16 + j;
           const double v = pn_row(code, k, z, nullptr);
@@ -293,7 +297,7 @@ struct Pn {
     for (int e = tid; e < N * LW; e += 64) {   // g_k = H_k (z_k - zref_k)
       const int k = e / LW, j = e % LW;
       const bool live = j < n || (j < nz && k < N - 1);
-      const double h = (k < N - 1) ? P.wd[j] : (j < n ? P.wf[j] : 0.0);
+      const double h = (k < N - 1) ? wd_[j] : (j < n ? wf_[j] : 0.0);
       gz[e] = live ? h * (zrow(cur, k)[j] - P.Zref[((size_t)inst * P.Nt + (size_t)(P.kref + k)) * LW + j]) : 0.0;
     }
     __syncthreads();
@@ -544,14 +548,14 @@ struct Pn {
       const int lim = (k == N - 1) ? n : nz;
       for (int j = 0; j < lim; ++j) {
         const double e = zr[j] - rr[j];
-        J += 0.5 * ((k < N - 1) ? P.wd[j] : P.wf[j]) * e * e;
+        J += 0.5 * ((k < N - 1) ? wd_[j] : wf_[j]) * e * e;
       }
       double z[LW];
       for (int j = 0; j < LW; ++j) z[j] = (j < lim) ? zr[j] : 0.0;
       if (k >= P.box_k0 && k <= P.box_k1)
         for (int j = 0; j < lim; ++j) {
-          if (P.zmax[j] < 1e300) cm = fmax(cm, z[j] - P.zmax[j]);
-          if (P.zmin[j] > -1e300) cm = fmax(cm, P.zmin[j] - z[j]);
+          if (zmax_[j] < 1e300) cm = fmax(cm, z[j] - zmax_[j]);
+          if (zmin_[j] > -1e300) cm = fmax(cm, zmin_[j] - z[j]);
         }
       if (P.ncrows > 0)
         for (int lane = 0; lane < LW; ++lane) {

@@ -46,6 +46,7 @@ struct PnW {
   double *E, *dv, *Ld, *Lo, *lam, *res, *cor, *Sv, *dtr, *spare, *tz, *gz, *rz;
   int *nb, *nst, *rinfo;
   double *Lc, *Lp, *vv;
+  const double *wd_, *wf_, *zmin_, *zmax_;  // this instance's row of the cost weights and of the bounds (Params::w_pi, b_pi)
   bool unit = false;
 
   __device__ PnW(const WParams& w) : W(w), P(w.P) {
@@ -80,7 +81,7 @@ struct PnW {
     if (j < n) return P.Xref[((size_t)inst * P.Nt + (kref + k)) * n + j];
     return (k < N - 1) ? P.Uref[((size_t)inst * (P.Nt - 1) + (kref + k)) * m + (j - n)] : 0.0;
   }
-  __device__ __forceinline__ double hdiag(int k, int j) const { return (k < N - 1) ? P.wd[j] : (j < n ? P.wf[j] : 0.0); }
+  __device__ __forceinline__ double hdiag(int k, int j) const { return (k < N - 1) ? wd_[j] : (j < n ? wf_[j] : 0.0); }
   __device__ __forceinline__ double hinv(int k, int j) const { return unit ? 1.0 : 1.0 / (hdiag(k, j) + P.o.rho_primal); }
   __device__ __forceinline__ size_t dynblk(int k) const {
     return (size_t)(P.dyn_per_instance ? inst : 0) * (P.ltv ? P.dyn_blocks : 1) + (P.ltv ? (size_t)kref * P.dyn_step_stride + k : 0);
@@ -101,9 +102,9 @@ struct PnW {
     if (Erow) for (int j = 0; j < nz; ++j) Erow[j] = 0.0;
     if (code < 256) {
       const int j = code & 127;
-      if (code < 128) { if (Erow) Erow[j] = 1.0; return z[j] - P.zmax[j]; }
+      if (code < 128) { if (Erow) Erow[j] = 1.0; return z[j] - zmax_[j]; }
       if (Erow) Erow[j] = -1.0;
-      return P.zmin[j] - z[j];
+      return zmin_[j] - z[j];
     }
     const int r0 = code - 256;
     auto val = [&](int r) {
@@ -159,7 +160,7 @@ struct PnW {
       const int lim = (k == N - 1) ? n : nz;
       for (int side = 0; side < 2; ++side)
         for (int j = 0; j < lim; ++j) {
-          const bool has = side == 0 ? (P.zmax[j] < 1e300) : (P.zmin[j] > -1e300);
+          const bool has = side == 0 ? (zmax_[j] < 1e300) : (zmin_[j] > -1e300);
           if (!has) continue;
           const int code = side * 128 + j;
           const double v = pn_row(code, k, z, nullptr);
@@ -441,6 +442,8 @@ struct PnW {
 
   __device__ void run(int instance, double ctol_user) {
     inst = instance;
+    wd_ = P.wd + (size_t)inst * P.w_pi * nz; wf_ = P.wf + (size_t)inst * P.w_pi * n;
+    zmin_ = P.zmin + (size_t)inst * P.b_pi * nz; zmax_ = P.zmax + (size_t)inst * P.b_pi * nz;
     const altro_opts& o = P.o;
     const int cur = P.cur[inst];
     const bool need = (P.status[inst] <= ALTRO_SOLVE_SUCCEEDED) && (P.cmax[inst] > ctol_user);
@@ -491,8 +494,8 @@ struct PnW {
       for (int j = lim; j < nz; ++j) z[j] = 0.0;
       if (k >= P.box_k0 && k <= P.box_k1)
         for (int j = 0; j < lim; ++j) {
-          if (P.zmax[j] < 1e300) cm = fmax(cm, z[j] - P.zmax[j]);
-          if (P.zmin[j] > -1e300) cm = fmax(cm, P.zmin[j] - z[j]);
+          if (zmax_[j] < 1e300) cm = fmax(cm, z[j] - zmax_[j]);
+          if (zmin_[j] > -1e300) cm = fmax(cm, zmin_[j] - z[j]);
         }
       for (int q = 0; q < P.Pn; ++q) {
         if (!row_on(k, q)) continue;

@@ -117,10 +117,12 @@ struct SolveParams {
   const double* Gcol;    // [Bp][NX][16]   Gcol[b][k][j] = [A B][k][j]
   const double* Grow;    // [Bp][16][16]   Grow[b][c][i] = [A B][i][c]
   const double* fvec;    // [Bp][16]       affine term (x lanes)
-  const double* wd;      // [16] dt*Q (x lanes) | dt*R (u lanes)
-  const double* wf;      // [16] Qf (x lanes) | 0
-  const double* zmin;    // [16]
-  const double* zmax;    // [16]
+  const double* wd;      // [16] dt*Q (x lanes) | dt*R (u lanes), or [Bp][16] (imask)
+  const double* wf;      // [16] Qf (x lanes) | 0, or [Bp][16]
+  const double* zmin;    // [16], or [Bp][16]
+  const double* zmax;    // [16], or [Bp][16]
+  unsigned imask;        // 15: the four tables are one row shared by the batch; ~0u: one row per instance (per-instance cost
+                         // weights or bounds).  Lane j reads element rowoff & imask (Solver::consts)
   double* x0;            // [Bp][16]
   const double* Zref;    // [Bp][Nt][16]
   const double* noise;   // [steps][B][n] unit normals of the plant noise (may be null)
@@ -395,6 +397,7 @@ struct RowState {
   int gconf;      // the last iteration of the last solve was confirmed by the costate sweep (its d is exactly 0)
   int ngc;        // iterations confirmed by the costate sweep (work counter)
   int nfo;        // iterations that took their gains from memory (work counter)
+  unsigned imask; // SolveParams::imask, kept here so that no register holds it across the kernel (Solver::consts)
 };
 
 template <int NX, int NU, bool CONES>
@@ -496,12 +499,17 @@ struct Solver {
     return (cm.type != CT_NONE) & (k >= cm.k0) & (k <= cm.k1);
   }
 
+  // Element of lane j in the cost / bound tables.  rowoff = inst * 16 + j is the lane's CURRENT identity: lone_enter and
+  // shadow_enter point inst / rowoff / rs at the row a lane works for before the phase starts, so a per-instance table is
+  // read at the row of that instance, not of the lane's own.  & 15 gives j (shared row), & ~0u the instance's row.
+  __device__ __forceinline__ unsigned wrow() const { return rowoff & rs->imask; }
   __device__ __forceinline__ LaneConst consts() const {
     LaneConst c;
-    c.wd = P.wd[j];
-    c.wf = P.wf[j];
-    c.zmin = P.zmin[j];
-    c.zmax = P.zmax[j];
+    const unsigned o = wrow();
+    c.wd = P.wd[o];
+    c.wf = P.wf[o];
+    c.zmin = P.zmin[o];
+    c.zmax = P.zmax[o];
     c.has_hi = c.zmax < 1e300;
     c.has_lo = c.zmin > -1e300;
     return c;
@@ -2101,7 +2109,7 @@ struct Solver {
       constexpr int C = decltype(c)::value;
       g[C] = ldg(P.Gcol, ((unsigned)inst * NX + C) * LW + j);
     });
-    const double thr = 0.25e-9 * P.wd[j];
+    const double thr = 0.25e-9 * P.wd[wrow()];
     const int N = P.N;
     bool gbig = false;
     double sv = ldg(P.Qz, qat(N - 1));  // terminal knot: l_x on the state lanes, 0 elsewhere
@@ -2230,6 +2238,7 @@ struct Solver {
       s.gconf = P.dzero[inst];
       s.ngc = 0;
       s.nfo = 0;
+      s.imask = P.imask;
       *rs = s;
       *ah = P.ahash[(unsigned)inst * LW + j];
       aset_clear(qhs);

@@ -50,6 +50,7 @@ struct Params {
   int ltv, dyn_per_instance;
   const double *A, *Bm, *f;            // column-major blocks [inst or 1][N-1 or 1][n*n | n*m | n]
   const double *wd, *wf, *zmin, *zmax;  // [n+m] stage weights (x dt), [n] terminal, [n+m] box
+  int w_pi, b_pi;                       // 1: wd / wf, resp. zmin / zmax, hold one row per instance ([B][n+m], [B][n])
   int box_k0, box_k1;
   const double* AconT;  // [N][n+m][Pn]: row r of knot k's table is column r
   const double* bcon;   // [N][Pn]
@@ -475,8 +476,14 @@ struct Solver {
     Xri = P.Xref + b * P.Nt * n; Uri = P.Uref + b * (P.Nt - 1) * m;
     if (fresh)
       for (int e = T; e < ly.total; e += 64) lds[e] = 0.0;
-    if (T < n) { cwx = P.wd[T]; cwfx = P.wf[T]; cxmax = P.zmax[T]; cxmin = P.zmin[T]; }
-    if (T < m) { cwu = P.wd[n + T]; cumax = P.zmax[n + T]; cumin = P.zmin[n + T]; }
+    {
+      const double* wdi = P.wd + b * P.w_pi * nz;
+      const double* wfi = P.wf + b * P.w_pi * n;
+      const double* zlo = P.zmin + b * P.b_pi * nz;
+      const double* zhi = P.zmax + b * P.b_pi * nz;
+      if (T < n) { cwx = wdi[T]; cwfx = wfi[T]; cxmax = zhi[T]; cxmin = zlo[T]; }
+      if (T < m) { cwu = wdi[n + T]; cumax = zhi[n + T]; cumin = zlo[n + T]; }
+    }
     if (fresh) block_sync();
   }
 

@@ -30,6 +30,22 @@ namespace altro_wide {
     return (code);       \
   } while (0)
 
+// Rows of box bounds given to altro_batch_set_bounds: no NaN, zmin <= zmax, and the finite sides of every row those of the BOX
+// as it was added (lo_fin / hi_fin): the pattern fixes the dual layout, only the values may differ from row to row.
+// Finite as the kernels test it: zmin > -1e300, zmax < 1e300.
+static inline const char* check_bound_rows(const double* zmin, const double* zmax, size_t rows, int nz, const bool* lo_fin,
+                                           const bool* hi_fin) {
+  for (size_t r = 0; r < rows; ++r)
+    for (int j = 0; j < nz; ++j) {
+      const double lo = zmin[r * nz + j], hi = zmax[r * nz + j];
+      if (std::isnan(lo) || std::isnan(hi)) return "altro_batch_set_bounds: NaN bound";
+      if (lo > hi) return "altro_batch_set_bounds: zmin > zmax";
+      if ((lo > -1e300) != lo_fin[j] || (hi < 1e300) != hi_fin[j])
+        return "altro_batch_set_bounds: the finite sides differ from those the BOX constraint was added with";
+    }
+  return nullptr;
+}
+
 // dst[b][len] <- src[b][cur[b]][len]
 __global__ void k_gather_plane(double* dst, const double* src, const int* cur, size_t len, int B) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -83,6 +99,9 @@ struct WideBackend {
   int dyn_blocks = 1, dyn_step_stride = 0;
   bool ltv = false, dyn_per_instance = false, have_dyn = false, have_cost = false, have_ref = false;
   int box_k0 = 0, box_k1 = -1, box_id = -1;
+  std::vector<bool> box_lo_fin, box_hi_fin;   // [n+m] finite sides of the BOX (host copy: polish_prepare, set_bounds)
+  int w_pi = 0, b_pi = 0;                     // wd / wf, resp. zmin / zmax, hold one row per instance
+  bool w_big = false, b_big = false;          // their device arrays have room for B rows
   struct Block {
     int id, sense, k0, k1, p, per_knot, r0;
     bool soc = false;
@@ -220,15 +239,61 @@ struct WideBackend {
   bool dyn_covers(int kref_) const { return !ltv || (long long)kref_ * dyn_step_stride + (d.N - 1) <= (long long)dyn_blocks; }
 
   int set_tracking_cost(const double* Qd, const double* Rd, const double* Qfd, double dt) {
+    return set_cost_rows(Qd, Rd, Qfd, dt, 1);
+  }
+  int set_tracking_cost_per_instance(const double* Qd, const double* Rd, const double* Qfd, double dt) {
+    return set_cost_rows(Qd, Rd, Qfd, dt, (size_t)d.batch);
+  }
+  // rows = 1: one row for the batch; rows = B: Qd [B][n], Rd [B][m], Qfd [B][n]
+  int set_cost_rows(const double* Qd, const double* Rd, const double* Qfd, double dt, size_t rows) {
     gains_valid = false;
     if (!Qd || !Rd || !Qfd || !(dt > 0.0)) return ALTRO_ERR_INVALID_ARG;
     WCHK(hipSetDevice(device));
-    std::vector<double> w(nz());
-    for (int i = 0; i < d.n; ++i) w[i] = dt * Qd[i];
-    for (int i = 0; i < d.m; ++i) w[d.n + i] = dt * Rd[i];
+    const size_t n = d.n, m = d.m, z = nz();
+    if (rows > 1 && !w_big) {   // the shared arrays hold one row: room for B rows from now on
+      WCHK(hipStreamSynchronize(stream));
+      WCHK(hipFree(wd)); wd = nullptr;
+      WCHK(hipFree(wf)); wf = nullptr;
+      int rc;
+      if ((rc = dalloc(&wd, rows * z)) || (rc = dalloc(&wf, rows * n))) return rc;
+      w_big = true;
+    }
+    std::vector<double> w(rows * z);
+    for (size_t r = 0; r < rows; ++r) {
+      for (size_t i = 0; i < n; ++i) w[r * z + i] = dt * Qd[r * n + i];
+      for (size_t i = 0; i < m; ++i) w[r * z + n + i] = dt * Rd[r * m + i];
+    }
     WCHK(hipMemcpy(wd, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice));
-    WCHK(hipMemcpy(wf, Qfd, d.n * sizeof(double), hipMemcpyHostToDevice));
+    WCHK(hipMemcpy(wf, Qfd, rows * n * sizeof(double), hipMemcpyHostToDevice));
+    w_pi = rows > 1 ? 1 : 0;
     have_cost = true;
+    return ALTRO_OK;
+  }
+
+  // altro_batch_set_bounds: new values for the BOX, one row for the batch or one per instance (per_instance != 0)
+  int set_bounds(int con_id, const double* zmin_, const double* zmax_, int per_instance) {
+    if (box_id < 0 || con_id != box_id) WFAIL(ALTRO_ERR_INVALID_ARG, "altro_batch_set_bounds: con_id is not a BOX constraint");
+    if (!zmin_ || !zmax_) return ALTRO_ERR_INVALID_ARG;
+    const size_t rows = per_instance ? (size_t)d.batch : 1, z = nz();
+    {
+      bool lfb[kMaxN + kMaxM], hfb[kMaxN + kMaxM];
+      for (size_t j = 0; j < z; ++j) { lfb[j] = box_lo_fin[j]; hfb[j] = box_hi_fin[j]; }
+      if (const char* e = check_bound_rows(zmin_, zmax_, rows, (int)z, lfb, hfb)) WFAIL(ALTRO_ERR_INVALID_ARG, e);
+    }
+    gains_valid = false;
+    WCHK(hipSetDevice(device));
+    if (rows > 1 && !b_big) {
+      WCHK(hipStreamSynchronize(stream));
+      WCHK(hipFree(zmin)); zmin = nullptr;
+      WCHK(hipFree(zmax)); zmax = nullptr;
+      int rc;
+      if ((rc = dalloc(&zmin, rows * z)) || (rc = dalloc(&zmax, rows * z))) return rc;
+      b_big = true;
+    }
+    WCHK(hipStreamSynchronize(stream));
+    WCHK(hipMemcpy(zmin, zmin_, rows * z * sizeof(double), hipMemcpyHostToDevice));
+    WCHK(hipMemcpy(zmax, zmax_, rows * z * sizeof(double), hipMemcpyHostToDevice));
+    b_pi = rows > 1 ? 1 : 0;
     return ALTRO_OK;
   }
 
@@ -242,6 +307,10 @@ struct WideBackend {
       if (box_id >= 0) WFAIL(ALTRO_ERR_UNSUPPORTED, "one BOX constraint per problem");
       WCHK(hipMemcpy(zmin, zmin_, nz() * sizeof(double), hipMemcpyHostToDevice));
       WCHK(hipMemcpy(zmax, zmax_, nz() * sizeof(double), hipMemcpyHostToDevice));
+      box_lo_fin.assign(nz(), false);
+      box_hi_fin.assign(nz(), false);
+      for (int j = 0; j < nz(); ++j) { box_lo_fin[j] = zmin_[j] > -1e300; box_hi_fin[j] = zmax_[j] < 1e300; }
+      b_pi = 0;
       box_k0 = k_first;
       box_k1 = k_last;
       box_id = ncon++;
@@ -427,7 +496,7 @@ struct WideBackend {
     Params p{};
     p.B = d.batch; p.n = d.n; p.m = d.m; p.N = d.N; p.Nt = Nt; p.np = np(); p.mp = mp(); p.Pn = Pn; p.Pp = pad4(Pn);
     p.ltv = ltv; p.dyn_per_instance = dyn_per_instance;
-    p.A = A; p.Bm = Bm; p.f = f; p.wd = wd; p.wf = wf; p.zmin = zmin; p.zmax = zmax;
+    p.A = A; p.Bm = Bm; p.f = f; p.wd = wd; p.wf = wf; p.zmin = zmin; p.zmax = zmax; p.w_pi = w_pi; p.b_pi = b_pi;
     p.box_k0 = box_k0; p.box_k1 = box_k1;
     p.AconT = AconT; p.bcon = bcon;
     p.con_istride = con_per_instance ? (size_t)d.N * nz() * Pn : 0;
@@ -460,12 +529,9 @@ struct WideBackend {
       if ((rc = dalloc(&pn_ran, B)) || (rc = dalloc(&pn_failed, B)) || (rc = dalloc(&pn_dfail, B)) || (rc = dalloc(&pn_res, B)) ||
           (rc = dalloc(&pn_dres0, B)) || (rc = dalloc(&pn_dres, B))) return rc;
     }
-    std::vector<double> lo(z), hi(z);
-    WCHK(hipMemcpy(lo.data(), zmin, z * sizeof(double), hipMemcpyDeviceToHost));
-    WCHK(hipMemcpy(hi.data(), zmax, z * sizeof(double), hipMemcpyDeviceToHost));
-    int sides = 0;
+    int sides = 0;   // from the host copy of the BOX's finite sides (common to every instance)
     if (box_k1 >= box_k0)
-      for (size_t j = 0; j < z; ++j) sides += (lo[j] > -1e300 ? 1 : 0) + (hi[j] < 1e300 ? 1 : 0);
+      for (size_t j = 0; j < z; ++j) sides += (box_lo_fin[j] ? 1 : 0) + (box_hi_fin[j] ? 1 : 0);
     const int bm = 2 * d.n + sides + Pn;
     const int slots = (int)(B < 64 ? B : 64);
     if (bm != pn_bm || slots != pn_slots || !pnE) {

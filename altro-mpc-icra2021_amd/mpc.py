@@ -20,9 +20,12 @@ def gen_tracking_problem(pb, N=None):
     n, m = pb.n, pb.m
     Xr, Ur = pb.Xtrack[:, :N], pb.Utrack[:, :N - 1]
     model = api.LinearModel(pb.A, pb.Bm, dt=pb.dt)
-    obj = api.TrackingObjective(np.full(n, pb.Qk), np.full(m, pb.Rk), np.full(n, pb.Qfk), Xr, Ur)
+    def w(v, k):   # scalar weight -> (k,); per-instance (B, k) as given
+        return np.full(k, v) if np.ndim(v) == 0 else np.asarray(v, dtype=np.float64)
+    obj = api.TrackingObjective(w(pb.Qk, n), w(pb.Rk, m), w(pb.Qfk, n), Xr, Ur)
     cons = api.ConstraintList(n, m, N)
-    cons.add_constraint(api.BoundConstraint(n, m, u_min=-pb.u_bnd, u_max=pb.u_bnd), (1, N - 1))
+    ub = pb.u_bnd if np.ndim(pb.u_bnd) == 0 else np.repeat(np.asarray(pb.u_bnd, dtype=np.float64)[:, None], m, axis=1)
+    cons.add_constraint(api.BoundConstraint(n, m, u_min=-ub, u_max=ub), (1, N - 1))
     return api.Problem(model, obj, cons, x0=Xr[:, 0].copy(), N=N, U0=Ur.copy())
 
 

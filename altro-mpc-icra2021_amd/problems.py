@@ -41,10 +41,10 @@ class RandomLinearBatch:
     Xtrack: np.ndarray  # (B, Nt, n)   long reference trajectory (gen_trajectory)
     Utrack: np.ndarray  # (B, Nt-1, m)
     noise: np.ndarray   # (S, B, n) unit normals for the 1 % plant noise, one row per MPC step
-    u_bnd: float = 3.0
-    Qk: float = 10.0
+    u_bnd: float = 3.0  # or (B,): per-instance bounds (gen_random_linear_hetero_batch)
+    Qk: float = 10.0    # or (B, n): per-instance diagonal weights
     Rk: float = 0.1
-    Qfk: float = 10.0
+    Qfk: float = 10.0   # or (B, n)
 
     @property
     def batch(self):
@@ -78,6 +78,23 @@ def gen_random_linear_batch(batch, n=12, m=4, N=50, steps=100, dt=0.1, seed=1, f
         X[:, k + 1] = np.einsum("bij,bj->bi", A, X[:, k]) + np.einsum("bij,bj->bi", Bm, U[:, k])
     return RandomLinearBatch(n=n, m=m, N=N, dt=dt, A=A, Bm=Bm, Xtrack=X, Utrack=U, noise=noise,
                              u_bnd=u_bnd)
+
+
+def gen_random_linear_hetero_batch(batch, n=12, m=4, N=50, steps=100, dt=0.1, seed=1, first_instance=0,
+                                   u_range=(1.5, 4.0)):
+    """A batch of DIFFERENT random-linear problems, as gen_random_linear draws them one by one
+    (random_linear_problem.jl:11-13,16-23): per instance Q = 10 rand(n), Qf = (N-1) Q and a bound u_bnd drawn
+    uniformly from u_range.  Dynamics, track and noise are those of gen_random_linear_batch with the same arguments;
+    the weights and bounds come from a generator of their own, so that batch does not change."""
+    pb = gen_random_linear_batch(batch, n=n, m=m, N=N, steps=steps, dt=dt, seed=seed, first_instance=first_instance)
+    Q = np.empty((batch, n))
+    ub = np.empty(batch)
+    for b in range(batch):
+        rng = np.random.default_rng([seed, first_instance + b, 0x51])
+        Q[b] = 10.0 * rng.random(n)
+        ub[b] = rng.uniform(*u_range)
+    pb.Qk, pb.Qfk, pb.u_bnd = Q, (N - 1) * Q, ub
+    return pb
 
 
 # ---------------------------------------------------------------------------------------------

@@ -174,6 +174,13 @@ int32_t altro_batch_set_dynamics(altro_handle* h, const double* A, const double*
  * Stage costs are scaled by dt, the terminal cost is not (random_linear_problem.jl:52-53). */
 int32_t altro_batch_set_tracking_cost(altro_handle* h, const double* Qdiag, const double* Rdiag,
                                       const double* Qfdiag, double dt);
+/* The same with weights PER INSTANCE: Qdiag [batch][n], Rdiag [batch][m], Qfdiag [batch][n] -- every problem of the batch
+ * owns its TrackingObjective, as the reference's generator builds them (random_linear_problem.jl:11-13: Q = Diagonal(10 rand(n)),
+ * Qf = (N-1) Q per problem; mpc.jl:26-29).  dt is common.  Callable wherever altro_batch_set_tracking_cost is; a call of
+ * either replaces what the other set.  Results of instance i are bit-identical to those of a handle given instance i's
+ * weights through altro_batch_set_tracking_cost.  Drops the stored gains. */
+int32_t altro_batch_set_tracking_cost_per_instance(altro_handle* h, const double* Qdiag, const double* Rdiag,
+                                                   const double* Qfdiag, double dt);
 
 /* add_constraint!(cons, con, inds): random_linear_problem.jl:23-24 (BoundConstraint),
  * rocket_landing_problem.jl:96,123-124,142,165, grasp_problem.jl:29-67, ALTROParams.jl:67-78.
@@ -200,6 +207,16 @@ int32_t altro_batch_add_constraint(altro_handle* h, int32_t kind, int32_t sense,
  * constraint was added with (per instance if it was); either may be NULL (unchanged). */
 int32_t altro_batch_update_constraint_data(altro_handle* h, int32_t con_id, const double* A,
                                            const double* b);
+/* New bounds for the BOX constraint con_id, in place: BoundConstraint(n, m; x_min, x_max, u_min, u_max) per problem
+ * (random_linear_problem.jl:16-23 draws u_bnd for each problem it generates).  per_instance = 0: zmin, zmax are one
+ * [n+m] pair for the batch; 1: [batch][n+m] each.  The knot range and the PATTERN of finite sides (which elements have a
+ * finite lower and which a finite upper bound, finite meaning zmin > -1e300 / zmax < 1e300) stay those the BOX was added
+ * with: they fix the layout of its duals.  ALTRO_ERR_INVALID_ARG for a con_id that is not a BOX (also before any BOX is
+ * added), a row whose pattern differs, a NaN, or zmin > zmax; nothing changes then.  Callable before the first solve, between
+ * solves and between MPC steps, like altro_batch_update_constraint_data; drops the stored gains.  Results of instance i are
+ * bit-identical to those of a handle whose BOX was added with instance i's row. */
+int32_t altro_batch_set_bounds(altro_handle* h, int32_t con_id, const double* zmin, const double* zmax,
+                               int32_t per_instance);
 
 /* TO.set_initial_state!: random_linear_problem.jl:130.  x0 is [batch][n]. */
 int32_t altro_batch_set_initial_state(altro_handle* h, const double* x0);
