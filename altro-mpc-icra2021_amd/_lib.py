@@ -37,7 +37,7 @@ EXPORTS = [
     "altro_mpc_prepare_async", "altro_batch_benchmark_solve", "altro_mpc_set_dynamics_track",
     "altro_batch_get_confirm_counter", "altro_batch_get_reuse_counter", "altro_batch_get_polish_stats",
     "altro_debug_set", "altro_batch_get_polish_dual_residuals", "altro_batch_set_tracking_cost_per_instance",
-    "altro_batch_set_bounds",
+    "altro_batch_set_bounds", "altro_mpc_set_log", "altro_mpc_get_log",
 ]
 """every symbol include/altro_batch.h declares"""
 
@@ -70,7 +70,7 @@ def build(force=False, verbose=False):
     """Generate the DPP block include and compile the HIP library for gfx950, in tree.  The library is several translation
     units (altro_batch.hip: the C-ABI, the 16-lane kernels, the polish; wide_inst.hip once per group of one-wave-per-instance
     kernels, solve_wide.h ALTRO_WIDE_KERNELS) compiled side by side -- one after the other they take ~6 minutes."""
-    srcs = [os.path.join(CSRC, f) for f in ("altro_batch.hip", "wide_inst.hip", "solve_dpp16.h", "solve_wide.h", "wide_backend.h", "launch_ring.h", "pn_polish.h", "pn_wide.h", "gen_dpp_blocks.py")]
+    srcs = [os.path.join(CSRC, f) for f in ("altro_batch.hip", "wide_inst.hip", "solve_dpp16.h", "solve_wide.h", "wide_backend.h", "launch_ring.h", "pn_polish.h", "pn_wide.h", "mpc_log.h", "gen_dpp_blocks.py")]
     srcs.append(os.path.join(os.path.dirname(_HERE), "include", "altro_batch.h"))
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):
         return LIB_PATH
@@ -127,6 +127,9 @@ def lib():
     if hasattr(L, "altro_batch_set_tracking_cost_per_instance"):
         L.altro_batch_set_tracking_cost_per_instance.argtypes = [H, dp, dp, dp, C.c_double]
         L.altro_batch_set_bounds.argtypes = [H, C.c_int32, dp, dp, C.c_int32]
+    if hasattr(L, "altro_mpc_set_log"):
+        L.altro_mpc_set_log.argtypes = [H, C.c_int32]
+        L.altro_mpc_get_log.argtypes = [H, C.c_int32, C.c_int32, dp, dp, ip, ip, ip, dp, dp]
     L.altro_batch_add_constraint.argtypes = [H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                              dp, dp, dp, dp, C.c_int32, ip]
     L.altro_batch_update_constraint_data.argtypes = [H, C.c_int32, dp, dp]

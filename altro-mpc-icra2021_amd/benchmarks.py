@@ -35,11 +35,35 @@ def _result(times_ms, iters, ok, B):
             "solve_succeeded": np.asarray(ok), "batch": B}
 
 
-def run_random_linear(n=12, m=4, N=50, batch=1024, steps=100, seed=1):
-    """run_MPC(prob_mpc, opts, Z_track, 100) (random_linear_problem.jl:85-189)."""
+def _result_from_log(launch_ms, log, B, launch_steps):
+    """The same Dict from the per-step log of fused launches: `iter` / `solve_succeeded` hold one row per STEP as before,
+    `time` one entry per LAUNCH of `launch_steps` steps (a fused launch has no per-step device times)."""
+    res = _result(launch_ms, log.iterations.copy(), log.solve_succeeded, B)
+    in_launch = np.array([min(launch_steps, log.steps - f) for f in range(0, log.steps, launch_steps)])
+    res["time_us_per_solve"] = 1e3 * res["time"] / (B * in_launch)
+    res["launch_steps"] = int(launch_steps)
+    return res
+
+
+def _run_fused(mp, steps, launch_steps, B):
+    """`steps` MPC steps in launches of `launch_steps` (the last one shorter), statistics of every step from the device log."""
+    mp.enable_log(steps)
+    t = []
+    for first in range(0, steps, launch_steps):
+        mp.run_async(min(launch_steps, steps - first), first)
+        mp.synchronize()
+        t.append(api.stats(mp.solver).tsolve_ms)
+    return _result_from_log(t, mp.log(0, steps), B, launch_steps)
+
+
+def run_random_linear(n=12, m=4, N=50, batch=1024, steps=100, seed=1, launch_steps=1):
+    """run_MPC(prob_mpc, opts, Z_track, 100) (random_linear_problem.jl:85-189).  launch_steps = K > 1: the steps run K to a
+    launch (altro_mpc_run_async) and `iter` / `solve_succeeded` come from the per-step log; `time` is then per launch."""
     pb = problems.gen_random_linear_batch(batch, n=n, m=m, N=N, steps=steps, seed=seed)
     mp = mpc.BatchMPC(pb)
     mp.initial_solve()
+    if launch_steps > 1:
+        return _run_fused(mp, steps, launch_steps, batch)
     t, it, ok = [], [], []
     for i in range(steps):
         mp.step(i)
@@ -60,9 +84,9 @@ def run_sweeps(batch=256, steps=100):
     return out
 
 
-def run_rocket(batch=256, N_mpc=21, steps=100, N_cold=301, dt=0.05, seed=1):
+def run_rocket(batch=256, N_mpc=21, steps=100, N_cold=301, dt=0.05, seed=1, launch_steps=1):
     """Cold solve of the landing problem, then conic tracking MPC along it (run_simple_rocket.jl:31-135,
-    simple_rocket.jl:59-82).  Instances differ in their initial state."""
+    simple_rocket.jl:59-82).  Instances differ in their initial state.  launch_steps: as in run_random_linear."""
     rp = problems.gen_rocket_problem(N=N_cold, tf=(N_cold - 1) * dt, Qfk=1e4, Rk=1.0, theta_thrust_max=5.0, theta_glideslope=45.0)
     rng = np.random.default_rng(seed)
     x0 = np.tile(rp.x0, (batch, 1)) + rng.standard_normal((batch, 6)) * np.array([1, 1, 1, .3, .3, .3]) * 0.5
@@ -79,12 +103,15 @@ def run_rocket(batch=256, N_mpc=21, steps=100, N_cold=301, dt=0.05, seed=1):
     mp = mpc.TrackMPC(prob, api.SolverOptions(**ROCKET_MPC_OPTS), Xt, Ut, noise,
                       (np.array([1e-3] * 3 + [1e-2] * 3), np.array([0, 0, 0, 1, 1, 1])))
     mp.initial_solve()
-    t, it, ok = [], [], []
-    for i in range(steps):
-        mp.step(i)
-        st = api.stats(mp.solver)
-        t.append(st.tsolve_ms); it.append(st.iterations.copy()); ok.append(st.status == api.SOLVE_SUCCEEDED)
-    res = _result(t, it, ok, batch)
+    if launch_steps > 1:
+        res = _run_fused(mp, steps, launch_steps, batch)
+    else:
+        t, it, ok = [], [], []
+        for i in range(steps):
+            mp.step(i)
+            st = api.stats(mp.solver)
+            t.append(st.tsolve_ms); it.append(st.iterations.copy()); ok.append(st.status == api.SOLVE_SUCCEEDED)
+        res = _result(t, it, ok, batch)
     res["cold"] = {"time": cst.tsolve_ms, "iter": cst.iterations, "solve_succeeded": cst.status == api.SOLVE_SUCCEEDED}
     return res
 
@@ -160,7 +187,11 @@ def run_quadruped(batch=256, N=15, steps=30, linearized_friction=True, seed=7):
 
 def summarise(res):
     it = np.asarray(res["iter"])
-    return {"batch": int(res["batch"]), "steps": int(it.shape[0]), "iterations_median": float(np.median(it)),
-            "iterations_mean": float(it.mean()), "iterations_max": int(it.max()),
-            "solve_succeeded_frac": float(np.mean(res["solve_succeeded"])),
-            "ms_per_step_median": float(np.median(res["time"])), "us_per_solve_median": float(np.median(res["time_us_per_solve"]))}
+    out = {"batch": int(res["batch"]), "steps": int(it.shape[0]), "iterations_median": float(np.median(it)),
+           "iterations_mean": float(it.mean()), "iterations_max": int(it.max()),
+           "solve_succeeded_frac": float(np.mean(res["solve_succeeded"])),
+           "ms_per_step_median": float(np.median(res["time"])), "us_per_solve_median": float(np.median(res["time_us_per_solve"]))}
+    if "launch_steps" in res:   # fused launches: `time` holds one entry per launch, a step's figure is its share of it
+        out["launch_steps"] = int(res["launch_steps"])
+        out["ms_per_step_median"] = out["us_per_solve_median"] * out["batch"] / 1e3
+    return out

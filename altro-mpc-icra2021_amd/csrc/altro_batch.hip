@@ -80,6 +80,8 @@ struct altro_handle {
   int* noise_grp = nullptr;
   int noise_mode = 0;
   int mpc_shift = 1;
+  double* mlog = nullptr;  // per-step log of the MPC loop (mpc_log.h): [mlog_cap][batch][16 + MLOG_TAIL]; null: off
+  int mlog_cap = 0;        // steps it holds
   // scheduling switches (altro_debug_set; the defaults are the product's behaviour)
   int reuse = 1;  // gain reuse (solve_dpp16.h fosweep); "no_reuse" switches it off (tests)
   int lone = 1;  // backward_lone (solve_dpp16.h); "no_lone" switches it off (tests: lone == four-row pass bit for bit)
@@ -290,6 +292,23 @@ __global__ void k_duals(double* __restrict__ host, double* __restrict__ Lb, cons
       Lb[dl] = host[lo];
     }
   }
+}
+
+// MPC log, projected_newton = 1: the solve kernel of a step's pair wrote the step's records, then the polish kernel moved the
+// trajectory and, where it ran, replaced cost / c_max / status.  The records take what the handle holds now: u0 <- first
+// control of the polished trajectory, and the three statistics altro_batch_get_stats reports after the step.
+// rec0 = the step's first record; one thread per instance.
+__global__ void k_log_polished(double* __restrict__ rec0, const double* __restrict__ Zp, const int* __restrict__ cur, size_t plane,
+                               const double* __restrict__ cost, const double* __restrict__ cmax, const int* __restrict__ status,
+                               int B, int N, int n, int m) {
+  const int inst = blockIdx.x * blockDim.x + threadIdx.x;
+  if (inst >= B) return;
+  double* r = rec0 + (size_t)inst * (LW + altro::MLOG_TAIL);
+  const double* z0 = Zp + (size_t)inst * (2 * (size_t)N + 1) * LW + (size_t)cur[inst] * plane;
+  for (int a = 0; a < m; ++a) r[n + a] = z0[n + a];
+  r[LW] = cost[inst];
+  r[LW + 1] = cmax[inst];
+  reinterpret_cast<int*>(r + LW + 2)[2] = status[inst];
 }
 
 // RD.shift_fill!(Z) on the current plane and Altro.shift_fill!(conSet) on the box duals
@@ -521,6 +540,7 @@ static int launch_solve(altro_handle* h, int first_step, int nsteps, int prepare
   p.simd_tab = h->mate ? h->simd_tab : nullptr;
   p.n_solves = h->n_solves; p.n_iters = h->n_iters; p.n_ok = h->n_ok; p.n_trials = h->n_trials;
   p.n_gconf = h->n_gconf; p.dzero = h->dzero;
+  p.mlog = (nsteps > 0 && !prepare_only) ? h->mlog : nullptr;  // MPC steps only (altro_mpc_run_async checked the capacity)
   p.o = h->o;
   if (h->o.projected_newton) {  // solve!(::ALTROSolver): the AL stage only has to reach the polish's tolerance
     if (h->o.projected_newton_tolerance >= 0) p.o.constraint_tolerance = h->o.projected_newton_tolerance;
@@ -928,10 +948,11 @@ static void free_dpp_backend(altro_handle* h) {
                    (void**)&h->n_ok, (void**)&h->n_trials, (void**)&h->Zsave, (void**)&h->n_gconf, (void**)&h->dzero, (void**)&h->Qz,
                    (void**)&h->Dff, (void**)&h->ahash, (void**)&h->kmu, (void**)&h->n_fo, (void**)&h->perm, (void**)&h->gscore,
                    (void**)&h->pn_ran, (void**)&h->pn_failed, (void**)&h->pn_res, (void**)&h->pn_dfail, (void**)&h->pn_dres0, (void**)&h->pn_dres, (void**)&h->pnE, (void**)&h->pndv, (void**)&h->pnLd, (void**)&h->pnLo,
-                   (void**)&h->pnvec, (void**)&h->pntz, (void**)&h->pnnb, (void**)&h->pnnst, (void**)&h->pnrinfo};
+                   (void**)&h->pnvec, (void**)&h->pntz, (void**)&h->pnnb, (void**)&h->pnnst, (void**)&h->pnrinfo, (void**)&h->mlog};
   for (void** p : ptrs)
     if (*p) { hipFree(*p); *p = nullptr; }
   h->stage_bytes = 0;
+  h->mlog_cap = 0;
   h->ring.destroy();
   if (h->bev0) { hipEventDestroy(h->bev0); h->bev0 = nullptr; }
   if (h->bev1) { hipEventDestroy(h->bev1); h->bev1 = nullptr; }
@@ -986,6 +1007,15 @@ static int migrate_to_wide(altro_handle* h) {
       wb->destroy();
       delete wb;
       return rcx;
+    }
+  }
+  if (h->mlog_cap > 0) {  // altro_mpc_set_log before the model: the setting moves with the handle (the records start empty)
+    const int rcl = wb->mpc_set_log(h->mlog_cap);
+    if (rcl) {
+      h->err = wb->err;
+      wb->destroy();
+      delete wb;
+      return rcl;
     }
   }
   free_dpp_backend(h);
@@ -1478,6 +1508,12 @@ static int enqueue_solve(altro_handle* h, int first_step, int nsteps) {
       rc = launch_solve(h, first_step + s, 1);
       h->kref = first_step + s + 1;
       if (!rc) rc = launch_polish(h);
+      if (!rc && h->mlog) {
+        double* rec0 = h->mlog + (size_t)(first_step + s) * (size_t)h->d.batch * (LW + altro::MLOG_TAIL);
+        hipLaunchKernelGGL(k_log_polished, grid_for((size_t)h->d.batch), dim3(256), 0, h->stream, rec0, h->Z, h->cur, (size_t)h->d.N * LW,
+                           h->cost, h->cmax, h->status, h->d.batch, h->d.N, h->d.n, h->d.m);
+        if (hipGetLastError() != hipSuccess) { h->err = "launch of the log kernel failed"; rc = ALTRO_ERR_HIP; }
+      }
     }
     if (rc) h->kref = kref0;
   } else {
@@ -1895,11 +1931,48 @@ int32_t altro_mpc_run_async(altro_handle* h, int32_t first_step, int32_t nsteps)
     if (nsteps < 1 || first_step < 0) FAIL(h, ALTRO_ERR_INVALID_ARG, "bad step range");
     if (h->noise && first_step + nsteps > h->noise_steps) FAIL(h, ALTRO_ERR_INVALID_ARG, "steps outside the uploaded noise");
     if (first_step + nsteps + h->d.N > h->Nt) FAIL(h, ALTRO_ERR_INVALID_ARG, "steps run past the end of the track");
+    if (h->mlog && first_step + nsteps > h->mlog_cap) FAIL(h, ALTRO_ERR_INVALID_ARG, "steps outside the capacity of the log (altro_mpc_set_log)");
     return enqueue_solve(h, first_step, nsteps);
   });
 }
 
 int32_t altro_mpc_step_async(altro_handle* h, int32_t step) { return altro_mpc_run_async(h, step, 1); }
+
+int32_t altro_mpc_set_log(altro_handle* h, int32_t capacity_steps) {
+  return guard(h, [&]() -> int32_t {
+    WIDE_FWD(h, mpc_set_log(capacity_steps));
+    if (!h) return ALTRO_ERR_INVALID_ARG;
+    if (capacity_steps < 0) FAIL(h, ALTRO_ERR_INVALID_ARG, "negative log capacity");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));  // a launch in flight may still be writing the old log
+    if (h->mlog) HIPCHK(h, hipFree(h->mlog));
+    h->mlog = nullptr;
+    h->mlog_cap = 0;
+    if (capacity_steps == 0) return ALTRO_OK;
+    const size_t bytes = (size_t)capacity_steps * (size_t)h->d.batch * (LW + altro::MLOG_TAIL) * sizeof(double);
+    HIPCHK(h, hipMalloc(&h->mlog, bytes));
+    HIPCHK(h, hipMemsetAsync(h->mlog, 0xFF, bytes, h->stream));  // never written: -1 / NaN
+    h->mlog_cap = capacity_steps;
+    return ALTRO_OK;
+  });
+}
+
+int32_t altro_mpc_get_log(altro_handle* h, int32_t first_step, int32_t nsteps, double* x0, double* u0, int32_t* iterations,
+                          int32_t* iterations_outer, int32_t* status, double* cost, double* c_max) {
+  return guard(h, [&]() -> int32_t {
+    WIDE_FWD(h, mpc_get_log(first_step, nsteps, x0, u0, iterations, iterations_outer, status, cost, c_max));
+    if (!h) return ALTRO_ERR_INVALID_ARG;
+    if (!h->mlog) FAIL(h, ALTRO_ERR_STATE, "no log: altro_mpc_set_log has not been called");
+    if (first_step < 0 || nsteps < 0 || first_step > h->mlog_cap - nsteps) FAIL(h, ALTRO_ERR_INVALID_ARG, "steps outside the capacity of the log");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const size_t rec = LW + altro::MLOG_TAIL, B = h->d.batch;
+    std::vector<double> img((size_t)nsteps * B * rec);
+    if (!img.empty()) HIPCHK(h, hipMemcpy(img.data(), h->mlog + (size_t)first_step * B * rec, img.size() * sizeof(double), hipMemcpyDeviceToHost));
+    altro::mlog_unpack(img.data(), (size_t)nsteps, B, rec, h->d.n, h->d.m, x0, u0, iterations, iterations_outer, status, cost, c_max);
+    return ALTRO_OK;
+  });
+}
 
 int32_t altro_mpc_set_dynamics_track(altro_handle* h, const double* A, const double* B, const double* f, int32_t nblocks,
                                      int32_t step_stride, int32_t per_instance) {

@@ -40,6 +40,7 @@
 #include <type_traits>
 
 #include "../../include/altro_batch.h"
+#include "mpc_log.h"
 
 // tuning knobs (defaults = the shipped configuration; overridable with -D for experiments)
 #ifndef ALTRO_PD_OPEN
@@ -189,6 +190,8 @@ struct SolveParams {
   long long* wave_cycles; // [Bp/4][16] shader cycles of the last launch, per wave (diagnostic):
                           // total, backward, closed rollouts, open rollouts, todorov, dual update,
                           // streaming line-search sweeps
+  double* mlog;          // per-step log of the MPC loop (mpc_log.h): [capacity][B][16 + MLOG_TAIL], or null (off, and in every
+                         // launch that is not an MPC step: plain solves, prepare-only).  Read ONCE, into RowState::lrec
   altro_opts o;
 };
 
@@ -398,6 +401,9 @@ struct RowState {
   int ngc;        // iterations confirmed by the costate sweep (work counter)
   int nfo;        // iterations that took their gains from memory (work counter)
   unsigned imask; // SolveParams::imask, kept here so that no register holds it across the kernel (Solver::consts)
+  double* lrec;   // MPC log: this instance's record of the launch's first step, null when nothing is logged (log off, plain
+                  // solve, padded slot).  Parked here like imask: the write is once per solve, no register waits for it
+  unsigned lstep; // doubles from one step's record of an instance to the next step's: B * (16 + MLOG_TAIL)
 };
 
 template <int NX, int NU, bool CONES>
@@ -2239,6 +2245,9 @@ struct Solver {
       s.ngc = 0;
       s.nfo = 0;
       s.imask = P.imask;
+      // records are indexed by the CALLER's instance (inst is already perm[slot] in a grouped launch); padded slots log nothing
+      s.lstep = (unsigned)P.B * (unsigned)(LW + MLOG_TAIL);
+      s.lrec = (P.mlog != nullptr && mpc && inst < P.B) ? P.mlog + ((size_t)first_step * (size_t)P.B + (size_t)inst) * (size_t)(LW + MLOG_TAIL) : nullptr;
       *rs = s;
       *ah = P.ahash[(unsigned)inst * LW + j];
       aset_clear(qhs);
@@ -2709,6 +2718,11 @@ struct Solver {
             rs->nsolve += 1;
             rs->nit += rs->iters;
             rs->nok += (rs->status == ALTRO_SOLVE_SUCCEEDED) ? 1 : 0;
+            if (double* lg = rs->lrec) {  // MPC log: the step's x0 | first control of the trajectory it leaves, and its statistics
+              lg += (size_t)rs->step * rs->lstep;
+              lg[j] = is_x ? ldg(P.x0, rowoff) : ldg(P.Z, plane(rs->cur) + zat(0));
+              if (j == 0) mlog_tail(lg + LW, rs->J, rs->cmax, rs->iters, rs->iters_outer, rs->status);
+            }
             rs->step += 1;
             rs->phase = PH_STEP_BEGIN;
           } else {

@@ -33,6 +33,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/altro_batch.h"
+#include "mpc_log.h"
 
 namespace altro_wide {
 
@@ -90,6 +91,7 @@ struct Params {
   // absolute knot, like the reference track) or N - 1 (one full table per MPC step).
   int dyn_blocks, dyn_step_stride;
   int compact;  // LDS carve-up with [Qux | Qu] and K inside W (wide_compact)
+  double* mlog;  // per-step log of the MPC loop (mpc_log.h): [capacity][B][n + m + MLOG_TAIL], or null (off)
   altro_opts o;
 };
 
@@ -3003,6 +3005,12 @@ struct Solver {
         WSTAMP(t_sh += wstamp() - tsh;)
       }
       solve_one();
+      if (mpc && P.mlog != nullptr) {  // MPC log: the step's x0, the first control of the trajectory it leaves, its statistics
+        double* lg = P.mlog + ((size_t)(first_step + s) * (size_t)P.B + (size_t)inst) * (size_t)(nz + altro::MLOG_TAIL);
+        if (T < n) lg[T] = x0i[T];
+        if (T < m) lg[n + T] = Up(cur)[T];
+        if (T == 0) altro::mlog_tail(lg + nz, P.cost[inst], P.cmax[inst], iters, iters_outer, status);  // (what solve_one just stored)
+      }
       nsolve++;
       nit += iters;
       nok += status == ALTRO_SOLVE_SUCCEEDED ? 1 : 0;

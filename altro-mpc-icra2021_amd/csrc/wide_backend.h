@@ -61,6 +61,22 @@ __global__ void k_scatter_plane(double* planes, const double* img, const int* cu
   planes[(b * 2 + cur[b]) * len + e] = img[t];
 }
 
+// MPC log, projected_newton = 1 (the twin of altro_batch.hip's k_log_polished): after the polish kernel of a step's pair the
+// step's records take the first control of the polished trajectory and the statistics the polish replaced where it ran.
+__global__ void k_log_polished_wide(double* __restrict__ rec0, const double* __restrict__ U, const int* __restrict__ cur,
+                                    const double* __restrict__ cost, const double* __restrict__ cmax, const int* __restrict__ status,
+                                    int B, int N, int n, int m) {
+  const int inst = blockIdx.x * blockDim.x + threadIdx.x;
+  if (inst >= B) return;
+  const size_t nv = (size_t)n + m;
+  double* r = rec0 + (size_t)inst * (nv + altro::MLOG_TAIL);
+  const double* u = U + ((size_t)inst * 2 + cur[inst]) * (size_t)(N - 1) * m;
+  for (int a = 0; a < m; ++a) r[n + a] = u[a];
+  r[nv] = cost[inst];
+  r[nv + 1] = cmax[inst];
+  reinterpret_cast<int*>(r + nv + 2)[2] = status[inst];
+}
+
 struct WideBackend {
   altro_dims d{};
   altro_opts o{};
@@ -96,6 +112,8 @@ struct WideBackend {
             *n_ok = nullptr, *n_gconf = nullptr, *n_gs = nullptr;
   size_t stage_bytes = 0;
   int Nt = 0, kref = 0, noise_steps = 0, noise_mode = 0, mpc_shift = 1;
+  double* mlog = nullptr;  // per-step log of the MPC loop (mpc_log.h): [mlog_cap][B][n + m + MLOG_TAIL]; null: off
+  int mlog_cap = 0;
   int dyn_blocks = 1, dyn_step_stride = 0;
   bool ltv = false, dyn_per_instance = false, have_dyn = false, have_cost = false, have_ref = false;
   int box_k0 = 0, box_k1 = -1, box_id = -1;
@@ -182,7 +200,7 @@ struct WideBackend {
     void* ptrs[] = {A, Bm, f, wd, wf, zmin, zmax, x0, Xref, Uref, X, U, Lb, Lc, mu, Kg, dg, trash, AconT, bcon, stage, cur, ctype,
                     rowk0, rowk1, rowc0, rowcp, iters, iters_outer, status, noise_grp, cost, cmax, Jtrace, ctrace, atrace, noise, noise_w,
                     n_backward, n_rollout, n_trials, n_solves, n_iters, n_ok, Xsave, Usave, Qz, n_gconf, n_gs, fac, bwst, aset,
-                    pn_ran, pn_failed, pn_dfail, pn_res, pn_dres0, pn_dres, pnE, pndv, pnLd, pnLo, pnvec, pntz, pnblk, pnnb, pnnst, pnrinfo};
+                    pn_ran, pn_failed, pn_dfail, pn_res, pn_dres0, pn_dres, pnE, pndv, pnLd, pnLo, pnvec, pntz, pnblk, pnnb, pnnst, pnrinfo, mlog};
     for (void* p : ptrs)
       if (p) hipFree(p);
     ring.destroy();
@@ -512,6 +530,7 @@ struct WideBackend {
     p.kref = kref;
     p.dyn_blocks = dyn_blocks; p.dyn_step_stride = dyn_step_stride;
     p.compact = compact();
+    p.mlog = mlog;   // (the kernel writes it in MPC steps only: mpc == 1)
     p.o = o;
     if (o.projected_newton) {  // solve!(::ALTROSolver): the AL stage only has to reach the polish's tolerance
       if (o.projected_newton_tolerance >= 0) p.o.constraint_tolerance = o.projected_newton_tolerance;
@@ -640,6 +659,12 @@ struct WideBackend {
         if (rc) err = "launch of the solve kernel failed";
         kref = first_step + s + 1;
         if (!rc) rc = polish_launch();
+        if (!rc && mlog) {
+          double* rec0 = mlog + (size_t)(first_step + s) * (size_t)d.batch * mlog_rec();
+          hipLaunchKernelGGL(k_log_polished_wide, dim3((unsigned)((d.batch + 255) / 256)), dim3(256), 0, stream, rec0, U, cur, cost, cmax, status,
+                             d.batch, d.N, d.n, d.m);
+          if (hipGetLastError() != hipSuccess) { err = "launch of the log kernel failed"; rc = ALTRO_ERR_HIP; }
+        }
       }
       if (rc) kref = kref0;
     } else {
@@ -845,10 +870,39 @@ struct WideBackend {
     noise_mode = mode;
     return ALTRO_OK;
   }
+  // per-step log of the MPC loop (include/altro_batch.h: altro_mpc_set_log / altro_mpc_get_log)
+  size_t mlog_rec() const { return (size_t)nz() + altro::MLOG_TAIL; }
+  int mpc_set_log(int capacity_steps) {
+    if (capacity_steps < 0) WFAIL(ALTRO_ERR_INVALID_ARG, "negative log capacity");
+    WCHK(hipSetDevice(device));
+    WCHK(hipStreamSynchronize(stream));  // a launch in flight may still be writing the old log
+    if (mlog) WCHK(hipFree(mlog));
+    mlog = nullptr;
+    mlog_cap = 0;
+    if (capacity_steps == 0) return ALTRO_OK;
+    const size_t bytes = (size_t)capacity_steps * (size_t)d.batch * mlog_rec() * sizeof(double);
+    WCHK(hipMalloc(&mlog, bytes));
+    WCHK(hipMemsetAsync(mlog, 0xFF, bytes, stream));  // never written: -1 / NaN
+    mlog_cap = capacity_steps;
+    return ALTRO_OK;
+  }
+  int mpc_get_log(int first_step, int nsteps, double* x0h, double* u0h, int32_t* it, int32_t* ito, int32_t* st, double* J, double* c) {
+    if (!mlog) WFAIL(ALTRO_ERR_STATE, "no log: altro_mpc_set_log has not been called");
+    if (first_step < 0 || nsteps < 0 || first_step > mlog_cap - nsteps) WFAIL(ALTRO_ERR_INVALID_ARG, "steps outside the capacity of the log");
+    WCHK(hipSetDevice(device));
+    WCHK(hipStreamSynchronize(stream));
+    const size_t rec = mlog_rec(), B = d.batch;
+    std::vector<double> img((size_t)nsteps * B * rec);
+    if (!img.empty()) WCHK(hipMemcpy(img.data(), mlog + (size_t)first_step * B * rec, img.size() * sizeof(double), hipMemcpyDeviceToHost));
+    altro::mlog_unpack(img.data(), (size_t)nsteps, B, rec, d.n, d.m, x0h, u0h, it, ito, st, J, c);
+    return ALTRO_OK;
+  }
+
   int mpc_run(int first_step, int nsteps) {
     if (nsteps < 1 || first_step < 0) WFAIL(ALTRO_ERR_INVALID_ARG, "bad step range");
     if (noise && first_step + nsteps > noise_steps) WFAIL(ALTRO_ERR_INVALID_ARG, "steps outside the uploaded noise");
     if (first_step + nsteps + d.N > Nt) WFAIL(ALTRO_ERR_INVALID_ARG, "steps run past the end of the track");
+    if (mlog && first_step + nsteps > mlog_cap) WFAIL(ALTRO_ERR_INVALID_ARG, "steps outside the capacity of the log (altro_mpc_set_log)");
     return enqueue(1, first_step, nsteps);
   }
 };

@@ -3,6 +3,7 @@ loop of benchmarks/random_linear_mpc/random_linear_problem.jl::run_MPC (:85-189)
 batched solver.  The OSQP twin of the reference is replaced by the offline oracle in tests/.
 """
 import ctypes as C
+from dataclasses import dataclass
 
 import numpy as np
 
@@ -27,6 +28,40 @@ def gen_tracking_problem(pb, N=None):
     ub = pb.u_bnd if np.ndim(pb.u_bnd) == 0 else np.repeat(np.asarray(pb.u_bnd, dtype=np.float64)[:, None], m, axis=1)
     cons.add_constraint(api.BoundConstraint(n, m, u_min=-ub, u_max=ub), (1, N - 1))
     return api.Problem(model, obj, cons, x0=Xr[:, 0].copy(), N=N, U0=Ur.copy())
+
+
+@dataclass
+class MPCLog:
+    """Per-step records of a device-resident MPC run (altro_mpc_get_log), step-major: what the reference's loops keep of
+    every step (simple_rocket.jl:137-205: X_traj[i+1] = prob_mpc.x0, iters[i], status[i], costs[i])."""
+    first: int                      # absolute index of the first step held
+    x0: np.ndarray                  # (S, B, n) initial state each step's solve started from
+    u0: np.ndarray                  # (S, B, m) first control of the trajectory the step left: what the next plant step applies
+    iterations: np.ndarray          # (S, B) int32
+    iterations_outer: np.ndarray    # (S, B) int32
+    status: np.ndarray              # (S, B) int32
+    cost: np.ndarray                # (S, B)
+    c_max: np.ndarray               # (S, B)
+
+    @property
+    def steps(self):
+        return self.x0.shape[0]
+
+    @property
+    def solve_succeeded(self):
+        return self.status == _lib.SOLVE_SUCCEEDED
+
+    def x_traj(self, x_start):
+        """The closed-loop trajectory the reference calls X_traj, (S + 1, B, n): `x_start` (B, n), the initial state the
+        handle held before step `first`, then x0 of every step (simple_rocket.jl:137,164)."""
+        return x_traj(x_start, self)
+
+
+def x_traj(x_start, log):
+    x_start = np.asarray(x_start, dtype=np.float64)
+    if x_start.shape != log.x0.shape[1:]:
+        raise ValueError(f"x_start is {x_start.shape}, the log holds states {log.x0.shape[1:]}")
+    return np.concatenate([x_start[None], log.x0], axis=0)
 
 
 class BatchMPC:
@@ -93,6 +128,30 @@ class BatchMPC:
         s._chk(s._L.altro_batch_get_initial_state(s.h, api._p(out)))
         return out
 
+    def enable_log(self, steps):
+        """Keep one record per MPC step on the device for steps 0 .. steps-1 (altro_mpc_set_log); 0 switches it off.
+        Remembers the initial state the handle holds now: the first row of closed_loop_trajectory()."""
+        s = self.solver
+        s._chk(s._L.altro_mpc_set_log(s.h, int(steps)))
+        self.log_steps = int(steps)
+        self.log_first, self.log_x_start = self.i, (self.x0() if steps else None)
+
+    def log(self, first=0, nsteps=None):
+        """MPCLog of steps first .. first+nsteps-1 (default: up to the step the loop has reached)."""
+        s = self.solver
+        nsteps = max(self.i - first, 0) if nsteps is None else nsteps
+        ip = C.POINTER(C.c_int32)
+        x0, u0 = np.empty((nsteps, s.B, s.n)), np.empty((nsteps, s.B, s.m))
+        it, ito, st = (np.empty((nsteps, s.B), dtype=np.int32) for _ in range(3))
+        cost, cm = np.empty((nsteps, s.B)), np.empty((nsteps, s.B))
+        s._chk(s._L.altro_mpc_get_log(s.h, int(first), int(nsteps), api._p(x0), api._p(u0), it.ctypes.data_as(ip),
+                                      ito.ctypes.data_as(ip), st.ctypes.data_as(ip), api._p(cost), api._p(cm)))
+        return MPCLog(int(first), x0, u0, it, ito, st, cost, cm)
+
+    def closed_loop_trajectory(self):
+        """X_traj of the steps run since enable_log: (S + 1, B, n)."""
+        return self.log(self.log_first).x_traj(self.log_x_start)
+
 
 class TrackMPC:
     """Device-resident MPC loop for any tracking problem: the solver is built on the first window
@@ -128,6 +187,9 @@ class TrackMPC:
     step = BatchMPC.step
     step_benchmark = BatchMPC.step_benchmark
     x0 = BatchMPC.x0
+    enable_log = BatchMPC.enable_log
+    log = BatchMPC.log
+    closed_loop_trajectory = BatchMPC.closed_loop_trajectory
 
 
 def _add_specs(cons, specs, n, m):

@@ -367,8 +367,34 @@ int32_t altro_mpc_prepare_async(altro_handle* h, int32_t step);
  * Instances are independent closed loops, so inside the launch each wavefront runs its own four
  * instances through all the steps without waiting for the rest of the batch; results are
  * bit-identical to nsteps calls of altro_mpc_step_async.  Per-step statistics are accumulated
- * (altro_batch_get_solve_counters); altro_batch_get_stats reports the last step. */
+ * (altro_batch_get_solve_counters); altro_batch_get_stats reports the last step; altro_mpc_set_log keeps every step's. */
 int32_t altro_mpc_run_async(altro_handle* h, int32_t first_step, int32_t nsteps);
+/* Per-step log of the device-resident MPC loop.  The reference's loops record every step -- X_traj[i+1] = prob_mpc.x0,
+ * iters[i], status[i], costs[i] (simple_rocket.jl:137-205, rocket_landing_problem.jl:262-337, random_linear_problem.jl:166-174,
+ * grasp_mpc.jl:93-94) -- while a fused launch returns the state after its LAST step; with the log on, every step of
+ * altro_mpc_step_async / altro_mpc_run_async also writes one small record on the device, read back once after the run.
+ * capacity_steps > 0: allocate a log of that many steps (slot = absolute step index, 0-based; every slot empty) and start
+ * logging; 0: stop and free.  Default: off -- no result, counter or launch differs from a handle without a log, and results
+ * do not depend on the log being on.  Synchronises the stream.  With a log set, a run whose steps reach past capacity_steps
+ * is refused (ALTRO_ERR_INVALID_ARG, nothing enqueued).  Plain solves, altro_batch_benchmark_solve and
+ * altro_mpc_prepare_async write nothing.  A handle that moves to the one-wave-per-instance kernel afterwards
+ * (altro_batch_set_dynamics per_knot, altro_mpc_set_dynamics_track) keeps the setting.
+ * ALTRO_ERR_INVALID_ARG: NULL handle, negative capacity. */
+int32_t altro_mpc_set_log(altro_handle* h, int32_t capacity_steps);
+/* Records of steps first_step .. first_step+nsteps-1, step-major, indexed by the caller's instance index whatever order the
+ * launch ran them in; any output pointer may be NULL:
+ *   x0 [nsteps][batch][n]   the initial state the step's solve started from (after plant step + noise): X_traj[i+1] of
+ *                           simple_rocket.jl:164
+ *   u0 [nsteps][batch][m]   first control of the trajectory the handle holds at the end of the step, i.e. the control the
+ *                           NEXT plant step applies (the polished one when projected_newton = 1)
+ *   iterations, iterations_outer, status [nsteps][batch] int32;  cost, c_max [nsteps][batch] double:
+ *                           what altro_batch_get_stats would have returned after that step (projected_newton = 1: cost,
+ *                           c_max and status after the polish, as altro_batch_get_stats reports them)
+ * Running a step again overwrites its slot; a slot no step has written since altro_mpc_set_log reads iterations =
+ * iterations_outer = status = -1 and NaN in every double.  Synchronises the stream.
+ * ALTRO_ERR_STATE: no log is set; ALTRO_ERR_INVALID_ARG: NULL handle, range outside the capacity. */
+int32_t altro_mpc_get_log(altro_handle* h, int32_t first_step, int32_t nsteps, double* x0, double* u0,
+                          int32_t* iterations, int32_t* iterations_outer, int32_t* status, double* cost, double* c_max);
 /* x0 currently installed: [batch][n] */
 int32_t altro_batch_get_initial_state(altro_handle* h, double* x0);
 

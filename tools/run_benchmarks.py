@@ -1,5 +1,7 @@
 """Run the reference's benchmark scripts (batched) on the GPU and print one JSON summary per run.
-Usage: python tools/run_benchmarks.py [random_linear|sweeps|rocket|grasp|quadruped|all] [batch] [results.npz | outdir/]
+Usage: python tools/run_benchmarks.py [--launch-steps K] [random_linear|sweeps|rocket|grasp|quadruped|all] [batch] [results.npz | outdir/]
+--launch-steps K > 1: random_linear and rocket run K MPC steps per launch (altro_mpc_run_async) and take every step's
+iterations / status from the device log; "time" is then per launch (the other benchmarks rewrite data between steps).
 The optional .npz holds, per benchmark, the reference's result Dict entries (random_linear_problem.jl:188)
 as arrays: "<name>/time" (ms per MPC step for the batch) and "<name>/iter" (steps x instances).  With a
 directory instead, the three sweeps are written as horizon_comp.h5, state_dim_comp.h5, control_dim_comp.h5 in
@@ -11,12 +13,17 @@ sys.path.insert(0, R)
 import altro_amd_loader
 import altro_mpc_icra2021_amd as altro
 from altro_mpc_icra2021_amd import benchmarks as Bm
+K = 1
+if "--launch-steps" in sys.argv:
+    a = sys.argv.index("--launch-steps")
+    K = int(sys.argv[a + 1])
+    del sys.argv[a:a + 2]
 which = sys.argv[1] if len(sys.argv) > 1 else "all"
 B = int(sys.argv[2]) if len(sys.argv) > 2 else 256
 out = {}
 raw = {}
 if which in ("all", "random_linear"):
-    r = Bm.run_random_linear(batch=B); raw["random_linear n=12 m=4 N=50"] = r
+    r = Bm.run_random_linear(batch=B, launch_steps=K); raw["random_linear n=12 m=4 N=50"] = r
     out["random_linear n=12 m=4 N=50"] = Bm.summarise(r)
 sweeps = None
 if which in ("all", "sweeps"):
@@ -25,7 +32,7 @@ if which in ("all", "sweeps"):
         for k, r in pts.items():
             out["%s %s" % (name, k)] = Bm.summarise(r); raw["%s %s" % (name, k)] = r
 if which in ("all", "rocket"):
-    r = Bm.run_rocket(batch=B); raw["rocket N_mpc=21"] = r
+    r = Bm.run_rocket(batch=B, launch_steps=K); raw["rocket N_mpc=21"] = r
     out["rocket N_mpc=21"] = Bm.summarise(r)
 if which in ("all", "grasp"):
     r = Bm.run_grasp(batch=min(B, 64), N_cold=101, tf=10.0); raw["grasp N_mpc=21"] = r
