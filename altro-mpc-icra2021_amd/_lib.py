@@ -38,6 +38,10 @@ EXPORTS = [
     "altro_batch_get_confirm_counter", "altro_batch_get_reuse_counter", "altro_batch_get_polish_stats",
     "altro_debug_set", "altro_batch_get_polish_dual_residuals", "altro_batch_set_tracking_cost_per_instance",
     "altro_batch_set_bounds", "altro_mpc_set_log", "altro_mpc_get_log",
+    "altro_batch_set_initial_state_dev", "altro_batch_set_reference_dev", "altro_batch_set_initial_trajectory_dev",
+    "altro_batch_set_dynamics_dev", "altro_batch_get_states_dev", "altro_batch_get_controls_dev",
+    "altro_batch_get_initial_state_dev", "altro_batch_get_first_knot_dev", "altro_batch_wait_stream",
+    "altro_batch_signal_stream",
 ]
 """every symbol include/altro_batch.h declares"""
 
@@ -70,7 +74,7 @@ def build(force=False, verbose=False):
     """Generate the DPP block include and compile the HIP library for gfx950, in tree.  The library is several translation
     units (altro_batch.hip: the C-ABI, the 16-lane kernels, the polish; wide_inst.hip once per group of one-wave-per-instance
     kernels, solve_wide.h ALTRO_WIDE_KERNELS) compiled side by side -- one after the other they take ~6 minutes."""
-    srcs = [os.path.join(CSRC, f) for f in ("altro_batch.hip", "wide_inst.hip", "solve_dpp16.h", "solve_wide.h", "wide_backend.h", "launch_ring.h", "pn_polish.h", "pn_wide.h", "mpc_log.h", "gen_dpp_blocks.py")]
+    srcs = [os.path.join(CSRC, f) for f in ("altro_batch.hip", "wide_inst.hip", "solve_dpp16.h", "solve_wide.h", "wide_backend.h", "launch_ring.h", "pn_polish.h", "pn_wide.h", "mpc_log.h", "device_io.h", "gen_dpp_blocks.py")]
     srcs.append(os.path.join(os.path.dirname(_HERE), "include", "altro_batch.h"))
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):
         return LIB_PATH
@@ -130,6 +134,18 @@ def lib():
     if hasattr(L, "altro_mpc_set_log"):
         L.altro_mpc_set_log.argtypes = [H, C.c_int32]
         L.altro_mpc_get_log.argtypes = [H, C.c_int32, C.c_int32, dp, dp, ip, ip, ip, dp, dp]
+    if hasattr(L, "altro_batch_get_first_knot_dev"):   # device-pointer I/O: addresses of GPU memory, passed as void pointers
+        vp = C.c_void_p
+        L.altro_batch_set_initial_state_dev.argtypes = [H, vp]
+        L.altro_batch_set_reference_dev.argtypes = [H, vp, vp]
+        L.altro_batch_set_initial_trajectory_dev.argtypes = [H, vp, vp]
+        L.altro_batch_set_dynamics_dev.argtypes = [H, vp, vp, vp, C.c_int32, C.c_int32]
+        L.altro_batch_get_states_dev.argtypes = [H, vp]
+        L.altro_batch_get_controls_dev.argtypes = [H, vp]
+        L.altro_batch_get_initial_state_dev.argtypes = [H, vp]
+        L.altro_batch_get_first_knot_dev.argtypes = [H, vp, vp, vp, vp]
+        L.altro_batch_wait_stream.argtypes = [H, vp]
+        L.altro_batch_signal_stream.argtypes = [H, vp]
     L.altro_batch_add_constraint.argtypes = [H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                              dp, dp, dp, dp, C.c_int32, ip]
     L.altro_batch_update_constraint_data.argtypes = [H, C.c_int32, dp, dp]
@@ -176,6 +192,41 @@ def lib():
             getattr(L, name).restype = C.c_int32
     _lib = L
     return L
+
+
+def hip_runtimes():
+    """Paths of the HIP runtime libraries (libamdhip64) mapped into this process, from /proc/self/maps."""
+    out = set()
+    try:
+        with open("/proc/self/maps") as f:
+            for line in f:
+                if "libamdhip64" in line:
+                    out.add(line.split(None, 5)[-1].strip())
+    except OSError:
+        pass
+    return sorted(out)
+
+
+_one_runtime = None
+
+
+def check_single_runtime():
+    """The tensor path hands addresses of torch's GPU memory to libaltro_hip.so, which means something only if both talk to
+    the SAME HIP runtime.  torch ships a libamdhip64 of its own with the soname of the system's: imported first, the dynamic
+    loader resolves this library's dependency to torch's copy and the process has one runtime; loaded the other way round
+    it maps both, and a torch pointer is unknown to the second.  Imports torch, loads the library, and raises AltroError
+    when more than one libamdhip64 is mapped."""
+    global _one_runtime
+    if _one_runtime:
+        return
+    import torch  # noqa: F401  (before lib(): see above)
+    lib()
+    rts = hip_runtimes()
+    if len(rts) > 1:
+        raise AltroError(ERR_STATE, "two HIP runtimes are mapped into this process (" + ", ".join(rts) + "): GPU tensors cannot be "
+                         "passed to libaltro_hip.so.  Import torch BEFORE the first use of this package (the library then "
+                         "binds to torch's libamdhip64), or pass numpy arrays.")
+    _one_runtime = True
 
 
 # Environment variables of the tests and measuring tools -> altro_debug_set keys.  The LIBRARY reads no environment; this

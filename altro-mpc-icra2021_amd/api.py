@@ -18,8 +18,18 @@ Julia name (reference call site)                      -> here
 
 Arrays are numpy, instance-major: X (B, N, n), U (B, N-1, m), A (B, n, n) in natural
 (row, col) indexing; conversion to the C-ABI's column-major blocks happens here.
+
+Device-resident I/O: set_initial_state, update_trajectory, initial_controls and set_dynamics also take torch tensors that
+live on the solver's GPU (the altro_*_dev entry points: nothing crosses PCIe, nothing synchronises), and states, controls
+and first_knot write into such tensors.  A GPU tensor is never copied, cast or moved behind the caller's back: float64,
+contiguous, on the solver's device and of the exact shape, or ValueError.  Matrices keep their natural (row, col) indexing;
+since the C-ABI reads column-major blocks, a dynamics tensor must be STORED column-major, i.e. `At.transpose(-1, -2)` of a
+contiguous tensor At that holds the transposed blocks.  Every tensor call is ordered against torch's current stream
+(wait_stream before, signal_stream after), so a caller that stays on one torch stream needs no synchronisation.  This
+module imports without torch.
 """
 import ctypes as C
+import sys
 from dataclasses import dataclass, field
 from typing import List, Optional
 
@@ -38,6 +48,89 @@ def _c(a):
 
 def _p(a):
     return None if a is None else a.ctypes.data_as(_DP)
+
+
+def _is_tensor(a):
+    """a torch tensor?  (without importing torch: if it was never imported there are no tensors)"""
+    torch = sys.modules.get("torch")
+    return torch is not None and isinstance(a, torch.Tensor)
+
+
+def _on_gpu(a):
+    """a torch tensor in GPU memory: takes the device path.  Everything else (numpy, lists, CPU tensors) goes through
+    np.asarray as before."""
+    return _is_tensor(a) and a.device.type != "cpu"
+
+
+def _dense_strides(shape, colmajor=False):
+    """element strides of a dense array of `shape`; colmajor: the last two dimensions stored transposed (column-major blocks)"""
+    shape = list(shape)
+    if colmajor:
+        shape[-1], shape[-2] = shape[-2], shape[-1]
+    st, acc = [], 1
+    for k in reversed(shape):
+        st.append(acc)
+        acc *= int(k)
+    st.reverse()
+    if colmajor:
+        st[-1], st[-2] = st[-2], st[-1]
+    return tuple(st)
+
+
+def check_device_tensor(t, shape, device, name="tensor", dtype="torch.float64", colmajor=False):
+    """The whole validation of a GPU tensor before its address is handed to the library -- a plain function of t.shape,
+    t.dtype, t.stride() and t.device, so any object with those four works.  Raises ValueError; never copies, casts or moves."""
+    shape = tuple(int(k) for k in shape)
+    if t.device.type != "cuda" or (t.device.index if t.device.index is not None else 0) != int(device):
+        raise ValueError(f"{name}: tensor on {t.device}, the solver runs on cuda:{int(device)}")
+    if str(t.dtype) != dtype:
+        raise ValueError(f"{name}: dtype {t.dtype}, expected {dtype} (no implicit cast)")
+    if tuple(t.shape) != shape:
+        raise ValueError(f"{name}: shape {tuple(t.shape)}, expected {shape}")
+    want = _dense_strides(shape, colmajor)
+    if any(k > 1 and int(a) != b for k, a, b in zip(shape, t.stride(), want)):
+        how = "stored column-major (the transpose(-1, -2) of a contiguous tensor)" if colmajor else "contiguous"
+        raise ValueError(f"{name}: strides {tuple(t.stride())}, expected {want}: the tensor must be {how} (no implicit copy)")
+    return t
+
+
+def _stream_handle(stream, device):
+    """hipStream_t of a torch stream (default: torch's current stream on `device`), as an integer address"""
+    if stream is None:
+        import torch
+        stream = torch.cuda.current_stream(device)
+    return C.c_void_p(int(getattr(stream, "cuda_stream", stream)) or None)
+
+
+def wait_stream(solver, stream=None):
+    """Work enqueued on the solver's stream from now on starts after everything enqueued so far on `stream` (a torch stream;
+    default torch's current one).  No host synchronisation (altro_batch_wait_stream)."""
+    solver._chk(solver._L.altro_batch_wait_stream(solver.h, _stream_handle(stream, solver.device)))
+
+
+def signal_stream(solver, stream=None):
+    """Work enqueued on `stream` from now on starts after everything enqueued so far on the solver's stream
+    (altro_batch_signal_stream)."""
+    solver._chk(solver._L.altro_batch_signal_stream(solver.h, _stream_handle(stream, solver.device)))
+
+
+class _bracket:
+    """wait_stream ... signal_stream against torch's current stream around the tensor calls inside"""
+
+    def __init__(self, solver):
+        self.solver = solver
+
+    def __enter__(self):
+        _lib.check_single_runtime()
+        wait_stream(self.solver)
+
+    def __exit__(self, *exc):
+        signal_stream(self.solver)
+        return False
+
+
+def _addr(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 def SolverOptions(**kw):
@@ -195,6 +288,7 @@ class ALTROSolver:
         B, n = prob.x0.shape
         m = np.asarray(prob.obj.R).shape[-1]
         self.B, self.n, self.m, self.N = B, n, m, prob.N
+        self.device = int(device)
         self.opts = opts if opts is not None else SolverOptions()
         dims = _lib.Dims(B, n, m, prob.N)
         h = C.c_void_p()
@@ -258,7 +352,11 @@ class ALTROSolver:
 
 def set_dynamics(solver, mdl):
     """Install (or replace) the dynamics: the quadruped controller rewrites model.A[k], B[k], d[k]
-    before every solve (altro_solver.jl:5-37)."""
+    before every solve (altro_solver.jl:5-37).  With GPU tensors (all of A, B and d, stored column-major: see the module
+    docstring) the tables are read on the device."""
+    if any(_on_gpu(a) for a in (mdl.A, mdl.B, mdl.d)):
+        with _bracket(solver):
+            return _set_dynamics_dev(solver, mdl)
     A = np.asarray(mdl.A, dtype=np.float64)
     Bm = np.asarray(mdl.B, dtype=np.float64)
     per_instance = A.ndim == (4 if mdl.per_knot else 3)
@@ -266,6 +364,23 @@ def set_dynamics(solver, mdl):
     Bc = _c(np.swapaxes(Bm, -1, -2))
     dc = _c(mdl.d) if mdl.d is not None else None
     solver._chk(solver._L.altro_batch_set_dynamics(solver.h, _p(Ac), _p(Bc), _p(dc), int(mdl.per_knot), int(per_instance)))
+
+
+def _set_dynamics_dev(solver, mdl):
+    A, Bm, d = mdl.A, mdl.B, mdl.d
+    if not (_on_gpu(A) and _on_gpu(Bm) and (d is None or _on_gpu(d))):
+        raise ValueError("set_dynamics: A, B and d must all be GPU tensors, or none of them")
+    n, m = solver.n, solver.m
+    lead_ndim = A.ndim - 2
+    if lead_ndim != (1 if mdl.per_knot else 0) and lead_ndim != (2 if mdl.per_knot else 1):
+        raise ValueError(f"set_dynamics: A of shape {tuple(A.shape)}")
+    per_instance = lead_ndim == (2 if mdl.per_knot else 1)
+    lead = ((solver.B,) if per_instance else ()) + ((solver.N - 1,) if mdl.per_knot else ())
+    check_device_tensor(A, lead + (n, n), solver.device, "A", colmajor=True)
+    check_device_tensor(Bm, lead + (n, m), solver.device, "B", colmajor=True)
+    if d is not None:
+        check_device_tensor(d, lead + (n,), solver.device, "d")
+    solver._chk(solver._L.altro_batch_set_dynamics_dev(solver.h, _addr(A), _addr(Bm), _addr(d), int(mdl.per_knot), int(per_instance)))
 
 
 def set_dynamics_track(solver, A, B, d=None, step_stride=1):
@@ -306,19 +421,48 @@ def set_options(solver, **kw):
     solver._chk(solver._L.altro_batch_set_options(solver.h, C.byref(solver.opts)))
 
 
+def _set_initial_state_dev(solver, x0):
+    check_device_tensor(x0, (solver.B, solver.n), solver.device, "x0")
+    solver._chk(solver._L.altro_batch_set_initial_state_dev(solver.h, _addr(x0)))
+
+
+def _update_trajectory_dev(solver, Xref, Uref):
+    if not (_on_gpu(Xref) and _on_gpu(Uref)):
+        raise ValueError("update_trajectory: Xref and Uref must both be GPU tensors, or neither")
+    check_device_tensor(Xref, (solver.B, solver.N, solver.n), solver.device, "Xref")
+    check_device_tensor(Uref, (solver.B, solver.N - 1, solver.m), solver.device, "Uref")
+    solver._chk(solver._L.altro_batch_set_reference_dev(solver.h, _addr(Xref), _addr(Uref)))
+
+
+def _initial_trajectory_dev(solver, X, U):
+    if X is not None:
+        check_device_tensor(X, (solver.B, solver.N, solver.n), solver.device, "X")
+    check_device_tensor(U, (solver.B, solver.N - 1, solver.m), solver.device, "U")
+    solver._chk(solver._L.altro_batch_set_initial_trajectory_dev(solver.h, _addr(X), _addr(U)))
+
+
 def set_initial_state(solver, x0):
+    if _on_gpu(x0):
+        with _bracket(solver):
+            return _set_initial_state_dev(solver, x0)
     x0 = _c(x0)
     assert x0.shape == (solver.B, solver.n)
     solver._chk(solver._L.altro_batch_set_initial_state(solver.h, _p(x0)))
 
 
 def update_trajectory(solver, Xref, Uref):
+    if _on_gpu(Xref) or _on_gpu(Uref):
+        with _bracket(solver):
+            return _update_trajectory_dev(solver, Xref, Uref)
     Xr, Ur = _c(Xref), _c(Uref)
     assert Xr.shape == (solver.B, solver.N, solver.n) and Ur.shape == (solver.B, solver.N - 1, solver.m)
     solver._chk(solver._L.altro_batch_set_reference(solver.h, _p(Xr), _p(Ur)))
 
 
 def initial_controls(solver, U):
+    if _on_gpu(U):
+        with _bracket(solver):
+            return _initial_trajectory_dev(solver, None, U)
     U = _c(U)
     assert U.shape == (solver.B, solver.N - 1, solver.m)
     solver._chk(solver._L.altro_batch_set_initial_trajectory(solver.h, None, _p(U)))
@@ -331,6 +475,17 @@ def shift_fill(solver, primal=True, dual=True):
 def solve(solver):
     solver._chk(solver._L.altro_batch_solve(solver.h))
     return solver
+
+
+def solve_async(solver):
+    """solve!(solver), only enqueued on the solver's stream (altro_batch_solve_async); pair with synchronize, or with
+    signal_stream / the tensor getters, which are ordered after it."""
+    solver._chk(solver._L.altro_batch_solve_async(solver.h))
+    return solver
+
+
+def synchronize(solver):
+    solver._chk(solver._L.altro_batch_synchronize(solver.h))
 
 
 def benchmark_solve(solver, samples=10, evals=10):
@@ -347,16 +502,71 @@ def benchmark_solve(solver, samples=10, evals=10):
     return ms
 
 
-def states(solver):
+def states(solver, out=None):
+    """states(solver): (B, N, n) numpy; out = a GPU tensor of that shape: written on the device and returned."""
+    if out is not None:
+        if not _on_gpu(out):
+            raise ValueError("states: out must be a GPU tensor")
+        with _bracket(solver):
+            check_device_tensor(out, (solver.B, solver.N, solver.n), solver.device, "out")
+            solver._chk(solver._L.altro_batch_get_states_dev(solver.h, _addr(out)))
+        return out
     X = np.empty((solver.B, solver.N, solver.n))
     solver._chk(solver._L.altro_batch_get_states(solver.h, _p(X)))
     return X
 
 
-def controls(solver):
+def controls(solver, out=None):
+    """controls(solver): (B, N-1, m) numpy; out = a GPU tensor of that shape: written on the device and returned."""
+    if out is not None:
+        if not _on_gpu(out):
+            raise ValueError("controls: out must be a GPU tensor")
+        with _bracket(solver):
+            check_device_tensor(out, (solver.B, solver.N - 1, solver.m), solver.device, "out")
+            solver._chk(solver._L.altro_batch_get_controls_dev(solver.h, _addr(out)))
+        return out
     U = np.empty((solver.B, solver.N - 1, solver.m))
     solver._chk(solver._L.altro_batch_get_controls(solver.h, _p(U)))
     return U
+
+
+def initial_state(solver, out=None):
+    """x0 currently installed: (B, n) numpy; out = a GPU tensor of that shape: written on the device and returned."""
+    if out is not None:
+        if not _on_gpu(out):
+            raise ValueError("initial_state: out must be a GPU tensor")
+        with _bracket(solver):
+            check_device_tensor(out, (solver.B, solver.n), solver.device, "out")
+            solver._chk(solver._L.altro_batch_get_initial_state_dev(solver.h, _addr(out)))
+        return out
+    x = np.empty((solver.B, solver.n))
+    solver._chk(solver._L.altro_batch_get_initial_state(solver.h, _p(x)))
+    return x
+
+
+def _first_knot_dev(solver, out=None):
+    import torch
+    if out is None:
+        dev = torch.device("cuda", solver.device)
+        out = (torch.empty((solver.B, solver.m), dtype=torch.float64, device=dev),
+               torch.empty((solver.B, solver.n), dtype=torch.float64, device=dev),
+               torch.empty((solver.B,), dtype=torch.int32, device=dev), torch.empty((solver.B,), dtype=torch.int32, device=dev))
+    u0, x1, st, it = out
+    for t, shape, dt, nm in ((u0, (solver.B, solver.m), "torch.float64", "u0"), (x1, (solver.B, solver.n), "torch.float64", "x1"),
+                             (st, (solver.B,), "torch.int32", "status"), (it, (solver.B,), "torch.int32", "iterations")):
+        if t is not None:
+            check_device_tensor(t, shape, solver.device, nm, dtype=dt)
+    solver._chk(solver._L.altro_batch_get_first_knot_dev(solver.h, _addr(u0), _addr(x1), _addr(st), _addr(it)))
+    return u0, x1, st, it
+
+
+def first_knot(solver, out=None):
+    """What an MPC consumer reads each tick, as GPU tensors and without a host synchronisation: (u0 (B, m) the control to
+    apply, x1 (B, n) the predicted next state, status (B,) int32, iterations (B,) int32) of the trajectory the solver holds
+    once its stream reaches this point (altro_batch_get_first_knot_dev).  out: a tuple of four tensors to write into, any of
+    them None to skip it; default: new tensors."""
+    with _bracket(solver):
+        return _first_knot_dev(solver, out)
 
 
 def get_duals(solver, con=0):

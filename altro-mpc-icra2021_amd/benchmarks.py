@@ -158,10 +158,55 @@ def run_grasp(batch=256, N_mpc=21, steps=30, N_cold=251, tf=25.0, seed=1):
     return res
 
 
-def run_quadruped(batch=256, N=15, steps=30, linearized_friction=True, seed=7):
+def _run_quadruped_device(qp, phases, batch, steps, x0, rng):
+    """The loop of run_quadruped with every per-tick array in GPU memory (mpc.ExternalMPC): the linearisation tables of the
+    16 gait phases for every tick are uploaded once and indexed on the device, the plant is torch arithmetic on the
+    predicted state, the noise is the host generator's, uploaded once.  Same numbers as the host loop, bit for bit."""
+    import torch
+    dev = torch.device("cuda", 0)
+    tabs = [[qp.dynamics(ph + i * qp.dt) for ph in phases] for i in range(steps + 1)]      # [tick][phase] -> (A, B, d)
+    # column-major blocks, as the C-ABI reads them: the tensors hold the transposed matrices
+    At = torch.from_numpy(np.ascontiguousarray(np.swapaxes(np.array([[t[0] for t in row] for row in tabs]), -1, -2))).to(dev)
+    Bt = torch.from_numpy(np.ascontiguousarray(np.swapaxes(np.array([[t[1] for t in row] for row in tabs]), -1, -2))).to(dev)
+    dt_ = torch.from_numpy(np.ascontiguousarray(np.array([[t[2] for t in row] for row in tabs]))).to(dev)
+    idx = torch.arange(batch, device=dev) % 16
+    noise = torch.from_numpy(np.stack([rng.standard_normal((batch, 12)) for _ in range(steps)])).to(dev)
+    dyn = lambda i: api.LinearModel(At[i].index_select(0, idx).transpose(-1, -2), Bt[i].index_select(0, idx).transpose(-1, -2),
+                                    dt_[i].index_select(0, idx), dt=qp.dt, per_knot=True)
+    A0 = dyn(0)
+    host = lambda t: t.cpu().numpy()
+    sv = api.ALTROSolver(mpc.quadruped_problem(qp, x0, host(A0.A), host(A0.B), host(A0.d)), api.SolverOptions(**problems.QUADRUPED_OPTS))
+    api.solve(sv)
+    loop = mpc.ExternalMPC(sv)
+    _, x1, _, _ = api.first_knot(sv)
+    its, sts, evs = [], [], []
+    for i in range(1, steps + 1):
+        xn = x1 + noise[i - 1] * 1e-3
+        _, x1, st, it = loop.tick(xn, dynamics=dyn(i))
+        its.append(it); sts.append(st)
+    torch.cuda.synchronize(dev)
+    it = torch.stack(its).cpu().numpy()
+    ok = torch.stack(sts).cpu().numpy() == api.SOLVE_SUCCEEDED
+    res = _result(np.full(steps, np.nan), it, ok, batch)   # (no per-tick device times: nothing waits for a tick here)
+    res["solver"] = sv
+    return res
+
+
+def run_quadruped(batch=256, N=15, steps=30, linearized_friction=True, seed=7, device_io=False, keep_solver=False):
     """foot_forces! (altro_solver.jl:40-88) in a loop: re-linearise the per-knot dynamics for the
     advancing trot schedule, set x0, shift primal and dual, solve.  The plant here is the linear
-    model's own first knot plus 1e-3 noise (the reference steps MuJoCo)."""
+    model's own first knot plus 1e-3 noise (the reference steps MuJoCo).
+    device_io=True: the same loop with every per-tick array in GPU memory (torch tensors; no PCIe copy, no host
+    synchronisation inside the loop; `time` is then NaN).  keep_solver=True: the result carries the solver ("solver")."""
+    if device_io:
+        qp = problems.gen_quadruped_problem(N=N, linearized_friction=linearized_friction)
+        rng = np.random.default_rng(seed)
+        phases = rng.uniform(0.0, 0.8, 16)
+        x0 = qp.x_des + rng.standard_normal((batch, 12)) * np.array([.02, .02, .02, .05, .05, .05, .3, .3, .1, .3, .3, .3])
+        res = _run_quadruped_device(qp, phases, batch, steps, x0, rng)
+        if not keep_solver:
+            res.pop("solver").close()
+        return res
     qp = problems.gen_quadruped_problem(N=N, linearized_friction=linearized_friction)
     rng = np.random.default_rng(seed)
     phases = rng.uniform(0.0, 0.8, 16)
@@ -182,7 +227,10 @@ def run_quadruped(batch=256, N=15, steps=30, linearized_friction=True, seed=7):
         api.solve(sv)
         st = api.stats(sv)
         t.append(st.tsolve_ms); it.append(st.iterations.copy()); ok.append(st.status == api.SOLVE_SUCCEEDED)
-    return _result(t, it, ok, batch)
+    res = _result(t, it, ok, batch)
+    if keep_solver:
+        res["solver"] = sv
+    return res
 
 
 def summarise(res):

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/altro_batch.h"
+#include "device_io.h"
 #include "launch_ring.h"
 #include "pn_polish.h"
 #include "solve_dpp16.h"
@@ -100,6 +101,8 @@ struct altro_handle {
   int *iters = nullptr, *iters_outer = nullptr, *status = nullptr;
   double *cost = nullptr, *cmax = nullptr, *Jtrace = nullptr, *ctrace = nullptr, *atrace = nullptr;
   double* stage = nullptr;  // device staging buffer for host<->device layout conversion
+  altro::StreamLink link;   // events of altro_batch_wait_stream / altro_batch_signal_stream (device_io.h)
+  int dev_via_stage = 0;    // "dev_via_stage": the _dev setters of x0 and the reference copy into `stage` first (measurement only)
   size_t stage_bytes = 0;
   int Nt = 0;    // knots held by Zref
   int kref = 0;  // current reference window start
@@ -651,6 +654,11 @@ int32_t altro_debug_set(altro_handle* h, const char* key, int32_t value) {
       return bad(ALTRO_ERR_UNSUPPORTED, "keep_gains exists in -DALTRO_DEBUG builds of the library only");
 #endif
     }
+    if (k == "dev_via_stage") {   // handle switch (16-lane backend): measurement of DESIGN.md 7c
+      if (!h) return bad(ALTRO_ERR_STATE, "dev_via_stage is a switch of a handle");
+      h->dev_via_stage = value != 0;
+      return ALTRO_OK;
+    }
     // create-time switches: which backend, and the LDS carve-up of the one-wave-per-instance backend
     int* pre = k == "force_wide" ? &g_dbg.force_wide : k == "wide_compact" ? &g_dbg.wide_compact : k == "wide_coop" ? &g_dbg.wide_coop
              : k == "wide_static_mask" ? &g_dbg.wide_static_mask : nullptr;
@@ -965,11 +973,13 @@ int32_t altro_batch_destroy(altro_handle* h) {
   if (!h) return ALTRO_OK;
   if (h->wide) {
     h->wide->destroy();
+    h->link.destroy();
     delete h->wide;
     delete h;
     return ALTRO_OK;
   }
   free_dpp_backend(h);
+  h->link.destroy();
   delete h;
   return ALTRO_OK;
 }
@@ -1023,6 +1033,33 @@ static int migrate_to_wide(altro_handle* h) {
   return ALTRO_OK;
 }
 
+// time-invariant dynamics of a 16-lane handle.  dev: A, B, f are device arrays (validated by the caller): the layout kernel
+// reads them where they are, nothing is staged and the stream is not synchronised
+static int set_dynamics_16(altro_handle* h, const double* A, const double* B, const double* f, int32_t per_instance, bool dev) {
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t n = h->d.n, m = h->d.m;
+  const size_t nb = per_instance ? h->d.batch : 1;
+  if (!dev) {
+    const size_t tot = nb * (n * n + n * m + n);
+    int rc = ensure_stage(h, tot * sizeof(double));
+    if (rc) return rc;
+    if ((rc = upload(h, A, nb * n * n, 0))) return rc;
+    if ((rc = upload(h, B, nb * n * m, nb * n * n))) return rc;
+    if (f && (rc = upload(h, f, nb * n, nb * (n * n + n * m)))) return rc;
+    A = h->stage;
+    B = h->stage + nb * n * n;
+    if (f) f = h->stage + nb * (n * n + n * m);
+  }
+  hipLaunchKernelGGL(k_pack_dyn, grid_for((size_t)h->Bp * LW), dim3(256), 0, h->stream, A, B, f, h->Gcol, h->Grow, h->fvec,
+                     h->d.batch, h->Bp, (int)n, (int)m, per_instance ? 1 : 0);
+  HIPCHK(h, hipGetLastError());
+  if (int rcd = drop_gains(h)) return rcd;
+  if (!dev) HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->have_dyn = true;
+  h->dyn_per_instance = per_instance != 0;
+  return ALTRO_OK;
+}
+
 int32_t altro_batch_set_dynamics(altro_handle* h, const double* A, const double* B, const double* f,
                                  int32_t per_knot, int32_t per_instance) {
   return guard(h, [&]() -> int32_t {
@@ -1035,24 +1072,7 @@ int32_t altro_batch_set_dynamics(altro_handle* h, const double* A, const double*
       if (rc2) h->err = h->wide->err;
       return rc2;
     }
-    HIPCHK(h, hipSetDevice(h->device));
-    const size_t n = h->d.n, m = h->d.m;
-    const size_t nb = per_instance ? h->d.batch : 1;
-    const size_t tot = nb * (n * n + n * m + n);
-    int rc = ensure_stage(h, tot * sizeof(double));
-    if (rc) return rc;
-    if ((rc = upload(h, A, nb * n * n, 0))) return rc;
-    if ((rc = upload(h, B, nb * n * m, nb * n * n))) return rc;
-    if (f && (rc = upload(h, f, nb * n, nb * (n * n + n * m)))) return rc;
-    hipLaunchKernelGGL(k_pack_dyn, grid_for((size_t)h->Bp * LW), dim3(256), 0, h->stream, h->stage,
-                       h->stage + nb * n * n, f ? h->stage + nb * (n * n + n * m) : nullptr, h->Gcol, h->Grow, h->fvec,
-                       h->d.batch, h->Bp, (int)n, (int)m, per_instance ? 1 : 0);
-    HIPCHK(h, hipGetLastError());
-    if (int rcd = drop_gains(h)) return rcd;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->have_dyn = true;
-    h->dyn_per_instance = per_instance != 0;
-    return ALTRO_OK;
+    return set_dynamics_16(h, A, B, f, per_instance, false);
   });
 }
 
@@ -1324,45 +1344,68 @@ int32_t altro_batch_set_bounds(altro_handle* h, int32_t con_id, const double* zm
   });
 }
 
+// Copy of a caller's device array into `stage` ("dev_via_stage": the alternative to packing from the caller's pointer that
+// DESIGN.md 7c measures).  The staging buffer grows only when a larger array than ever before arrives.
+static int stage_d2d(altro_handle* h, const double* src, size_t count, size_t stage_off_elems = 0) {
+  HIPCHK(h, hipMemcpyAsync(h->stage + stage_off_elems, src, count * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  return ALTRO_OK;
+}
+
+// dev: x0 is a device array (validated by the caller); only enqueues
+static int set_x0_16(altro_handle* h, const double* x0, bool dev) {
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t cnt = (size_t)h->d.batch * h->d.n;
+  if (!dev || h->dev_via_stage) {
+    int rc = ensure_stage(h, cnt * sizeof(double));
+    if (rc) return rc;
+    if ((rc = dev ? stage_d2d(h, x0, cnt) : upload(h, x0, cnt))) return rc;
+    x0 = h->stage;
+  }
+  hipLaunchKernelGGL(k_pack_x0, grid_for((size_t)h->Bp * LW), dim3(256), 0, h->stream, x0, h->x0, h->d.batch,
+                     h->Bp, h->d.n);
+  HIPCHK(h, hipGetLastError());
+  if (!dev) HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->have_x0 = true;
+  return ALTRO_OK;
+}
+
 int32_t altro_batch_set_initial_state(altro_handle* h, const double* x0) {
   return guard(h, [&]() -> int32_t {
     WIDE_FWD(h, set_initial_state(x0));
     if (!h || !x0) return ALTRO_ERR_INVALID_ARG;
-    HIPCHK(h, hipSetDevice(h->device));
-    const size_t cnt = (size_t)h->d.batch * h->d.n;
+    return set_x0_16(h, x0, false);
+  });
+}
+
+static int get_x0_16(altro_handle* h, double* x0, bool dev) {
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t cnt = (size_t)h->d.batch * h->d.n;
+  if (!dev) {
     int rc = ensure_stage(h, cnt * sizeof(double));
     if (rc) return rc;
-    if ((rc = upload(h, x0, cnt))) return rc;
-    hipLaunchKernelGGL(k_pack_x0, grid_for((size_t)h->Bp * LW), dim3(256), 0, h->stream, h->stage, h->x0, h->d.batch,
-                       h->Bp, h->d.n);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->have_x0 = true;
-    return ALTRO_OK;
-  });
+  }
+  hipLaunchKernelGGL(k_unpack_x0, grid_for((size_t)h->d.batch * LW), dim3(256), 0, h->stream, dev ? x0 : h->stage, h->x0,
+                     h->d.batch, h->d.n);
+  HIPCHK(h, hipGetLastError());
+  if (dev) return ALTRO_OK;
+  HIPCHK(h, hipMemcpyAsync(x0, h->stage, cnt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return ALTRO_OK;
 }
 
 int32_t altro_batch_get_initial_state(altro_handle* h, double* x0) {
   return guard(h, [&]() -> int32_t {
     WIDE_FWD(h, get_initial_state(x0));
     if (!h || !x0) return ALTRO_ERR_INVALID_ARG;
-    HIPCHK(h, hipSetDevice(h->device));
-    const size_t cnt = (size_t)h->d.batch * h->d.n;
-    int rc = ensure_stage(h, cnt * sizeof(double));
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_unpack_x0, grid_for((size_t)h->d.batch * LW), dim3(256), 0, h->stream, h->stage, h->x0,
-                       h->d.batch, h->d.n);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(x0, h->stage, cnt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return ALTRO_OK;
+    return get_x0_16(h, x0, false);
   });
 }
 
-static int set_ref_common(altro_handle* h, const double* Xref, const double* Uref, int Nt) {
+static int set_ref_common(altro_handle* h, const double* Xref, const double* Uref, int Nt, bool dev = false) {
   const size_t B = h->d.batch, n = h->d.n, m = h->d.m;
   const size_t cx = B * Nt * n, cu = B * (Nt - 1) * m;
-  int rc = ensure_stage(h, (cx + cu) * sizeof(double));
+  const bool staged = !dev || h->dev_via_stage;
+  int rc = staged ? ensure_stage(h, (cx + cu) * sizeof(double)) : ALTRO_OK;
   if (rc) return rc;
   if ((size_t)Nt * h->Bp * LW * sizeof(double) >= (1ull << 32)) FAIL(h, ALTRO_ERR_UNSUPPORTED, "reference trajectory too large for one handle (below 4 GiB)");
   if (h->Nt != Nt) {
@@ -1371,12 +1414,16 @@ static int set_ref_common(altro_handle* h, const double* Xref, const double* Ure
     HIPCHK(h, hipMalloc(&h->Zref, (size_t)Nt * h->Bp * LW * sizeof(double)));
     h->Nt = Nt;
   }
-  if ((rc = upload(h, Xref, cx, 0))) return rc;
-  if ((rc = upload(h, Uref, cu, cx))) return rc;
-  hipLaunchKernelGGL(k_pack_ref, grid_for((size_t)h->Bp * LW), dim3(256), 0, h->stream, h->stage, h->stage + cx,
+  if (staged) {
+    if ((rc = dev ? stage_d2d(h, Xref, cx, 0) : upload(h, Xref, cx, 0))) return rc;
+    if ((rc = dev ? stage_d2d(h, Uref, cu, cx) : upload(h, Uref, cu, cx))) return rc;
+    Xref = h->stage;
+    Uref = h->stage + cx;
+  }
+  hipLaunchKernelGGL(k_pack_ref, grid_for((size_t)h->Bp * LW), dim3(256), 0, h->stream, Xref, Uref,
                      h->Zref, h->d.batch, h->Bp, Nt, (int)n, (int)m);
   HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (!dev) HIPCHK(h, hipStreamSynchronize(h->stream));
   h->kref = 0;
   h->have_ref = true;
   return ALTRO_OK;
@@ -1391,23 +1438,32 @@ int32_t altro_batch_set_reference(altro_handle* h, const double* Xref, const dou
   });
 }
 
-int32_t altro_batch_set_initial_trajectory(altro_handle* h, const double* X, const double* U) {
-  return guard(h, [&]() -> int32_t {
-    WIDE_FWD(h, set_initial_trajectory(X, U));
-    if (!h || !U) return ALTRO_ERR_INVALID_ARG;
-    HIPCHK(h, hipSetDevice(h->device));
-    const size_t B = h->d.batch, N = h->d.N, n = h->d.n, m = h->d.m;
-    const size_t cx = X ? B * N * n : 0, cu = B * (N - 1) * m;
+static int set_traj_16(altro_handle* h, const double* X, const double* U, bool dev) {
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t B = h->d.batch, N = h->d.N, n = h->d.n, m = h->d.m;
+  const size_t cx = X ? B * N * n : 0, cu = B * (N - 1) * m;
+  const int have_x = X ? 1 : 0;
+  if (!dev) {
     int rc = ensure_stage(h, (cx + cu) * sizeof(double));
     if (rc) return rc;
     if (X && (rc = upload(h, X, cx, 0))) return rc;
     if ((rc = upload(h, U, cu, cx))) return rc;
-    const size_t plane = N * (size_t)LW;   // offset of plane 1 inside an instance's block of Z
-    hipLaunchKernelGGL(k_pack_traj, grid_for((size_t)h->Bp * LW), dim3(256), 0, h->stream, h->stage, h->stage + cx, h->Z,
-                       h->cur, plane, (int)B, h->Bp, (int)N, (int)n, (int)m, 1, X ? 1 : 0);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return ALTRO_OK;
+    X = h->stage;
+    U = h->stage + cx;
+  }
+  const size_t plane = N * (size_t)LW;   // offset of plane 1 inside an instance's block of Z
+  hipLaunchKernelGGL(k_pack_traj, grid_for((size_t)h->Bp * LW), dim3(256), 0, h->stream, X, U, h->Z,
+                     h->cur, plane, (int)B, h->Bp, (int)N, (int)n, (int)m, 1, have_x);
+  HIPCHK(h, hipGetLastError());
+  if (!dev) HIPCHK(h, hipStreamSynchronize(h->stream));
+  return ALTRO_OK;
+}
+
+int32_t altro_batch_set_initial_trajectory(altro_handle* h, const double* X, const double* U) {
+  return guard(h, [&]() -> int32_t {
+    WIDE_FWD(h, set_initial_trajectory(X, U));
+    if (!h || !U) return ALTRO_ERR_INVALID_ARG;
+    return set_traj_16(h, X, U, false);
   });
 }
 
@@ -1555,13 +1611,19 @@ int32_t altro_batch_solve(altro_handle* h) {
   });
 }
 
-static int get_traj(altro_handle* h, double* X, double* U) {
+static int get_traj(altro_handle* h, double* X, double* U, bool dev = false) {
   HIPCHK(h, hipSetDevice(h->device));
   const size_t B = h->d.batch, N = h->d.N, n = h->d.n, m = h->d.m;
   const size_t cx = B * N * n, cu = B * (N - 1) * m;
+  const size_t plane = N * (size_t)LW;
+  if (dev) {  // the unpack kernel writes the caller's device arrays; only enqueued
+    hipLaunchKernelGGL(k_unpack_traj, grid_for(B * LW), dim3(256), 0, h->stream, X, U, h->Z, h->cur, plane, (int)B, h->Bp, (int)N,
+                       (int)n, (int)m);
+    HIPCHK(h, hipGetLastError());
+    return ALTRO_OK;
+  }
   int rc = ensure_stage(h, (cx + cu) * sizeof(double));
   if (rc) return rc;
-  const size_t plane = N * (size_t)LW;
   hipLaunchKernelGGL(k_unpack_traj, grid_for(B * LW), dim3(256), 0, h->stream, X ? h->stage : nullptr,
                      U ? h->stage + cx : nullptr, h->Z, h->cur, plane, (int)B, h->Bp, (int)N, (int)n, (int)m);
   HIPCHK(h, hipGetLastError());
@@ -2038,6 +2100,150 @@ int32_t altro_batch_benchmark_solve(altro_handle* h, int32_t samples, int32_t ev
     return ALTRO_OK;
   });
 }
+
+// ------------------------------------------------------------------ device-pointer I/O (include/altro_batch.h)
+// Every entry point validates ALL its pointers first (device_io.h: dev_extent_check) and refuses with ALTRO_ERR_INVALID_ARG
+// before anything is enqueued or changed; then it only enqueues on the handle's stream.
+static int32_t dev_null_handle(const char* fn) {
+  g_create_err = std::string(fn) + ": null handle";
+  return ALTRO_ERR_INVALID_ARG;
+}
+static int dev_arg(altro_handle* h, const char* fn, const char* what, const void* p, size_t bytes, bool optional = false) {
+  if (!p && optional) return ALTRO_OK;
+  if (const char* e = altro::dev_extent_check(p, bytes, h->device))
+    FAIL(h, ALTRO_ERR_INVALID_ARG, std::string(fn) + ": " + what + ": " + e);
+  return ALTRO_OK;
+}
+#define DEV_ENTER(h, fn)                      \
+  if (!(h)) return dev_null_handle(fn);       \
+  HIPCHK(h, hipSetDevice((h)->device));       \
+  const char* const fn_ = fn;                 \
+  const size_t B_ = (h)->d.batch, N_ = (h)->d.N, n_ = (h)->d.n, m_ = (h)->d.m; \
+  (void)B_; (void)N_; (void)n_; (void)m_
+#define DEV_ARG(h, what, p, count, type, optional)                                         \
+  do {                                                                                      \
+    if (int rc_ = dev_arg(h, fn_, what, p, (size_t)(count) * sizeof(type), optional)) return rc_; \
+  } while (0)
+// forward to the wide backend when the handle runs on it (after the validation)
+#define DEV_WIDE(h, call)                  \
+  do {                                     \
+    if ((h)->wide) {                       \
+      const int rc_ = (h)->wide->call;     \
+      if (rc_) (h)->err = (h)->wide->err;  \
+      return rc_;                          \
+    }                                      \
+  } while (0)
+
+int32_t altro_batch_set_initial_state_dev(altro_handle* h, const double* x0) {
+  return guard(h, [&]() -> int32_t {
+    DEV_ENTER(h, "altro_batch_set_initial_state_dev");
+    DEV_ARG(h, "x0", x0, B_ * n_, double, false);
+    DEV_WIDE(h, set_initial_state_dev(x0));
+    return set_x0_16(h, x0, true);
+  });
+}
+
+int32_t altro_batch_get_initial_state_dev(altro_handle* h, double* x0) {
+  return guard(h, [&]() -> int32_t {
+    DEV_ENTER(h, "altro_batch_get_initial_state_dev");
+    DEV_ARG(h, "x0", x0, B_ * n_, double, false);
+    DEV_WIDE(h, get_initial_state_dev(x0));
+    return get_x0_16(h, x0, true);
+  });
+}
+
+int32_t altro_batch_set_reference_dev(altro_handle* h, const double* Xref, const double* Uref) {
+  return guard(h, [&]() -> int32_t {
+    DEV_ENTER(h, "altro_batch_set_reference_dev");
+    DEV_ARG(h, "Xref", Xref, B_ * N_ * n_, double, false);
+    DEV_ARG(h, "Uref", Uref, B_ * (N_ - 1) * m_, double, false);
+    DEV_WIDE(h, set_reference_dev(Xref, Uref));
+    return set_ref_common(h, Xref, Uref, h->d.N, true);
+  });
+}
+
+int32_t altro_batch_set_initial_trajectory_dev(altro_handle* h, const double* X, const double* U) {
+  return guard(h, [&]() -> int32_t {
+    DEV_ENTER(h, "altro_batch_set_initial_trajectory_dev");
+    DEV_ARG(h, "X", X, B_ * N_ * n_, double, true);
+    DEV_ARG(h, "U", U, B_ * (N_ - 1) * m_, double, false);
+    DEV_WIDE(h, set_initial_trajectory_dev(X, U));
+    return set_traj_16(h, X, U, true);
+  });
+}
+
+int32_t altro_batch_set_dynamics_dev(altro_handle* h, const double* A, const double* B, const double* f, int32_t per_knot,
+                                     int32_t per_instance) {
+  return guard(h, [&]() -> int32_t {
+    DEV_ENTER(h, "altro_batch_set_dynamics_dev");
+    const size_t nb = (per_instance ? B_ : 1) * (per_knot ? N_ - 1 : 1);
+    DEV_ARG(h, "A", A, nb * n_ * n_, double, false);
+    DEV_ARG(h, "B", B, nb * n_ * m_, double, false);
+    DEV_ARG(h, "f", f, nb * n_, double, true);
+    DEV_WIDE(h, set_dynamics_dev(A, B, f, per_knot, per_instance));
+    if (per_knot) {  // the first call on an (n, m) of the 16-lane set: the handle moves to the one-wave-per-instance kernel
+      const int rc = migrate_to_wide(h);
+      if (rc) return rc;
+      const int rc2 = h->wide->set_dynamics_dev(A, B, f, per_knot, per_instance);
+      if (rc2) h->err = h->wide->err;
+      return rc2;
+    }
+    return set_dynamics_16(h, A, B, f, per_instance, true);
+  });
+}
+
+int32_t altro_batch_get_states_dev(altro_handle* h, double* X) {
+  return guard(h, [&]() -> int32_t {
+    DEV_ENTER(h, "altro_batch_get_states_dev");
+    DEV_ARG(h, "X", X, B_ * N_ * n_, double, false);
+    DEV_WIDE(h, get_planes_dev(X, nullptr));
+    return get_traj(h, X, nullptr, true);
+  });
+}
+
+int32_t altro_batch_get_controls_dev(altro_handle* h, double* U) {
+  return guard(h, [&]() -> int32_t {
+    DEV_ENTER(h, "altro_batch_get_controls_dev");
+    DEV_ARG(h, "U", U, B_ * (N_ - 1) * m_, double, false);
+    DEV_WIDE(h, get_planes_dev(nullptr, U));
+    return get_traj(h, nullptr, U, true);
+  });
+}
+
+int32_t altro_batch_get_first_knot_dev(altro_handle* h, double* u0, double* x1, int32_t* status, int32_t* iterations) {
+  return guard(h, [&]() -> int32_t {
+    DEV_ENTER(h, "altro_batch_get_first_knot_dev");
+    DEV_ARG(h, "u0", u0, B_ * m_, double, true);
+    DEV_ARG(h, "x1", x1, B_ * n_, double, true);
+    DEV_ARG(h, "status", status, B_, int32_t, true);
+    DEV_ARG(h, "iterations", iterations, B_, int32_t, true);
+    if (!u0 && !x1 && !status && !iterations) return ALTRO_OK;
+    DEV_WIDE(h, get_first_knot_dev(u0, x1, status, iterations));
+    hipLaunchKernelGGL(altro::k_first_knot, grid_for(B_ * LW), dim3(256), 0, h->stream, u0, x1, status, iterations, h->Z, h->cur,
+                       h->status, h->iters, N_ * (size_t)LW, (int)B_, (int)N_, (int)n_, (int)m_);
+    HIPCHK(h, hipGetLastError());
+    return ALTRO_OK;
+  });
+}
+
+int32_t altro_batch_wait_stream(altro_handle* h, void* producer) {
+  return guard(h, [&]() -> int32_t {
+    DEV_ENTER(h, "altro_batch_wait_stream");
+    HIPCHK(h, h->link.wait(h->wide ? h->wide->stream : h->stream, (hipStream_t)producer));
+    return ALTRO_OK;
+  });
+}
+
+int32_t altro_batch_signal_stream(altro_handle* h, void* consumer) {
+  return guard(h, [&]() -> int32_t {
+    DEV_ENTER(h, "altro_batch_signal_stream");
+    HIPCHK(h, h->link.signal(h->wide ? h->wide->stream : h->stream, (hipStream_t)consumer));
+    return ALTRO_OK;
+  });
+}
+#undef DEV_ENTER
+#undef DEV_ARG
+#undef DEV_WIDE
 
 int32_t altro_batch_get_stream(altro_handle* h, void** stream) {
   return guard(h, [&]() -> int32_t {

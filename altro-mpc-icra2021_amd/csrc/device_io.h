@@ -1,0 +1,104 @@
+// device_io.h -- what the device-pointer entry points (altro_*_dev, altro_batch_wait_stream / _signal_stream;
+// include/altro_batch.h) share between the two backends: the validation of a caller's device pointer, the pair of events a
+// handle orders its stream against a caller's stream with, and the read-out kernels of altro_batch_get_first_knot_dev.
+// Nothing here synchronises a stream or touches host memory.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+namespace altro {
+
+// A caller's pointer may reach a kernel only if the runtime knows it as device memory of the handle's device and the
+// allocation it lies in holds at least `bytes` from that address on.  Returns nullptr when it does, else the reason.
+// (hipPointerGetAttributes answers an error for plain host memory: an error is a refusal, and is cleared.)
+inline const char* dev_extent_check(const void* p, size_t bytes, int device) {
+  if (!p) return "null pointer";
+  hipPointerAttribute_t at{};
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return "not a pointer the HIP runtime knows (host memory?)";
+  }
+  if (at.type != hipMemoryTypeDevice) return "not device memory";
+  if (at.device != device) return "memory of another device than the handle's";
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
+    (void)hipGetLastError();
+    return "the extent of the allocation is unknown to the HIP runtime";
+  }
+  const uintptr_t a = (uintptr_t)p, b0 = (uintptr_t)base;
+  if (a < b0 || a - b0 > size || size - (a - b0) < bytes) return "the allocation is shorter than the array the call reads or writes";
+  return nullptr;
+}
+
+// Stream hand-over without the host: an event recorded on one stream and waited on by the other.  One event per direction,
+// created on first use, owned and reused by the handle (a recorded event may be recorded again: a wait already enqueued keeps
+// the state it captured).
+struct StreamLink {
+  hipEvent_t ev_in = nullptr, ev_out = nullptr;
+  hipError_t wait(hipStream_t self, hipStream_t producer) {
+    hipError_t e;
+    if (!ev_in && (e = hipEventCreateWithFlags(&ev_in, hipEventDisableTiming)) != hipSuccess) return e;
+    if ((e = hipEventRecord(ev_in, producer)) != hipSuccess) return e;
+    return hipStreamWaitEvent(self, ev_in, 0);
+  }
+  hipError_t signal(hipStream_t self, hipStream_t consumer) {
+    hipError_t e;
+    if (!ev_out && (e = hipEventCreateWithFlags(&ev_out, hipEventDisableTiming)) != hipSuccess) return e;
+    if ((e = hipEventRecord(ev_out, self)) != hipSuccess) return e;
+    return hipStreamWaitEvent(consumer, ev_out, 0);
+  }
+  void destroy() {
+    if (ev_in) hipEventDestroy(ev_in);
+    if (ev_out) hipEventDestroy(ev_out);
+    ev_in = ev_out = nullptr;
+  }
+};
+
+// altro_batch_get_first_knot_dev, 16-lane backend: Zp holds [Bp] blocks of (2N + 1) knots x 16 lanes, two planes of N knots;
+// lanes 0..n-1 of a knot are its state, n..n+m-1 its control.  One thread per (instance, lane) reads plane cur[inst]:
+// u0 <- control of knot 0, x1 <- state of knot 1; lane 0 also copies the instance's status and iteration count.
+__global__ void k_first_knot(double* __restrict__ u0, double* __restrict__ x1, int* __restrict__ status_out, int* __restrict__ iters_out,
+                             const double* __restrict__ Zp, const int* __restrict__ cur, const int* __restrict__ status,
+                             const int* __restrict__ iters, size_t plane, int B, int N, int n, int m) {
+  constexpr int LW_ = 16;
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= B * LW_) return;
+  const int inst = t / LW_, j = t % LW_;
+  const double* src = Zp + (size_t)inst * (2 * (size_t)N + 1) * LW_ + (size_t)cur[inst] * plane;
+  if (j < n) {
+    if (x1) x1[(size_t)inst * n + j] = src[LW_ + j];
+  } else if (j < n + m) {
+    if (u0) u0[(size_t)inst * m + (j - n)] = src[j];
+  }
+  if (j == 0) {
+    if (status_out) status_out[inst] = status[inst];
+    if (iters_out) iters_out[inst] = iters[inst];
+  }
+}
+
+// The same on the one-wave-per-instance backend: X [B][2][N][n], U [B][2][N-1][m].  One thread per (instance, element of
+// z = [x; u]).
+__global__ void k_first_knot_wide(double* __restrict__ u0, double* __restrict__ x1, int* __restrict__ status_out, int* __restrict__ iters_out,
+                                  const double* __restrict__ X, const double* __restrict__ U, const int* __restrict__ cur,
+                                  const int* __restrict__ status, const int* __restrict__ iters, int B, int N, int n, int m) {
+  const int nz = n + m;
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (size_t)B * nz) return;
+  const size_t inst = t / nz;
+  const int j = (int)(t - inst * nz);
+  const size_t pl = inst * 2 + cur[inst];
+  if (j < n) {
+    if (x1) x1[inst * n + j] = X[(pl * N + 1) * n + j];
+  } else {
+    if (u0) u0[inst * m + (j - n)] = U[pl * (size_t)(N - 1) * m + (j - n)];
+  }
+  if (j == 0) {
+    if (status_out) status_out[inst] = status[inst];
+    if (iters_out) iters_out[inst] = iters[inst];
+  }
+}
+
+}  // namespace altro

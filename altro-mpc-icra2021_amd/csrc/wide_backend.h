@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/altro_batch.h"
+#include "device_io.h"
 #include "launch_ring.h"
 #include "solve_wide.h"
 #include "pn_wide.h"
@@ -115,6 +116,7 @@ struct WideBackend {
   double* mlog = nullptr;  // per-step log of the MPC loop (mpc_log.h): [mlog_cap][B][n + m + MLOG_TAIL]; null: off
   int mlog_cap = 0;
   int dyn_blocks = 1, dyn_step_stride = 0;
+  size_t dyn_table_blocks = 0;   // blocks the tables A, Bm, f have room for (set_dynamics_dev reuses them while it is unchanged)
   bool ltv = false, dyn_per_instance = false, have_dyn = false, have_cost = false, have_ref = false;
   int box_k0 = 0, box_k1 = -1, box_id = -1;
   std::vector<bool> box_lo_fin, box_hi_fin;   // [n+m] finite sides of the BOX (host copy: polish_prepare, set_bounds)
@@ -227,8 +229,43 @@ struct WideBackend {
     WCHK(hipMemcpy(Bm, B_, blocks_ * n * m * sizeof(double), hipMemcpyHostToDevice));
     if (f_) WCHK(hipMemcpy(f, f_, blocks_ * n * sizeof(double), hipMemcpyHostToDevice));
     else WCHK(hipMemset(f, 0, blocks_ * n * sizeof(double)));
+    dyn_table_blocks = blocks_;
     dyn_per_instance = per_instance != 0;
     have_dyn = true;
+    return ALTRO_OK;
+  }
+  // The same from device arrays (already validated), stream-ordered: the tables are reused while the block count is that
+  // of the previous call; a call that changes it reallocates, and synchronises to do so, as the host call always does.
+  int upload_dynamics_dev(const double* A_, const double* B_, const double* f_, size_t blocks_per_instance, int per_instance) {
+    if (!A_ || !B_) return ALTRO_ERR_INVALID_ARG;
+    WCHK(hipSetDevice(device));
+    const size_t n = d.n, m = d.m;
+    const size_t blocks_ = (per_instance ? (size_t)d.batch : 1) * blocks_per_instance;
+    if (blocks_ != dyn_table_blocks || !A || !Bm || !f) {
+      WCHK(hipStreamSynchronize(stream));
+      for (double** p : {&A, &Bm, &f})
+        if (*p) { WCHK(hipFree(*p)); *p = nullptr; }
+      dyn_table_blocks = 0;
+      WCHK(hipMalloc(&A, blocks_ * n * n * sizeof(double)));
+      WCHK(hipMalloc(&Bm, blocks_ * n * m * sizeof(double)));
+      WCHK(hipMalloc(&f, blocks_ * n * sizeof(double)));
+      dyn_table_blocks = blocks_;
+    }
+    WCHK(hipMemcpyAsync(A, A_, blocks_ * n * n * sizeof(double), hipMemcpyDeviceToDevice, stream));
+    WCHK(hipMemcpyAsync(Bm, B_, blocks_ * n * m * sizeof(double), hipMemcpyDeviceToDevice, stream));
+    if (f_) WCHK(hipMemcpyAsync(f, f_, blocks_ * n * sizeof(double), hipMemcpyDeviceToDevice, stream));
+    else WCHK(hipMemsetAsync(f, 0, blocks_ * n * sizeof(double), stream));
+    dyn_per_instance = per_instance != 0;
+    have_dyn = true;
+    return ALTRO_OK;
+  }
+  int set_dynamics_dev(const double* A_, const double* B_, const double* f_, int per_knot, int per_instance) {
+    gains_valid = false;
+    const int rc = upload_dynamics_dev(A_, B_, f_, per_knot ? (size_t)(d.N - 1) : 1, per_instance);
+    if (rc) return rc;
+    ltv = per_knot != 0;
+    dyn_blocks = per_knot ? d.N - 1 : 1;
+    dyn_step_stride = 0;
     return ALTRO_OK;
   }
 
@@ -448,6 +485,36 @@ struct WideBackend {
     return ALTRO_OK;
   }
 
+  // device twins of the three calls around (altro_*_dev: pointers already validated; stream-ordered copies, no synchronisation)
+  int set_initial_state_dev(const double* x) {
+    WCHK(hipSetDevice(device));
+    WCHK(hipMemcpyAsync(x0, x, (size_t)d.batch * d.n * sizeof(double), hipMemcpyDeviceToDevice, stream));
+    return ALTRO_OK;
+  }
+  int get_initial_state_dev(double* x) {
+    WCHK(hipSetDevice(device));
+    WCHK(hipMemcpyAsync(x, x0, (size_t)d.batch * d.n * sizeof(double), hipMemcpyDeviceToDevice, stream));
+    return ALTRO_OK;
+  }
+  int set_reference_dev(const double* Xr, const double* Ur) {
+    WCHK(hipSetDevice(device));
+    const int Nt_ = d.N;
+    if (Nt_ != Nt || !Xref) {   // another window length than the stored one: reallocate, as the host call does
+      WCHK(hipStreamSynchronize(stream));
+      if (Xref) WCHK(hipFree(Xref));
+      if (Uref) WCHK(hipFree(Uref));
+      Xref = Uref = nullptr;
+      WCHK(hipMalloc(&Xref, (size_t)d.batch * Nt_ * d.n * sizeof(double)));
+      WCHK(hipMalloc(&Uref, (size_t)d.batch * (Nt_ - 1) * d.m * sizeof(double)));
+      Nt = Nt_;
+    }
+    WCHK(hipMemcpyAsync(Xref, Xr, (size_t)d.batch * Nt * d.n * sizeof(double), hipMemcpyDeviceToDevice, stream));
+    WCHK(hipMemcpyAsync(Uref, Ur, (size_t)d.batch * (Nt - 1) * d.m * sizeof(double), hipMemcpyDeviceToDevice, stream));
+    kref = 0;
+    have_ref = true;
+    return ALTRO_OK;
+  }
+
   int set_ref_common(const double* Xr, const double* Ur, int Nt_) {
     WCHK(hipSetDevice(device));
     WCHK(hipStreamSynchronize(stream));
@@ -491,6 +558,32 @@ struct WideBackend {
     if (!Uh) return ALTRO_ERR_INVALID_ARG;
     WCHK(hipSetDevice(device));
     return put_planes(Xh, Uh);
+  }
+  // device twins: the scatter / gather kernels run on the caller's arrays, no staging copy
+  int set_initial_trajectory_dev(const double* Xd, const double* Ud) {
+    WCHK(hipSetDevice(device));
+    const size_t B = d.batch, lx = (size_t)d.N * d.n, lu = (size_t)(d.N - 1) * d.m;
+    if (Xd) hipLaunchKernelGGL(k_scatter_plane, dim3((unsigned)((B * lx + 255) / 256)), dim3(256), 0, stream, X, Xd, cur, lx, (int)B);
+    hipLaunchKernelGGL(k_scatter_plane, dim3((unsigned)((B * lu + 255) / 256)), dim3(256), 0, stream, U, Ud, cur, lu, (int)B);
+    WCHK(hipGetLastError());
+    return ALTRO_OK;
+  }
+  int get_planes_dev(double* Xd, double* Ud) {
+    WCHK(hipSetDevice(device));
+    const size_t B = d.batch, lx = (size_t)d.N * d.n, lu = (size_t)(d.N - 1) * d.m;
+    if (Xd) hipLaunchKernelGGL(k_gather_plane, dim3((unsigned)((B * lx + 255) / 256)), dim3(256), 0, stream, Xd, X, cur, lx, (int)B);
+    if (Ud) hipLaunchKernelGGL(k_gather_plane, dim3((unsigned)((B * lu + 255) / 256)), dim3(256), 0, stream, Ud, U, cur, lu, (int)B);
+    WCHK(hipGetLastError());
+    return ALTRO_OK;
+  }
+  // altro_batch_get_first_knot_dev: one kernel that reads plane cur[b] (device_io.h)
+  int get_first_knot_dev(double* u0d, double* x1d, int32_t* st, int32_t* it) {
+    WCHK(hipSetDevice(device));
+    const size_t thr = (size_t)d.batch * nz();
+    hipLaunchKernelGGL(altro::k_first_knot_wide, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, stream, u0d, x1d, st, it, X, U, cur,
+                       status, iters, d.batch, d.N, d.n, d.m);
+    WCHK(hipGetLastError());
+    return ALTRO_OK;
   }
   int get_planes(double* Xh, double* Uh) {
     WCHK(hipSetDevice(device));

@@ -192,6 +192,46 @@ class TrackMPC:
     closed_loop_trajectory = BatchMPC.closed_loop_trajectory
 
 
+class ExternalMPC:
+    """MPC loop for a plant the CALLER owns (a simulator, a learned model, a re-linearisation: the reference's foot_forces!,
+    altro_solver.jl:40-88, where MuJoCo is the plant), with every array in GPU memory: one `tick` is
+    set x0 [, new reference window] [, new dynamics]; primal + dual shift_fill; solve; read the first knot -- enqueued on
+    the solver's stream between one wait_stream and one signal_stream against torch's current stream, with no host
+    synchronisation and no copy over PCIe.  The tensors returned are ready in torch's stream order.  The solver must hold
+    a solution to shift (api.solve once before the loop), as in the reference."""
+
+    def __init__(self, solver, shift=True):
+        self.solver = solver
+        self.shift = bool(shift)
+        self.i = 0
+
+    def tick(self, x0, Xref=None, Uref=None, dynamics=None, out=None):
+        """x0 (B, n); Xref (B, N, n) and Uref (B, N-1, m): the new reference window (both or neither); dynamics: an
+        api.LinearModel of column-major-stored tensors (api module docstring) -- all GPU tensors on the solver's device.
+        Returns (u0, x1, status, iterations) as api.first_knot does (out: tensors to write into)."""
+        s = self.solver
+        if not api._on_gpu(x0):
+            raise ValueError("ExternalMPC.tick takes GPU tensors; the numpy loop is api.set_initial_state / shift_fill / solve")
+        if (Xref is None) != (Uref is None):
+            raise ValueError("tick: give Xref and Uref together")
+        _lib.check_single_runtime()
+        api.wait_stream(s)
+        try:
+            api._set_initial_state_dev(s, x0)
+            if Xref is not None:
+                api._update_trajectory_dev(s, Xref, Uref)
+            if dynamics is not None:
+                api._set_dynamics_dev(s, dynamics)
+            if self.shift:
+                api.shift_fill(s, True, True)
+            api.solve_async(s)
+            res = api._first_knot_dev(s, out)
+        finally:
+            api.signal_stream(s)
+        self.i += 1
+        return res
+
+
 def _add_specs(cons, specs, n, m):
     from . import problems as P
     for c in specs:

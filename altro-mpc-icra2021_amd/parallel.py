@@ -32,6 +32,23 @@ def gather_results(U1, status, device=None):
     return ug.reshape(-1, u.shape[-1]).cpu().numpy(), sg.reshape(-1).cpu().numpy()
 
 
+def gather_first_knot(u0, status):
+    """The same gather for the tensors api.first_knot / mpc.ExternalMPC.tick return: u0 (B, m) float64 and status (B,) int32
+    stay on their device (no numpy round trip) and the gathered tensors are returned there: (world*B, m) and (world*B,).
+    The collective runs on torch's current stream, which first_knot has ordered after the solve.  Without an initialised
+    process group it returns its inputs."""
+    import torch
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()):
+        return u0, status
+    world = dist.get_world_size()
+    ug = torch.empty((world * u0.shape[0],) + tuple(u0.shape[1:]), dtype=u0.dtype, device=u0.device)
+    sg = torch.empty((world * status.shape[0],), dtype=status.dtype, device=status.device)
+    dist.all_gather_into_tensor(ug, u0.contiguous())
+    dist.all_gather_into_tensor(sg, status.contiguous())
+    return ug, sg
+
+
 class RankGroup:
     """The process-group side of bench.py's timed region, in one place so that the CPU tests run the very
     code the driver launches on 8 GPUs (there with backend "nccl" = RCCL, in tests/ with "gloo"):

@@ -408,11 +408,64 @@ int32_t altro_batch_get_initial_state(altro_handle* h, double* x0);
  *   "keep_gains"   the setters stop dropping the stored gains (the product then returns results from STALE gains: it
  *                  exists to show that the tests notice).  Compiled into -DALTRO_DEBUG builds only; a release build
  *                  answers ALTRO_ERR_UNSUPPORTED.
+ *   "dev_via_stage" (handle only, 16-lane kernels)   altro_batch_set_initial_state_dev / _set_reference_dev copy the caller's
+ *                  array into the staging buffer before the layout kernel reads it (the alternative DESIGN.md 7c measures)
  * Unknown key: ALTRO_ERR_INVALID_ARG. */
 int32_t altro_debug_set(altro_handle* h, const char* key, int32_t value);
 
-/* the handle's hipStream_t, for callers that order their own device work after a solve */
+/* the handle's hipStream_t, for callers that order their own device work after a solve (see also
+ * altro_batch_wait_stream / altro_batch_signal_stream below) */
 int32_t altro_batch_get_stream(altro_handle* h, void** stream);
+
+
+/* ---- device-pointer I/O: set and read a batch in GPU memory, stream-ordered.
+ * The reference's loops hand Julia arrays to the solver on every tick (TO.set_initial_state!, update_trajectory!,
+ * update_dynamics_matrices!: random_linear_problem.jl:130-133, altro_solver.jl:5-37,60-71) and read states(solver) /
+ * controls(solver) back; for a plant, a learned model or a linearisation that runs on the same GPU as the batch these are
+ * the same calls on arrays that never leave HBM.
+ * Every `_dev` entry point takes DEVICE pointers (hipMalloc memory of the handle's device; a ROCArray, a torch tensor) to
+ * FP64 / int32 arrays in exactly the layout of the host call of the same name.  It only enqueues on the handle's stream:
+ * it does not synchronise, does not touch host memory, and does not allocate while the shapes are those of the previous
+ * call.  The library has consumed (setters) or produced (getters) the caller's buffer once the handle's stream has passed
+ * that point -- order other streams against it with altro_batch_wait_stream / altro_batch_signal_stream, or wait with
+ * altro_batch_synchronize.  The library keeps no caller pointer after its stream has passed the call.
+ * Validation happens before anything is enqueued or changed: every pointer must be known to the HIP runtime as device memory
+ * of the handle's device (hipPointerGetAttributes) and the allocation it lies in must hold at least the bytes the call reads
+ * or writes from that address on (hipMemGetAddressRange).  Otherwise -- a host pointer, memory of another device, a buffer
+ * that is too short, NULL where it is not allowed, a NULL handle -- the call returns ALTRO_ERR_INVALID_ARG with a message in
+ * altro_last_error (of the handle; of NULL for a NULL handle), nothing is launched and the handle is unchanged and usable.
+ * A setter leaves the handle in the byte-identical device state its host twin would, a getter writes byte-identical values.
+ * Not covered, on purpose (set once, or packed on the host): constraint tables, cost weights, bounds, duals, gains, traces,
+ * altro_mpc_set_track / _noise / _dynamics_track and the MPC log. */
+
+/* altro_batch_set_initial_state with x0 [batch][n] on the device */
+int32_t altro_batch_set_initial_state_dev(altro_handle* h, const double* x0);
+/* altro_batch_set_reference with Xref [batch][N][n], Uref [batch][N-1][m] on the device */
+int32_t altro_batch_set_reference_dev(altro_handle* h, const double* Xref, const double* Uref);
+/* altro_batch_set_initial_trajectory with X [batch][N][n] (may be NULL), U [batch][N-1][m] on the device */
+int32_t altro_batch_set_initial_trajectory_dev(altro_handle* h, const double* X, const double* U);
+/* altro_batch_set_dynamics with A, B, f (f may be NULL) on the device; drops the stored gains, and per_knot != 0 on an (n, m)
+ * of the 16-lane set must be the first call after create, as for the host call.  On the one-wave-per-instance kernel the
+ * tables are reused while the number of blocks is that of the previous call (host or device); a call that changes it, or that
+ * moves the handle to that kernel, allocates and synchronises the stream once. */
+int32_t altro_batch_set_dynamics_dev(altro_handle* h, const double* A, const double* B, const double* f,
+                                     int32_t per_knot, int32_t per_instance);
+/* altro_batch_get_states / _get_controls / _get_initial_state into device arrays X [batch][N][n], U [batch][N-1][m],
+ * x0 [batch][n] */
+int32_t altro_batch_get_states_dev(altro_handle* h, double* X);
+int32_t altro_batch_get_controls_dev(altro_handle* h, double* U);
+int32_t altro_batch_get_initial_state_dev(altro_handle* h, double* x0);
+/* What an MPC consumer reads each tick (altro_solver.jl:84-88: the forces of knot 1; random_linear_problem.jl:125-129: the
+ * plant step from the first control), in one kernel that reads the current trajectory directly: u0 [batch][m] the first
+ * control, x1 [batch][n] the state the model predicts after it (knot 1), status, iterations [batch] int32 as
+ * altro_batch_get_stats reports them.  Any pointer may be NULL (skipped). */
+int32_t altro_batch_get_first_knot_dev(altro_handle* h, double* u0, double* x1, int32_t* status, int32_t* iterations);
+/* Stream hand-over without the host: an event recorded on one stream and waited on by the other (the events belong to the
+ * handle and are reused).  wait_stream: work enqueued on the handle's stream from now on starts after everything enqueued so
+ * far on `producer` (a hipStream_t).  signal_stream: work enqueued on `consumer` from now on starts after everything enqueued
+ * so far on the handle's stream.  NULL names the default stream. */
+int32_t altro_batch_wait_stream(altro_handle* h, void* producer);
+int32_t altro_batch_signal_stream(altro_handle* h, void* consumer);
 
 #ifdef __cplusplus
 }

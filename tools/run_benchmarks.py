@@ -1,13 +1,19 @@
 """Run the reference's benchmark scripts (batched) on the GPU and print one JSON summary per run.
-Usage: python tools/run_benchmarks.py [--launch-steps K] [random_linear|sweeps|rocket|grasp|quadruped|all] [batch] [results.npz | outdir/]
+Usage: python tools/run_benchmarks.py [--launch-steps K] [--device-io] [random_linear|sweeps|rocket|grasp|quadruped|all] [batch] [results.npz | outdir/]
 --launch-steps K > 1: random_linear and rocket run K MPC steps per launch (altro_mpc_run_async) and take every step's
 iterations / status from the device log; "time" is then per launch (the other benchmarks rewrite data between steps).
+--device-io: the quadruped loop keeps every per-tick array in GPU memory (torch tensors, mpc.ExternalMPC): no per-tick device
+times then ("time" is NaN), iterations and status as before.
 The optional .npz holds, per benchmark, the reference's result Dict entries (random_linear_problem.jl:188)
 as arrays: "<name>/time" (ms per MPC step for the batch) and "<name>/iter" (steps x instances).  With a
 directory instead, the three sweeps are written as horizon_comp.h5, state_dim_comp.h5, control_dim_comp.h5 in
 the shape of the reference's *.jld2 result files (results_io.py: `results` + `Ns`, readable by
 benchmarks/plotting.jl::comparison_plot after a five-line HDF5.jl loader)."""
 import sys, os, json
+DEVICE_IO = "--device-io" in sys.argv
+if DEVICE_IO:
+    sys.argv.remove("--device-io")
+    import torch  # noqa: F401  (before the library is loaded: one HIP runtime in the process)
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, R)
 import altro_amd_loader
@@ -39,7 +45,7 @@ if which in ("all", "grasp"):
     out["grasp N_mpc=21"] = Bm.summarise(r)
 if which in ("all", "quadruped"):
     for nm, lin in (("quadruped N=15 pyramids", True), ("quadruped N=15 cones", False)):
-        r = Bm.run_quadruped(batch=B, linearized_friction=lin); raw[nm] = r
+        r = Bm.run_quadruped(batch=B, linearized_friction=lin, device_io=DEVICE_IO); raw[nm] = r
         out[nm] = Bm.summarise(r)
 for k, v in out.items():
     print(json.dumps({"benchmark": k, **v}), flush=True)
