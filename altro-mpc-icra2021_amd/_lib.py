@@ -30,7 +30,7 @@ EXPORTS = [
     "altro_batch_set_options", "altro_batch_solve", "altro_batch_solve_async",
     "altro_batch_synchronize", "altro_batch_get_states", "altro_batch_get_controls",
     "altro_batch_get_duals", "altro_batch_set_duals", "altro_batch_get_stats",
-    "altro_batch_get_alpha_trace", "altro_batch_get_gains", "altro_batch_last_solve_ms", "altro_batch_timing_reset", "altro_batch_timing_get",
+    "altro_batch_get_alpha_trace", "altro_batch_get_gains", "altro_batch_get_gain_factors", "altro_batch_last_solve_ms", "altro_batch_timing_reset", "altro_batch_timing_get",
     "altro_batch_get_work_counters", "altro_batch_get_wave_cycles", "altro_batch_get_solve_counters", "altro_mpc_run_async",
     "altro_mpc_set_noise_model", "altro_mpc_set_shift", "altro_mpc_set_track", "altro_mpc_set_noise",
     "altro_mpc_step_async", "altro_batch_get_initial_state", "altro_batch_get_stream",
@@ -165,6 +165,8 @@ def lib():
     L.altro_batch_get_stats.argtypes = [H, ip, ip, ip, dp, dp, dp, dp]
     L.altro_batch_get_alpha_trace.argtypes = [H, dp]
     L.altro_batch_get_gains.argtypes = [H, dp, dp]
+    if hasattr(L, "altro_batch_get_gain_factors"):
+        L.altro_batch_get_gain_factors.argtypes = [H, dp]
     L.altro_batch_last_solve_ms.argtypes = [H, C.POINTER(C.c_float)]
     L.altro_batch_timing_reset.argtypes = [H]
     L.altro_batch_timing_get.argtypes = [H, C.POINTER(C.c_float), C.c_int32, ip]

@@ -729,3 +729,10 @@ def gains(solver):
     d = np.empty((solver.B, solver.N - 1, solver.m))
     solver._chk(solver._L.altro_batch_get_gains(solver.h, _p(K), _p(d)))
     return np.swapaxes(K, -1, -2).copy(), d
+
+
+def gain_factors(solver):
+    """Factors of Quu = L D L' kept with the gains (16-lane kernels): (B, N-1, m, m), 1 / D on the diagonal, L below it."""
+    F = np.empty((solver.B, solver.N - 1, solver.m, solver.m))
+    solver._chk(solver._L.altro_batch_get_gain_factors(solver.h, _p(F)))
+    return F

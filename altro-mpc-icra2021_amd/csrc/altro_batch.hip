@@ -84,6 +84,7 @@ struct altro_handle {
   double* mlog = nullptr;  // per-step log of the MPC loop (mpc_log.h): [mlog_cap][batch][16 + MLOG_TAIL]; null: off
   int mlog_cap = 0;        // steps it holds
   // scheduling switches (altro_debug_set; the defaults are the product's behaviour)
+  bool d_in_kd = false;  // the last solve launch's kernel keeps d in the gain rows (altro::kd_holds_d), not in Dff
   int reuse = 1;  // gain reuse (solve_dpp16.h fosweep); "no_reuse" switches it off (tests)
   int lone = 1;  // backward_lone (solve_dpp16.h); "no_lone" switches it off (tests: lone == four-row pass bit for bit)
   int group_max_steps = 32;  // fused launches of more steps are not grouped ("group_max_steps": diagnostic)
@@ -564,6 +565,7 @@ static int launch_solve(altro_handle* h, int first_step, int nsteps, int prepare
   const dim3 grid(h->Bp / IPW), block(64);
   const int n = h->d.n, m = h->d.m;
   const bool cones = h->ncrows > 0;
+  h->d_in_kd = altro::kd_holds_d(m, cones);
 #define ALTRO_LAUNCH(NX_, NU_)                                                                            \
   do {                                                                                                    \
     if (cones) hipLaunchKernelGGL((altro::solve_kernel<NX_, NU_, true>), grid, block, 0, h->stream, p);  \
@@ -1727,6 +1729,13 @@ int32_t altro_batch_get_alpha_trace(altro_handle* h, double* alpha_trace) {
   });
 }
 
+// KD of the handle on the host (gains, factors of Quu and, where the last launch's kernel keeps it there, d)
+static int fetch_kd(altro_handle* h, std::vector<double>& kd) {
+  kd.resize((size_t)h->d.N * h->Bp * h->d.m * LW);
+  HIPCHK(h, hipMemcpy(kd.data(), h->KD, kd.size() * sizeof(double), hipMemcpyDeviceToHost));
+  return ALTRO_OK;
+}
+
 int32_t altro_batch_get_gains(altro_handle* h, double* K, double* d) {
   return guard(h, [&]() -> int32_t {
     WIDE_FWD(h, get_gains(K, d));
@@ -1734,23 +1743,50 @@ int32_t altro_batch_get_gains(altro_handle* h, double* K, double* d) {
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     const size_t n = h->d.n, m = h->d.m, N = h->d.N, B = h->d.batch, Bp = h->Bp;
-    std::vector<double> kd(N * Bp * m * LW);
-    HIPCHK(h, hipMemcpy(kd.data(), h->KD, kd.size() * sizeof(double), hipMemcpyDeviceToHost));
+    std::vector<double> kd;
+    if (int rc = fetch_kd(h, kd)) return rc;
     // an iteration confirmed by the costate sweep ran no backward pass: K is the previous pass's (the same
     // matrix: the active set was verified unchanged), its feedforward terms are zero (include/altro_batch.h, strict)
     std::vector<int> dz(Bp);
     HIPCHK(h, hipMemcpy(dz.data(), h->dzero, Bp * sizeof(int), hipMemcpyDeviceToHost));
-    std::vector<double> df((N + 1) * Bp * LW);
-    HIPCHK(h, hipMemcpy(df.data(), h->Dff, df.size() * sizeof(double), hipMemcpyDeviceToHost));
     // device layout KD [instance][k][control a][lane]: state lane j holds K[a][j] (the control lanes carry the factors of
-    // Quu); Dff [instance][k (N + 1 rows)][lane]: control lane n+a holds d[a]
+    // Quu and, in the box-only kernels, d: altro::kd_drow / kd_dcol); Dff [instance][k (N + 1 rows)][lane], conic kernels:
+    // control lane n+a holds d[a].  Which of the two the last launch wrote: launch_solve recorded it
+    const bool dkd = h->d_in_kd;
+    std::vector<double> df;
+    if (d && !dkd) {
+      df.resize((N + 1) * Bp * LW);
+      HIPCHK(h, hipMemcpy(df.data(), h->Dff, df.size() * sizeof(double), hipMemcpyDeviceToHost));
+    }
     for (size_t b = 0; b < B; ++b)
       for (size_t k = 0; k + 1 < N; ++k)
         for (size_t a = 0; a < m; ++a) {
           const double* row = kd.data() + ((b * N + k) * m + a) * LW;
           if (K) for (size_t j = 0; j < n; ++j) K[((b * (N - 1) + k) * n + j) * m + a] = row[j];
-          if (d) d[(b * (N - 1) + k) * m + a] = dz[b] ? 0.0 : df[(b * (N + 1) + k) * LW + n + a];
+          if (d) {
+            const double da = dkd ? kd[((b * N + k) * m + altro::kd_drow((int)a)) * LW + n + altro::kd_dcol((int)a, (int)m)]
+                                  : df[(b * (N + 1) + k) * LW + n + a];
+            d[(b * (N - 1) + k) * m + a] = dz[b] ? 0.0 : da;
+          }
         }
+    return ALTRO_OK;
+  });
+}
+
+int32_t altro_batch_get_gain_factors(altro_handle* h, double* F) {
+  return guard(h, [&]() -> int32_t {
+    if (!h || !F) return ALTRO_ERR_INVALID_ARG;
+    if (h->wide) FAIL(h, ALTRO_ERR_UNSUPPORTED, "the one-wave-per-instance kernels keep no factors of Quu");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const size_t n = h->d.n, m = h->d.m, N = h->d.N, B = h->d.batch;
+    std::vector<double> kd;
+    if (int rc = fetch_kd(h, kd)) return rc;
+    for (size_t b = 0; b < B; ++b)
+      for (size_t k = 0; k + 1 < N; ++k)
+        for (size_t a = 0; a < m; ++a)
+          for (size_t c = 0; c < m; ++c)   // control lane n + c of gain row a: entry (a, c) of the factors, c <= a
+            F[((b * (N - 1) + k) * m + a) * m + c] = (c <= a) ? kd[((b * N + k) * m + a) * LW + n + c] : 0.0;
     return ALTRO_OK;
   });
 }

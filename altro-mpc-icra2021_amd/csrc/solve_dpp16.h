@@ -107,6 +107,16 @@ struct ASet {
   unsigned w[ASET_WORDS];
 };
 
+// Where the feedforward term d[a] of a knot lives in the knot's gain rows KD[..][m][16] of the box-only kernels (m >= 3):
+// control lane n + kd_dcol(a, m) of gain row kd_drow(a).  Row r keeps entry (r, b) of the factors of Quu on its control lanes
+// b <= r, so the lanes b > r are free: d[a] for a >= 1 sits on its own lane n + a of row 0, d[0] on the last control lane of
+// row 1.  Two rows, so that the first-order sweep's store of d touches two lines of a knot; the one mapping for the kernels
+// (Solver::d_ofs, store_gains) and for altro_batch_get_gains.
+// kd_holds_d: which kernels use it (the conic ones keep the array Dff) -- Solver::DKD and the host's launch_solve share it.
+constexpr bool kd_holds_d(int m, bool cones) { return !cones && m >= 3; }
+constexpr int kd_drow(int a) { return a == 0 ? 1 : 0; }
+constexpr int kd_dcol(int a, int m) { return a == 0 ? m - 1 : a; }
+
 struct SolveParams {
   int B, Bp, N;
   int Nt;                // knots held by Zref (rows per instance)
@@ -165,8 +175,9 @@ struct SolveParams {
   double* Qz;            // [Bp][N+1][16] gradient of the AL cost at the trajectory the last alpha = 1 rollout produced
                          // (l_x on the state lanes, l_u on the control lanes; knot N = trash): input of the costate sweep
   double* KD;            // [Bp][N][NU][16] gains: row a = K[a][0..NX-1] in the x lanes; lane NX + b (b <= a) holds entry (a, b) of
-                         // the factors of Quu = L D L' (1 / D_a on the diagonal, L below it); block N-1 = trash
-  double* Dff;           // [Bp][N+1][16] feedforward terms: d[a] on lane NX + a (knot N = trash)
+                         // the factors of Quu = L D L' (1 / D_a on the diagonal, L below it); block N-1 = trash.  Box-only kernels:
+                         // the feedforward term d[a] on lane NX + kd_dcol(a) of row kd_drow(a), lanes the factors leave free
+  double* Dff;           // [Bp][N+1][16] feedforward terms of the conic kernels: d[a] on lane NX + a (knot N = trash)
   ASet* ahash;           // [Bp][16] per lane: active set of the backward pass that left the gains in KD (kept between launches)
   double* kmu;           // [Bp] penalty of that pass; < 0: the gains in KD must not be reused
   long long* n_fo;       // [Bp] iterations that took their gains from memory (first-order sweep instead of a backward pass)
@@ -544,7 +555,7 @@ struct Solver {
   // its own megabyte and a per-lane row index cost a quarter-rate v_mul_lo_u32.
   //   Z    [Bp][2 N + 1][16]  rows 0..N-1 plane 0, N..2N-1 plane 1, row 2 N the trash row
   //   Zref [Bp][Nt][16]
-  //   Lc, Qz, Dff [Bp][N + 1][16]  (row N = trash)
+  //   Lc, Qz, Dff [Bp][N + 1][16]  (row N = trash; Dff: conic kernels only, see d_ofs)
   __device__ __forceinline__ unsigned zat(int r) const { return ((unsigned)inst * (2u * (unsigned)P.N + 1u) + (unsigned)r) * LW + j; }
   __device__ __forceinline__ unsigned rat(int k) const { return ((unsigned)inst * (unsigned)P.Nt + (unsigned)k) * LW + j; }
   __device__ __forceinline__ unsigned qat(int k) const { return ((unsigned)inst * ((unsigned)P.N + 1u) + (unsigned)k) * LW + j; }
@@ -562,6 +573,34 @@ struct Solver {
   }
   static __device__ __forceinline__ int imin(int a, int b) { return a < b ? a : b; }
   static __device__ __forceinline__ int imax(int a, int b) { return a > b ? a : b; }
+  // Feedforward terms in the gain rows (box-only kernels; kd_drow / kd_dcol above).  Gain row a uses its control lanes only
+  // for b <= a, so with NU >= 3 the rows 0 and 1 have the NU lanes to spare that d needs: the closed-loop rollouts get d with
+  // the gain loads they issue anyway and no array of one 128-byte row per knot for NU numbers is written and read back.
+  // d_ofs: the element offset from kd_at(k, 0) of control lane NX + a to ITS d[a] -- 0 for a >= 1 (its own lane of row 0),
+  // LW + NU - 1 for a = 0 (the last control lane of row 1) -- and 0 on the other lanes.  The conic kernels keep Dff.
+  static constexpr bool DKD = kd_holds_d(NU, CONES);
+  __device__ __forceinline__ unsigned d_ofs() const {
+    return (j == NX) ? (unsigned)(kd_drow(0) * LW + kd_dcol(0, NU)) : 0u;
+  }
+  // Element offsets from kd_at(k, 0) of the gain loads of a closed-loop rollout.  NU <= 4: slot s of lane l holds gain row
+  // A = ((s ^ (l & 3)) - NX) & 3, the order in which the xor butterfly of the rollouts leaves the sum of row A in lane NX + A;
+  // kval: the slot is a gain row on a state lane.  NU > 4: slot c is row c.  DKD: a control lane's products are zeros
+  // whatever it loads (dx = 0 there), so its slot 0 fetches the lane's own d instead.
+  static constexpr int KS = (NU <= 4) ? 4 : NU;
+  __device__ __forceinline__ void gain_slots(unsigned (&kofs)[KS], bool (&kval)[KS]) const {
+    sfor<0, KS>([&](auto c) {
+      constexpr int S = decltype(c)::value;
+      const int A = (NU <= 4) ? (((S ^ (j & 3)) - NX) & 3) : S;
+      kval[S] = is_x & (A < NU);
+      kofs[S] = (unsigned)imin(A, NU - 1) * LW;
+    });
+    if constexpr (DKD) kofs[0] = is_u ? d_ofs() : kofs[0];
+  }
+  // this lane's feedforward term of knot k (control lanes; anything finite elsewhere)
+  __device__ __forceinline__ double d_load(int k) const {
+    if constexpr (DKD) return ldg(P.KD, kd_at(k, 0) + d_ofs());
+    else return ldg(P.Dff, qat(k));
+  }
 
   // Who of the waves on this SIMD has more work left.  The launch ends with its slowest wave, and while two waves share a
   // SIMD the VALU is issue-bound: the one that issues first runs at the speed it would have alone, the other
@@ -675,8 +714,8 @@ struct Solver {
 
   struct KnotIn {
     double z, zr, lhi, llo;
-    double kcol[NU <= 4 ? 4 : NU];  // closed loop: x lane j holds K[:, j] (slot order: see rollout)
-    double dff;                     // closed loop: u lane NX + a holds d[a]
+    double kcol[NU <= 4 ? 4 : NU];  // closed loop: x lane j holds K[:, j] (slot order: see gain_slots)
+    double dff;                     // closed loop, !DKD: u lane NX + a holds d[a] (DKD: slot 0 of kcol, see gain_slots)
     double lc, lcn;   // dual of this lane's constraint row at the knot and at the next one (CONES)
   };
 
@@ -728,18 +767,9 @@ struct Solver {
     double lim = is_x ? P.o.max_state_value : P.o.max_control_value;
     asm volatile("" : "+v"(lim));
 
-    // NU <= 4: slot s of lane l holds gain row A = ((s ^ (l & 3)) - NX) & 3, the order in which the
-    // xor butterfly of `stage` leaves the sum of row A in lane NX + A (and d[A] in that lane's slot 0)
-    unsigned kofs[4] = {0u, 0u, 0u, 0u};
-    bool kval[4] = {false, false, false, false};
-    if constexpr (!OPEN && NU <= 4) {
-      sfor<0, 4>([&](auto c) {
-        constexpr int S = decltype(c)::value;
-        const int A = ((S ^ (j & 3)) - NX) & 3;
-        kval[S] = is_x & (A < NU);
-        kofs[S] = (unsigned)imin(A, NU - 1) * LW;
-      });
-    }
+    unsigned kofs[KS] = {};
+    bool kval[KS] = {};
+    if constexpr (!OPEN) gain_slots(kofs, kval);  // slot order of the gain rows, and d in slot 0 of the control lanes
 
     // operands of stage knot k (k clamped to 0..N-2 by the callers)
     auto load = [&](int k, KnotIn& in, ConK& ck) {
@@ -751,12 +781,8 @@ struct Solver {
       in.lhi = ldg(P.Lb, lb_at(kk, 0));
       in.llo = ldg(P.Lb, lb_at(kk, 1));
       if constexpr (!OPEN) {
-        if constexpr (NU <= 4) {
-          sfor<0, 4>([&](auto c) { in.kcol[decltype(c)::value] = ldg(P.KD, kd_at(k, 0) + kofs[decltype(c)::value]); });
-        } else {
-          sfor<0, NU>([&](auto c) { in.kcol[decltype(c)::value] = ldg(P.KD, kd_at(k, decltype(c)::value)); });
-        }
-        in.dff = ldg(P.Dff, qat(k));
+        sfor<0, KS>([&](auto c) { in.kcol[decltype(c)::value] = ldg(P.KD, kd_at(k, 0) + kofs[decltype(c)::value]); });
+        if constexpr (!DKD) in.dff = ldg(P.Dff, qat(k));
       }
       in.lc = 0.0;
       in.lcn = 0.0;
@@ -786,7 +812,7 @@ struct Solver {
         // du = K dx: x lane j contributes K[:, j] dx_j; the NX-lane sums run as DPP FMAs
         const double dx = is_x ? (xb - in.z) : 0.0;
         double du;
-        const double dff = in.dff;
+        const double dff = DKD ? in.kcol[0] : in.dff;  // (DKD: slot 0 of a control lane is its d, see gain_slots)
         if constexpr (NU <= 4) {
           // four row sums over the x lanes in 15 VALU: lanes trade two slots with lane^1, one with
           // lane^2 (afterwards every lane of a quad holds the quad's part of row (l&3)-NX), then the
@@ -881,7 +907,7 @@ struct Solver {
       asm volatile("" : "+v"(ring[U].z), "+v"(ring[U].zr), "+v"(ring[U].lhi), "+v"(ring[U].llo));
       if constexpr (!OPEN) {
         landed(ring[U].kcol);
-        asm volatile("" : "+v"(ring[U].dff));
+        if constexpr (!DKD) asm volatile("" : "+v"(ring[U].dff));
       }
     });
     const int ngroups = (N - 1) / PD;
@@ -975,19 +1001,11 @@ struct Solver {
     const bool wl = shift && bounded;    // shifted duals are written back
     double lim = is_x ? P.o.max_state_value : P.o.max_control_value;
     asm volatile("" : "+v"(lim));
-    unsigned kofs[4] = {0u, 0u, 0u, 0u};
-    bool kval[4] = {false, false, false, false};
-    if constexpr (!OPEN && NU <= 4) {  // slot order of the gain rows: see rollout()
-      sfor<0, 4>([&](auto c) {
-        constexpr int S = decltype(c)::value;
-        const int A = ((S ^ (j & 3)) - NX) & 3;
-        kval[S] = is_x & (A < NU);
-        kofs[S] = (unsigned)imin(A, NU - 1) * LW;
-      });
-    }
-    constexpr int KS = (NU <= 4) ? 4 : NU;
+    unsigned kofs[KS] = {};
+    bool kval[KS] = {};
+    if constexpr (!OPEN) gain_slots(kofs, kval);  // see rollout()
     struct Rec {  // operands of the recurrence of four knots: the same for every row
-      double z[4], kcol[OPEN ? 1 : 4][OPEN ? 1 : KS], dff[OPEN ? 1 : 4];
+      double z[4], kcol[OPEN ? 1 : 4][OPEN ? 1 : KS], dff[(OPEN || DKD) ? 1 : 4];
     };
     struct Cst {  // operands of the cost terms of this row's knot of the group
       double zr, lhi, llo;
@@ -998,12 +1016,8 @@ struct Solver {
         const int ku = imin(k0 + U, N - 2);
         r.z[U] = ldg(P.Z, zs + zat(shu ? imin(ku + 1, N - 2) : ku));
         if constexpr (!OPEN) {
-          if constexpr (NU <= 4) {
-            sfor<0, 4>([&](auto c) { r.kcol[U][decltype(c)::value] = ldg(P.KD, kd_at(ku, 0) + kofs[decltype(c)::value]); });
-          } else {
-            sfor<0, NU>([&](auto c) { r.kcol[U][decltype(c)::value] = ldg(P.KD, kd_at(ku, decltype(c)::value)); });
-          }
-          r.dff[U] = ldg(P.Dff, qat(ku));
+          sfor<0, KS>([&](auto c) { r.kcol[U][decltype(c)::value] = ldg(P.KD, kd_at(ku, 0) + kofs[decltype(c)::value]); });
+          if constexpr (!DKD) r.dff[U] = ldg(P.Dff, qat(ku));
         }
       });
     };
@@ -1054,7 +1068,10 @@ struct Solver {
               du = (j == NX + A) ? da : du;
             });
           }
-          const double ub = r.z[U] + du + r.dff[U];  // alpha = 1
+          double dffu;  // (DKD: slot 0 of a control lane is its d, see gain_slots)
+          if constexpr (DKD) dffu = r.kcol[U][0];
+          else dffu = r.dff[U];
+          const double ub = r.z[U] + du + dffu;  // alpha = 1
           zbu = is_x ? xb : ub;
         }
         zb[U] = zbu;
@@ -1161,7 +1178,7 @@ struct Solver {
         constexpr int Tt = decltype(t)::value;
         const int k = imin(k0 + Tt, N - 2);
         u[Tt] = ldg(P.Z, zs + zat(k));
-        d[Tt] = ldg(P.Dff, qat(k));
+        d[Tt] = d_load(k);
       });
       sfor<0, UN>([&](auto t) {
         constexpr int Tt = decltype(t)::value;
@@ -1639,21 +1656,29 @@ struct Solver {
     dtiny = !row_any(dbig, lane);
   }
 
-  // Gains of one knot out (kk / kf: the knot, or the trash slots N-1 of KD and N of Dff for rows that sit the pass out).
+  // Gains of one knot out (kk: the knot, or the trash block N-1 of KD for rows that sit the pass out; kf, kernels that keep
+  // Dff only: the knot, or its trash row N).
   // Every lane stores its own column: x lane j the K[a][j]; u lane NX + b the factors of Quu the first-order sweep
   // needs to get d from Qu without a backward pass -- entry (a, b) of [1 / D on the diagonal, L below] in gain row a --
-  // and, in Dff, lane NX + a the feedforward term d[a] (on the u lanes kd[] is the solve of Qu, i.e. d).
+  // and the feedforward terms d[a] (on the u lanes kd[] is the solve of Qu, i.e. d): in the free control lanes of gain rows
+  // 0 and 1 (DKD, see d_ofs), else on lane NX + a of Dff.
   __device__ __forceinline__ void store_gains(int kk, int kf, const double (&kd)[NU], const double (&L)[NU][NU],
                                               const double (&dinv)[NU]) const {
+    // dl: d[a] on control lane NX + a, K[0][j] on the x lanes
     double dl = kd[0];
     sfor<1, NU>([&](auto a) {
       constexpr int A = decltype(a)::value;
       dl = (j == NX + A) ? kd[A] : dl;
     });
-    stg(P.Dff, qat(kf), dl);
+    if constexpr (!DKD) stg(P.Dff, qat(kf), dl);
     sfor<0, NU>([&](auto a) {
       constexpr int A = decltype(a)::value;
       double v = kd[A];
+      // DKD: the free control lanes of rows 0 and 1 take d -- row 0 is dl but for its diagonal lane, row 1 gets d[0] (every u
+      // lane holds every d[a] in kd[])
+      static_assert(kd_drow(0) == 1 && kd_drow(1) == 0 && kd_dcol(1, NU) == 1, "store_gains spells the mapping out");
+      if constexpr (DKD && A == 0) v = dl;
+      if constexpr (DKD && A == 1) v = (j == NX + kd_dcol(0, NU)) ? kd[0] : v;
       sfor<0, A>([&](auto b) {
         constexpr int Bq = decltype(b)::value;
         v = (j == NX + Bq) ? L[A][Bq] : v;
@@ -1672,8 +1697,9 @@ struct Solver {
   //     dV += (d'Qu, -1/2 d'Qu)
   // (identities of backward() with rho = 0).  l_z at the current trajectory was left in the plane Qz by the rollout that
   // produced it.  One 12-FMA product per knot on the critical path (s_{k+1} -> s_k); the solve for d hangs off it.
-  // Writes d into Dff (rows with live), returns dV and the tiny-feedforward flag of backward().  54 % of the backward
-  // passes of the headline workload are of this kind (tools/gpu_reuse_diag.py).
+  // Writes d where store_gains puts it (rows with live: one store per knot, only the NU lanes that change), returns dV and
+  // the tiny-feedforward flag of backward().  54 % of the backward passes of the headline workload are of this kind
+  // (tools/gpu_reuse_diag.py).
   __device__ void fosweep(bool live, double& dV1, double& dV2, bool& dtiny) {
     phase_begin();
     prio_serial();
@@ -1706,12 +1732,16 @@ struct Solver {
     // memory counter is in order: a store issued between the loads of the next group and the wait for them is waited for
     // as well -- issued a few instructions earlier, that was a full store round trip per group of PD knots.
     double dst_[PD];
+    const unsigned dofs = DKD ? d_ofs() : 0u;
     int kst = N;  // first knot of the pending stores (N: none yet -> the trash row)
     sfor<0, PD>([&](auto u) { dst_[decltype(u)::value] = 0.0; });
     auto flush = [&]() {
       sfor<0, PD>([&](auto u) {
         constexpr int U = decltype(u)::value;
-        stg(P.Dff, qat((live & (kst - U >= 0) & (kst < N)) ? kst - U : N), dst_[U]);
+        const bool on = live & (kst - U >= 0) & (kst < N);
+        // DKD: a control lane sends its d to its slot of the knot's gain rows, every other lane a zero to the trash block
+        if constexpr (DKD) stg(P.KD, kd_at((on & is_u) ? kst - U : N - 1, 0) + dofs, dst_[U]);
+        else stg(P.Dff, qat(on ? kst - U : N), dst_[U]);
       });
     };
     auto group = [&](In (&cur_)[PD], In (&nxt)[PD]) {

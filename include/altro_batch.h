@@ -270,6 +270,9 @@ int32_t altro_batch_get_alpha_trace(altro_handle* h, double* alpha_trace);
 /* feedback gains K [batch][N-1] blocks of m x n (column-major) and feedforward d [batch][N-1][m]
  * left by the last backward pass of the last solve (backwardpass!, ilqr K/d; either may be NULL) */
 int32_t altro_batch_get_gains(altro_handle* h, double* K, double* d);
+/* factors of Quu = L D L' kept with the gains for the first-order sweep (16-lane kernels; ALTRO_ERR_UNSUPPORTED on the
+ * one-wave-per-instance path): F [batch][N-1][m][m] row-major, entry (a, a) = 1 / D_a, (a, b < a) = L[a][b], 0 above */
+int32_t altro_batch_get_gain_factors(altro_handle* h, double* F);
 /* device time of the last solve launch sequence on the handle's stream, HIP events (ms) */
 int32_t altro_batch_last_solve_ms(altro_handle* h, float* ms);
 /* Launch-duration history of the solve kernel (HIP events recorded on the handle's stream around
