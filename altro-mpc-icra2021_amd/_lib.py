@@ -42,6 +42,8 @@ EXPORTS = [
     "altro_batch_set_dynamics_dev", "altro_batch_get_states_dev", "altro_batch_get_controls_dev",
     "altro_batch_get_initial_state_dev", "altro_batch_get_first_knot_dev", "altro_batch_wait_stream",
     "altro_batch_signal_stream",
+    "altro_batch_set_active", "altro_batch_set_active_dev", "altro_batch_get_active",
+    "altro_batch_restart_instances", "altro_batch_restart_instances_dev",
 ]
 """every symbol include/altro_batch.h declares"""
 
@@ -146,6 +148,13 @@ def lib():
         L.altro_batch_get_first_knot_dev.argtypes = [H, vp, vp, vp, vp]
         L.altro_batch_wait_stream.argtypes = [H, vp]
         L.altro_batch_signal_stream.argtypes = [H, vp]
+    if hasattr(L, "altro_batch_set_active"):   # per-instance active mask and cold restart
+        vp = C.c_void_p
+        L.altro_batch_set_active.argtypes = [H, ip]
+        L.altro_batch_set_active_dev.argtypes = [H, vp]
+        L.altro_batch_get_active.argtypes = [H, ip]
+        L.altro_batch_restart_instances.argtypes = [H, ip, dp, dp]
+        L.altro_batch_restart_instances_dev.argtypes = [H, vp, vp, vp]
     L.altro_batch_add_constraint.argtypes = [H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                              dp, dp, dp, dp, C.c_int32, ip]
     L.altro_batch_update_constraint_data.argtypes = [H, C.c_int32, dp, dp]

@@ -468,6 +468,65 @@ def initial_controls(solver, U):
     solver._chk(solver._L.altro_batch_set_initial_trajectory(solver.h, None, _p(U)))
 
 
+def _flags_i32(a, B, name):
+    a = np.ascontiguousarray(np.asarray(a) != 0, dtype=np.int32)
+    if a.shape != (B,):
+        raise ValueError(f"{name}: shape {a.shape}, expected ({B},)")
+    return a
+
+
+def _set_active_dev(solver, active):
+    check_device_tensor(active, (solver.B,), solver.device, "active", dtype="torch.int32")
+    solver._chk(solver._L.altro_batch_set_active_dev(solver.h, _addr(active)))
+
+
+def set_active(solver, active):
+    """Per-instance active mask (altro_batch_set_active): solves, shift_fill and MPC steps then act on the instances with a
+    nonzero entry only, and everything the solver holds for the others stays as it is.  active: (B,) numpy / list, or an
+    int32 GPU tensor (device path, stream-ordered); None clears the mask."""
+    if active is None:
+        solver._chk(solver._L.altro_batch_set_active(solver.h, None))
+    elif _on_gpu(active):
+        with _bracket(solver):
+            _set_active_dev(solver, active)
+    else:
+        a = _flags_i32(active, solver.B, "active")
+        solver._chk(solver._L.altro_batch_set_active(solver.h, a.ctypes.data_as(_IP)))
+
+
+def get_active(solver):
+    """(B,) int32 of 0 / 1: the mask in force (all ones when none is set)"""
+    a = np.empty(solver.B, dtype=np.int32)
+    solver._chk(solver._L.altro_batch_get_active(solver.h, a.ctypes.data_as(_IP)))
+    return a
+
+
+def _restart_instances_dev(solver, which, U, X=None):
+    check_device_tensor(which, (solver.B,), solver.device, "which", dtype="torch.int32")
+    if X is not None:
+        check_device_tensor(X, (solver.B, solver.N, solver.n), solver.device, "X")
+    check_device_tensor(U, (solver.B, solver.N - 1, solver.m), solver.device, "U")
+    solver._chk(solver._L.altro_batch_restart_instances_dev(solver.h, _addr(which), _addr(X), _addr(U)))
+
+
+def restart_instances(solver, which, U, X=None):
+    """Cold restart of the instances `which` selects (altro_batch_restart_instances): trajectory <- rows of (X, U), zero
+    duals, initial penalty, no stored gains, statistics of an unsolved instance -- their next solve is that of a new solver.
+    which (B,), U (B, N-1, m), X (B, N, n) or None: numpy, or all GPU tensors (which int32; device path)."""
+    if _on_gpu(which) or _on_gpu(U) or _on_gpu(X):
+        if not (_on_gpu(which) and _on_gpu(U) and (X is None or _on_gpu(X))):
+            raise ValueError("restart_instances: which, U and X must all be GPU tensors, or none of them")
+        with _bracket(solver):
+            return _restart_instances_dev(solver, which, U, X)
+    w = _flags_i32(which, solver.B, "which")
+    U = _c(U)
+    assert U.shape == (solver.B, solver.N - 1, solver.m)
+    if X is not None:
+        X = _c(X)
+        assert X.shape == (solver.B, solver.N, solver.n)
+    solver._chk(solver._L.altro_batch_restart_instances(solver.h, w.ctypes.data_as(_IP), _p(X), _p(U)))
+
+
 def shift_fill(solver, primal=True, dual=True):
     solver._chk(solver._L.altro_batch_shift_fill(solver.h, int(primal), int(dual)))
 

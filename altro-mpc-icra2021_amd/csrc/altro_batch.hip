@@ -103,6 +103,7 @@ struct altro_handle {
   double *cost = nullptr, *cmax = nullptr, *Jtrace = nullptr, *ctrace = nullptr, *atrace = nullptr;
   double* stage = nullptr;  // device staging buffer for host<->device layout conversion
   altro::StreamLink link;   // events of altro_batch_wait_stream / altro_batch_signal_stream (device_io.h)
+  altro::InstanceFlags flags;  // active mask and restart selection of a 16-lane handle, [Bp] (device_io.h; a wide handle's live in its backend)
   int dev_via_stage = 0;    // "dev_via_stage": the _dev setters of x0 and the reference copy into `stage` first (measurement only)
   size_t stage_bytes = 0;
   int Nt = 0;    // knots held by Zref
@@ -304,9 +305,10 @@ __global__ void k_duals(double* __restrict__ host, double* __restrict__ Lb, cons
 // rec0 = the step's first record; one thread per instance.
 __global__ void k_log_polished(double* __restrict__ rec0, const double* __restrict__ Zp, const int* __restrict__ cur, size_t plane,
                                const double* __restrict__ cost, const double* __restrict__ cmax, const int* __restrict__ status,
-                               int B, int N, int n, int m) {
+                               const int* __restrict__ active, int B, int N, int n, int m) {
   const int inst = blockIdx.x * blockDim.x + threadIdx.x;
   if (inst >= B) return;
+  if (active != nullptr && active[inst] == 0) return;  // the solve kernel wrote no record: the slot stays "never written"
   double* r = rec0 + (size_t)inst * (LW + altro::MLOG_TAIL);
   const double* z0 = Zp + (size_t)inst * (2 * (size_t)N + 1) * LW + (size_t)cur[inst] * plane;
   for (int a = 0; a < m; ++a) r[n + a] = z0[n + a];
@@ -319,10 +321,11 @@ __global__ void k_log_polished(double* __restrict__ rec0, const double* __restri
 // (random_linear_problem.jl:136,139): entry k <- entry k+1, last entry kept.
 __global__ void k_shift(double* __restrict__ Zp, const int* __restrict__ cur, size_t plane, double* __restrict__ Lb,
                         int nbp, int Bp, int N, int n, int m, int k0, int k1, int primal, int dual,
-                        double* __restrict__ Lc, const int* __restrict__ cmeta, int ncrows) {
+                        double* __restrict__ Lc, const int* __restrict__ cmeta, int ncrows, const int* __restrict__ active) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= Bp * LW) return;
   const int inst = t / LW, j = t % LW;
+  if (active != nullptr && active[inst] == 0) return;  // altro_batch_set_active: an inactive instance is not shifted
   const size_t ks = LW;  // rows of an instance are consecutive (instance-major arrays)
   if (primal) {
     double* z = Zp + (size_t)inst * (2 * (size_t)N + 1) * LW + (size_t)cur[inst] * plane + j;
@@ -343,6 +346,51 @@ __global__ void k_shift(double* __restrict__ Zp, const int* __restrict__ cur, si
       const int* cm = cmeta + ((size_t)k * LW + j) * 4;
       if (cm[0] != 0 && k < cm[2]) lc[(size_t)k * ks] = lc[(size_t)(k + 1) * ks];
     }
+  }
+}
+
+// altro_batch_restart_instances: the instances `which` selects go back to what a freshly created handle holds, with (X, U) as
+// their trajectory.  One thread per (instance, lane), the rows of k_pack_traj for the current plane; then the instance's box
+// and constraint-row duals <- 0 (trash rows included), penalty <- the 1.0 a new handle starts from (a solve with
+// reset_penalties = 1 begins at penalty_initial either way), no stored gains (kmu < 0, active set cleared, dzero = 0), and
+// the statistics of an instance that has not been solved.  The accumulating counters stay.
+__global__ void k_restart(const int* __restrict__ which, const double* __restrict__ X, const double* __restrict__ U,
+                          double* __restrict__ Zp, const int* __restrict__ cur, size_t plane, double* __restrict__ Lb, int nbp,
+                          double* __restrict__ Lc, double* __restrict__ mu, double* __restrict__ kmu, altro::ASet* __restrict__ ahash,
+                          int* __restrict__ dzero, int* __restrict__ iters, int* __restrict__ iters_outer, int* __restrict__ status,
+                          double* __restrict__ cost, double* __restrict__ cmax, double* __restrict__ Jtrace, double* __restrict__ ctrace,
+                          double* __restrict__ atrace, int B, int N, int n, int m, int have_x) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= B * LW) return;
+  const int inst = t / LW, j = t % LW;
+  if (which[inst] == 0) return;
+  double* dst = Zp + (size_t)inst * (2 * (size_t)N + 1) * LW + (size_t)cur[inst] * plane;
+  for (int k = 0; k < N; ++k) {
+    if (j < n) {
+      if (have_x) dst[(size_t)k * LW + j] = X[((size_t)inst * N + k) * n + j];
+    } else {
+      dst[(size_t)k * LW + j] = (j < n + m && k < N - 1) ? U[((size_t)inst * (N - 1) + k) * m + (j - n)] : 0.0;
+    }
+  }
+  double* lb = Lb + (size_t)inst * (N + 1) * 2 * nbp;
+  for (int e = j; e < (N + 1) * 2 * nbp; e += LW) lb[e] = 0.0;
+  double* lc = Lc + (size_t)inst * (N + 1) * LW;
+  for (int k = 0; k <= N; ++k) lc[(size_t)k * LW + j] = 0.0;
+  altro::ASet z{};
+  ahash[(size_t)inst * LW + j] = z;
+  static_assert(ALTRO_TRACE_LEN == LW, "one trace entry per lane");
+  Jtrace[(size_t)inst * ALTRO_TRACE_LEN + j] = 0.0;
+  ctrace[(size_t)inst * ALTRO_TRACE_LEN + j] = 0.0;
+  atrace[(size_t)inst * ALTRO_TRACE_LEN + j] = 0.0;
+  if (j == 0) {
+    mu[inst] = 1.0;
+    kmu[inst] = -1.0;
+    dzero[inst] = 0;
+    iters[inst] = 0;
+    iters_outer[inst] = 0;
+    status[inst] = ALTRO_UNSOLVED;
+    cost[inst] = 0.0;
+    cmax[inst] = 0.0;
   }
 }
 
@@ -384,8 +432,10 @@ __global__ void k_plane_copy(double* __restrict__ Zp, double* __restrict__ Zs, c
 // knot at (or within 2 % of) a bound.  It is a scheduling heuristic only: results do not depend on which rows share a
 // wave (tests: instance results do not depend on the batch; lone-row == four-row pass bit for bit).
 // one 16-lane row per instance (lane j = element j of z: coalesced 128-byte reads), 16 instances per block
+constexpr int GROUP_BINS = 34;   // scores 0 .. 32 of the active instances, and one bin behind them for the inactive ones
 __global__ void k_group_score(const double* __restrict__ Zref, const double* __restrict__ zmin, const double* __restrict__ zmax,
-                              unsigned imask, int* __restrict__ score, int Bp, int Nt, int first, int nsteps, int k0, int k1, int nz) {
+                              unsigned imask, int* __restrict__ score, int Bp, int Nt, int first, int nsteps, int k0, int k1, int nz,
+                              const int* __restrict__ active) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   const int b = t / LW, j = t % LW;
   const bool live = b < Bp;
@@ -393,7 +443,7 @@ __global__ void k_group_score(const double* __restrict__ Zref, const double* __r
   const int W = k1 - k0 + 1;                 // knots of a window that carry the box rows
   const int a0 = first + 1 + k0;             // first absolute knot touched by the launch's windows
   const int na = nsteps + W - 1;             // absolute knots touched
-  if (na > 256 || W < 1) { if (live && j == 0) score[b] = 0; return; }
+  if (na > 256 || W < 1) { if (live && j == 0) score[b] = (active != nullptr && active[b] == 0) ? GROUP_BINS - 1 : 0; return; }
   const unsigned bo = ((unsigned)bb * LW + j) & imask;   // the instance's row of per-instance bounds (SolveParams::imask)
   const double lo = zmin[bo], hi = zmax[bo];
   const bool fl = (j < nz) && lo > -1e300, fh = (j < nz) && hi < 1e300;
@@ -415,12 +465,14 @@ __global__ void k_group_score(const double* __restrict__ Zref, const double* __r
     cnt -= (int)((bits[out >> 6] >> (out & 63)) & 1ull);
     if (in < na) cnt += (int)((bits[in >> 6] >> (in & 63)) & 1ull);
   }
-  score[b] = sc;
+  // (active scores stay below the last bin, which belongs to the inactive instances of a masked launch: they sort behind
+  //  everything else, four to a wave, and those waves leave at their first step begin)
+  sc = sc < GROUP_BINS - 2 ? sc : GROUP_BINS - 2;
+  score[b] = (active != nullptr && active[b] == 0) ? GROUP_BINS - 1 : sc;
 }
 
 // perm = the instances in ascending order of (score, index): a stable counting sort in ONE block of 256 threads (thread t
 // owns a contiguous chunk of instances; scores are at most GROUP_BINS - 1 = the steps of a grouped launch)
-constexpr int GROUP_BINS = 33;
 __global__ void __launch_bounds__(256) k_group_rank(const int* __restrict__ score, int* __restrict__ perm, int Bp, int mode) {
   __shared__ int cnt[GROUP_BINS][257];
   __shared__ int base[GROUP_BINS + 1];
@@ -551,6 +603,7 @@ static int launch_solve(altro_handle* h, int first_step, int nsteps, int prepare
     else { p.o.constraint_tolerance = 0.0; p.o.kickout_max_penalty = 1; }
   }
   p.perm = nullptr;
+  p.active = h->flags.mask();
   // fused MPC launches of box-constrained problems: group the instances by how many of the launch's steps will need
   // backward passes (see k_group_score); everything else runs in instance order
   // (short launches only: over 100 steps nearly every window meets a bound at some point, the score stops separating the
@@ -558,7 +611,7 @@ static int launch_solve(altro_handle* h, int first_step, int nsteps, int prepare
   //  measured 20 steps +2 %, 100 steps -3 %, tools/gpu_ab.py)
   if (h->group && h->reuse && !h->o.strict && nsteps >= 4 && nsteps <= h->group_max_steps && !prepare_only && h->ncrows == 0 && h->box_k1 >= h->box_k0 && h->Bp <= 32768) {
     hipLaunchKernelGGL(k_group_score, grid_for((size_t)h->Bp * LW), dim3(256), 0, h->stream, h->Zref, h->zmin, h->zmax, tab_imask(h), h->gscore, h->Bp, h->Nt,
-                       first_step, nsteps, h->box_k0, h->box_k1, h->d.n + h->d.m);
+                       first_step, nsteps, h->box_k0, h->box_k1, h->d.n + h->d.m, h->flags.mask());
     hipLaunchKernelGGL(k_group_rank, dim3(1), dim3(256), 0, h->stream, h->gscore, h->perm, h->Bp, h->group);
     p.perm = h->perm;
   }
@@ -975,12 +1028,14 @@ int32_t altro_batch_destroy(altro_handle* h) {
   if (!h) return ALTRO_OK;
   if (h->wide) {
     h->wide->destroy();
+    h->flags.destroy();
     h->link.destroy();
     delete h->wide;
     delete h;
     return ALTRO_OK;
   }
   free_dpp_backend(h);
+  h->flags.destroy();
   h->link.destroy();
   delete h;
   return ALTRO_OK;
@@ -1030,6 +1085,8 @@ static int migrate_to_wide(altro_handle* h) {
       return rcl;
     }
   }
+  wb->flags = h->flags;   // a mask set before the model moves with the handle (its buffers hold Bp >= batch entries)
+  h->flags = altro::InstanceFlags{};
   free_dpp_backend(h);
   h->wide = wb;
   return ALTRO_OK;
@@ -1477,7 +1534,7 @@ int32_t altro_batch_shift_fill(altro_handle* h, int32_t primal, int32_t dual) {
     const size_t plane = (size_t)h->d.N * LW;
     hipLaunchKernelGGL(k_shift, grid_for((size_t)h->Bp * LW), dim3(256), 0, h->stream, h->Z, h->cur, plane, h->Lb,
                        h->nbp, h->Bp, h->d.N, h->d.n, h->d.m, h->box_k0, h->box_k1, primal ? 1 : 0, dual ? 1 : 0, h->Lc,
-                       h->cmeta, h->ncrows);
+                       h->cmeta, h->ncrows, h->flags.mask());
     HIPCHK(h, hipGetLastError());
     return ALTRO_OK;
   });
@@ -1530,7 +1587,7 @@ static int launch_polish(altro_handle* h) {
   q.con_istride = h->con_per_instance ? (unsigned)(h->d.N * LW * LW) : 0u;
   q.Grow = h->Grow; q.fvec = h->fvec; q.wd = h->wd; q.wf = h->wf; q.zmin = h->zmin; q.zmax = h->zmax; q.x0 = h->x0;
   q.wstride = q.bstride = tab_imask(h) == 15u ? 0u : (unsigned)LW;
-  q.Acon = h->Acon; q.bcon = h->bcon; q.cmeta = h->cmeta;
+  q.Acon = h->Acon; q.bcon = h->bcon; q.cmeta = h->cmeta; q.active = h->flags.mask();
   q.Z = h->Z; q.Zref = h->Zref; q.kref = h->kref; q.cur = h->cur; q.status = h->status; q.cost = h->cost; q.cmax = h->cmax;
   q.pn_ran = h->pn_ran; q.pn_failed = h->pn_failed; q.pn_res = h->pn_res;
   q.Lb = h->Lb; q.Lc = h->Lc; q.bslot = h->bslot; q.nbp = h->nbp;
@@ -1569,7 +1626,7 @@ static int enqueue_solve(altro_handle* h, int first_step, int nsteps) {
       if (!rc && h->mlog) {
         double* rec0 = h->mlog + (size_t)(first_step + s) * (size_t)h->d.batch * (LW + altro::MLOG_TAIL);
         hipLaunchKernelGGL(k_log_polished, grid_for((size_t)h->d.batch), dim3(256), 0, h->stream, rec0, h->Z, h->cur, (size_t)h->d.N * LW,
-                           h->cost, h->cmax, h->status, h->d.batch, h->d.N, h->d.n, h->d.m);
+                           h->cost, h->cmax, h->status, h->flags.mask(), h->d.batch, h->d.N, h->d.n, h->d.m);
         if (hipGetLastError() != hipSuccess) { h->err = "launch of the log kernel failed"; rc = ALTRO_ERR_HIP; }
       }
     }
@@ -2106,6 +2163,7 @@ int32_t altro_batch_benchmark_solve(altro_handle* h, int32_t samples, int32_t ev
     WIDE_FWD(h, benchmark_solve(samples, evals, sample_ms));
     if (!h) return ALTRO_ERR_INVALID_ARG;
     if (samples < 1 || evals < 1) FAIL(h, ALTRO_ERR_INVALID_ARG, "samples and evals must be positive");
+    if (h->flags.on) FAIL(h, ALTRO_ERR_STATE, "altro_batch_benchmark_solve restores and repeats whole batches: clear the active mask first");
     HIPCHK(h, hipSetDevice(h->device));
     const size_t plane = (size_t)h->d.N * LW;
     if (!h->Zsave) HIPCHK(h, hipMalloc(&h->Zsave, plane * h->Bp * sizeof(double)));
@@ -2259,6 +2317,89 @@ int32_t altro_batch_get_first_knot_dev(altro_handle* h, double* u0, double* x1, 
                        h->status, h->iters, N_ * (size_t)LW, (int)B_, (int)N_, (int)n_, (int)m_);
     HIPCHK(h, hipGetLastError());
     return ALTRO_OK;
+  });
+}
+
+// ---- per-instance active mask and cold restart
+static int set_active_common(altro_handle* h, const int32_t* active, bool dev) {
+  altro::InstanceFlags& fl = h->wide ? h->wide->flags : h->flags;
+  const hipStream_t st = h->wide ? h->wide->stream : h->stream;
+  if (!active) { fl.on = false; return ALTRO_OK; }
+  HIPCHK(h, fl.load(false, active, dev, h->d.batch, h->wide ? h->d.batch : h->Bp, st));
+  if (!dev) HIPCHK(h, hipStreamSynchronize(st));
+  fl.on = true;
+  return ALTRO_OK;
+}
+
+int32_t altro_batch_set_active(altro_handle* h, const int32_t* active) {
+  return guard(h, [&]() -> int32_t {
+    if (!h) return dev_null_handle("altro_batch_set_active");
+    HIPCHK(h, hipSetDevice(h->device));
+    return set_active_common(h, active, false);
+  });
+}
+
+int32_t altro_batch_set_active_dev(altro_handle* h, const int32_t* active) {
+  return guard(h, [&]() -> int32_t {
+    DEV_ENTER(h, "altro_batch_set_active_dev");
+    DEV_ARG(h, "active", active, B_, int32_t, true);
+    return set_active_common(h, active, true);
+  });
+}
+
+int32_t altro_batch_get_active(altro_handle* h, int32_t* active) {
+  return guard(h, [&]() -> int32_t {
+    if (!h) return dev_null_handle("altro_batch_get_active");
+    if (!active) FAIL(h, ALTRO_ERR_INVALID_ARG, "altro_batch_get_active: null pointer");
+    const altro::InstanceFlags& fl = h->wide ? h->wide->flags : h->flags;
+    const size_t B = h->d.batch;
+    if (!fl.on) { for (size_t i = 0; i < B; ++i) active[i] = 1; return ALTRO_OK; }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->wide ? h->wide->stream : h->stream));
+    HIPCHK(h, hipMemcpy(active, fl.active, B * sizeof(int), hipMemcpyDeviceToHost));
+    return ALTRO_OK;
+  });
+}
+
+// X, U: host arrays (staged) or validated device arrays (read where they are); `which` likewise, through InstanceFlags
+static int restart_16(altro_handle* h, const int32_t* which, const double* X, const double* U, bool dev) {
+  const size_t B = h->d.batch, N = h->d.N, n = h->d.n, m = h->d.m;
+  const size_t cx = X ? B * N * n : 0, cu = B * (N - 1) * m;
+  if (!dev) {
+    int rc = ensure_stage(h, (cx + cu) * sizeof(double));
+    if (rc) return rc;
+    if (X && (rc = upload(h, X, cx, 0))) return rc;
+    if ((rc = upload(h, U, cu, cx))) return rc;
+    X = X ? h->stage : nullptr;
+    U = h->stage + cx;
+  }
+  HIPCHK(h, h->flags.load(true, which, dev, (int)B, h->Bp, h->stream));
+  hipLaunchKernelGGL(k_restart, grid_for(B * LW), dim3(256), 0, h->stream, h->flags.which, X, U, h->Z, h->cur, N * (size_t)LW, h->Lb,
+                     h->nbp, h->Lc, h->mu, h->kmu, h->ahash, h->dzero, h->iters, h->iters_outer, h->status, h->cost, h->cmax,
+                     h->Jtrace, h->ctrace, h->atrace, (int)B, (int)N, (int)n, (int)m, X ? 1 : 0);
+  HIPCHK(h, hipGetLastError());
+  if (!dev) HIPCHK(h, hipStreamSynchronize(h->stream));
+  return ALTRO_OK;
+}
+
+int32_t altro_batch_restart_instances(altro_handle* h, const int32_t* which, const double* X, const double* U) {
+  return guard(h, [&]() -> int32_t {
+    if (!h) return dev_null_handle("altro_batch_restart_instances");
+    if (!which || !U) FAIL(h, ALTRO_ERR_INVALID_ARG, "altro_batch_restart_instances: which and U are required");
+    HIPCHK(h, hipSetDevice(h->device));
+    DEV_WIDE(h, restart(which, X, U, false));
+    return restart_16(h, which, X, U, false);
+  });
+}
+
+int32_t altro_batch_restart_instances_dev(altro_handle* h, const int32_t* which, const double* X, const double* U) {
+  return guard(h, [&]() -> int32_t {
+    DEV_ENTER(h, "altro_batch_restart_instances_dev");
+    DEV_ARG(h, "which", which, B_, int32_t, false);
+    DEV_ARG(h, "X", X, B_ * N_ * n_, double, true);
+    DEV_ARG(h, "U", U, B_ * (N_ - 1) * m_, double, false);
+    DEV_WIDE(h, restart(which, X, U, true));
+    return restart_16(h, which, X, U, true);
   });
 }
 

@@ -57,6 +57,50 @@ struct StreamLink {
   }
 };
 
+// Per-instance active mask and restart selection (altro_batch_set_active / _restart_instances, host and _dev forms): the
+// library's own copies of the caller's int32 arrays, normalised to 0 / 1, `cap` entries (the batch padded to whole waves on
+// the 16-lane backend; padded slots hold 0: inactive whenever a mask is set, never restarted).  Both buffers are allocated
+// by the first call that needs them and reused from then on.
+__global__ void k_flags_copy(int* __restrict__ dst, const int* __restrict__ src, int B, int cap) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= cap) return;
+  dst[i] = (i < B && src[i] != 0) ? 1 : 0;
+}
+struct InstanceFlags {
+  int* active = nullptr;  // [cap]; read by the kernels only while `on`
+  int* which = nullptr;   // [cap] selection of the restart in flight
+  int* hstage = nullptr;  // [cap] where a host array lands before it is normalised
+  bool on = false;        // a mask is set (off: every entry point acts on the whole batch)
+  const int* mask() const { return on ? active : nullptr; }
+  hipError_t ensure(int cap) {
+    hipError_t e;
+    if (!active && (e = hipMalloc(&active, (size_t)cap * sizeof(int))) != hipSuccess) return e;
+    if (!which && (e = hipMalloc(&which, (size_t)cap * sizeof(int))) != hipSuccess) return e;
+    if (!hstage && (e = hipMalloc(&hstage, (size_t)cap * sizeof(int))) != hipSuccess) return e;
+    return hipSuccess;
+  }
+  // active (or which) <- the caller's array src [B], on the host (copied through hstage; the caller waits for the stream
+  // before it returns) or on the device (read where it is); the same kernel writes dst either way
+  hipError_t load(bool to_which, const int* src, bool dev, int B, int cap, hipStream_t st) {
+    hipError_t e;
+    if ((e = ensure(cap)) != hipSuccess) return e;
+    int* dst = to_which ? which : active;
+    if (!dev) {
+      if ((e = hipMemcpyAsync(hstage, src, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+      src = hstage;
+    }
+    hipLaunchKernelGGL(k_flags_copy, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, st, dst, src, B, cap);
+    return hipGetLastError();
+  }
+  void destroy() {
+    if (active) hipFree(active);
+    if (which) hipFree(which);
+    if (hstage) hipFree(hstage);
+    active = which = hstage = nullptr;
+    on = false;
+  }
+};
+
 // altro_batch_get_first_knot_dev, 16-lane backend: Zp holds [Bp] blocks of (2N + 1) knots x 16 lanes, two planes of N knots;
 // lanes 0..n-1 of a knot are its state, n..n+m-1 its control.  One thread per (instance, lane) reads plane cur[inst]:
 // u0 <- control of knot 0, x1 <- state of knot 1; lane 0 also copies the instance's status and iteration count.

@@ -35,6 +35,8 @@ struct PnParams {
   unsigned wstride, bstride;  // rows of wd / wf and of zmin / zmax: 0 (one row [16] for the batch) or 16 ([Bp][16] per instance)
   const double *Acon, *bcon;
   const int* cmeta;
+  const int* active;      // [Bp] 0 / 1 per instance (altro_batch_set_active), or null: all.  An inactive instance is not polished
+                          // and keeps its polish statistics
   double* Z;              // [Bp][2 N + 1][16] (two planes of N rows + trash row per instance): plane cur is polished, plane cur^1 is the trial buffer
   const double* Zref;     // window start kref
   int kref;
@@ -602,6 +604,7 @@ struct Pn {
 
 __global__ void __launch_bounds__(64) pn_kernel(PnParams p) {
   __shared__ double lds[2 * BMAX * (BMAX + 1) + 4 * BMAX];
+  if (p.active != nullptr && p.active[blockIdx.x] == 0) return;  // block-uniform, before any barrier
   Pn s(p, lds);
   s.run();
 }

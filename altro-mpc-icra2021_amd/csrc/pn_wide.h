@@ -539,6 +539,7 @@ struct PnW {
 __global__ void __launch_bounds__(64) pnw_kernel(WParams w, double ctol_user) {
   PnW s(w);
   for (int inst = blockIdx.x; inst < w.P.B; inst += gridDim.x) {
+    if (w.P.active != nullptr && w.P.active[inst] == 0) continue;  // block-uniform: not polished, its statistics stay
     s.run(inst, ctol_user);
     __syncthreads();
   }

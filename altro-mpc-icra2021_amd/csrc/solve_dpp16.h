@@ -204,6 +204,9 @@ struct SolveParams {
   double* mlog;          // per-step log of the MPC loop (mpc_log.h): [capacity][B][16 + MLOG_TAIL], or null (off, and in every
                          // launch that is not an MPC step: plain solves, prepare-only).  Read ONCE, into RowState::lrec
   altro_opts o;
+  const int* active;     // [Bp] 0 / 1 per instance (altro_batch_set_active; padded slots 0), or null: every instance is active.
+                         // Read ONCE per row, into RowState::act: an inactive row never begins a step and finish() skips it.
+                         // (last, so that every other argument keeps its offset in the kernel argument segment)
 };
 
 template <int K>
@@ -415,7 +418,13 @@ struct RowState {
   double* lrec;   // MPC log: this instance's record of the launch's first step, null when nothing is logged (log off, plain
                   // solve, padded slot).  Parked here like imask: the write is once per solve, no register waits for it
   unsigned lstep; // doubles from one step's record of an instance to the next step's: B * (16 + MLOG_TAIL)
+  int act;        // SolveParams::active of this row's instance (1 when no mask is set).  0: the row starts with step = STEP_NEVER,
+                  // past the steps of any launch, so the wave loop as it stands never gives it `go`: from its first step begin
+                  // it is PH_DONE -- no plant step, no dual reset, no kref update, no solve, no log record -- and takes part in
+                  // the wave's phases only as a shadow of a live row; the slowest-row estimate (min of the rows' steps) skips
+                  // it.  finish() reads the flag and stores nothing for such a row.  Parked here like imask
 };
+constexpr int STEP_NEVER = 1 << 30;
 
 template <int NX, int NU, bool CONES>
 struct Solver {
@@ -2267,7 +2276,8 @@ struct Solver {
       s.iters = s.iters_outer = s.outer = s.it = s.dj_zero = s.shift = s.last = 0;
       s.cur = P.cur[inst];
       s.kref = P.kref;
-      s.step = 0;
+      s.act = (P.active == nullptr || P.active[inst] != 0) ? 1 : 0;
+      s.step = s.act ? 0 : STEP_NEVER;
       s.nbw = s.nro = s.nsolve = s.nit = s.nok = s.ntr = 0;
       s.kmu = P.kmu[inst];
       s.qvalid = 0;
@@ -2775,6 +2785,7 @@ struct Solver {
   }
 
   __device__ void finish() {
+    if (rs->act == 0) return;  // an inactive instance keeps everything the library owns for it, validity of its gains included
     if (!P.prepare_only) P.ahash[(unsigned)inst * LW + j] = *ah;
     if (j == 0 && !P.prepare_only) {  // a prepare-only launch leaves the statistics of the last solve alone
       P.iters[inst] = rs->iters;

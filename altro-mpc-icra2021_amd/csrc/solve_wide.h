@@ -92,6 +92,8 @@ struct Params {
   int dyn_blocks, dyn_step_stride;
   int compact;  // LDS carve-up with [Qux | Qu] and K inside W (wide_compact)
   double* mlog;  // per-step log of the MPC loop (mpc_log.h): [capacity][B][n + m + MLOG_TAIL], or null (off)
+  const int* active;  // [B] 0 / 1 per instance (altro_batch_set_active), or null: every instance is active.  The block of an
+                      // inactive instance returns before its first barrier (wide_kernel, wide_shift_kernel)
   altro_opts o;
 };
 
@@ -3133,6 +3135,8 @@ constexpr int wide_waves(int MC, bool SM) { return SM ? (MC <= 8 ? ALTRO_WIDE_WA
 template <int MC, bool SM, int NPC = 0, int PRC = -1>
 __global__ void __launch_bounds__(SM ? 64 : 256, wide_waves(MC, SM)) wide_kernel(Params P, int mpc, int first_step, int nsteps) {
   extern __shared__ double lds[];
+  // block-uniform, before any barrier and before the helper waves of a cooperative block start to wait for commands
+  if (P.active != nullptr && P.active[blockIdx.x] == 0) return;
   if (!SM && threadIdx.x >= 64) {  // helper waves: no solver state, only products on command
     coop_helper(lds, lds_layout(P.n, P.m, P.Pn, P.compact).cmd);
     return;
@@ -3155,6 +3159,7 @@ inline int wide_block_threads(int n, int m, size_t lds_bytes, int coop_mode = -1
 #ifndef ALTRO_WIDE_TU
 __global__ void __launch_bounds__(64) wide_shift_kernel(Params P, int primal, int dual) {
   extern __shared__ double lds[];
+  if (P.active != nullptr && P.active[blockIdx.x] == 0) return;
   Solver<0, false> s(P, lds);
   s.cur = P.cur[s.inst];
   s.shift(primal != 0, dual != 0);

@@ -66,9 +66,10 @@ __global__ void k_scatter_plane(double* planes, const double* img, const int* cu
 // step's records take the first control of the polished trajectory and the statistics the polish replaced where it ran.
 __global__ void k_log_polished_wide(double* __restrict__ rec0, const double* __restrict__ U, const int* __restrict__ cur,
                                     const double* __restrict__ cost, const double* __restrict__ cmax, const int* __restrict__ status,
-                                    int B, int N, int n, int m) {
+                                    const int* __restrict__ active, int B, int N, int n, int m) {
   const int inst = blockIdx.x * blockDim.x + threadIdx.x;
   if (inst >= B) return;
+  if (active != nullptr && active[inst] == 0) return;  // the solve kernel wrote no record: the slot stays "never written"
   const size_t nv = (size_t)n + m;
   double* r = rec0 + (size_t)inst * (nv + altro::MLOG_TAIL);
   const double* u = U + ((size_t)inst * 2 + cur[inst]) * (size_t)(N - 1) * m;
@@ -76,6 +77,45 @@ __global__ void k_log_polished_wide(double* __restrict__ rec0, const double* __r
   r[nv] = cost[inst];
   r[nv + 1] = cmax[inst];
   reinterpret_cast<int*>(r + nv + 2)[2] = status[inst];
+}
+
+// The stored gains of every instance are no longer valid (a setter changed something they depend on) and the next launch is
+// masked: the flag that says so is one per handle, and the launch clears it for the instances it runs only.  So the
+// inactive instances lose their stored pass here, word 128 of their reuse state (solve_wide.h: bw_ok).
+__global__ void k_drop_stored_pass(unsigned* __restrict__ bwst, int B) {
+  const int inst = blockIdx.x * blockDim.x + threadIdx.x;
+  if (inst < B) bwst[(size_t)inst * 136 + 128] = 0u;
+}
+
+// altro_batch_restart_instances on this backend (the twin of altro_batch.hip's k_restart): one block of 64 threads per
+// instance; a selected instance takes rows `inst` of (X, U) into its current planes and goes back to what a freshly created
+// handle holds -- zero duals, penalty 1.0, a zeroed reuse state (no stored pass, default roles of the active-set planes,
+// which are cleared too) and the statistics of an instance that has not been solved.  The accumulating counters stay.
+__global__ void __launch_bounds__(64) k_restart_wide(const int* __restrict__ which, const double* __restrict__ Xs, const double* __restrict__ Us,
+                                                     Params P) {
+  const int inst = blockIdx.x, T = threadIdx.x;
+  if (which[inst] == 0) return;
+  const size_t N = P.N, n = P.n, m = P.m, z = n + m, pl = (size_t)inst * 2 + P.cur[inst];
+  if (Xs != nullptr)
+    for (size_t e = T; e < N * n; e += 64) P.X[pl * N * n + e] = Xs[(size_t)inst * N * n + e];
+  for (size_t e = T; e < (N - 1) * m; e += 64) P.U[pl * (N - 1) * m + e] = Us[(size_t)inst * (N - 1) * m + e];
+  for (size_t e = T; e < N * 2 * z; e += 64) P.Lb[(size_t)inst * N * 2 * z + e] = 0.0;
+  for (size_t e = T; e < N * (size_t)P.Pn; e += 64) P.Lc[(size_t)inst * N * P.Pn + e] = 0.0;
+  for (size_t e = T; e < 136; e += 64) P.bwst[(size_t)inst * 136 + e] = 0u;
+  for (size_t e = T; e < 3 * N * 64; e += 64) P.aset[(size_t)inst * 3 * N * 64 + e] = 0;
+  if (T < ALTRO_TRACE_LEN) {
+    P.Jtrace[(size_t)inst * ALTRO_TRACE_LEN + T] = 0.0;
+    P.ctrace[(size_t)inst * ALTRO_TRACE_LEN + T] = 0.0;
+    P.atrace[(size_t)inst * ALTRO_TRACE_LEN + T] = 0.0;
+  }
+  if (T == 0) {
+    P.mu[inst] = 1.0;
+    P.iters[inst] = 0;
+    P.iters_outer[inst] = 0;
+    P.status[inst] = ALTRO_UNSOLVED;
+    P.cost[inst] = 0.0;
+    P.cmax[inst] = 0.0;
+  }
 }
 
 struct WideBackend {
@@ -86,6 +126,7 @@ struct WideBackend {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool timed = false;
   altro::LaunchRing ring;
+  altro::InstanceFlags flags;  // active mask and restart selection, [batch] (device_io.h)
   std::string err;
   // device
   double *A = nullptr, *Bm = nullptr, *f = nullptr, *wd = nullptr, *wf = nullptr, *zmin = nullptr, *zmax = nullptr;
@@ -206,6 +247,7 @@ struct WideBackend {
     for (void* p : ptrs)
       if (p) hipFree(p);
     ring.destroy();
+    flags.destroy();
     for (hipEvent_t e : bench_ev) hipEventDestroy(e);
     bench_ev.clear();
     if (ev0) hipEventDestroy(ev0);
@@ -624,6 +666,7 @@ struct WideBackend {
     p.dyn_blocks = dyn_blocks; p.dyn_step_stride = dyn_step_stride;
     p.compact = compact();
     p.mlog = mlog;   // (the kernel writes it in MPC steps only: mpc == 1)
+    p.active = flags.mask();
     p.o = o;
     if (o.projected_newton) {  // solve!(::ALTROSolver): the AL stage only has to reach the polish's tolerance
       if (o.projected_newton_tolerance >= 0) p.o.constraint_tolerance = o.projected_newton_tolerance;
@@ -742,6 +785,8 @@ struct WideBackend {
     WCHK(ring.next(&h0, &h1));
     WCHK(hipEventRecord(ev0, stream));
     WCHK(hipEventRecord(h0, stream));
+    if (flags.on && !gains_valid && !debug_keep_gains)   // the instances this launch leaves out lose their stored pass too
+      hipLaunchKernelGGL(k_drop_stored_pass, dim3((unsigned)((d.batch + 255) / 256)), dim3(256), 0, stream, bwst, d.batch);
     if (o.projected_newton && mpc) {
       // the steps of a fused launch as nsteps pairs of (one-step solve kernel, polish kernel): the next step's shift starts
       // from the polished trajectory and the projected multipliers, as after solve!(::ALTROSolver)
@@ -755,7 +800,7 @@ struct WideBackend {
         if (!rc && mlog) {
           double* rec0 = mlog + (size_t)(first_step + s) * (size_t)d.batch * mlog_rec();
           hipLaunchKernelGGL(k_log_polished_wide, dim3((unsigned)((d.batch + 255) / 256)), dim3(256), 0, stream, rec0, U, cur, cost, cmax, status,
-                             d.batch, d.N, d.n, d.m);
+                             flags.mask(), d.batch, d.N, d.n, d.m);
           if (hipGetLastError() != hipSuccess) { err = "launch of the log kernel failed"; rc = ALTRO_ERR_HIP; }
         }
       }
@@ -794,6 +839,7 @@ struct WideBackend {
   // benchmark_solve!(solver; samples, evals): see include/altro_batch.h
   int benchmark_solve(int samples, int evals, float* sample_ms) {
     if (samples < 1 || evals < 1) WFAIL(ALTRO_ERR_INVALID_ARG, "samples and evals must be positive");
+    if (flags.on) WFAIL(ALTRO_ERR_STATE, "altro_batch_benchmark_solve restores and repeats whole batches: clear the active mask first");
     WCHK(hipSetDevice(device));
     const size_t B = d.batch, lx = (size_t)d.N * d.n, lu = (size_t)(d.N - 1) * d.m;
     if (!Xsave) WCHK(hipMalloc(&Xsave, B * lx * sizeof(double)));
@@ -826,6 +872,27 @@ struct WideBackend {
       if (sample_ms) sample_ms[s_] = ms / (float)evals;
     }
     WCHK(hipStreamSynchronize(stream));
+    return ALTRO_OK;
+  }
+
+  // altro_batch_restart_instances(_dev): which [B], Xs [B][N][n] (may be null), Us [B][N-1][m]; dev: device arrays, already
+  // validated, read where they are and nothing synchronises; else host arrays through the staging buffer
+  int restart(const int32_t* which, const double* Xs, const double* Us, bool dev) {
+    WCHK(hipSetDevice(device));
+    int rc = pack_constraints();   // (before the first solve: the dual rows of constraints added so far must exist)
+    if (rc) return rc;
+    const size_t B = d.batch, lx = (size_t)d.N * d.n, lu = (size_t)(d.N - 1) * d.m;
+    if (!dev) {
+      if ((rc = ensure_stage(B * (lx + lu) * sizeof(double)))) return rc;
+      if (Xs) WCHK(hipMemcpyAsync(stage, Xs, B * lx * sizeof(double), hipMemcpyHostToDevice, stream));
+      WCHK(hipMemcpyAsync(stage + B * lx, Us, B * lu * sizeof(double), hipMemcpyHostToDevice, stream));
+      Xs = Xs ? stage : nullptr;
+      Us = stage + B * lx;
+    }
+    WCHK(flags.load(true, which, dev, (int)B, (int)B, stream));
+    hipLaunchKernelGGL(k_restart_wide, dim3((unsigned)B), dim3(64), 0, stream, flags.which, Xs, Us, params());
+    WCHK(hipGetLastError());
+    if (!dev) WCHK(hipStreamSynchronize(stream));
     return ALTRO_OK;
   }
 

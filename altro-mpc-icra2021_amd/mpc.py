@@ -128,6 +128,11 @@ class BatchMPC:
         s._chk(s._L.altro_batch_get_initial_state(s.h, api._p(out)))
         return out
 
+    def set_active(self, active):
+        """Per-instance active mask of the loop (api.set_active; None clears it): inactive instances take no plant step, are
+        not shifted or solved, and their slots of log() stay never written (iterations = status = -1, NaN)."""
+        api.set_active(self.solver, active)
+
     def enable_log(self, steps):
         """Keep one record per MPC step on the device for steps 0 .. steps-1 (altro_mpc_set_log); 0 switches it off.
         Remembers the initial state the handle holds now: the first row of closed_loop_trajectory()."""
@@ -187,6 +192,7 @@ class TrackMPC:
     step = BatchMPC.step
     step_benchmark = BatchMPC.step_benchmark
     x0 = BatchMPC.x0
+    set_active = BatchMPC.set_active
     enable_log = BatchMPC.enable_log
     log = BatchMPC.log
     closed_loop_trajectory = BatchMPC.closed_loop_trajectory
@@ -205,15 +211,30 @@ class ExternalMPC:
         self.shift = bool(shift)
         self.i = 0
 
-    def tick(self, x0, Xref=None, Uref=None, dynamics=None, out=None):
+    def tick(self, x0, Xref=None, Uref=None, dynamics=None, out=None, active=None, restart=None, U_restart=None):
         """x0 (B, n); Xref (B, N, n) and Uref (B, N-1, m): the new reference window (both or neither); dynamics: an
         api.LinearModel of column-major-stored tensors (api module docstring) -- all GPU tensors on the solver's device.
+        active (B,) int32: the instances this tick shifts and solves; it stays set as the solver's mask (api.set_active).
+        restart (B,) int32: instances that start cold this tick (api.restart_instances) from the controls U_restart
+        (B, N-1, m; default Uref) -- they are not shifted, and are solved if active.  With neither, a mask the solver holds
+        stays in force; restart without active means every instance is active, and leaves no mask set.  For an inactive
+        instance the tensors returned hold its last values.
         Returns (u0, x1, status, iterations) as api.first_knot does (out: tensors to write into)."""
         s = self.solver
         if not api._on_gpu(x0):
             raise ValueError("ExternalMPC.tick takes GPU tensors; the numpy loop is api.set_initial_state / shift_fill / solve")
         if (Xref is None) != (Uref is None):
             raise ValueError("tick: give Xref and Uref together")
+        shift_mask = None
+        if restart is not None:
+            if U_restart is None:
+                U_restart = Uref
+            if U_restart is None:
+                raise ValueError("tick: restart needs U_restart (or the Uref of the same tick)")
+            if self.shift:   # mask arithmetic on the caller's stream, before the bracket: a restarted instance is not shifted
+                import torch
+                on = active if active is not None else torch.ones_like(restart)
+                shift_mask = ((on != 0) & (restart == 0)).to(torch.int32)
         _lib.check_single_runtime()
         api.wait_stream(s)
         try:
@@ -222,8 +243,18 @@ class ExternalMPC:
                 api._update_trajectory_dev(s, Xref, Uref)
             if dynamics is not None:
                 api._set_dynamics_dev(s, dynamics)
+            if restart is not None:
+                api._restart_instances_dev(s, restart, U_restart)
             if self.shift:
+                if shift_mask is not None:
+                    api._set_active_dev(s, shift_mask)
+                elif active is not None:
+                    api._set_active_dev(s, active)
                 api.shift_fill(s, True, True)
+            if active is not None:
+                api._set_active_dev(s, active)
+            elif shift_mask is not None:     # no mask given: the shift's was this tick's own
+                api.set_active(s, None)
             api.solve_async(s)
             res = api._first_knot_dev(s, out)
         finally:

@@ -246,7 +246,8 @@ int32_t altro_batch_synchronize(altro_handle* h);
  * and times stored in the reference's *.jld2 files measure (the statistics of the LAST repetition;
  * random_linear_problem.jl:171-173).  On return the handle holds the result of the last repetition.
  * sample_ms (may be NULL) receives `samples` values: device time of one sample divided by evals,
- * i.e. BenchmarkTools' per-evaluation time of each sample, in ms for the whole batch.  Synchronous. */
+ * i.e. BenchmarkTools' per-evaluation time of each sample, in ms for the whole batch.  Synchronous.
+ * ALTRO_ERR_STATE while an active mask is set (altro_batch_set_active). */
 int32_t altro_batch_benchmark_solve(altro_handle* h, int32_t samples, int32_t evals, float* sample_ms);
 
 /* states(solver), controls(solver), Altro.get_duals: random_linear_problem.jl:177-181 */
@@ -461,8 +462,46 @@ int32_t altro_batch_get_initial_state_dev(altro_handle* h, double* x0);
 /* What an MPC consumer reads each tick (altro_solver.jl:84-88: the forces of knot 1; random_linear_problem.jl:125-129: the
  * plant step from the first control), in one kernel that reads the current trajectory directly: u0 [batch][m] the first
  * control, x1 [batch][n] the state the model predicts after it (knot 1), status, iterations [batch] int32 as
- * altro_batch_get_stats reports them.  Any pointer may be NULL (skipped). */
+ * altro_batch_get_stats reports them.  Any pointer may be NULL (skipped).  For an instance that is inactive
+ * (altro_batch_set_active) these are its LAST values: those of the last solve it took part in. */
 int32_t altro_batch_get_first_knot_dev(altro_handle* h, double* u0, double* x1, int32_t* status, int32_t* iterations);
+
+/* ---- per-instance active mask and cold restart: ragged batches of closed loops.
+ * The reference runs one problem per loop, and a loop that ends simply stops calling solve! (simple_rocket.jl:137-205); in a
+ * batch the instance whose rocket has landed, or whose episode has ended and is re-spawned, sits among others that go on.
+ *
+ * Active mask.  active [batch], nonzero = active; NULL = every instance (the default: with no mask set nothing differs, bit for
+ * bit).  The library copies the array into a buffer of its own and keeps no caller pointer.  While a mask is set,
+ * altro_batch_solve / _solve_async, altro_batch_shift_fill, altro_mpc_step_async / _run_async / _prepare_async and the
+ * projected-Newton polish behind them (projected_newton = 1) launch work for the active instances only.  For an inactive
+ * instance NOTHING the library owns changes: trajectory, current plane and x0 (it takes no plant step inside a fused run),
+ * the duals of every constraint, the penalty, the statistics (iterations, status, cost, c_max, the three traces), gains, gain
+ * factors and their validity, every work / solve / confirm / reuse counter, the polish statistics, and its slots of the MPC
+ * log, which stay in the "never written" state of altro_mpc_get_log.  The results of an active instance are bit-identical to
+ * those of the same call sequence on a handle with no mask.  Setters and getters are not masked: the caller may write x0 or a
+ * reference for any instance.  A launch under a mask with no active instance is still a launch: it takes its slot of
+ * altro_batch_timing_get.  altro_batch_benchmark_solve with a mask set returns ALTRO_ERR_STATE (its restore / repeat protocol
+ * is about whole batches).
+ * altro_batch_set_active_dev: `active` on the device, under the rules of the device-pointer block above (validated before
+ * anything is enqueued, stream-ordered, no host synchronisation, no allocation after the first call); it leaves the handle in
+ * the device state its host twin would.  altro_batch_get_active: the mask in force as 0 / 1, all ones when none is set;
+ * synchronises the stream.
+ * ALTRO_ERR_INVALID_ARG (nothing changes): NULL handle; get_active: NULL array; _dev: what the device-pointer block refuses. */
+int32_t altro_batch_set_active(altro_handle* h, const int32_t* active);
+int32_t altro_batch_set_active_dev(altro_handle* h, const int32_t* active);
+int32_t altro_batch_get_active(altro_handle* h, int32_t* active);
+/* Cold restart of single instances.  which [batch], nonzero selects an instance; X [batch][N][n] (may be NULL, as in
+ * altro_batch_set_initial_trajectory) and U [batch][N-1][m]: only the rows of selected instances are read.  For each selected
+ * instance the trajectory becomes (X, U), the duals of every constraint become zero, the penalty becomes the initial value a
+ * new handle holds, the stored gains are dropped (no valid gains, active set cleared), and status becomes ALTRO_UNSOLVED with
+ * iteration counts, cost, c_max and traces as a new handle holds them.  Instances not selected are untouched, bit for bit, and
+ * the counters that accumulate since altro_batch_timing_reset are not reset.  x0 and the reference are the caller's to set.
+ * Contract: the next solve of a restarted instance gives, bit for bit, what a freshly created handle given the same problem
+ * data, that instance's x0, reference and (X, U) gives on its first solve.  Independent of the active mask.
+ * _dev: which, X, U on the device, under the rules of the device-pointer block.
+ * ALTRO_ERR_INVALID_ARG (nothing changes, the handle stays usable): NULL handle, NULL which or U; _dev: what that block refuses. */
+int32_t altro_batch_restart_instances(altro_handle* h, const int32_t* which, const double* X, const double* U);
+int32_t altro_batch_restart_instances_dev(altro_handle* h, const int32_t* which, const double* X, const double* U);
 /* Stream hand-over without the host: an event recorded on one stream and waited on by the other (the events belong to the
  * handle and are reused).  wait_stream: work enqueued on the handle's stream from now on starts after everything enqueued so
  * far on `producer` (a hipStream_t).  signal_stream: work enqueued on `consumer` from now on starts after everything enqueued
