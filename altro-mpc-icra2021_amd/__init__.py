@@ -15,4 +15,4 @@ from .api import (ALTROSolver, AltroError, BoundConstraint, ConstraintList, Goal
                   SolverOptions, TrackingObjective, benchmark_solve, confirm_counter, reuse_counter, polish_stats, polish_dual_residuals, controls, cost, get_duals, initial_controls,
                   iterations, max_violation, set_duals, set_initial_state, set_options, set_tracking_cost, shift_fill,
                   solve, solve_counters, states, stats, status, timing_get, timing_reset, update_constraint_data, update_trajectory,
-                  wave_cycles, work_counters)
+                  wave_cycles, wave_passes, work_counters)

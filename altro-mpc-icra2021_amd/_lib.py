@@ -31,7 +31,7 @@ EXPORTS = [
     "altro_batch_synchronize", "altro_batch_get_states", "altro_batch_get_controls",
     "altro_batch_get_duals", "altro_batch_set_duals", "altro_batch_get_stats",
     "altro_batch_get_alpha_trace", "altro_batch_get_gains", "altro_batch_get_gain_factors", "altro_batch_last_solve_ms", "altro_batch_timing_reset", "altro_batch_timing_get",
-    "altro_batch_get_work_counters", "altro_batch_get_wave_cycles", "altro_batch_get_solve_counters", "altro_mpc_run_async",
+    "altro_batch_get_work_counters", "altro_batch_get_wave_cycles", "altro_batch_get_wave_passes", "altro_batch_get_solve_counters", "altro_mpc_run_async",
     "altro_mpc_set_noise_model", "altro_mpc_set_shift", "altro_mpc_set_track", "altro_mpc_set_noise",
     "altro_mpc_step_async", "altro_batch_get_initial_state", "altro_batch_get_stream",
     "altro_mpc_prepare_async", "altro_batch_benchmark_solve", "altro_mpc_set_dynamics_track",
@@ -181,6 +181,8 @@ def lib():
     L.altro_batch_timing_get.argtypes = [H, C.POINTER(C.c_float), C.c_int32, ip]
     L.altro_batch_get_work_counters.argtypes = [H, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.altro_batch_get_wave_cycles.argtypes = [H, C.POINTER(C.c_int64), C.c_int32, ip]
+    if hasattr(L, "altro_batch_get_wave_passes"):   # (absent from an older build given through ALTRO_HIP_LIB, see below)
+        L.altro_batch_get_wave_passes.argtypes = [H, C.POINTER(C.c_int64), C.c_int32, ip]
     i64 = C.POINTER(C.c_int64)
     L.altro_batch_get_solve_counters.argtypes = [H, i64, i64, i64]
     L.altro_mpc_run_async.argtypes = [H, C.c_int32, C.c_int32]
@@ -244,7 +246,7 @@ def check_single_runtime():
 # harness forwards these variables to its explicit entry point whenever a solver is created (api.ALTROSolver), so that
 # `ALTRO_NO_LONE=1 python tools/...` and pytest's monkeypatch.setenv keep working.  (variable, key, default, negate)
 DEBUG_ENV = [
-    ("ALTRO_NO_LONE", "no_lone", 0), ("ALTRO_NO_SHADOW", "no_shadow", 0), ("ALTRO_NO_RESYNC", "no_resync", 0),
+    ("ALTRO_NO_LONE", "no_lone", 0), ("ALTRO_NO_PAIR", "no_pair", 0), ("ALTRO_NO_SHADOW", "no_shadow", 0), ("ALTRO_NO_RESYNC", "no_resync", 0),
     ("ALTRO_NO_GROUP", "no_group", 0), ("ALTRO_NO_REUSE", "no_reuse", 0), ("ALTRO_NO_QZ_PASS", "no_qz_pass", 0), ("ALTRO_NO_MATE_RANK", "no_mate_rank", 0), ("ALTRO_GROUP_MAX_STEPS", "group_max_steps", 32),
     ("ALTRO_DEBUG_TRACE_WAVE", "trace_wave", -1), ("ALTRO_FORCE_WIDE", "force_wide", 0),
     ("ALTRO_WIDE_COMPACT", "wide_compact", -1), ("ALTRO_WIDE_COOP", "wide_coop", -1),

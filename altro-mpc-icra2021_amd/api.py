@@ -761,6 +761,17 @@ def wave_cycles(solver):
     return out.reshape(-1, 16)
 
 
+def wave_passes(solver):
+    """(waves, 8) per wave of the last solve launch (16-lane kernels): column 0 (every build) backward passes run in the
+    pair form; in the -DALTRO_PHASE_STAMPS build also 1-3 four-row passes with 2, 3 and 4 rows needing them, 4-6 their
+    ticks, 7 the ticks of the pair passes."""
+    cnt = C.c_int32(0)
+    solver._chk(solver._L.altro_batch_get_wave_passes(solver.h, None, 0, C.byref(cnt)))
+    out = np.zeros(cnt.value, dtype=np.int64)
+    solver._chk(solver._L.altro_batch_get_wave_passes(solver.h, out.ctypes.data_as(C.POINTER(C.c_int64)), cnt.value, C.byref(cnt)))
+    return out.reshape(-1, 8)
+
+
 def solve_counters(solver):
     """(solves, iLQR iterations, SOLVE_SUCCEEDED count) per instance since timing_reset."""
     i64 = C.POINTER(C.c_int64)

@@ -34,7 +34,7 @@ static thread_local std::string g_create_err;
 // a measuring tool that wants a scheduling feature off says so through the entry point -- with a null handle for the
 // handles this thread creates afterwards, with a handle for that handle.
 struct DebugSwitches {
-  int lone = 1, shadow = 1, resync = 1, reuse = 1, useqz = 1, mate = 1;
+  int lone = 1, pair = 1, shadow = 1, resync = 1, reuse = 1, useqz = 1, mate = 1;
   int group = 1;             // 0 off, 1 sorted, 2-4: other slot orders (k_group_rank)
   int group_max_steps = 32;
   int trace_wave = -1;       // -DALTRO_PHASE_STAMPS builds
@@ -87,6 +87,7 @@ struct altro_handle {
   bool d_in_kd = false;  // the last solve launch's kernel keeps d in the gain rows (altro::kd_holds_d), not in Dff
   int reuse = 1;  // gain reuse (solve_dpp16.h fosweep); "no_reuse" switches it off (tests)
   int lone = 1;  // backward_lone (solve_dpp16.h); "no_lone" switches it off (tests: lone == four-row pass bit for bit)
+  int pair = 1;  // backward_pair (two rows need a pass); "no_pair" keeps the four-row form for them
   int group_max_steps = 32;  // fused launches of more steps are not grouped ("group_max_steps": diagnostic)
   int shadow = 1;  // "no_shadow": rows that sit a phase out keep their own instance (solve_dpp16.h shadow_enter)
   int useqz = 1;   // "no_qz_pass": backward passes always recompute their cost / box expansion (solve_dpp16.h backward QV)
@@ -585,7 +586,7 @@ static int launch_solve(altro_handle* h, int first_step, int nsteps, int prepare
   p.Gcol = h->Gcol; p.Grow = h->Grow; p.fvec = h->fvec;
   p.wd = h->wd; p.wf = h->wf; p.zmin = h->zmin; p.zmax = h->zmax; p.imask = tab_imask(h);
   p.x0 = h->x0; p.Zref = h->Zref; p.Z = h->Z; p.cur = h->cur;
-  p.Lb = h->Lb; p.bslot = h->bslot; p.nbp = h->nbp; p.mu = h->mu; p.lone = h->lone; p.useqz = h->useqz; p.shadow = h->shadow; p.reuse = h->reuse; p.resync = h->resync; p.dbg_wave = h->dbg_wave;
+  p.Lb = h->Lb; p.bslot = h->bslot; p.nbp = h->nbp; p.mu = h->mu; p.lone = h->lone; p.pair = h->pair; p.useqz = h->useqz; p.shadow = h->shadow; p.reuse = h->reuse; p.resync = h->resync; p.dbg_wave = h->dbg_wave;
   p.Dff = h->Dff; p.ahash = h->ahash; p.kmu = h->kmu; p.n_fo = h->n_fo;
   p.Qz = h->Qz;
   p.Acon = h->Acon; p.bcon = h->bcon; p.cmeta = h->cmeta; p.ckn = h->ckn; p.con_inv = h->con_inv;
@@ -724,9 +725,10 @@ int32_t altro_debug_set(altro_handle* h, const char* key, int32_t value) {
     }
     DebugSwitches tmp;
     DebugSwitches& d = h ? tmp : g_dbg;
-    if (h) { tmp.mate = h->mate; tmp.lone = h->lone; tmp.useqz = h->useqz; tmp.shadow = h->shadow; tmp.resync = h->resync; tmp.reuse = h->reuse; tmp.group = h->group;
+    if (h) { tmp.mate = h->mate; tmp.lone = h->lone; tmp.pair = h->pair; tmp.useqz = h->useqz; tmp.shadow = h->shadow; tmp.resync = h->resync; tmp.reuse = h->reuse; tmp.group = h->group;
              tmp.group_max_steps = h->group_max_steps; tmp.trace_wave = h->dbg_wave; }
     if (k == "no_lone") d.lone = value ? 0 : 1;
+    else if (k == "no_pair") d.pair = value ? 0 : 1;
     else if (k == "no_qz_pass") d.useqz = value ? 0 : 1;
     else if (k == "no_shadow") d.shadow = value ? 0 : 1;
     else if (k == "no_resync") d.resync = value ? 0 : 1;
@@ -740,7 +742,7 @@ int32_t altro_debug_set(altro_handle* h, const char* key, int32_t value) {
     if (h && !h->wide) {
       const bool reuse_changed = h->reuse != tmp.reuse;
       h->mate = tmp.mate;
-      h->lone = tmp.lone; h->useqz = tmp.useqz; h->shadow = tmp.shadow; h->resync = tmp.resync; h->reuse = tmp.reuse; h->group = tmp.group;
+      h->lone = tmp.lone; h->pair = tmp.pair; h->useqz = tmp.useqz; h->shadow = tmp.shadow; h->resync = tmp.resync; h->reuse = tmp.reuse; h->group = tmp.group;
       h->group_max_steps = tmp.group_max_steps; h->dbg_wave = tmp.trace_wave;
       if (reuse_changed) { HIPCHK(h, hipSetDevice(h->device)); return drop_gains(h); }
     }
@@ -850,7 +852,7 @@ int32_t altro_batch_create(const altro_dims* dims, const altro_opts* opts, int32
     if (opts) h->o = *opts; else altro_default_opts(&h->o);
     h->device = device;
     h->mate = g_dbg.mate;
-    h->lone = g_dbg.lone; h->useqz = g_dbg.useqz; h->shadow = g_dbg.shadow; h->resync = g_dbg.resync; h->reuse = g_dbg.reuse; h->group = g_dbg.group;
+    h->lone = g_dbg.lone; h->pair = g_dbg.pair; h->useqz = g_dbg.useqz; h->shadow = g_dbg.shadow; h->resync = g_dbg.resync; h->reuse = g_dbg.reuse; h->group = g_dbg.group;
     h->group_max_steps = g_dbg.group_max_steps; h->dbg_wave = g_dbg.trace_wave; h->debug_keep_gains = g_dbg.keep_gains != 0;
     h->Bp = (dims->batch + IPW - 1) / IPW * IPW;
     auto fail = [&](const char* what, hipError_t er) {
@@ -948,7 +950,7 @@ int32_t altro_batch_create(const altro_dims* dims, const altro_opts* opts, int32
     CCHK(hipMemsetAsync(h->atrace, 0, Bp * ALTRO_TRACE_LEN * sizeof(double), h->stream));
     CCHK(hipMalloc(&h->n_backward, Bp * sizeof(long long)));
     CCHK(hipMalloc(&h->n_rollout, Bp * sizeof(long long)));
-    CCHK(hipMalloc(&h->wave_cycles, (Bp * 4 + 4096) * sizeof(long long)));
+    CCHK(hipMalloc(&h->wave_cycles, (Bp * 6 + 4096) * sizeof(long long)));
     CCHK(hipMalloc(&h->simd_tab, (size_t)65536 * 16 * sizeof(unsigned)));
     CCHK(hipMemsetAsync(h->simd_tab, 0, (size_t)65536 * 16 * sizeof(unsigned), h->stream));
     CCHK(hipMalloc(&h->n_solves, Bp * sizeof(long long)));
@@ -963,7 +965,7 @@ int32_t altro_batch_create(const altro_dims* dims, const altro_opts* opts, int32
     CCHK(hipMemsetAsync(h->n_solves, 0, Bp * sizeof(long long), h->stream));
     CCHK(hipMemsetAsync(h->n_iters, 0, Bp * sizeof(long long), h->stream));
     CCHK(hipMemsetAsync(h->n_ok, 0, Bp * sizeof(long long), h->stream));
-    CCHK(hipMemsetAsync(h->wave_cycles, 0, (Bp * 4 + 4096) * sizeof(long long), h->stream));
+    CCHK(hipMemsetAsync(h->wave_cycles, 0, (Bp * 6 + 4096) * sizeof(long long), h->stream));
     CCHK(hipMemsetAsync(h->n_backward, 0, Bp * sizeof(long long), h->stream));
     CCHK(hipMemsetAsync(h->n_rollout, 0, Bp * sizeof(long long), h->stream));
     CCHK(hipMemsetAsync(h->Z, 0, (2 * N + 1) * row * sizeof(double), h->stream));
@@ -2003,6 +2005,19 @@ int32_t altro_batch_get_wave_cycles(altro_handle* h, int64_t* cycles, int32_t ca
     const int32_t n = h->Bp / IPW * 16 + ((capacity >= h->Bp / IPW * 16 + 4096) ? 4096 : 0);
     *count = n;
     if (cycles) HIPCHK(h, hipMemcpy(cycles, h->wave_cycles, (size_t)(n < capacity ? n : capacity) * sizeof(long long), hipMemcpyDeviceToHost));
+    return ALTRO_OK;
+  });
+}
+
+int32_t altro_batch_get_wave_passes(altro_handle* h, int64_t* passes, int32_t capacity, int32_t* count) {
+  return guard(h, [&]() -> int32_t {
+    if (h && h->wide) { if (count) *count = 0; return ALTRO_OK; }
+    if (!h || !count) return ALTRO_ERR_INVALID_ARG;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const int32_t n = h->Bp / IPW * 8;
+    *count = n;
+    if (passes) HIPCHK(h, hipMemcpy(passes, h->wave_cycles + (size_t)h->Bp / IPW * 16 + 4096, (size_t)(n < capacity ? n : capacity) * sizeof(long long), hipMemcpyDeviceToHost));
     return ALTRO_OK;
   });
 }

@@ -154,6 +154,7 @@ struct SolveParams {
   int resync;            // 1: rows wait a turn to stay in step with their wave-mates (run(), phase A)
   int reuse;             // 1: gain reuse (fosweep) allowed; ALTRO_NO_REUSE=1 at create time switches it off
   int shadow;  // rows that sit a phase out take the identity of a row that takes part (Solver::shadow_enter)
+  int pair;              // 1: a backward pass that exactly two rows of a wave need runs two DPP rows per instance (backward_pair)
   int lone;              // 1: a backward pass that only one row of a wave needs runs spread over the four DPP rows (backward_lone)
   int useqz;             // 1: a backward pass over a trajectory a rollout has just produced reads its expansion back from Qz (backward QV)
   // generic affine constraints (LINEAR eq/ineq, SOC): up to 16 constraint rows per knot, row r
@@ -198,7 +199,8 @@ struct SolveParams {
   long long* n_gconf;    // [Bp] iterations confirmed by the costate sweep instead of a backward pass
   int* dzero;            // [Bp] 1: the feedforward terms of the last solve's last iteration are zero (costate-confirmed)
   unsigned* simd_tab;    // [65536][16] or null: per physical SIMD and wave slot, the work a resident wave has left (see Solver::mate_rank)
-  long long* wave_cycles; // [Bp/4][16] shader cycles of the last launch, per wave (diagnostic):
+  long long* wave_cycles; // [Bp/4][16] shader cycles of the last launch, per wave (diagnostic); behind them 4096 words of
+                          // trace and [Bp/4][8] pass records (altro_batch_get_wave_passes):
                           // total, backward, closed rollouts, open rollouts, todorov, dual update,
                           // streaming line-search sweeps
   double* mlog;          // per-step log of the MPC loop (mpc_log.h): [capacity][B][16 + MLOG_TAIL], or null (off, and in every
@@ -253,6 +255,13 @@ __device__ __forceinline__ bool wave_any(bool p) { return __ballot(p) != 0ull; }
 // cycle stamp for the per-phase diagnostic counters (one asm statement, fenced both sides).
 // Compiled in only with -DALTRO_PHASE_STAMPS (diagnostic build): the accumulators cost
 // registers in the production kernel.
+// -DALTRO_NO_PAIR_PASS compiles the pair pass out: the kernel of the commit before it, for A/B builds and for the rows-alive
+// counters of a phase-stamp build on that kernel (tools/build_stamps.sh -DALTRO_NO_PAIR_PASS)
+#ifdef ALTRO_NO_PAIR_PASS
+#define ALTRO_PAIR_PASS false
+#else
+#define ALTRO_PAIR_PASS true
+#endif
 #ifdef ALTRO_PHASE_STAMPS
 #define ALTRO_STAMP(x) x
 #else
@@ -439,6 +448,7 @@ struct Solver {
   unsigned* simd_row = nullptr;  // this wave's SIMD in P.simd_tab (16 wave slots), or null
   unsigned wave_slot = 0;
   int turns = 0;           // turns of the wave loop so far
+  int n_pair = 0;          // backward passes of this launch that ran as backward_pair (altro_batch_get_wave_passes [0])
   int n_lone = 0;          // backward passes of this launch that ran as backward_lone (diagnostic, wave_cycles[7])
   ASet* ah;    // this lane's active set of the backward pass that left the gains in KD (LDS; kept in P.ahash between launches)
   ASet* qhs;   // this lane's active set of the trajectory in Qz (LDS)
@@ -450,7 +460,8 @@ struct Solver {
   unsigned lslot;    // this lane's slot in the compact dual rows (0 for unbounded lanes: dummy)
   bool bounded;
   ALTRO_STAMP(long long t_bw; long long t_rc; long long t_ro; long long t_td; long long t_du; long long t_ls; long long t_fo; long long t_aj; long long t_bl;
-              long long c_bw; long long c_fo; long long c_aj; long long c_rc; long long c_ls; long long t_start;)
+              long long c_bw; long long c_fo; long long c_aj; long long c_rc; long long c_ls; long long t_start;
+              long long c_b2; long long c_b3; long long c_b4; long long t_b2; long long t_b3; long long t_b4; long long t_bp;)   // four-row passes by rows alive (2, 3, 4): how many, ticks; pair passes: ticks
 
   struct LaneConst {
     double wd, wf, zmin, zmax;
@@ -484,7 +495,8 @@ struct Solver {
       bounded = sl >= 0;
       lslot = bounded ? (unsigned)sl : 0u;
     }
-    ALTRO_STAMP(t_bw = t_rc = t_ro = t_td = t_du = t_ls = t_fo = t_aj = t_bl = c_bw = c_fo = c_aj = c_rc = c_ls = 0;)
+    ALTRO_STAMP(t_bw = t_rc = t_ro = t_td = t_du = t_ls = t_fo = t_aj = t_bl = c_bw = c_fo = c_aj = c_rc = c_ls = 0;
+                c_b2 = c_b3 = c_b4 = t_b2 = t_b3 = t_b4 = t_bp = 0;)
   }
 
   // ---- generic constraint rows (CONES): this lane owns constraint row j of every knot
@@ -2140,6 +2152,266 @@ struct Solver {
     dtiny = !row_any(dbig, lane);
   }
 
+  // ---- pair backward pass ---------------------------------------------------------------------------------
+  // When exactly two rows of the wave need a backward pass, the four-row form runs two DPP rows on operands nobody
+  // reads.  backward_pair() gives each of the two instances two adjacent DPP rows: DPP rows 0-1 work for the first row
+  // that needs the pass, rows 2-3 for the second.  Row r of a pair owns rows r*RLP .. r*RLP + RLP-1 of S, W = S [A B] and
+  // Qxx (row 0 also the vector s) and rows NX + r*RQP.. of [Qux Quu] -- backward_lone's split with two owners, its
+  // all-gather cut to the one v_permlane16_swap level (the pairs never trade with each other); box expansion, L D L',
+  // the gain solves and dV run redundantly in both rows.  Same chains of FMAs in the same order as backward<false, SYM>:
+  // bit-identical (tests: no_pair against the default).  The caller points inst / rowoff / rs / sm / ah / qhs of the
+  // lanes at their pair's row before the call (pair_enter).  rho == 0 only.
+  static __device__ __forceinline__ void pair_gather(double v, double (&o)[2]) {
+    // o[q] = v of the same lane of DPP row q of this lane's pair
+    const int lo = __double2loint(v), hi = __double2hiint(v);
+    const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);  // [0] = rows 0,0 | 2,2   [1] = rows 1,1 | 3,3
+    const auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+    o[0] = __hiloint2double(b[0], a[0]);
+    o[1] = __hiloint2double(b[1], a[1]);
+  }
+  static __device__ __forceinline__ double pair_gather0(double v) {  // v of the same lane of the pair's first DPP row
+    const int lo = __double2loint(v), hi = __double2hiint(v);
+    const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+    const auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+    return __hiloint2double(b[0], a[0]);
+  }
+  // Pair phases: DPP rows 0-1 take the identity of row ra of the wave, DPP rows 2-3 that of row rb (both wave-uniform)
+  __device__ __forceinline__ LoneCtx pair_enter(int ra, int rb) {
+    LoneCtx c{inst, rowoff, rs, sm, ah, qhs};
+    const int ia = __builtin_amdgcn_readlane(inst, ra * LW), ib = __builtin_amdgcn_readlane(inst, rb * LW);
+    const int lrow = (lane < 32) ? ra : rb;
+    inst = (lane < 32) ? ia : ib;
+    rowoff = (unsigned)inst * LW + j;
+    rs = c.rs - (lane >> 4) + lrow;
+    sm = c.sm - (lane >> 4) * (LW * (LW + 1)) + lrow * (LW * (LW + 1));
+    ah = c.ah - lane + lrow * LW + j;
+    qhs = c.qhs - lane + lrow * LW + j;
+    return c;
+  }
+  __device__ __forceinline__ void pair_leave(const LoneCtx& c) { lone_leave(c); }
+
+  template <bool SYM, bool QV = false>   // QV: the expansion read back from Qz and the trajectory's active set (see backward())
+  __device__ void backward_pair(double& dV1, double& dV2, bool& fail, bool& dtiny) {
+    using BK = Blk<NX, NU>;
+    constexpr int RL = BK::RLP, RQ = BK::RQP;
+    phase_begin();
+    const int rr = (lane >> 4) & 1;  // the half of its instance this DPP row owns
+    const LaneConst lc = consts();
+    const double mu = rs->mu;
+    const int kref = rs->kref;
+    const unsigned zs = plane(rs->cur);
+    // g: [A B] by columns as in backward(); gp: the columns this row's own output rows need as broadcast operands,
+    // moved to lanes 0..: lane t < RL holds column rr*RL + t, lane RL + u holds control column NX + rr*RQ + u
+    double g[NX], gp[NX];
+    {
+      const int pc = (j < RL) ? rr * RL + j : NX + rr * RQ + (j - RL);
+      const bool pv = (j < RL) ? (rr * RL + j < NX) : ((j - RL < RQ) && (rr * RQ + (j - RL) < NU));
+      sfor<0, NX>([&](auto c) {
+        constexpr int C = decltype(c)::value;
+        g[C] = ldg(P.Gcol, ((unsigned)inst * NX + C) * LW + j);
+        const double v = ldg(P.Gcol, ((unsigned)inst * NX + C) * LW + (pv ? pc : 0));
+        gp[C] = pv ? v : 0.0;
+      });
+    }
+    const int N = P.N;
+    // which global row of S / Qxx a local slot of this DPP row holds, and whether this lane is its diagonal
+    bool diag_x[RL], own_x[RL], diag_u[RQ];
+    sfor<0, RL>([&](auto t) {
+      constexpr int Tt = decltype(t)::value;
+      own_x[Tt] = rr * RL + Tt < NX;
+      diag_x[Tt] = own_x[Tt] & (j == rr * RL + Tt);
+    });
+    sfor<0, RQ>([&](auto u) {
+      constexpr int U = decltype(u)::value;
+      diag_u[U] = (rr * RQ + U < NU) & (j == NX + rr * RQ + U);
+    });
+    const int psrc = (lane & 48) + ((rr * RL + j) & 15);  // lane whose [Qux] entry slot j of this row's S rows needs
+    ASet* const ta = ah;   // (pair_enter has pointed it at the instance's set; both DPP rows OR the same bits)
+    if constexpr (QV) aset_copy(ta, qhs);
+    else aset_clear(ta);
+    double Sl[RL + 1];
+    {
+      const int k = N - 1;
+      double qz, hz;
+      if constexpr (QV) {
+        qz = ldg(P.Qz, qat(k));
+        hz = hz_of(lc.wf, mu, aset_get(qhs, k));
+      } else {
+        const double z = ldg(P.Z, zs + zat(k));
+        const double zr = ldg(P.Zref, rat(kref + k));
+        const double lhi = ldg(P.Lb, lb_at(k, 0)), llo = ldg(P.Lb, lb_at(k, 1));
+        qz = lc.wf * (z - zr);
+        hz = lc.wf;
+        unsigned codeT;
+        box_expand(lc, mu, z, lhi, llo, box_at(k) & is_x, qz, hz, codeT);
+        aset_add(ta, codeT, k);
+      }
+      sfor<0, RL>([&](auto t) { Sl[decltype(t)::value] = diag_x[decltype(t)::value] ? hz : 0.0; });
+      Sl[RL] = (is_x & (rr == 0)) ? qz : 0.0;
+    }
+    dV1 = 0.0;
+    dV2 = 0.0;
+    fail = false;
+    bool dbig = false;
+    double* my = sm;
+    double z = ldg(P.Z, zs + zat(N - 2)), zr = QV ? ldg(P.Qz, qat(N - 2)) : ldg(P.Zref, rat(kref + N - 2));   // QV: zr carries Qz
+    double lhi = 0.0, llo = 0.0;
+    if constexpr (!QV) {
+      lhi = ldg(P.Lb, lb_at(N - 2, 0));
+      llo = ldg(P.Lb, lb_at(N - 2, 1));
+    }
+    asm volatile("" : "+v"(z), "+v"(zr));  // waited for once, outside the loop: see backward()
+    if constexpr (!QV) asm volatile("" : "+v"(lhi), "+v"(llo));
+    for (int k = N - 2; k >= 0; --k) {  // body: one basic block
+      const int km = imax(k - 1, 0);
+      const double zn = ldg(P.Z, zs + zat(km));
+      const double zrn = QV ? ldg(P.Qz, qat(km)) : ldg(P.Zref, rat(kref + km));
+      double lhin = 0.0, llon = 0.0;
+      if constexpr (!QV) {
+        lhin = ldg(P.Lb, lb_at(km, 0));
+        llon = ldg(P.Lb, lb_at(km, 1));
+      }
+      double qz, hz;
+      if constexpr (QV) {
+        qz = zr;
+        hz = hz_of(lc.wd, mu, aset_get(qhs, k));
+      } else {
+        qz = lc.wd * (z - zr);
+        hz = lc.wd;
+        unsigned code;
+        box_expand(lc, mu, z, lhi, llo, box_at(k), qz, hz, code);
+        aset_add(ta, code, k);
+      }
+      // this row's rows of W = [S; s'] G
+      double wl[RL + 1];
+      sfor<0, RL + 1>([&](auto t) { wl[decltype(t)::value] = 0.0; });
+      BK::SGP(wl, Sl, g);
+      // all rows of W to both DPP rows of the pair
+      double wa[NX + 1];
+      sfor<0, RL>([&](auto t) {
+        constexpr int Tt = decltype(t)::value;
+        double o[2];
+        pair_gather(wl[Tt], o);
+        sfor<0, 2>([&](auto q) {
+          constexpr int Q = decltype(q)::value;
+          if constexpr (Q * RL + Tt < NX) wa[Q * RL + Tt] = o[Q];
+        });
+      });
+      wa[NX] = pair_gather0(wl[RL]);
+      // this row's rows of H = G' W + diag(lzz): RL rows of Qxx, RQ rows of [Qux Quu]
+      double hl[RL + RQ];
+      sfor<0, RL>([&](auto t) { hl[decltype(t)::value] = diag_x[decltype(t)::value] ? hz : 0.0; });
+      sfor<0, RQ>([&](auto u) { hl[RL + decltype(u)::value] = diag_u[decltype(u)::value] ? hz : 0.0; });
+      BK::GTWP(hl, gp, wa);
+      const double gz = qz + wa[NX];  // Qx[j] on x lanes, Qu[a] on u lanes
+      // rows of [Qux Quu] to both DPP rows: hq[a] = what backward() calls h[NX + a]
+      double hq[NU];
+      sfor<0, RQ>([&](auto u) {
+        constexpr int U = decltype(u)::value;
+        double o[2];
+        pair_gather(hl[RL + U], o);
+        sfor<0, 2>([&](auto q) {
+          constexpr int Q = decltype(q)::value;
+          if constexpr (Q * RQ + U < NU) hq[Q * RQ + U] = o[Q];
+        });
+      });
+      // the broadcast operand of S = Qxx + Qux'K on this row's rows: Qux[a][i] of row i = rr*RL + t sits on lane i
+      // (requested here: the ds_bpermute round trip hides behind the factorisation)
+      double rp[NU];
+      sfor<0, NU>([&](auto a) { rp[decltype(a)::value] = lane_gather(hq[decltype(a)::value], psrc); });
+      double quu[NU][NU];
+      double qu[NU];
+      sfor<0, NU>([&](auto a) {
+        constexpr int A = decltype(a)::value;
+        qu[A] = bcast<NX + A>(gz);
+        sfor<0, A + 1>([&](auto b) {
+          constexpr int Bq = decltype(b)::value;
+          quu[A][Bq] = bcast<NX + Bq>(hq[A]);
+        });
+      });
+      double L[NU][NU], Ld[NU][NU], dinv[NU];
+      sfor<0, NU>([&](auto jc) {
+        constexpr int Jc = decltype(jc)::value;
+        double dd = quu[Jc][Jc];
+        sfor<0, Jc>([&](auto kk) {
+          constexpr int Kk = decltype(kk)::value;
+          dd -= L[Jc][Kk] * Ld[Jc][Kk];
+        });
+        fail = fail | !(dd > 0.0);
+        dinv[Jc] = rcp_nr(dd);
+        sfor<Jc + 1, NU>([&](auto ii) {
+          constexpr int I = decltype(ii)::value;
+          double v = quu[I][Jc];
+          sfor<0, Jc>([&](auto kk) {
+            constexpr int Kk = decltype(kk)::value;
+            v -= L[I][Kk] * Ld[Jc][Kk];
+          });
+          Ld[I][Jc] = v;
+          L[I][Jc] = v * dinv[Jc];
+        });
+      });
+      double r[NU], kd[NU];
+      sfor<0, NU>([&](auto a) {
+        constexpr int A = decltype(a)::value;
+        r[A] = is_x ? hq[A] : qu[A];
+      });
+      {
+        double y[NU];
+        sfor<0, NU>([&](auto ii) {
+          constexpr int I = decltype(ii)::value;
+          double v = r[I];
+          sfor<0, I>([&](auto kk) { v -= L[I][decltype(kk)::value] * y[decltype(kk)::value]; });
+          y[I] = v;
+        });
+        sfor<0, NU>([&](auto ir) {
+          constexpr int I = NU - 1 - decltype(ir)::value;
+          double v = y[I] * dinv[I];
+          sfor<I + 1, NU>([&](auto kk) { v -= L[decltype(kk)::value][I] * kd[decltype(kk)::value]; });
+          kd[I] = v;
+        });
+        sfor<0, NU>([&](auto a) { kd[decltype(a)::value] = -kd[decltype(a)::value]; });
+      }
+      {
+        double dm = fabs(kd[0]);
+        sfor<1, NU>([&](auto a) { dm = fmax(dm, fabs(kd[decltype(a)::value])); });
+        dbig = dbig | (is_u & !(dm <= 1e-9 * (1.0 + fabs(z))));
+      }
+      double dd_[NU];
+      sfor<0, NU>([&](auto a) { dd_[decltype(a)::value] = bcast<NX>(kd[decltype(a)::value]); });
+      double snew = gz, t1 = 0.0;
+      sfor<0, NU>([&](auto a) {
+        constexpr int A = decltype(a)::value;
+        snew += r[A] * dd_[A];
+        t1 += dd_[A] * qu[A];
+      });
+      dV1 += t1;
+      dV2 += -0.5 * t1;
+      store_gains((rr == 0) ? k : N - 1, (rr == 0) ? k : N, kd, L, dinv);  // one row of each pair stores; the other hits the trash slots
+      BK::CTGP0(hl, kd, rp);  // S = Qxx + Qux'K on this row's rows
+      if constexpr (SYM) {
+        sfor<0, RL>([&](auto t) {
+          constexpr int Tt = decltype(t)::value;
+          my[(rr * RL + Tt) * (LW + 1) + j] = hl[Tt];  // rows >= NX of the tile are never read by a state lane
+        });
+        __builtin_amdgcn_wave_barrier();
+        sfor<0, RL>([&](auto t) {
+          constexpr int Tt = decltype(t)::value;
+          const double st = my[j * (LW + 1) + ((rr * RL + Tt) & 15)];
+          Sl[Tt] = 0.5 * (hl[Tt] + st);
+        });
+        __builtin_amdgcn_wave_barrier();
+      } else {
+        sfor<0, RL>([&](auto t) { Sl[decltype(t)::value] = hl[decltype(t)::value]; });
+      }
+      Sl[RL] = (rr == 0) ? snew : 0.0;
+      z = zn;
+      zr = zrn;
+      lhi = lhin;
+      llo = llon;
+    }
+    dtiny = !row_any(dbig, lane);
+  }
+
   // Costate sweep (default mode, box-only problems): lambda_N = l_x(N), lambda_k = l_x(k) + A' lambda_{k+1},
   // g_k = l_u(k) + B' lambda_{k+1} -- the first-order part of the backward pass, one 12-FMA product per knot
   // instead of 396.  l_x, l_u at the current trajectory were left in the plane Qz by the alpha = 1 rollout that
@@ -2478,7 +2750,9 @@ struct Solver {
             const bool with_rho = wave_any(rs->rho != 0.0);
             const unsigned long long bm = __ballot(bwrow);
             const int nbwr = (int)((bm & 1ull) + ((bm >> 16) & 1ull) + ((bm >> 32) & 1ull) + ((bm >> 48) & 1ull));
+            ALTRO_STAMP(int took = 0;)   // 1: lone form, 2: pair form
             if (!CONES && P.lone && !with_rho && nbwr == 1) {
+              ALTRO_STAMP(took = 1;)
               // exactly one row needs the pass: all four DPP rows work on that row's instance (backward_lone)
               const LoneCtx ctx = lone_enter(first_row(bm));
               double a1, a2;
@@ -2495,6 +2769,34 @@ struct Solver {
                 dtiny = dt;
               }
               n_lone++;
+            } else if (ALTRO_PAIR_PASS && NX == 12 && !CONES && P.lone && P.pair && !with_rho && nbwr == 2) {
+              ALTRO_STAMP(took = 2;)
+              // exactly two rows need the pass: two DPP rows for each of their instances (backward_pair)
+              if constexpr (ALTRO_PAIR_PASS && NX == 12 && !CONES) {
+                const int ra = (bm & 1ull) ? 0 : (((bm >> 16) & 1ull) ? 1 : 2);
+                const int rb = ((bm >> 48) & 1ull) ? 3 : (((bm >> 32) & 1ull) ? 2 : 1);
+                // the Qz form as in the four-row pass: both rows hold a trajectory a rollout has just produced
+                const bool useq = (P.useqz != 0) && (P.N <= ASET_MAXN) && !wave_any(bwrow && (rs->qvalid == 0));
+                const LoneCtx ctx = pair_enter(ra, rb);
+                double a1, a2;
+                bool pf, dt;
+                if (o.strict) { if (useq) backward_pair<true, true>(a1, a2, pf, dt); else backward_pair<true, false>(a1, a2, pf, dt); }
+                else { if (useq) backward_pair<false, true>(a1, a2, pf, dt); else backward_pair<false, false>(a1, a2, pf, dt); }
+                pair_leave(ctx);
+                // each row of the wave takes the outputs of the DPP rows that worked for it
+                const unsigned long long fb = __ballot(pf), tb = __ballot(dt);
+                const bool second = (lane >> 4) == rb;
+                const double a1b = row_value(a1, 2), a2b = row_value(a2, 2);
+                a1 = row_value(a1, 0);
+                a2 = row_value(a2, 0);
+                fail = bwrow && (((second ? (fb >> 32) : fb) & 0xffffull) != 0ull);
+                if (bwrow) {
+                  dV1 = second ? a1b : a1;
+                  dV2 = second ? a2b : a2;
+                  dtiny = ((second ? (tb >> 32) : tb) & 1ull) != 0ull;
+                }
+                n_pair++;
+              }
             } else {
               double b1, b2;
               bool bt;
@@ -2518,7 +2820,13 @@ struct Solver {
                 dtiny = bt;
               }
             }
-            ALTRO_STAMP(const long long te = stamp() - ts; if (nbwr == 1 && !CONES && P.lone && !with_rho) t_bl += te; else { t_bw += te; c_bw++; })
+            ALTRO_STAMP(const long long te = stamp() - ts;
+                        if (took == 1) t_bl += te;
+                        else if (took == 2) t_bp += te;
+                        else {
+                          t_bw += te; c_bw++;
+                          if (nbwr == 2) { c_b2++; t_b2 += te; } else if (nbwr == 3) { c_b3++; t_b3 += te; } else if (nbwr == 4) { c_b4++; t_b4 += te; }
+                        })
             fail = row_any(fail, lane) && bwrow;
             double rho = rs->rho, drho = rs->drho;
             if (bwrow) rs->kmu = (!fail && rho == 0.0) ? rs->mu : -1.0;
@@ -2832,6 +3140,10 @@ __global__ void __launch_bounds__(64, (CONES || NU > 4) ? 1 : ALTRO_WAVES_PER_SI
     ALTRO_STAMP(wc[1] = s.t_bw; wc[2] = s.t_rc; wc[3] = s.t_ro; wc[4] = s.t_td; wc[5] = s.t_du; wc[6] = s.t_ls; wc[8] = s.t_bl; wc[9] = s.t_fo; wc[10] = s.t_aj;
                 wc[11] = s.c_bw; wc[12] = s.c_fo; wc[13] = s.c_aj; wc[14] = s.c_rc; wc[15] = s.c_ls;)
     wc[7] = s.n_lone;
+    // the pass records behind the cycle records and the trace: [wave][8]
+    long long* wp = p.wave_cycles + (size_t)gridDim.x * 16 + 4096 + (size_t)blockIdx.x * 8;
+    wp[0] = s.n_pair;
+    ALTRO_STAMP(wp[1] = s.c_b2; wp[2] = s.c_b3; wp[3] = s.c_b4; wp[4] = s.t_b2; wp[5] = s.t_b3; wp[6] = s.t_b4; wp[7] = s.t_bp;)
 #ifdef ALTRO_PHASE_STAMPS
     {  // which SIMD the wave ran on (HW_ID: simd 5:4, cu 11:8, sh 12, se 15:13; XCC_ID 3:0): who shares a SIMD with whom
       const unsigned a = __builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 4);

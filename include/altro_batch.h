@@ -325,6 +325,12 @@ int32_t altro_batch_get_polish_dual_residuals(altro_handle* h, double* before, d
  * first-order sweeps, [13] costate sweeps, [14] closed-loop rollouts, [15] trial sweeps.  count = 16 * waves. */
 int32_t altro_batch_get_wave_cycles(altro_handle* h, int64_t* cycles, int32_t capacity, int32_t* count);
 
+/* Pass records of the last solve launch (16-lane kernels), 8 words per wave.  [0] (every build) backward passes that ran
+ * in the pair form (two rows of the wave needed one; "no_pair" keeps the four-row form).  Diagnostic builds
+ * (-DALTRO_PHASE_STAMPS) also fill [1..3] four-row passes with 2, 3 and 4 rows needing them, [4..6] their ticks and
+ * [7] the ticks of the pair passes.  count = 8 * waves; 0 for the one-wave-per-instance backend. */
+int32_t altro_batch_get_wave_passes(altro_handle* h, int64_t* passes, int32_t capacity, int32_t* count);
+
 /* ---- device-resident MPC harness (reference random_linear_problem.jl:121-139, mpc.jl:11-47).
  * The reference's MPC loop runs on the host around solve!; for a batch that lives in HBM the
  * same update sequence is provided on device so that no step crosses PCIe. */
@@ -406,7 +412,7 @@ int32_t altro_batch_get_initial_state(altro_handle* h, double* x0);
  * environment; a test or a measuring tool that wants one of the kernels' scheduling features off -- to show that it
  * changes no result, or to time it -- says so here.  h == NULL: for the handles THIS THREAD creates afterwards;
  * otherwise for that handle, from its next launch on.  Keys (value 0 restores the default):
- *   "no_lone", "no_shadow", "no_resync", "no_group", "no_reuse", "no_qz_pass", "no_mate_rank"   one scheduling feature of the 16-lane kernels off
+ *   "no_lone", "no_pair", "no_shadow", "no_resync", "no_group", "no_reuse", "no_qz_pass", "no_mate_rank"   one scheduling feature of the 16-lane kernels off
  *   "group_mode" 0..4, "group_max_steps", "trace_wave"              slot order of a grouped launch / diagnostic builds
  *   "force_wide", "wide_compact", "wide_coop", "wide_static_mask"   read at altro_batch_create: NULL handle only
  *   "keep_gains"   the setters stop dropping the stored gains (the product then returns results from STALE gains: it

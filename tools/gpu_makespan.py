@@ -22,6 +22,20 @@ fmt = lambda row: " ".join(("%s %.2fM" % (n, row[i] / 1e6)) if not n.startswith(
 print("mean wave  :", fmt(wcs.mean(0)))
 for nm, ci, ti in (("four-row pass", 11, 1), ("lone pass", 7, 8), ("first-order sweep", 12, 9), ("costate sweep", 13, 10), ("closed rollout", 14, 2), ("trial sweep", 15, 6)):
     print("  %-18s %.0fk cycles each" % (nm, wcs[:, ti].sum() / max(1.0, wcs[:, ci].sum()) / 1e3))
+# backward passes by form, and the four-row ones by how many rows needed them (diagnostic build)
+wp = altro.wave_passes(mp.solver).astype(float)
+if wp.any():
+    print("  %-18s %.0fk cycles each (%.1f per wave)" % ("pair pass", wp[:, 7].sum() / max(1.0, wp[:, 0].sum()) / 1e3, wp[:, 0].mean()))
+    slow = np.argsort(-wcs[:, 0])[:max(1, wcs.shape[0] // 20)]
+    for nm, sel in (("all waves", np.arange(wcs.shape[0])), ("slowest 5 %", slow)):
+        c, t = wp[sel, 1:4].sum(0), wp[sel, 4:7].sum(0)
+        print("four-row passes by rows that need them, %s (%d waves): " % (nm, len(sel)) + "; ".join(
+            "%d rows: %d (%.1f %%, %.0fk cycles each)" % (a + 2, c[a], 100.0 * c[a] / max(1.0, c.sum()), t[a] / max(1.0, c[a]) / 1e3) for a in range(3)))
+        print("    two-row passes carry %.2f %% of these waves' cycles (%.2fM of %.2fM per wave); lone %.1f, pair %.1f, four-row %.1f passes per wave" % (
+            100.0 * t[0] / wcs[sel, 0].sum(), t[0] / len(sel) / 1e6, wcs[sel, 0].mean() / 1e6, wcs[sel, 7].mean(), wp[sel, 0].mean(), wcs[sel, 11].mean()))
+    for w in np.argsort(-wcs[:, 0])[:5]:
+        print("    wave %5d: total %.2fM; four-row passes with 2/3/4 rows %d/%d/%d, cycles %.2fM/%.2fM/%.2fM; pair %d; lone %d" % (
+            w, wcs[w, 0] / 1e6, wp[w, 1], wp[w, 2], wp[w, 3], wp[w, 4] / 1e6, wp[w, 5] / 1e6, wp[w, 6] / 1e6, wp[w, 0], wcs[w, 7]))
 st = altro.stats(mp.solver)
 print("kernel ms %.2f" % st.tsolve_ms)
 nb, nr, ntr = altro.work_counters(mp.solver)
