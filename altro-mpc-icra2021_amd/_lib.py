@@ -44,6 +44,7 @@ EXPORTS = [
     "altro_batch_signal_stream",
     "altro_batch_set_active", "altro_batch_set_active_dev", "altro_batch_get_active",
     "altro_batch_restart_instances", "altro_batch_restart_instances_dev",
+    "altro_mpc_set_clock", "altro_mpc_set_clock_dev", "altro_mpc_get_clock",
 ]
 """every symbol include/altro_batch.h declares"""
 
@@ -76,7 +77,7 @@ def build(force=False, verbose=False):
     """Generate the DPP block include and compile the HIP library for gfx950, in tree.  The library is several translation
     units (altro_batch.hip: the C-ABI, the 16-lane kernels, the polish; wide_inst.hip once per group of one-wave-per-instance
     kernels, solve_wide.h ALTRO_WIDE_KERNELS) compiled side by side -- one after the other they take ~6 minutes."""
-    srcs = [os.path.join(CSRC, f) for f in ("altro_batch.hip", "wide_inst.hip", "solve_dpp16.h", "solve_wide.h", "wide_backend.h", "launch_ring.h", "pn_polish.h", "pn_wide.h", "mpc_log.h", "device_io.h", "gen_dpp_blocks.py")]
+    srcs = [os.path.join(CSRC, f) for f in ("altro_batch.hip", "wide_inst.hip", "solve_dpp16.h", "solve_wide.h", "wide_backend.h", "launch_ring.h", "pn_polish.h", "pn_wide.h", "mpc_log.h", "device_io.h", "episode_clock.h", "gen_dpp_blocks.py")]
     srcs.append(os.path.join(os.path.dirname(_HERE), "include", "altro_batch.h"))
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):
         return LIB_PATH
@@ -155,6 +156,10 @@ def lib():
         L.altro_batch_get_active.argtypes = [H, ip]
         L.altro_batch_restart_instances.argtypes = [H, ip, dp, dp]
         L.altro_batch_restart_instances_dev.argtypes = [H, vp, vp, vp]
+    if hasattr(L, "altro_mpc_set_clock"):   # per-instance episode clock
+        L.altro_mpc_set_clock.argtypes = [H, ip, ip]
+        L.altro_mpc_set_clock_dev.argtypes = [H, C.c_void_p, C.c_void_p]
+        L.altro_mpc_get_clock.argtypes = [H, ip, ip, ip]
     L.altro_batch_add_constraint.argtypes = [H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                              dp, dp, dp, dp, C.c_int32, ip]
     L.altro_batch_update_constraint_data.argtypes = [H, C.c_int32, dp, dp]

@@ -501,6 +501,49 @@ def get_active(solver):
     return a
 
 
+def _clock_i32(a, B, name):
+    """(B,) int32 from an integer array or list; anything else is refused before the library sees it"""
+    a = np.asarray(a)
+    if a.shape != (B,):
+        raise ValueError(f"{name}: shape {a.shape}, expected ({B},)")
+    if a.dtype.kind not in "iu":
+        raise TypeError(f"{name}: dtype {a.dtype}, expected an integer type")
+    if a.size and (a.min() < np.iinfo(np.int32).min or a.max() > np.iinfo(np.int32).max):
+        raise ValueError(f"{name}: values outside int32")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def set_clock(solver, start, length=None):
+    """Per-instance episode clock of the device-resident MPC loop (altro_mpc_set_clock): at absolute step i instance b is at
+    local step i - start[b] and takes the step only while 0 <= local step < length[b] (length None: until its track ends);
+    otherwise it is idle, exactly as an inactive instance is.  start, length: (B,) integer numpy arrays / lists, or int32
+    GPU tensors (device path, stream-ordered); start None clears the clock."""
+    if start is None:
+        if length is not None:
+            raise ValueError("set_clock: length without start")
+        solver._chk(solver._L.altro_mpc_set_clock(solver.h, None, None))
+    elif _on_gpu(start) or _on_gpu(length):
+        if not (_on_gpu(start) and (length is None or _on_gpu(length))):
+            raise ValueError("set_clock: start and length must both be GPU tensors, or neither")
+        check_device_tensor(start, (solver.B,), solver.device, "start", dtype="torch.int32")
+        if length is not None:
+            check_device_tensor(length, (solver.B,), solver.device, "length", dtype="torch.int32")
+        with _bracket(solver):
+            solver._chk(solver._L.altro_mpc_set_clock_dev(solver.h, _addr(start), _addr(length)))
+    else:
+        st = _clock_i32(start, solver.B, "start")
+        ln = None if length is None else _clock_i32(length, solver.B, "length")
+        solver._chk(solver._L.altro_mpc_set_clock(solver.h, st.ctypes.data_as(_IP), None if ln is None else ln.ctypes.data_as(_IP)))
+
+
+def get_clock(solver):
+    """(start, length, window), each (B,) int32: the clock in force and every instance's reference window (with no clock:
+    zeros, -1 = unbounded, and the solver's one window)"""
+    out = [np.empty(solver.B, dtype=np.int32) for _ in range(3)]
+    solver._chk(solver._L.altro_mpc_get_clock(solver.h, *(a.ctypes.data_as(_IP) for a in out)))
+    return tuple(out)
+
+
 def _restart_instances_dev(solver, which, U, X=None):
     check_device_tensor(which, (solver.B,), solver.device, "which", dtype="torch.int32")
     if X is not None:

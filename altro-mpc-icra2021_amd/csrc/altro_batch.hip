@@ -105,6 +105,7 @@ struct altro_handle {
   double* stage = nullptr;  // device staging buffer for host<->device layout conversion
   altro::StreamLink link;   // events of altro_batch_wait_stream / altro_batch_signal_stream (device_io.h)
   altro::InstanceFlags flags;  // active mask and restart selection of a 16-lane handle, [Bp] (device_io.h; a wide handle's live in its backend)
+  altro::EpisodeClock clock;   // per-instance episode clock of a 16-lane handle, [Bp] (device_io.h; a wide handle's lives in its backend)
   int dev_via_stage = 0;    // "dev_via_stage": the _dev setters of x0 and the reference copy into `stage` first (measurement only)
   size_t stage_bytes = 0;
   int Nt = 0;    // knots held by Zref
@@ -360,7 +361,7 @@ __global__ void k_restart(const int* __restrict__ which, const double* __restric
                           double* __restrict__ Lc, double* __restrict__ mu, double* __restrict__ kmu, altro::ASet* __restrict__ ahash,
                           int* __restrict__ dzero, int* __restrict__ iters, int* __restrict__ iters_outer, int* __restrict__ status,
                           double* __restrict__ cost, double* __restrict__ cmax, double* __restrict__ Jtrace, double* __restrict__ ctrace,
-                          double* __restrict__ atrace, int B, int N, int n, int m, int have_x) {
+                          double* __restrict__ atrace, int* __restrict__ window, int B, int N, int n, int m, int have_x) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= B * LW) return;
   const int inst = t / LW, j = t % LW;
@@ -392,6 +393,7 @@ __global__ void k_restart(const int* __restrict__ which, const double* __restric
     status[inst] = ALTRO_UNSOLVED;
     cost[inst] = 0.0;
     cmax[inst] = 0.0;
+    if (window != nullptr) window[inst] = 0;   // under an episode clock (altro_mpc_set_clock): back to the track's first window
   }
 }
 
@@ -436,15 +438,26 @@ __global__ void k_plane_copy(double* __restrict__ Zp, double* __restrict__ Zs, c
 constexpr int GROUP_BINS = 34;   // scores 0 .. 32 of the active instances, and one bin behind them for the inactive ones
 __global__ void k_group_score(const double* __restrict__ Zref, const double* __restrict__ zmin, const double* __restrict__ zmax,
                               unsigned imask, int* __restrict__ score, int Bp, int Nt, int first, int nsteps, int k0, int k1, int nz,
-                              const int* __restrict__ active) {
+                              const int* __restrict__ active, altro::ClockArgs clk, int N) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   const int b = t / LW, j = t % LW;
   const bool live = b < Bp;
   const int bb = live ? b : Bp - 1;
+  bool off = active != nullptr && active[bb] == 0;   // the instance takes no step of this launch: the last bin
+  if (clk.start != nullptr) {
+    // episode clock: the windows of the instance are those of its own local steps, and only the steps it ticks count
+    // (row-uniform: the sixteen lanes of an instance take the same path, and the ballots below look at their own row only)
+    int lo, hi;
+    altro::clock_span(clk.start[bb], altro::clock_lmax(clk.length[bb], Nt, N, 0, 0), first, nsteps, lo, hi);
+    const bool ticks = hi > lo;   // (then 0 <= first + lo - start < Nt: computed only then, any int32 start is safe)
+    first = ticks ? (int)((long long)first + lo - clk.start[bb]) : 0;
+    nsteps = ticks ? hi - lo : 0;
+    off = off || !ticks;
+  }
   const int W = k1 - k0 + 1;                 // knots of a window that carry the box rows
   const int a0 = first + 1 + k0;             // first absolute knot touched by the launch's windows
   const int na = nsteps + W - 1;             // absolute knots touched
-  if (na > 256 || W < 1) { if (live && j == 0) score[b] = (active != nullptr && active[b] == 0) ? GROUP_BINS - 1 : 0; return; }
+  if (na > 256 || W < 1 || nsteps == 0) { if (live && j == 0) score[b] = off ? GROUP_BINS - 1 : 0; return; }
   const unsigned bo = ((unsigned)bb * LW + j) & imask;   // the instance's row of per-instance bounds (SolveParams::imask)
   const double lo = zmin[bo], hi = zmax[bo];
   const bool fl = (j < nz) && lo > -1e300, fh = (j < nz) && hi < 1e300;
@@ -469,7 +482,7 @@ __global__ void k_group_score(const double* __restrict__ Zref, const double* __r
   // (active scores stay below the last bin, which belongs to the inactive instances of a masked launch: they sort behind
   //  everything else, four to a wave, and those waves leave at their first step begin)
   sc = sc < GROUP_BINS - 2 ? sc : GROUP_BINS - 2;
-  score[b] = (active != nullptr && active[b] == 0) ? GROUP_BINS - 1 : sc;
+  score[b] = off ? GROUP_BINS - 1 : sc;
 }
 
 // perm = the instances in ascending order of (score, index): a stable counting sort in ONE block of 256 threads (thread t
@@ -605,6 +618,7 @@ static int launch_solve(altro_handle* h, int first_step, int nsteps, int prepare
   }
   p.perm = nullptr;
   p.active = h->flags.mask();
+  p.clk = h->clock.args();
   // fused MPC launches of box-constrained problems: group the instances by how many of the launch's steps will need
   // backward passes (see k_group_score); everything else runs in instance order
   // (short launches only: over 100 steps nearly every window meets a bound at some point, the score stops separating the
@@ -612,7 +626,7 @@ static int launch_solve(altro_handle* h, int first_step, int nsteps, int prepare
   //  measured 20 steps +2 %, 100 steps -3 %, tools/gpu_ab.py)
   if (h->group && h->reuse && !h->o.strict && nsteps >= 4 && nsteps <= h->group_max_steps && !prepare_only && h->ncrows == 0 && h->box_k1 >= h->box_k0 && h->Bp <= 32768) {
     hipLaunchKernelGGL(k_group_score, grid_for((size_t)h->Bp * LW), dim3(256), 0, h->stream, h->Zref, h->zmin, h->zmax, tab_imask(h), h->gscore, h->Bp, h->Nt,
-                       first_step, nsteps, h->box_k0, h->box_k1, h->d.n + h->d.m, h->flags.mask());
+                       first_step, nsteps, h->box_k0, h->box_k1, h->d.n + h->d.m, h->flags.mask(), h->clock.args(), h->d.N);
     hipLaunchKernelGGL(k_group_rank, dim3(1), dim3(256), 0, h->stream, h->gscore, h->perm, h->Bp, h->group);
     p.perm = h->perm;
   }
@@ -1031,6 +1045,7 @@ int32_t altro_batch_destroy(altro_handle* h) {
   if (h->wide) {
     h->wide->destroy();
     h->flags.destroy();
+    h->clock.destroy();
     h->link.destroy();
     delete h->wide;
     delete h;
@@ -1038,6 +1053,7 @@ int32_t altro_batch_destroy(altro_handle* h) {
   }
   free_dpp_backend(h);
   h->flags.destroy();
+  h->clock.destroy();
   h->link.destroy();
   delete h;
   return ALTRO_OK;
@@ -1089,6 +1105,8 @@ static int migrate_to_wide(altro_handle* h) {
   }
   wb->flags = h->flags;   // a mask set before the model moves with the handle (its buffers hold Bp >= batch entries)
   h->flags = altro::InstanceFlags{};
+  wb->clock = h->clock;   // and so does an episode clock
+  h->clock = altro::EpisodeClock{};
   free_dpp_backend(h);
   h->wide = wb;
   return ALTRO_OK;
@@ -1484,6 +1502,10 @@ static int set_ref_common(altro_handle* h, const double* Xref, const double* Ure
   hipLaunchKernelGGL(k_pack_ref, grid_for((size_t)h->Bp * LW), dim3(256), 0, h->stream, Xref, Uref,
                      h->Zref, h->d.batch, h->Bp, Nt, (int)n, (int)m);
   HIPCHK(h, hipGetLastError());
+  if (h->clock.on) {   // a new track installs window 0 for every instance, as it does for the handle's kref
+    hipLaunchKernelGGL(altro::k_clock_window, altro::EpisodeClock::grid(h->Bp), dim3(256), 0, h->stream, h->clock.window, (const int*)nullptr, 0, h->Bp);
+    HIPCHK(h, hipGetLastError());
+  }
   if (!dev) HIPCHK(h, hipStreamSynchronize(h->stream));
   h->kref = 0;
   h->have_ref = true;
@@ -1581,7 +1603,8 @@ static int prepare_polish(altro_handle* h) {
   return ALTRO_OK;
 }
 
-static int launch_polish(altro_handle* h) {
+// mask: the instances to polish (null: all) -- the active mask, or under an episode clock the mask of the step just solved
+static int launch_polish(altro_handle* h, const int* mask) {
   const int bm = h->pn_bm;
   altro_pn::PnParams q{};
   q.B = h->d.batch; q.Bp = h->Bp; q.N = h->d.N; q.Nt = h->Nt; q.n = h->d.n; q.m = h->d.m; q.bm = bm;
@@ -1589,8 +1612,8 @@ static int launch_polish(altro_handle* h) {
   q.con_istride = h->con_per_instance ? (unsigned)(h->d.N * LW * LW) : 0u;
   q.Grow = h->Grow; q.fvec = h->fvec; q.wd = h->wd; q.wf = h->wf; q.zmin = h->zmin; q.zmax = h->zmax; q.x0 = h->x0;
   q.wstride = q.bstride = tab_imask(h) == 15u ? 0u : (unsigned)LW;
-  q.Acon = h->Acon; q.bcon = h->bcon; q.cmeta = h->cmeta; q.active = h->flags.mask();
-  q.Z = h->Z; q.Zref = h->Zref; q.kref = h->kref; q.cur = h->cur; q.status = h->status; q.cost = h->cost; q.cmax = h->cmax;
+  q.Acon = h->Acon; q.bcon = h->bcon; q.cmeta = h->cmeta; q.active = mask;
+  q.Z = h->Z; q.Zref = h->Zref; q.kref = h->kref; q.win = h->clock.on ? h->clock.window : nullptr; q.cur = h->cur; q.status = h->status; q.cost = h->cost; q.cmax = h->cmax;
   q.pn_ran = h->pn_ran; q.pn_failed = h->pn_failed; q.pn_res = h->pn_res;
   q.Lb = h->Lb; q.Lc = h->Lc; q.bslot = h->bslot; q.nbp = h->nbp;
   q.pn_dfail = h->pn_dfail; q.pn_dres0 = h->pn_dres0; q.pn_dres = h->pn_dres;
@@ -1608,8 +1631,9 @@ static int enqueue_solve(altro_handle* h, int first_step, int nsteps) {
   if (rc) return rc;
   if ((rc = pack_constraints(h))) return rc;
   h->con_locked = true;
+  // (under an episode clock every instance has a window of its own, kept inside the track by the tick rule on the device)
   const int last_kref = nsteps > 0 ? first_step + nsteps : h->kref;
-  if (last_kref + h->d.N > h->Nt) FAIL(h, ALTRO_ERR_STATE, "reference window runs past the end of the stored trajectory");
+  if (!h->clock.on && last_kref + h->d.N > h->Nt) FAIL(h, ALTRO_ERR_STATE, "reference window runs past the end of the stored trajectory");
   // everything that can refuse the launch comes before it takes a slot of the timing ring
   if (h->o.projected_newton && (rc = prepare_polish(h))) return rc;
   if (!supported_dims(h->d.n, h->d.m)) FAIL(h, ALTRO_ERR_UNSUPPORTED, "no kernel built for this (n, m)");
@@ -1622,20 +1646,27 @@ static int enqueue_solve(altro_handle* h, int first_step, int nsteps) {
     // launch run as nsteps pairs of (one-step solve kernel, polish kernel) on the stream, the polish over the step's window
     const int kref0 = h->kref;
     for (int s = 0; s < nsteps && !rc; ++s) {
+      const int* mask = h->flags.mask();
+      if (h->clock.on) {   // the polish and the log kernel skip the instances that are idle AT THIS STEP
+        hipLaunchKernelGGL(altro::k_clock_step_mask, altro::EpisodeClock::grid(h->Bp), dim3(256), 0, h->stream, h->clock.stepmask, h->clock.args(),
+                           h->flags.mask(), first_step + s, h->Nt, h->d.N, 0, 0, h->Bp);
+        if (hipGetLastError() != hipSuccess) { h->err = "launch of the step-mask kernel failed"; rc = ALTRO_ERR_HIP; break; }
+        mask = h->clock.stepmask;
+      }
       rc = launch_solve(h, first_step + s, 1);
       h->kref = first_step + s + 1;
-      if (!rc) rc = launch_polish(h);
+      if (!rc) rc = launch_polish(h, mask);
       if (!rc && h->mlog) {
         double* rec0 = h->mlog + (size_t)(first_step + s) * (size_t)h->d.batch * (LW + altro::MLOG_TAIL);
         hipLaunchKernelGGL(k_log_polished, grid_for((size_t)h->d.batch), dim3(256), 0, h->stream, rec0, h->Z, h->cur, (size_t)h->d.N * LW,
-                           h->cost, h->cmax, h->status, h->flags.mask(), h->d.batch, h->d.N, h->d.n, h->d.m);
+                           h->cost, h->cmax, h->status, mask, h->d.batch, h->d.N, h->d.n, h->d.m);
         if (hipGetLastError() != hipSuccess) { h->err = "launch of the log kernel failed"; rc = ALTRO_ERR_HIP; }
       }
     }
     if (rc) h->kref = kref0;
   } else {
     rc = launch_solve(h, first_step, nsteps);
-    if (!rc && h->o.projected_newton) rc = launch_polish(h);
+    if (!rc && h->o.projected_newton) rc = launch_polish(h, h->flags.mask());
   }
   // (a launch that failed after all -- a HIP error -- still closes its slot: every slot handed out has both events)
   HIPCHK(h, hipEventRecord(h1, h->stream));
@@ -2100,7 +2131,8 @@ int32_t altro_mpc_run_async(altro_handle* h, int32_t first_step, int32_t nsteps)
     if (!h) return ALTRO_ERR_INVALID_ARG;
     if (nsteps < 1 || first_step < 0) FAIL(h, ALTRO_ERR_INVALID_ARG, "bad step range");
     if (h->noise && first_step + nsteps > h->noise_steps) FAIL(h, ALTRO_ERR_INVALID_ARG, "steps outside the uploaded noise");
-    if (first_step + nsteps + h->d.N > h->Nt) FAIL(h, ALTRO_ERR_INVALID_ARG, "steps run past the end of the track");
+    // (under an episode clock an instance that runs off the end of its track goes idle there: altro_mpc_set_clock)
+    if (!h->clock.on && first_step + nsteps + h->d.N > h->Nt) FAIL(h, ALTRO_ERR_INVALID_ARG, "steps run past the end of the track");
     if (h->mlog && first_step + nsteps > h->mlog_cap) FAIL(h, ALTRO_ERR_INVALID_ARG, "steps outside the capacity of the log (altro_mpc_set_log)");
     return enqueue_solve(h, first_step, nsteps);
   });
@@ -2163,7 +2195,7 @@ int32_t altro_mpc_prepare_async(altro_handle* h, int32_t step) {
     if (!h) return ALTRO_ERR_INVALID_ARG;
     if (step < 0) FAIL(h, ALTRO_ERR_INVALID_ARG, "bad step");
     if (h->noise && step + 1 > h->noise_steps) FAIL(h, ALTRO_ERR_INVALID_ARG, "step outside the uploaded noise");
-    if (step + 1 + h->d.N > h->Nt) FAIL(h, ALTRO_ERR_INVALID_ARG, "step runs past the end of the track");
+    if (!h->clock.on && step + 1 + h->d.N > h->Nt) FAIL(h, ALTRO_ERR_INVALID_ARG, "step runs past the end of the track");
     HIPCHK(h, hipSetDevice(h->device));
     int rc = check_ready(h);
     if (rc) return rc;
@@ -2179,6 +2211,7 @@ int32_t altro_batch_benchmark_solve(altro_handle* h, int32_t samples, int32_t ev
     if (!h) return ALTRO_ERR_INVALID_ARG;
     if (samples < 1 || evals < 1) FAIL(h, ALTRO_ERR_INVALID_ARG, "samples and evals must be positive");
     if (h->flags.on) FAIL(h, ALTRO_ERR_STATE, "altro_batch_benchmark_solve restores and repeats whole batches: clear the active mask first");
+    if (h->clock.on) FAIL(h, ALTRO_ERR_STATE, "altro_batch_benchmark_solve restores and repeats whole batches: clear the episode clock first");
     HIPCHK(h, hipSetDevice(h->device));
     const size_t plane = (size_t)h->d.N * LW;
     if (!h->Zsave) HIPCHK(h, hipMalloc(&h->Zsave, plane * h->Bp * sizeof(double)));
@@ -2391,7 +2424,7 @@ static int restart_16(altro_handle* h, const int32_t* which, const double* X, co
   HIPCHK(h, h->flags.load(true, which, dev, (int)B, h->Bp, h->stream));
   hipLaunchKernelGGL(k_restart, grid_for(B * LW), dim3(256), 0, h->stream, h->flags.which, X, U, h->Z, h->cur, N * (size_t)LW, h->Lb,
                      h->nbp, h->Lc, h->mu, h->kmu, h->ahash, h->dzero, h->iters, h->iters_outer, h->status, h->cost, h->cmax,
-                     h->Jtrace, h->ctrace, h->atrace, (int)B, (int)N, (int)n, (int)m, X ? 1 : 0);
+                     h->Jtrace, h->ctrace, h->atrace, h->clock.on ? h->clock.window : nullptr, (int)B, (int)N, (int)n, (int)m, X ? 1 : 0);
   HIPCHK(h, hipGetLastError());
   if (!dev) HIPCHK(h, hipStreamSynchronize(h->stream));
   return ALTRO_OK;
@@ -2415,6 +2448,72 @@ int32_t altro_batch_restart_instances_dev(altro_handle* h, const int32_t* which,
     DEV_ARG(h, "U", U, B_ * (N_ - 1) * m_, double, false);
     DEV_WIDE(h, restart(which, X, U, true));
     return restart_16(h, which, X, U, true);
+  });
+}
+
+// ---- per-instance episode clock
+static int set_clock_common(altro_handle* h, const int32_t* start, const int32_t* length, bool dev) {
+  altro::EpisodeClock& ck = h->wide ? h->wide->clock : h->clock;
+  const hipStream_t st = h->wide ? h->wide->stream : h->stream;
+  int& kref = h->wide ? h->wide->kref : h->kref;
+  const size_t B = h->d.batch;
+  if (!start) {   // clear: the handle goes back to ONE window, which must be the one every instance holds
+    if (!ck.on) return ALTRO_OK;
+    std::vector<int> w(B);
+    HIPCHK(h, hipStreamSynchronize(st));
+    HIPCHK(h, hipMemcpy(w.data(), ck.window, B * sizeof(int), hipMemcpyDeviceToHost));
+    for (size_t i = 1; i < B; ++i)
+      if (w[i] != w[0]) FAIL(h, ALTRO_ERR_STATE, "altro_mpc_set_clock: the instances hold different reference windows, the clock cannot be cleared");
+    kref = w[0];
+    ck.on = false;
+    return ALTRO_OK;
+  }
+  if ((h->wide ? h->wide->Nt : h->Nt) < 1 || !(h->wide ? h->wide->have_ref : h->have_ref))
+    FAIL(h, ALTRO_ERR_STATE, "altro_mpc_set_clock: no track (altro_mpc_set_track)");
+  HIPCHK(h, ck.load(start, length, dev, (int)B, h->wide ? (int)B : h->Bp, kref, st));
+  if (!dev) HIPCHK(h, hipStreamSynchronize(st));
+  ck.on = true;
+  return ALTRO_OK;
+}
+
+int32_t altro_mpc_set_clock(altro_handle* h, const int32_t* start, const int32_t* length) {
+  return guard(h, [&]() -> int32_t {
+    if (!h) return dev_null_handle("altro_mpc_set_clock");
+    HIPCHK(h, hipSetDevice(h->device));
+    return set_clock_common(h, start, length, false);
+  });
+}
+
+int32_t altro_mpc_set_clock_dev(altro_handle* h, const int32_t* start, const int32_t* length) {
+  return guard(h, [&]() -> int32_t {
+    DEV_ENTER(h, "altro_mpc_set_clock_dev");
+    DEV_ARG(h, "start", start, B_, int32_t, true);
+    DEV_ARG(h, "length", length, B_, int32_t, true);
+    return set_clock_common(h, start, length, true);
+  });
+}
+
+int32_t altro_mpc_get_clock(altro_handle* h, int32_t* start, int32_t* length, int32_t* window) {
+  return guard(h, [&]() -> int32_t {
+    if (!h) return dev_null_handle("altro_mpc_get_clock");
+    if (!start && !length && !window) FAIL(h, ALTRO_ERR_INVALID_ARG, "altro_mpc_get_clock: every output pointer is null");
+    const altro::EpisodeClock& ck = h->wide ? h->wide->clock : h->clock;
+    const size_t B = h->d.batch;
+    if (!ck.on) {
+      const int kref = h->wide ? h->wide->kref : h->kref;
+      for (size_t i = 0; i < B; ++i) {
+        if (start) start[i] = 0;
+        if (length) length[i] = -1;
+        if (window) window[i] = kref;
+      }
+      return ALTRO_OK;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->wide ? h->wide->stream : h->stream));
+    if (start) HIPCHK(h, hipMemcpy(start, ck.start, B * sizeof(int), hipMemcpyDeviceToHost));
+    if (length) HIPCHK(h, hipMemcpy(length, ck.length, B * sizeof(int), hipMemcpyDeviceToHost));
+    if (window) HIPCHK(h, hipMemcpy(window, ck.window, B * sizeof(int), hipMemcpyDeviceToHost));
+    return ALTRO_OK;
   });
 }
 

@@ -8,6 +8,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "episode_clock.h"
+
 namespace altro {
 
 // A caller's pointer may reach a kernel only if the runtime knows it as device memory of the handle's device and the
@@ -97,6 +99,77 @@ struct InstanceFlags {
     if (which) hipFree(which);
     if (hstage) hipFree(hstage);
     active = which = hstage = nullptr;
+    on = false;
+  }
+};
+
+// Per-instance episode clock (altro_mpc_set_clock, host and _dev forms; episode_clock.h has the tick rule): the library's own
+// copies of the caller's two int32 arrays and the per-instance reference window, `cap` entries each (the batch padded to
+// whole waves on the 16-lane backend; padded slots hold start 0, length 0: they never tick).  length: a caller's negative
+// entry is stored as 0 (no local step is below it), -1 stands for "no length array".  All buffers are allocated by the first
+// call and reused from then on.
+__global__ void k_clock_load(int* __restrict__ start, int* __restrict__ length, const int* __restrict__ src_start,
+                             const int* __restrict__ src_length, int B, int cap) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= cap) return;
+  start[i] = i < B ? src_start[i] : 0;
+  length[i] = i < B ? (src_length != nullptr ? (src_length[i] > 0 ? src_length[i] : 0) : -1) : 0;
+}
+// which == nullptr: every entry; else the entries it selects (the rewind of altro_batch_restart_instances)
+__global__ void k_clock_window(int* __restrict__ window, const int* __restrict__ which, int value, int cap) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < cap && (which == nullptr || which[i] != 0)) window[i] = value;
+}
+// mask[i] = instance i takes part in absolute step `step`: active (null: all) and ticking.  What the polish and the log kernel
+// behind a one-step solve kernel go by (projected_newton = 1 inside the MPC loop)
+__global__ void k_clock_step_mask(int* __restrict__ mask, ClockArgs clk, const int* __restrict__ active, int step, int Nt, int N,
+                                  int dyn_blocks, int dyn_step_stride, int cap) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= cap) return;
+  int lo, hi;
+  clock_span(clk.start[i], clock_lmax(clk.length[i], Nt, N, dyn_blocks, dyn_step_stride), step, 1, lo, hi);
+  mask[i] = (hi > lo && (active == nullptr || active[i] != 0)) ? 1 : 0;
+}
+struct EpisodeClock {
+  int* start = nullptr;     // [cap]
+  int* length = nullptr;    // [cap]
+  int* window = nullptr;    // [cap] kept by the kernels while `on`
+  int* stepmask = nullptr;  // [cap] k_clock_step_mask of the step being enqueued
+  int* hstage = nullptr;    // [2 cap] where host arrays land
+  bool on = false;
+  ClockArgs args() const { return on ? ClockArgs{start, length, window} : ClockArgs{nullptr, nullptr, nullptr}; }
+  static dim3 grid(int cap) { return dim3((unsigned)((cap + 255) / 256)); }
+  hipError_t ensure(int cap) {
+    hipError_t e;
+    int** bufs[] = {&start, &length, &window, &stepmask};
+    for (int** b : bufs)
+      if (!*b && (e = hipMalloc(b, (size_t)cap * sizeof(int))) != hipSuccess) return e;
+    if (!hstage && (e = hipMalloc(&hstage, 2 * (size_t)cap * sizeof(int))) != hipSuccess) return e;
+    return hipSuccess;
+  }
+  // start / length <- the caller's arrays [B] (src_length may be null), on the host (through hstage; the caller waits for the
+  // stream before it returns) or on the device; a clock that was off starts every window at `kref`, one that was on keeps them
+  hipError_t load(const int* src_start, const int* src_length, bool dev, int B, int cap, int kref, hipStream_t st) {
+    hipError_t e;
+    if ((e = ensure(cap)) != hipSuccess) return e;
+    if (!dev) {
+      if ((e = hipMemcpyAsync(hstage, src_start, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+      src_start = hstage;
+      if (src_length) {
+        if ((e = hipMemcpyAsync(hstage + cap, src_length, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+        src_length = hstage + cap;
+      }
+    }
+    hipLaunchKernelGGL(k_clock_load, grid(cap), dim3(256), 0, st, start, length, src_start, src_length, B, cap);
+    if (!on) hipLaunchKernelGGL(k_clock_window, grid(cap), dim3(256), 0, st, window, (const int*)nullptr, kref, cap);
+    return hipGetLastError();
+  }
+  void destroy() {
+    int** bufs[] = {&start, &length, &window, &stepmask, &hstage};
+    for (int** b : bufs) {
+      if (*b) hipFree(*b);
+      *b = nullptr;
+    }
     on = false;
   }
 };

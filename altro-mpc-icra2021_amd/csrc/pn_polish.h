@@ -40,6 +40,7 @@ struct PnParams {
   double* Z;              // [Bp][2 N + 1][16] (two planes of N rows + trash row per instance): plane cur is polished, plane cur^1 is the trial buffer
   const double* Zref;     // window start kref
   int kref;
+  const int* win;         // [Bp] per-instance window start (altro_mpc_set_clock), or null: kref for every instance
   int* cur;
   int* status;
   double *cost, *cmax;
@@ -65,7 +66,7 @@ __device__ __forceinline__ double wave_max(double v) {
 
 struct Pn {
   const PnParams& P;
-  int inst, tid, N, n, m, nz, bm;
+  int inst, tid, N, n, m, nz, bm, kref;
   double *E, *dv, *Ld, *Lo, *lam, *res, *cor, *Sv, *dtr, *spare, *tz, *gz, *rz;
   const double *wd_, *wf_, *zmin_, *zmax_;  // this instance's row of the cost weights and of the bounds
   bool unit = false;   // the metric H = I of the multiplier projection (D D' instead of D H^-1 D')
@@ -77,6 +78,7 @@ struct Pn {
   __device__ Pn(const PnParams& p, double* lds) : P(p) {
     inst = blockIdx.x;
     tid = threadIdx.x;
+    kref = P.win != nullptr ? P.win[inst] : P.kref;
     N = P.N; n = P.n; m = P.m; nz = n + m; bm = P.bm;
     const size_t i = (size_t)inst;
     wd_ = P.wd + i * P.wstride; wf_ = P.wf + i * P.wstride;
@@ -300,7 +302,7 @@ struct Pn {
       const int k = e / LW, j = e % LW;
       const bool live = j < n || (j < nz && k < N - 1);
       const double h = (k < N - 1) ? wd_[j] : (j < n ? wf_[j] : 0.0);
-      gz[e] = live ? h * (zrow(cur, k)[j] - P.Zref[((size_t)inst * P.Nt + (size_t)(P.kref + k)) * LW + j]) : 0.0;
+      gz[e] = live ? h * (zrow(cur, k)[j] - P.Zref[((size_t)inst * P.Nt + (size_t)(kref + k)) * LW + j]) : 0.0;
     }
     __syncthreads();
     for (int k = tid; k < N; k += 64) {        // lam0: the AL duals of the active box / linear rows
@@ -546,7 +548,7 @@ struct Pn {
     double J = 0.0, cm = 0.0;
     for (int k = tid; k < N; k += 64) {
       const double* zr = zrow(cur, k);
-      const double* rr = P.Zref + ((size_t)inst * P.Nt + (size_t)(P.kref + k)) * LW;
+      const double* rr = P.Zref + ((size_t)inst * P.Nt + (size_t)(kref + k)) * LW;
       const int lim = (k == N - 1) ? n : nz;
       for (int j = 0; j < lim; ++j) {
         const double e = zr[j] - rr[j];

@@ -442,6 +442,7 @@ struct PnW {
 
   __device__ void run(int instance, double ctol_user) {
     inst = instance;
+    kref = P.clk.start != nullptr ? P.clk.window[inst] : P.kref;   // altro_mpc_set_clock: the instance's own window
     wd_ = P.wd + (size_t)inst * P.w_pi * nz; wf_ = P.wf + (size_t)inst * P.w_pi * n;
     zmin_ = P.zmin + (size_t)inst * P.b_pi * nz; zmax_ = P.zmax + (size_t)inst * P.b_pi * nz;
     const altro_opts& o = P.o;

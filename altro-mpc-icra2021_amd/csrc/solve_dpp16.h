@@ -40,6 +40,7 @@
 #include <type_traits>
 
 #include "../../include/altro_batch.h"
+#include "episode_clock.h"
 #include "mpc_log.h"
 
 // tuning knobs (defaults = the shipped configuration; overridable with -D for experiments)
@@ -209,6 +210,9 @@ struct SolveParams {
   const int* active;     // [Bp] 0 / 1 per instance (altro_batch_set_active; padded slots 0), or null: every instance is active.
                          // Read ONCE per row, into RowState::act: an inactive row never begins a step and finish() skips it.
                          // (last, so that every other argument keeps its offset in the kernel argument segment)
+  ClockArgs clk;         // per-instance episode clock (altro_mpc_set_clock; [Bp], padded slots never tick), clk.start null: none.
+                         // Read ONCE per row, into RowState::t0 / t1 / kref; finish() writes the row's window back.  (behind
+                         // `active`, for the same reason)
 };
 
 template <int K>
@@ -432,6 +436,11 @@ struct RowState {
                   // it is PH_DONE -- no plant step, no dual reset, no kref update, no solve, no log record -- and takes part in
                   // the wave's phases only as a shadow of a live row; the slowest-row estimate (min of the rows' steps) skips
                   // it.  finish() reads the flag and stores nothing for such a row.  Parked here like imask
+  int cstart;     // episode clock: ClockArgs::start of the row's instance, 0 without a clock: local step = absolute step - cstart
+  int t0, t1;     // episode clock: the launch-relative steps [t0, t1) this row ticks (episode_clock.h).  A row about to begin a
+                  // step moves its step counter over the idle steps first -- no plant step, no dual reset, no kref update, no
+                  // record for them -- and to STEP_NEVER once none is left; a row with no tick in the launch starts with
+                  // act = 0.  Without a clock, and in plain solves, the two words are not read
 };
 constexpr int STEP_NEVER = 1 << 30;
 
@@ -2549,6 +2558,17 @@ struct Solver {
       s.cur = P.cur[inst];
       s.kref = P.kref;
       s.act = (P.active == nullptr || P.active[inst] != 0) ? 1 : 0;
+      s.t0 = 0;
+      s.t1 = STEP_NEVER;
+      s.cstart = 0;
+      if (P.clk.start != nullptr) {  // altro_mpc_set_clock: the instance's own window, and the steps of this launch it ticks
+        s.kref = P.clk.window[inst];
+        if (mpc) {
+          s.cstart = P.clk.start[inst];
+          clock_span(s.cstart, clock_lmax(P.clk.length[inst], P.Nt, P.N, 0, 0), first_step, nsteps, s.t0, s.t1);
+          if (s.t1 <= s.t0) s.act = 0;  // idle for the whole launch: treated as an inactive instance is
+        }
+      }
       s.step = s.act ? 0 : STEP_NEVER;
       s.nbw = s.nro = s.nsolve = s.nit = s.nok = s.ntr = 0;
       s.kmu = P.kmu[inst];
@@ -2576,6 +2596,12 @@ struct Solver {
         // one (measured on the pass-heavy waves of a grouped launch: 50 passes in 20 steps).  So a row about to begin
         // a step waits one turn while a wave-mate is in the second turn of its solve: if that solve ends there (it
         // nearly always does) they begin the next step together.  A mate deep in a hard solve is not waited for.
+        if (P.clk.start != nullptr && mpc && ph == PH_STEP_BEGIN) {
+          // episode clock: idle steps are passed over before anything looks at the step counter, so that neither the hold
+          // below nor the slowest-row estimate waits for them (every lane of the row writes the same word)
+          const int stp = rs->step;
+          rs->step = stp >= rs->t1 ? STEP_NEVER : imax(stp, rs->t0);
+        }
         const bool mid = (ph == PH_ITER) && (rs->it == 1) && (rs->iters == 1);
         const bool hold = !CONES && mpc && (P.resync != 0) && wave_any(mid);
         const bool begin = (ph == PH_STEP_BEGIN) && !(hold && rs->step < nsteps);
@@ -2597,8 +2623,10 @@ struct Solver {
             }
           }
           if (begin) {
+            // update_trajectory!(obj, Z_track, k_mpc): the window of the row's LOCAL step (cstart = 0 without a clock); the
+            // noise row above and the log slot are those of the absolute step
+            if (go && mpc) rs->kref = first_step + stp - rs->cstart + 1;
             if (go && !P.prepare_only) {
-              if (mpc) rs->kref = first_step + stp + 1;  // update_trajectory!(obj, Z_track, k_mpc)
               if (o.reset_penalties) rs->mu = mu0;
               rs->status = ALTRO_UNSOLVED;
               rs->iters = 0;
@@ -2688,8 +2716,22 @@ struct Solver {
         const RowState* r0 = rs - (lane >> 4);
         int ms = r0[0].step;
         sfor<1, IPW>([&](auto q) { ms = imin(ms, r0[decltype(q)::value].step); });
+        int left = nsteps - imin(ms, nsteps);
+        if (P.clk.start != nullptr && mpc) {
+          // episode clock: the work a row has done and has left are the steps it TICKS, not the steps the launch counts --
+          // ms <- the fewest ticks done among the rows that tick at all, left <- the most ticks any row still has
+          ms = STEP_NEVER;
+          left = 0;
+          sfor<0, IPW>([&](auto q) {
+            const RowState& r = r0[decltype(q)::value];
+            const int total = r.act ? r.t1 - r.t0 : 0;
+            const int togo = imin(imax(r.t1 - imax(r.step, r.t0), 0), total);
+            left = imax(left, togo);
+            ms = total > 0 ? imin(ms, total - togo) : ms;
+          });
+        }
         hard_wave = wave_any((rs->phase == PH_ITER) && (rs->iters >= 2)) || (ALTRO_PRIO_LAG > 0 && turns - 2 * ms >= ALTRO_PRIO_LAG + 2);
-        if (simd_row != nullptr && mpc) hard_wave = mate_rank(nsteps - imin(ms, nsteps), ms);
+        if (simd_row != nullptr && mpc) hard_wave = mate_rank(left, imin(ms, nsteps));
       }
       prio_base();
       {
@@ -3094,6 +3136,7 @@ struct Solver {
 
   __device__ void finish() {
     if (rs->act == 0) return;  // an inactive instance keeps everything the library owns for it, validity of its gains included
+    if (P.clk.start != nullptr && j == 0) P.clk.window[inst] = rs->kref;  // (a row that ticked, or a plain solve: unchanged then)
     if (!P.prepare_only) P.ahash[(unsigned)inst * LW + j] = *ah;
     if (j == 0 && !P.prepare_only) {  // a prepare-only launch leaves the statistics of the last solve alone
       P.iters[inst] = rs->iters;

@@ -33,6 +33,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/altro_batch.h"
+#include "episode_clock.h"
 #include "mpc_log.h"
 
 namespace altro_wide {
@@ -95,6 +96,9 @@ struct Params {
   const int* active;  // [B] 0 / 1 per instance (altro_batch_set_active), or null: every instance is active.  The block of an
                       // inactive instance returns before its first barrier (wide_kernel, wide_shift_kernel)
   altro_opts o;
+  altro::ClockArgs clk;  // per-instance episode clock (altro_mpc_set_clock; [B]), clk.start null: none.  run() reads the instance's
+                         // window instead of kref, skips the steps it is idle at and writes the window back; a block with no tick
+                         // in the launch returns like an inactive one.  (last: every other argument keeps its offset)
 };
 
 __host__ __device__ inline int pad16(int v) { return (v + 15) & ~15; }
@@ -2975,10 +2979,12 @@ struct Solver {
     }
   }
 
+  // first_step, nsteps: the absolute steps the instance takes -- under an episode clock wide_kernel has already cut the launch
+  // down to the interval it ticks, so no bound of the clock is alive in here
   __device__ __forceinline__ void run(int mpc, int first_step, int nsteps) {
     cur = P.cur[inst];
     mu = P.mu[inst];
-    kref = P.kref;
+    kref = P.clk.start != nullptr ? P.clk.window[inst] : P.kref;
     nbw = nro = ntr = 0;
     {  // the gain-reuse state of the previous launch (one launch of K steps and K launches of one step decide alike)
       const unsigned* st = P.bwst + (size_t)inst * 136;
@@ -2995,13 +3001,15 @@ struct Solver {
     if (!P.ltv) load_dyn(0);                                   // time-invariant dynamics stay resident in LDS
     if (Pn > 0 && P.con_static) build_static_Ac();           // and so does a time-invariant constraint table
     wsync();
-    const int steps = mpc ? nsteps : 1;
     WSTAMP(const long long trun = wstamp();)
+    // (block-uniform bounds: the steps an instance is idle at are outside first_step .. first_step + nsteps - 1, so none of their barriers is entered)
+    const int steps = mpc ? nsteps : 1;
     for (int s = 0; s < steps; ++s) {
       if (mpc) {
         WSTAMP(const long long tsh = wstamp();)
-        do_plant_step(first_step + s);
+        do_plant_step(first_step + s);   // the noise row and the log slot below are those of the ABSOLUTE step
         kref = first_step + s + 1;  // update_trajectory!(obj, Z_track, k_mpc)
+        if (P.clk.start != nullptr) kref -= P.clk.start[inst];   // k_mpc is the instance's local step (re-read: nothing of the clock stays in a register)
         if (mpc == 2) break;        // altro_mpc_prepare_async: new x0 only, no shift, no solve
         if (P.mpc_shift) do_shift();
         WSTAMP(t_sh += wstamp() - tsh;)
@@ -3020,6 +3028,7 @@ struct Solver {
     if (T == 0) {
       P.cur[inst] = cur;
       P.mu[inst] = mu;
+      if (P.clk.start != nullptr) P.clk.window[inst] = kref;   // (a plain solve writes back what it read)
       P.n_backward[inst] += nbw;
       P.n_rollout[inst] += nro;
 #ifdef ALTRO_WIDE_STAMPS
@@ -3137,6 +3146,13 @@ __global__ void __launch_bounds__(SM ? 64 : 256, wide_waves(MC, SM)) wide_kernel
   extern __shared__ double lds[];
   // block-uniform, before any barrier and before the helper waves of a cooperative block start to wait for commands
   if (P.active != nullptr && P.active[blockIdx.x] == 0) return;
+  if (P.clk.start != nullptr && mpc) {  // episode clock: the launch shrinks to the one interval of its steps the instance ticks (episode_clock.h)
+    int lo, hi;
+    altro::clock_span(P.clk.start[blockIdx.x], altro::clock_lmax(P.clk.length[blockIdx.x], P.Nt, P.N, P.ltv ? P.dyn_blocks : 0, P.dyn_step_stride), first_step, nsteps, lo, hi);
+    if (hi <= lo) return;   // idle for the whole launch: left alone like an inactive one
+    first_step += lo;
+    nsteps = hi - lo;
+  }
   if (!SM && threadIdx.x >= 64) {  // helper waves: no solver state, only products on command
     coop_helper(lds, lds_layout(P.n, P.m, P.Pn, P.compact).cmd);
     return;

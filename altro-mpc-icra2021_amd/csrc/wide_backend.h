@@ -115,6 +115,7 @@ __global__ void __launch_bounds__(64) k_restart_wide(const int* __restrict__ whi
     P.status[inst] = ALTRO_UNSOLVED;
     P.cost[inst] = 0.0;
     P.cmax[inst] = 0.0;
+    if (P.clk.start != nullptr) P.clk.window[inst] = 0;   // under an episode clock: back to the track's first window
   }
 }
 
@@ -127,6 +128,7 @@ struct WideBackend {
   bool timed = false;
   altro::LaunchRing ring;
   altro::InstanceFlags flags;  // active mask and restart selection, [batch] (device_io.h)
+  altro::EpisodeClock clock;   // per-instance episode clock, [batch] (device_io.h)
   std::string err;
   // device
   double *A = nullptr, *Bm = nullptr, *f = nullptr, *wd = nullptr, *wf = nullptr, *zmin = nullptr, *zmax = nullptr;
@@ -248,6 +250,7 @@ struct WideBackend {
       if (p) hipFree(p);
     ring.destroy();
     flags.destroy();
+    clock.destroy();
     for (hipEvent_t e : bench_ev) hipEventDestroy(e);
     bench_ev.clear();
     if (ev0) hipEventDestroy(ev0);
@@ -325,6 +328,15 @@ struct WideBackend {
   int mpc_set_dynamics_track(const double* A_, const double* B_, const double* f_, int nblocks, int step_stride, int per_instance) {
     gains_valid = false;
     if (nblocks < d.N - 1 || (step_stride != 1 && step_stride != d.N - 1)) WFAIL(ALTRO_ERR_INVALID_ARG, "bad dynamics track shape");
+    if (clock.on) {   // the windows live on the device and a plain solve reads the blocks of the window it holds: all must exist
+      std::vector<int> w(d.batch);
+      WCHK(hipSetDevice(device));
+      WCHK(hipStreamSynchronize(stream));
+      WCHK(hipMemcpy(w.data(), clock.window, w.size() * sizeof(int), hipMemcpyDeviceToHost));
+      for (int v : w)
+        if ((long long)v * step_stride + (d.N - 1) > (long long)nblocks)
+          WFAIL(ALTRO_ERR_STATE, "the dynamics track ends before the window an instance holds (altro_mpc_set_clock)");
+    }
     const int rc = upload_dynamics(A_, B_, f_, (size_t)nblocks, per_instance);
     if (rc) return rc;
     ltv = true;
@@ -554,6 +566,10 @@ struct WideBackend {
     WCHK(hipMemcpyAsync(Uref, Ur, (size_t)d.batch * (Nt - 1) * d.m * sizeof(double), hipMemcpyDeviceToDevice, stream));
     kref = 0;
     have_ref = true;
+    if (clock.on) {   // a new track installs window 0 for every instance, as it does for the handle's kref
+      hipLaunchKernelGGL(altro::k_clock_window, altro::EpisodeClock::grid(d.batch), dim3(256), 0, stream, clock.window, (const int*)nullptr, 0, d.batch);
+      WCHK(hipGetLastError());
+    }
     return ALTRO_OK;
   }
 
@@ -572,6 +588,10 @@ struct WideBackend {
     WCHK(hipMemcpy(Uref, Ur, (size_t)d.batch * (Nt - 1) * d.m * sizeof(double), hipMemcpyHostToDevice));
     kref = 0;
     have_ref = true;
+    if (clock.on) {   // a new track installs window 0 for every instance, as it does for the handle's kref
+      hipLaunchKernelGGL(altro::k_clock_window, altro::EpisodeClock::grid(d.batch), dim3(256), 0, stream, clock.window, (const int*)nullptr, 0, d.batch);
+      WCHK(hipGetLastError());
+    }
     return ALTRO_OK;
   }
   int set_reference(const double* Xr, const double* Ur) {
@@ -667,6 +687,7 @@ struct WideBackend {
     p.compact = compact();
     p.mlog = mlog;   // (the kernel writes it in MPC steps only: mpc == 1)
     p.active = flags.mask();
+    p.clk = clock.args();
     p.o = o;
     if (o.projected_newton) {  // solve!(::ALTROSolver): the AL stage only has to reach the polish's tolerance
       if (o.projected_newton_tolerance >= 0) p.o.constraint_tolerance = o.projected_newton_tolerance;
@@ -709,9 +730,11 @@ struct WideBackend {
     }
     return ALTRO_OK;
   }
-  int polish_launch() {
+  // mask: the instances to polish (null: all) -- the active mask, or under an episode clock the mask of the step just solved
+  int polish_launch(const int* mask) {
     altro_pnw::WParams w{};
     w.P = params();
+    w.P.active = mask;
     w.P.o = o;   // the caller's tolerances (params() carries the AL stage's)
     w.bm = pn_bm; w.nslots = pn_slots;
     w.pn_ran = pn_ran; w.pn_failed = pn_failed; w.pn_dfail = pn_dfail; w.pn_res = pn_res; w.pn_dres0 = pn_dres0; w.pn_dres = pn_dres;
@@ -775,32 +798,42 @@ struct WideBackend {
     WCHK(hipSetDevice(device));
     int rc = prepare_launch();
     if (rc) return rc;
+    // (under an episode clock every instance has a window of its own, kept inside the track and the dynamics track by the
+    //  tick rule on the device)
     const int last_kref = mpc ? first_step + nsteps : kref;
-    if (last_kref + d.N > Nt) WFAIL(ALTRO_ERR_STATE, "reference window runs past the end of the stored trajectory");
+    if (!clock.on && last_kref + d.N > Nt) WFAIL(ALTRO_ERR_STATE, "reference window runs past the end of the stored trajectory");
     if (mpc && ltv && dyn_step_stride == 0)
       WFAIL(ALTRO_ERR_UNSUPPORTED, "the device MPC loop over per-knot dynamics needs their table for every step: altro_mpc_set_dynamics_track");
-    if (!dyn_covers(last_kref)) WFAIL(ALTRO_ERR_STATE, "the dynamics track ends before the last step's window");
+    if (!clock.on && !dyn_covers(last_kref)) WFAIL(ALTRO_ERR_STATE, "the dynamics track ends before the last step's window");
     if (o.projected_newton && (rc = polish_prepare())) return rc;
     hipEvent_t h0, h1;
     WCHK(ring.next(&h0, &h1));
     WCHK(hipEventRecord(ev0, stream));
     WCHK(hipEventRecord(h0, stream));
-    if (flags.on && !gains_valid && !debug_keep_gains)   // the instances this launch leaves out lose their stored pass too
+    // (under an episode clock the instances idle for the whole launch are left out in the same way)
+    if ((flags.on || clock.on) && !gains_valid && !debug_keep_gains)   // the instances this launch leaves out lose their stored pass too
       hipLaunchKernelGGL(k_drop_stored_pass, dim3((unsigned)((d.batch + 255) / 256)), dim3(256), 0, stream, bwst, d.batch);
     if (o.projected_newton && mpc) {
       // the steps of a fused launch as nsteps pairs of (one-step solve kernel, polish kernel): the next step's shift starts
       // from the polished trajectory and the projected multipliers, as after solve!(::ALTROSolver)
       const int kref0 = kref;
       for (int s = 0; s < nsteps && !rc; ++s) {
+        const int* mask = flags.mask();
+        if (clock.on) {   // the polish and the log kernel skip the instances that are idle AT THIS STEP
+          hipLaunchKernelGGL(altro::k_clock_step_mask, altro::EpisodeClock::grid(d.batch), dim3(256), 0, stream, clock.stepmask, clock.args(), flags.mask(),
+                             first_step + s, Nt, d.N, ltv ? dyn_blocks : 0, dyn_step_stride, d.batch);
+          if (hipGetLastError() != hipSuccess) { err = "launch of the step-mask kernel failed"; rc = ALTRO_ERR_HIP; break; }
+          mask = clock.stepmask;
+        }
         hipLaunchKernelGGL(wide_kernel_for(d.n, d.m, Pn), dim3(d.batch), dim3(wide_block_threads(d.n, d.m, lds_bytes(), coop_mode)), lds_bytes(), stream, params(), mpc, first_step + s, 1);
         rc = hipGetLastError() == hipSuccess ? ALTRO_OK : ALTRO_ERR_HIP;
         if (rc) err = "launch of the solve kernel failed";
         kref = first_step + s + 1;
-        if (!rc) rc = polish_launch();
+        if (!rc) rc = polish_launch(mask);
         if (!rc && mlog) {
           double* rec0 = mlog + (size_t)(first_step + s) * (size_t)d.batch * mlog_rec();
           hipLaunchKernelGGL(k_log_polished_wide, dim3((unsigned)((d.batch + 255) / 256)), dim3(256), 0, stream, rec0, U, cur, cost, cmax, status,
-                             flags.mask(), d.batch, d.N, d.n, d.m);
+                             mask, d.batch, d.N, d.n, d.m);
           if (hipGetLastError() != hipSuccess) { err = "launch of the log kernel failed"; rc = ALTRO_ERR_HIP; }
         }
       }
@@ -809,7 +842,7 @@ struct WideBackend {
       hipLaunchKernelGGL(wide_kernel_for(d.n, d.m, Pn), dim3(d.batch), dim3(wide_block_threads(d.n, d.m, lds_bytes(), coop_mode)), lds_bytes(), stream, params(), mpc, first_step, nsteps);
       rc = hipGetLastError() == hipSuccess ? ALTRO_OK : ALTRO_ERR_HIP;
       if (rc) err = "launch of the solve kernel failed";
-      if (!rc && o.projected_newton) rc = polish_launch();
+      if (!rc && o.projected_newton) rc = polish_launch(flags.mask());
     }
     gains_valid = true;  // (until a setter changes something the stored gains depend on)
     WCHK(hipEventRecord(h1, stream));   // (every slot of the ring handed out has both events)
@@ -824,9 +857,9 @@ struct WideBackend {
   int mpc_prepare(int step) {
     if (step < 0) WFAIL(ALTRO_ERR_INVALID_ARG, "bad step");
     if (noise && step + 1 > noise_steps) WFAIL(ALTRO_ERR_INVALID_ARG, "step outside the uploaded noise");
-    if (step + 1 + d.N > Nt) WFAIL(ALTRO_ERR_INVALID_ARG, "step runs past the end of the track");
+    if (!clock.on && step + 1 + d.N > Nt) WFAIL(ALTRO_ERR_INVALID_ARG, "step runs past the end of the track");
     if (ltv && dyn_step_stride == 0) WFAIL(ALTRO_ERR_UNSUPPORTED, "the device plant step over per-knot dynamics needs altro_mpc_set_dynamics_track");
-    if (!dyn_covers(step + 1)) WFAIL(ALTRO_ERR_STATE, "the dynamics track ends before this step's window");
+    if (!clock.on && !dyn_covers(step + 1)) WFAIL(ALTRO_ERR_STATE, "the dynamics track ends before this step's window");
     WCHK(hipSetDevice(device));
     int rc = prepare_launch();
     if (rc) return rc;
@@ -840,6 +873,7 @@ struct WideBackend {
   int benchmark_solve(int samples, int evals, float* sample_ms) {
     if (samples < 1 || evals < 1) WFAIL(ALTRO_ERR_INVALID_ARG, "samples and evals must be positive");
     if (flags.on) WFAIL(ALTRO_ERR_STATE, "altro_batch_benchmark_solve restores and repeats whole batches: clear the active mask first");
+    if (clock.on) WFAIL(ALTRO_ERR_STATE, "altro_batch_benchmark_solve restores and repeats whole batches: clear the episode clock first");
     WCHK(hipSetDevice(device));
     const size_t B = d.batch, lx = (size_t)d.N * d.n, lu = (size_t)(d.N - 1) * d.m;
     if (!Xsave) WCHK(hipMalloc(&Xsave, B * lx * sizeof(double)));
@@ -1061,7 +1095,8 @@ struct WideBackend {
   int mpc_run(int first_step, int nsteps) {
     if (nsteps < 1 || first_step < 0) WFAIL(ALTRO_ERR_INVALID_ARG, "bad step range");
     if (noise && first_step + nsteps > noise_steps) WFAIL(ALTRO_ERR_INVALID_ARG, "steps outside the uploaded noise");
-    if (first_step + nsteps + d.N > Nt) WFAIL(ALTRO_ERR_INVALID_ARG, "steps run past the end of the track");
+    // (under an episode clock an instance that runs off the end of its track goes idle there: altro_mpc_set_clock)
+    if (!clock.on && first_step + nsteps + d.N > Nt) WFAIL(ALTRO_ERR_INVALID_ARG, "steps run past the end of the track");
     if (mlog && first_step + nsteps > mlog_cap) WFAIL(ALTRO_ERR_INVALID_ARG, "steps outside the capacity of the log (altro_mpc_set_log)");
     return enqueue(1, first_step, nsteps);
   }

@@ -81,6 +81,7 @@ class BatchMPC:
         s._chk(s._L.altro_mpc_set_track(s.h, api._p(Xt), api._p(Ut), pb.Nt))
         nz = api._c(pb.noise)
         s._chk(s._L.altro_mpc_set_noise(s.h, api._p(nz), nz.shape[0]))
+        self._U0 = Ut[:, :s.N - 1]   # controls of the track's first window: what a respawned instance starts from
         self.i = 0
 
     def initial_solve(self):
@@ -133,6 +134,40 @@ class BatchMPC:
         not shifted or solved, and their slots of log() stay never written (iterations = status = -1, NaN)."""
         api.set_active(self.solver, active)
 
+    def set_clock(self, start, length=None):
+        """Per-instance episode clock of the loop (api.set_clock; start None clears it): instance b takes absolute step i as
+        its local step i - start[b], with that step's window, and is idle outside 0 <= local step < length[b]."""
+        api.set_clock(self.solver, start, length)
+
+    def respawn(self, which, x0, at_step, U=None):
+        """Start the instances `which` (indices) over between two launches: from `at_step` on they run a new episode from
+        x0 (len(which), n), as a new solver given that x0 would run its steps 0, 1, ... -- with the noise rows of the
+        absolute steps.  The recipe: cold restart from the controls U (len(which), N-1, m; default the track's first window),
+        which under the clock rewinds their window to 0; set their x0; a plain solve under a mask of just those instances
+        (the solve before the loop); the previous mask back; start[which] = at_step.  Sets an all-zero clock first when none
+        is set.  Synchronises."""
+        s = self.solver
+        which = np.atleast_1d(np.asarray(which, dtype=np.int64))
+        sel = np.zeros(s.B, dtype=np.int32)
+        sel[which] = 1
+        x0 = np.asarray(x0, dtype=np.float64).reshape(len(which), s.n)
+        start, length, _ = api.get_clock(s)
+        api.set_clock(s, start, None if (length < 0).all() else length)   # (a clock must be in force for the rewind)
+        Ufull = np.ascontiguousarray(self._U0)
+        if U is not None:
+            Ufull = Ufull.copy()
+            Ufull[which] = np.asarray(U, dtype=np.float64).reshape(len(which), s.N - 1, s.m)
+        api.restart_instances(s, sel, Ufull)
+        xall = self.x0()
+        xall[which] = x0
+        api.set_initial_state(s, xall)
+        mask = api.get_active(s)
+        api.set_active(s, sel)
+        api.solve(s)
+        api.set_active(s, None if mask.all() else mask)
+        start[which] = int(at_step)
+        api.set_clock(s, start, None if (length < 0).all() else length)
+
     def enable_log(self, steps):
         """Keep one record per MPC step on the device for steps 0 .. steps-1 (altro_mpc_set_log); 0 switches it off.
         Remembers the initial state the handle holds now: the first row of closed_loop_trajectory()."""
@@ -183,6 +218,7 @@ class TrackMPC:
                 s._chk(s._L.altro_mpc_set_noise_model(s.h, 2, api._p(w), None))
         if not shift:
             s._chk(s._L.altro_mpc_set_shift(s.h, 0))
+        self._U0 = Ut[:, :s.N - 1]
         self.i = 0
 
     initial_solve = BatchMPC.initial_solve
@@ -193,6 +229,8 @@ class TrackMPC:
     step_benchmark = BatchMPC.step_benchmark
     x0 = BatchMPC.x0
     set_active = BatchMPC.set_active
+    set_clock = BatchMPC.set_clock
+    respawn = BatchMPC.respawn
     enable_log = BatchMPC.enable_log
     log = BatchMPC.log
     closed_loop_trajectory = BatchMPC.closed_loop_trajectory

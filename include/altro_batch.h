@@ -508,6 +508,49 @@ int32_t altro_batch_get_active(altro_handle* h, int32_t* active);
  * ALTRO_ERR_INVALID_ARG (nothing changes, the handle stays usable): NULL handle, NULL which or U; _dev: what that block refuses. */
 int32_t altro_batch_restart_instances(altro_handle* h, const int32_t* which, const double* X, const double* U);
 int32_t altro_batch_restart_instances_dev(altro_handle* h, const int32_t* which, const double* X, const double* U);
+/* ---- per-instance episode clock: staggered and re-spawned episodes inside the device-resident MPC loop.
+ * The reference runs one closed loop per problem, each from its own step 0 (simple_rocket.jl:137-205,
+ * random_linear_problem.jl:121-139); in a batch the episodes start and end at different times, and without a clock
+ * altro_mpc_step_async / _run_async put every instance at the SAME step of its track.
+ *
+ * altro_mpc_set_clock: start [batch] (any int32, negative too), length [batch] or NULL (unbounded; a negative entry counts
+ * as 0).  start == NULL clears the clock.  The library copies the arrays into buffers of its own and keeps no caller pointer.
+ * With no clock set nothing differs, bit for bit.  Needs a track (altro_mpc_set_track).
+ * While a clock is set, instance b at absolute step i -- the index passed to altro_mpc_step_async / _run_async /
+ * _prepare_async -- is at LOCAL step l = i - start[b], and it ticks at step i iff
+ *     0 <= l,   l < length[b] (when given),   l + 1 + N <= Nt (its next window fits the track),
+ *     and with altro_mpc_set_dynamics_track: (l + 1) * step_stride + N - 2 < nblocks (so do that window's blocks);
+ * otherwise it is idle at that step.  Running off the end of a track ends the episode and is no error: under a clock the
+ * "steps run past the end of the track" refusals of the three calls give way to this rule (the noise-range and log-capacity
+ * checks stay, keyed by the absolute step).  The rule is evaluated on the device: the host never needs the values.
+ * A ticking instance does what step l does on a handle without a clock -- plant step, reference window <- l + 1, dynamics
+ * block r = l + 1, primal and dual shift, solve, and with projected_newton = 1 the polish over that window -- except that its
+ * plant step takes the noise row of the ABSOLUTE step, noise[i][b] (a re-spawned instance does not replay the noise of its
+ * first life), and its log record goes to slot i.
+ * An idle instance is treated as an inactive one is (altro_batch_set_active): nothing the library owns for it changes, its
+ * log slot i stays never written; an instance the active mask leaves out is idle whatever its clock says.
+ * Per-instance window.  The reference window becomes per-instance state: altro_mpc_set_clock on a handle without a clock
+ * starts every instance at the handle's current window (a call that only changes a clock in force keeps the windows); a
+ * tick sets it to l + 1; altro_batch_restart_instances(_dev) under a clock rewinds the selected instances to window 0 (without
+ * a clock that call is unchanged); altro_mpc_set_track / altro_batch_set_reference put every instance back to window 0.  Plain
+ * solves and the polish read the instance's own window; altro_mpc_set_dynamics_track under a clock is refused (ALTRO_ERR_STATE)
+ * when its table ends before the window some instance holds.  Clearing the clock while the windows differ is refused
+ * (ALTRO_ERR_STATE): one scalar cannot hold them; when they agree, that window becomes the handle's.
+ * Re-spawning between two launches: restart the instance (window 0), set its x0, run altro_batch_solve under a mask of just
+ * that instance, restore the mask, set start[b] to the next absolute step -- from there its records are those of a new
+ * handle's solve-then-steps 0, 1, ... with the noise rows of the absolute steps.
+ * altro_mpc_set_clock_dev: the arrays on the device, under the rules of the device-pointer block (validated before anything
+ * is enqueued, stream-ordered, no host synchronisation unless it clears, no allocation after the first call); it leaves the
+ * handle in the device state its host twin would.
+ * altro_mpc_get_clock: start, length (-1: unbounded), window, each [batch], any may be NULL but not all; with no clock set
+ * start = 0, length = -1 and window = the handle's window for every instance.  Synchronises the stream.
+ * altro_batch_benchmark_solve under a clock returns ALTRO_ERR_STATE, as under a mask.  A handle that moves to the
+ * one-wave-per-instance kernel afterwards keeps the clock, as it keeps the log setting.
+ * ALTRO_ERR_INVALID_ARG (nothing changes): NULL handle; get_clock with all three outputs NULL; _dev: what the device-pointer
+ * block refuses.  ALTRO_ERR_STATE: no track set; the clearing case above. */
+int32_t altro_mpc_set_clock(altro_handle* h, const int32_t* start, const int32_t* length);
+int32_t altro_mpc_set_clock_dev(altro_handle* h, const int32_t* start, const int32_t* length);
+int32_t altro_mpc_get_clock(altro_handle* h, int32_t* start, int32_t* length, int32_t* window);
 /* Stream hand-over without the host: an event recorded on one stream and waited on by the other (the events belong to the
  * handle and are reused).  wait_stream: work enqueued on the handle's stream from now on starts after everything enqueued so
  * far on `producer` (a hipStream_t).  signal_stream: work enqueued on `consumer` from now on starts after everything enqueued
