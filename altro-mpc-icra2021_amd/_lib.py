@@ -45,6 +45,7 @@ EXPORTS = [
     "altro_batch_set_active", "altro_batch_set_active_dev", "altro_batch_get_active",
     "altro_batch_restart_instances", "altro_batch_restart_instances_dev",
     "altro_mpc_set_clock", "altro_mpc_set_clock_dev", "altro_mpc_get_clock",
+    "altro_batch_update_constraint_data_dev", "altro_batch_set_bounds_dev", "altro_batch_get_dev_refusals",
 ]
 """every symbol include/altro_batch.h declares"""
 
@@ -160,6 +161,10 @@ def lib():
         L.altro_mpc_set_clock.argtypes = [H, ip, ip]
         L.altro_mpc_set_clock_dev.argtypes = [H, C.c_void_p, C.c_void_p]
         L.altro_mpc_get_clock.argtypes = [H, ip, ip, ip]
+    if hasattr(L, "altro_batch_update_constraint_data_dev"):   # constraint data and bounds from device pointers
+        L.altro_batch_update_constraint_data_dev.argtypes = [H, C.c_int32, C.c_void_p, C.c_void_p]
+        L.altro_batch_set_bounds_dev.argtypes = [H, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]
+        L.altro_batch_get_dev_refusals.argtypes = [H, C.POINTER(C.c_int64)]
     L.altro_batch_add_constraint.argtypes = [H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                              dp, dp, dp, dp, C.c_int32, ip]
     L.altro_batch_update_constraint_data.argtypes = [H, C.c_int32, dp, dp]

@@ -19,7 +19,8 @@ Julia name (reference call site)                      -> here
 Arrays are numpy, instance-major: X (B, N, n), U (B, N-1, m), A (B, n, n) in natural
 (row, col) indexing; conversion to the C-ABI's column-major blocks happens here.
 
-Device-resident I/O: set_initial_state, update_trajectory, initial_controls and set_dynamics also take torch tensors that
+Device-resident I/O: set_initial_state, update_trajectory, initial_controls, set_dynamics, update_constraint_data and
+set_bounds also take torch tensors that
 live on the solver's GPU (the altro_*_dev entry points: nothing crosses PCIe, nothing synchronises), and states, controls
 and first_knot write into such tensors.  A GPU tensor is never copied, cast or moved behind the caller's back: float64,
 contiguous, on the solver's device and of the exact shape, or ValueError.  Matrices keep their natural (row, col) indexing;
@@ -410,9 +411,33 @@ def set_tracking_cost(solver, Q, R, Qf, dt=None):
 
 def set_bounds(solver, con, zmin, zmax):
     """New bounds of the BOX constraint `con` (index into the problem's constraint list), in place: (n+m,) each for the
-    batch or (B, n+m) each per instance; the finite sides must be those the BOX was added with (altro_batch_set_bounds)."""
+    batch or (B, n+m) each per instance; the finite sides must be those the BOX was added with (altro_batch_set_bounds).
+    With GPU tensors (both) the rows are checked and written on the device (altro_batch_set_bounds_dev): a row that fails
+    leaves that instance's bounds as they were and is counted (dev_refusals) instead of raising."""
+    if _on_gpu(zmin) or _on_gpu(zmax):
+        if not (_on_gpu(zmin) and _on_gpu(zmax)):
+            raise ValueError("set_bounds: zmin and zmax must both be GPU tensors, or neither")
+        with _bracket(solver):
+            return _set_bounds_dev(solver, con, zmin, zmax)
     pi, (lo, hi) = _rows((zmin, zmax), solver.B)
     solver._chk(solver._L.altro_batch_set_bounds(solver.h, solver.con_ids[con], _p(lo), _p(hi), int(pi)))
+
+
+def _set_bounds_dev(solver, con, zmin, zmax):
+    nz = solver.n + solver.m
+    pi = len(zmin.shape) == 2
+    shape = (solver.B, nz) if pi else (nz,)
+    check_device_tensor(zmin, shape, solver.device, "zmin")
+    check_device_tensor(zmax, shape, solver.device, "zmax")
+    solver._chk(solver._L.altro_batch_set_bounds_dev(solver.h, solver.con_ids[con], _addr(zmin), _addr(zmax), int(pi)))
+
+
+def dev_refusals(solver):
+    """rows the device-side check of set_bounds (GPU tensors) has refused since the solver was created
+    (altro_batch_get_dev_refusals); synchronises"""
+    v = C.c_int64(0)
+    solver._chk(solver._L.altro_batch_get_dev_refusals(solver.h, C.byref(v)))
+    return int(v.value)
 
 
 def set_options(solver, **kw):
@@ -824,9 +849,33 @@ def solve_counters(solver):
 
 
 def update_constraint_data(solver, con, A=None, b=None):
-    """In-place mutation of a constraint's (per-knot) data: grasp_mpc_helpers.jl:46-55."""
+    """In-place mutation of a constraint's (per-knot) data: grasp_mpc_helpers.jl:46-55.  With GPU tensors (A, b in the
+    shape the constraint was given with; either may be None) the rows are written on the device, stream-ordered
+    (altro_batch_update_constraint_data_dev)."""
+    if _on_gpu(A) or _on_gpu(b):
+        if not ((A is None or _on_gpu(A)) and (b is None or _on_gpu(b))):
+            raise ValueError("update_constraint_data: A and b must both be GPU tensors (or None), or neither")
+        with _bracket(solver):
+            return _update_constraint_data_dev(solver, con, A, b)
     solver._chk(solver._L.altro_batch_update_constraint_data(
         solver.h, solver.con_ids[con], _p(_c(A)) if A is not None else None, _p(_c(b)) if b is not None else None))
+
+
+def con_data_shape(solver, con):
+    """shape of the A a LINEAR / SOC constraint of the problem was given with (b: the same without the last dimension)"""
+    c, first, last = solver.prob.constraints.items[con]
+    if isinstance(c, BoundConstraint):
+        raise AltroError(_lib.ERR_INVALID_ARG, "update_constraint_data: a BoundConstraint has no A, b (set_bounds)")
+    return tuple(np.shape(c.A))
+
+
+def _update_constraint_data_dev(solver, con, A, b):
+    shape = con_data_shape(solver, con)
+    if A is not None:
+        check_device_tensor(A, shape, solver.device, "A")
+    if b is not None:
+        check_device_tensor(b, shape[:-1], solver.device, "b")
+    solver._chk(solver._L.altro_batch_update_constraint_data_dev(solver.h, solver.con_ids[con], _addr(A), _addr(b)))
 
 
 def alpha_trace(solver):

@@ -116,9 +116,41 @@ def run_rocket(batch=256, N_mpc=21, steps=100, N_cold=301, dt=0.05, seed=1, laun
     return res
 
 
-def run_grasp(batch=256, N_mpc=21, steps=30, N_cold=251, tf=25.0, seed=1):
+def _run_grasp_device(sv, gp, Xt, Ut, batch, N_mpc, steps, rng):
+    """The loop of run_grasp with every per-tick array in GPU memory (mpc.ExternalMPC): the cold solve's trajectory and its
+    per-knot constraint tables are uploaded once and every window is a slice of them on the device, the plant is torch
+    arithmetic, the noise is the host generator's, uploaded once."""
+    import torch
+    dev = torch.device("cuda", sv.device)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+    Xt_d, Ut_d = up(Xt), up(Ut)
+    tabs = [(up(c.A), up(c.b)) for c in gp.constraints[1:]]
+    A_d, B_d, f_d = up(gp.A.T), up(gp.Bm.T), up(gp.f)
+    noise = up(np.stack([rng.standard_normal((batch, 6)) for _ in range(steps)]))
+    loop = mpc.ExternalMPC(sv)
+    x = up(np.tile(Xt[0], (batch, 1)))
+    u0, _, _, _ = api.first_knot(sv)
+    its, sts = [], []
+    for i in range(1, steps + 1):
+        xn = x @ A_d + u0 @ B_d + f_d
+        xn = xn + noise[i - 1] * xn.abs().max(dim=1, keepdim=True).values / 100.0
+        Xr = Xt_d[i:i + N_mpc].expand(batch, -1, -1).contiguous()
+        Ur = Ut_d[i:i + N_mpc - 1].expand(batch, -1, -1).contiguous()
+        data = {ci: (A[i:i + N_mpc - 1], b[i:i + N_mpc - 1]) for ci, (A, b) in enumerate(tabs)}
+        u0, _, st, it = loop.tick(xn, Xr, Ur, constraint_data=data)
+        x = xn
+        its.append(it); sts.append(st)
+    torch.cuda.synchronize(dev)
+    it = torch.stack(its).cpu().numpy()
+    ok = torch.stack(sts).cpu().numpy() == api.SOLVE_SUCCEEDED
+    return _result(np.full(steps, np.nan), it, ok, batch)   # (no per-tick device times: nothing waits for a tick here)
+
+
+def run_grasp(batch=256, N_mpc=21, steps=30, N_cold=251, tf=25.0, seed=1, device_io=False):
     """Cold grasp solve, then run_grasp_mpc (grasp_mpc.jl:8-104): every step rewrites the per-knot
-    constraint data of the shifted window (grasp_mpc_helpers.jl:1-55)."""
+    constraint data of the shifted window (grasp_mpc_helpers.jl:1-55).
+    device_io=True: the same loop with every per-tick array in GPU memory (no PCIe copy, no host synchronisation inside the
+    loop; `time` is then NaN)."""
     import copy
     gp = problems.gen_grasp_problem(N=N_cold, tf=tf)
     x0c = np.tile(gp.x0, (batch, 1))
@@ -139,6 +171,12 @@ def run_grasp(batch=256, N_mpc=21, steps=30, N_cold=251, tf=25.0, seed=1):
     sv = api.ALTROSolver(mpc.constrained_problem(tp, np.tile(Xt[0], (batch, 1)), Xr, Ur, U0=Ur.copy()), api.SolverOptions(**GRASP_MPC_OPTS))
     api.solve(sv)
     rng = np.random.default_rng(seed)
+    cold_res = {"time": cst.tsolve_ms, "iter": cst.iterations[:1], "solve_succeeded": cst.status[:1] == api.SOLVE_SUCCEEDED}
+    if device_io:
+        res = _run_grasp_device(sv, gp, Xt, Ut, batch, N_mpc, steps, rng)
+        sv.close()
+        res["cold"] = cold_res
+        return res
     t, it, ok = [], [], []
     for i in range(1, steps + 1):
         X, U = api.states(sv), api.controls(sv)
@@ -154,7 +192,7 @@ def run_grasp(batch=256, N_mpc=21, steps=30, N_cold=251, tf=25.0, seed=1):
         st = api.stats(sv)
         t.append(st.tsolve_ms); it.append(st.iterations.copy()); ok.append(st.status == api.SOLVE_SUCCEEDED)
     res = _result(t, it, ok, batch)
-    res["cold"] = {"time": cst.tsolve_ms, "iter": cst.iterations[:1], "solve_succeeded": cst.status[:1] == api.SOLVE_SUCCEEDED}
+    res["cold"] = cold_res
     return res
 
 

@@ -64,6 +64,8 @@ struct altro_handle {
   double *wd = nullptr, *wf = nullptr, *zmin = nullptr, *zmax = nullptr;  // [16] each, or [Bp][16] (tab_rows)
   // host copies of the cost weights and bounds: [rows][16] each, rows = 1 (shared by the batch) or batch (per instance)
   std::vector<double> wd_h, wf_h, zmin_h, zmax_h;
+  bool bnd_stale = false;                // altro_batch_set_bounds_dev wrote the device rows: zmin_h / zmax_h are refreshed before use
+  unsigned long long* refusals = nullptr;  // device counter: rows altro_batch_set_bounds_dev refused since create
   bool cost_pi = false, bnd_pi = false;  // per-instance cost weights / bounds: the device tables then hold Bp rows (imask)
   int tab_cap = 1;                       // rows the device tables have room for
   bool box_lo_fin[LW] = {}, box_hi_fin[LW] = {};  // finite sides of the BOX as it was added (altro_batch_set_bounds)
@@ -128,6 +130,7 @@ struct altro_handle {
     int per_knot, per_instance;
     std::vector<double> A, b;  // A row-major p x nz blocks: [instance if per_instance][knot of the range if per_knot]
     int lanes[LW];
+    bool stale = false;        // altro_batch_update_constraint_data_dev wrote the device rows: A, b are refreshed before use
   };
   std::vector<ConBlock> cons;
   int* lanebuf = nullptr;  // device scratch [16] for dual transfers
@@ -561,7 +564,21 @@ static bool supported_dims(int n, int m) {
 // given per instance -- [Bp][16] each (imask ~0u: element inst * 16 + j), the padded instances repeating the last row.
 static unsigned tab_imask(const altro_handle* h) { return (h->cost_pi || h->bnd_pi) ? ~0u : 15u; }
 
+// Host mirror of the bounds after altro_batch_set_bounds_dev: the rows the device holds are read back before anything
+// reads zmin_h / zmax_h (the callers synchronise already).  The mirror holds 1 row or `batch` rows (bnd_pi), and a `_dev`
+// write never changes which: the device table holds at least as many.
+static int refresh_bounds_mirror(altro_handle* h) {
+  if (!h->bnd_stale) return ALTRO_OK;
+  const size_t rows = h->zmin_h.size() / LW;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipMemcpy(h->zmin_h.data(), h->zmin, rows * LW * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(h->zmax_h.data(), h->zmax, rows * LW * sizeof(double), hipMemcpyDeviceToHost));
+  h->bnd_stale = false;
+  return ALTRO_OK;
+}
+
 static int upload_tables(altro_handle* h) {
+  if (int rcm = refresh_bounds_mirror(h)) return rcm;
   const bool pi = h->cost_pi || h->bnd_pi;
   const size_t rows = pi ? (size_t)h->Bp : 1;
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -951,6 +968,8 @@ int32_t altro_batch_create(const altro_dims* dims, const altro_opts* opts, int32
     CCHK(hipMemsetAsync(h->n_fo, 0, Bp * sizeof(long long), h->stream));
     CCHK(hipMemsetAsync(h->Qz, 0, (N + 1) * row * sizeof(double), h->stream));
     CCHK(hipMalloc(&h->cur, Bp * sizeof(int)));
+    CCHK(hipMalloc(&h->refusals, sizeof(unsigned long long)));
+    CCHK(hipMemsetAsync(h->refusals, 0, sizeof(unsigned long long), h->stream));
     CCHK(hipMalloc(&h->perm, Bp * sizeof(int)));
     CCHK(hipMalloc(&h->gscore, Bp * sizeof(int)));
     CCHK(hipMalloc(&h->iters, Bp * sizeof(int)));
@@ -1027,7 +1046,7 @@ static void free_dpp_backend(altro_handle* h) {
                    (void**)&h->n_ok, (void**)&h->n_trials, (void**)&h->Zsave, (void**)&h->n_gconf, (void**)&h->dzero, (void**)&h->Qz,
                    (void**)&h->Dff, (void**)&h->ahash, (void**)&h->kmu, (void**)&h->n_fo, (void**)&h->perm, (void**)&h->gscore,
                    (void**)&h->pn_ran, (void**)&h->pn_failed, (void**)&h->pn_res, (void**)&h->pn_dfail, (void**)&h->pn_dres0, (void**)&h->pn_dres, (void**)&h->pnE, (void**)&h->pndv, (void**)&h->pnLd, (void**)&h->pnLo,
-                   (void**)&h->pnvec, (void**)&h->pntz, (void**)&h->pnnb, (void**)&h->pnnst, (void**)&h->pnrinfo, (void**)&h->mlog};
+                   (void**)&h->pnvec, (void**)&h->pntz, (void**)&h->pnnb, (void**)&h->pnnst, (void**)&h->pnrinfo, (void**)&h->mlog, (void**)&h->refusals};
   for (void** p : ptrs)
     if (*p) { hipFree(*p); *p = nullptr; }
   h->stage_bytes = 0;
@@ -1199,8 +1218,36 @@ int32_t altro_batch_set_tracking_cost_per_instance(altro_handle* h, const double
 // goal at knot N-1 and the stage constraints on 0..N-2).  Every cone takes the first p lanes of an
 // aligned quad, linear rows fill whatever lanes remain (also the spare lanes of a cone's quad).
 // Redone whenever a constraint is added before the first solve.
+// Host mirrors after altro_batch_update_constraint_data_dev: the rows a `_dev` call wrote exist on the device only.  Before
+// anything reads cb.A / cb.b (pack_constraints rebuilds the tables from the blocks of EVERY constraint) the device tables are
+// read back and the stale blocks are taken out of them, the exact inverse of the packing below.  Synchronises; its callers do.
+static int refresh_con_mirrors(altro_handle* h) {
+  bool any = false;
+  for (const auto& cb : h->cons) any = any || cb.stale;
+  if (!any) return ALTRO_OK;
+  const size_t nz = h->d.n + h->d.m, N = h->d.N, B = h->d.batch;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipMemcpy(h->Acon_h.data(), h->Acon, h->Acon_h.size() * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(h->bcon_h.data(), h->bcon, h->bcon_h.size() * sizeof(double), hipMemcpyDeviceToHost));
+  for (auto& cb : h->cons) {
+    if (!cb.stale) continue;
+    const size_t nk = cb.per_knot ? (size_t)(cb.k1 - cb.k0 + 1) : 1;
+    for (size_t ib = 0; ib < (cb.per_instance ? B : 1); ++ib)
+      for (size_t kk = 0; kk < nk; ++kk)
+        for (int r = 0; r < cb.p; ++r) {
+          const size_t blk = ib * nk + kk;
+          const size_t et = (ib * N + (size_t)cb.k0 + kk) * LW + cb.lanes[r];
+          for (size_t jj = 0; jj < nz; ++jj) cb.A[(blk * cb.p + r) * nz + jj] = h->Acon_h[et * LW + jj];
+          cb.b[blk * cb.p + r] = h->bcon_h[et];
+        }
+    cb.stale = false;
+  }
+  return ALTRO_OK;
+}
+
 static int pack_constraints(altro_handle* h) {
   if (!h->con_dirty) return ALTRO_OK;
+  if (int rcm = refresh_con_mirrors(h)) return rcm;
   const int nz = h->d.n + h->d.m, N = h->d.N;
   // one table per instance as soon as any block carries per-instance data (grasp_mpc_helpers.jl:46-55 mutates each
   // problem's own per-knot tables); the lane assignment (cmeta) is common to the batch either way
@@ -1388,6 +1435,7 @@ int32_t altro_batch_update_constraint_data(altro_handle* h, int32_t con_id, cons
     for (auto& cb : h->cons) {
       if (cb.id != con_id) continue;
       const size_t nblk = (cb.per_knot ? (size_t)(cb.k1 - cb.k0 + 1) : 1) * (cb.per_instance ? (size_t)h->d.batch : 1);
+      if (int rcm = refresh_con_mirrors(h)) return rcm;   // (a `_dev` update before this one: its rows come back first)
       if (A) cb.A.assign(A, A + nblk * cb.p * nz);
       if (b) cb.b.assign(b, b + nblk * cb.p);
       // same lanes, new coefficients: refresh the tables (the solver sees it at the next solve, as
@@ -1415,6 +1463,7 @@ int32_t altro_batch_set_bounds(altro_handle* h, int32_t con_id, const double* zm
       for (int j = 0; j < nz; ++j) { lo[r * LW + j] = zmin[r * nz + j]; hi[r * LW + j] = zmax[r * nz + j]; }
     h->zmin_h.swap(lo);
     h->zmax_h.swap(hi);
+    h->bnd_stale = false;   // (the whole mirror is new)
     h->bnd_pi = per_instance != 0;
     if (int rc = upload_tables(h)) return rc;
     if (int rcd = drop_gains(h)) return rcd;
@@ -2364,6 +2413,110 @@ int32_t altro_batch_get_first_knot_dev(altro_handle* h, double* u0, double* x1, 
     hipLaunchKernelGGL(altro::k_first_knot, grid_for(B_ * LW), dim3(256), 0, h->stream, u0, x1, status, iterations, h->Z, h->cur,
                        h->status, h->iters, N_ * (size_t)LW, (int)B_, (int)N_, (int)n_, (int)m_);
     HIPCHK(h, hipGetLastError());
+    return ALTRO_OK;
+  });
+}
+
+// ---- constraint data and bounds from device pointers
+// altro_batch_update_constraint_data with A, b on the device: the rows go straight to the constraint's lanes of Acon / bcon.
+// cmeta, ckn, the duals and the lane assignment are untouched.  con_inv (the sweeps load a lane's row once, from its
+// canonical knot) survives only an update that cannot break it: one shared block, fanned out to every knot.
+int32_t altro_batch_update_constraint_data_dev(altro_handle* h, int32_t con_id, const double* A, const double* b) {
+  return guard(h, [&]() -> int32_t {
+    DEV_ENTER(h, "altro_batch_update_constraint_data_dev");
+    const int box_id = h->wide ? h->wide->box_id : h->box_id;
+    if (box_id >= 0 && con_id == box_id) FAIL(h, ALTRO_ERR_INVALID_ARG, std::string(fn_) + ": con_id is a BOX constraint (altro_batch_set_bounds_dev)");
+    altro_handle::ConBlock* cb = nullptr;
+    altro_wide::WideBackend::Block* bl = nullptr;
+    size_t nblk = 0, p = 0;
+    if (h->wide) {
+      if ((bl = h->wide->find(con_id))) {
+        nblk = (bl->per_knot ? (size_t)(bl->k1 - bl->k0 + 1) : 1) * (bl->per_instance ? B_ : 1);
+        p = bl->p;
+      }
+    } else {
+      for (auto& c : h->cons)
+        if (c.id == con_id) cb = &c;
+      if (cb) {
+        nblk = (cb->per_knot ? (size_t)(cb->k1 - cb->k0 + 1) : 1) * (cb->per_instance ? B_ : 1);
+        p = cb->p;
+      }
+    }
+    if (!nblk) FAIL(h, ALTRO_ERR_INVALID_ARG, std::string(fn_) + ": unknown constraint id");
+    if (!A && !b) FAIL(h, ALTRO_ERR_INVALID_ARG, std::string(fn_) + ": A and b are both null");
+    DEV_ARG(h, "A", A, nblk * p * (n_ + m_), double, true);
+    DEV_ARG(h, "b", b, nblk * p, double, true);
+    DEV_WIDE(h, update_constraint_data_dev(bl, A, b));
+    if (h->con_dirty) {   // (only after a packing that failed: the tables are rebuilt on the host first)
+      if (int rc = pack_constraints(h)) return rc;
+    }
+    altro::ConLanes lanes{};
+    for (int r = 0; r < LW; ++r) lanes.lane[r] = cb->lanes[r] >= 0 ? cb->lanes[r] : 0;
+    const int nk = cb->k1 - cb->k0 + 1;
+    const size_t ninst = h->con_per_instance ? (size_t)h->Bp : 1;
+    hipLaunchKernelGGL(altro::k_pack_con_rows, grid_for(ninst * nk * p * LW), dim3(256), 0, h->stream, h->Acon, h->bcon, A, b, lanes, (int)ninst,
+                       (int)B_, (int)N_, (int)(n_ + m_), cb->k0, nk, (int)p, cb->per_knot, cb->per_instance);
+    HIPCHK(h, hipGetLastError());
+    if (cb->per_knot || cb->per_instance) h->con_inv = 0;
+    cb->stale = true;
+    return drop_gains(h);
+  });
+}
+
+// altro_batch_set_bounds with zmin, zmax on the device: checked and written row by row on the device (device_io.h:
+// k_set_bounds_rows).  Going from one shared row to one row per instance is the one case that changes the tables' shape: it
+// goes through upload_tables (every row starts as the old shared row), which synchronises.  A shared row given while the
+// tables hold one row per instance is written to every row and the tables keep their shape: equal rows, the same results.
+int32_t altro_batch_set_bounds_dev(altro_handle* h, int32_t con_id, const double* zmin, const double* zmax, int32_t per_instance) {
+  return guard(h, [&]() -> int32_t {
+    DEV_ENTER(h, "altro_batch_set_bounds_dev");
+    const int box_id = h->wide ? h->wide->box_id : h->box_id;
+    if (box_id < 0 || con_id != box_id) FAIL(h, ALTRO_ERR_INVALID_ARG, std::string(fn_) + ": con_id is not a BOX constraint");
+    const size_t rows = per_instance ? B_ : 1;
+    DEV_ARG(h, "zmin", zmin, rows * (n_ + m_), double, false);
+    DEV_ARG(h, "zmax", zmax, rows * (n_ + m_), double, false);
+    DEV_WIDE(h, set_bounds_dev(zmin, zmax, per_instance));
+    if (per_instance && !h->bnd_pi) {
+      if (int rc = refresh_bounds_mirror(h)) return rc;
+      std::vector<double> lo(B_ * LW), hi(B_ * LW);
+      for (size_t r = 0; r < B_; ++r) {
+        std::memcpy(&lo[r * LW], h->zmin_h.data(), LW * sizeof(double));
+        std::memcpy(&hi[r * LW], h->zmax_h.data(), LW * sizeof(double));
+      }
+      h->zmin_h.swap(lo);
+      h->zmax_h.swap(hi);
+      h->bnd_pi = true;
+      if (int rc = upload_tables(h)) {   // the handle keeps the shape it had
+        h->zmin_h.swap(lo);
+        h->zmax_h.swap(hi);
+        h->bnd_pi = false;
+        return rc;
+      }
+    }
+    altro::FinMask fin{};
+    for (int j = 0; j < LW; ++j) {
+      if (h->box_lo_fin[j]) fin.lo[0] |= 1ull << j;
+      if (h->box_hi_fin[j]) fin.hi[0] |= 1ull << j;
+    }
+    const size_t trows = (h->cost_pi || h->bnd_pi) ? (size_t)h->Bp : 1;
+    hipLaunchKernelGGL(altro::k_set_bounds_rows, grid_for(trows * LW), dim3(256), 0, h->stream, h->zmin, h->zmax, zmin, zmax, fin, (int)(n_ + m_), LW,
+                       (int)trows, (int)B_, per_instance ? 1 : 0, h->refusals);
+    HIPCHK(h, hipGetLastError());
+    h->bnd_stale = true;
+    return drop_gains(h);
+  });
+}
+
+int32_t altro_batch_get_dev_refusals(altro_handle* h, int64_t* rows) {
+  return guard(h, [&]() -> int32_t {
+    if (!h) return dev_null_handle("altro_batch_get_dev_refusals");
+    if (!rows) FAIL(h, ALTRO_ERR_INVALID_ARG, "altro_batch_get_dev_refusals: null pointer");
+    DEV_WIDE(h, get_dev_refusals(rows));
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    unsigned long long v = 0;
+    HIPCHK(h, hipMemcpy(&v, h->refusals, sizeof(v), hipMemcpyDeviceToHost));
+    *rows = (int64_t)v;
     return ALTRO_OK;
   });
 }

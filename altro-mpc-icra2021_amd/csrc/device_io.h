@@ -1,10 +1,12 @@
 // device_io.h -- what the device-pointer entry points (altro_*_dev, altro_batch_wait_stream / _signal_stream;
 // include/altro_batch.h) share between the two backends: the validation of a caller's device pointer, the pair of events a
-// handle orders its stream against a caller's stream with, and the read-out kernels of altro_batch_get_first_knot_dev.
+// handle orders its stream against a caller's stream with, the read-out kernels of altro_batch_get_first_knot_dev, and the
+// kernels that write constraint rows and box bounds from a caller's device arrays.
 // Nothing here synchronises a stream or touches host memory.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 
@@ -173,6 +175,94 @@ struct EpisodeClock {
     on = false;
   }
 };
+
+// altro_batch_update_constraint_data_dev, 16-lane backend: the caller's rows A [ninst_src][nk_src][p][nz] (row-major), b
+// [ninst_src][nk_src][p] go straight to the lanes pack_constraints gave the constraint: Acon [ninst][N][16 lanes][16 columns],
+// bcon [ninst][N][16].  One thread per (table slot ib, knot of the range, row, column 0..15); columns >= nz are written as 0,
+// padded slots ib >= B mirror instance B - 1, a constraint with one block (per_knot = 0) fans out to every knot of its range
+// and one with shared data (per_instance = 0) to every slot of the table.  A or b may be null (left as it is).
+struct ConLanes {
+  int lane[16];
+};
+__global__ void k_pack_con_rows(double* __restrict__ Acon, double* __restrict__ bcon, const double* __restrict__ A,
+                                const double* __restrict__ b, ConLanes lanes, int ninst, int B, int N, int nz, int k0, int nk, int p,
+                                int per_knot, int per_instance) {
+  constexpr int LW_ = 16;
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (size_t)ninst * nk * p * LW_) return;
+  const int col = (int)(t % LW_);
+  const int r = (int)((t / LW_) % p);
+  const int kk = (int)((t / LW_ / p) % nk);
+  const size_t ib = t / LW_ / p / nk;
+  const size_t src = ib < (size_t)B ? ib : (size_t)B - 1;
+  const size_t nks = per_knot ? (size_t)nk : 1;
+  const size_t blk = (per_instance ? src * nks : 0) + (per_knot ? (size_t)kk : 0);
+  const size_t et = (ib * N + (size_t)(k0 + kk)) * LW_ + lanes.lane[r];
+  if (A) Acon[et * LW_ + col] = col < nz ? A[(blk * p + r) * nz + col] : 0.0;
+  if (b && col == 0) bcon[et] = b[blk * p + r];
+}
+
+// The same on the one-wave-per-instance backend: AconT [ninst][N][z][P] (transposed), bcon [ninst][N][P]; the constraint's
+// rows are r0 .. r0 + p - 1 of the P rows.  One thread per (table slot, knot of the range, row, element of z).
+__global__ void k_pack_con_rows_wide(double* __restrict__ AconT, double* __restrict__ bcon, const double* __restrict__ A,
+                                     const double* __restrict__ b, int ninst, int N, int z, int P, int r0, int k0, int nk, int p,
+                                     int per_knot, int per_instance) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (size_t)ninst * nk * p * z) return;
+  const int j = (int)(t % z);
+  const int r = (int)((t / z) % p);
+  const int kk = (int)((t / z / p) % nk);
+  const size_t ib = t / z / p / nk;
+  const size_t nks = per_knot ? (size_t)nk : 1;
+  const size_t blk = (per_instance ? ib * nks : 0) + (per_knot ? (size_t)kk : 0);
+  const size_t e = ib * N + (size_t)(k0 + kk);
+  if (A) AconT[(e * z + j) * P + r0 + r] = A[(blk * p + r) * z + j];
+  if (b && j == 0) bcon[e * P + r0 + r] = b[blk * p + r];
+}
+
+// altro_batch_set_bounds_dev, both backends.  One 16-lane group per row of the device tables zmin / zmax [rows][stride]
+// (stride 16 on the 16-lane backend, n + m on the other); the group of row ib reads the caller's row src = ib (per_instance;
+// rows ib >= B repeat row B - 1) or row 0 (shared), checks on the device what check_bound_rows checks on the host -- no NaN,
+// zmin <= zmax, the finite sides those the BOX was added with (bit j of fin.lo / fin.hi; finite as the kernels test it) --
+// and writes it only if the whole row passes, with the infinities of the absent sides and of the columns past nz regenerated.
+// A row that fails leaves its table row as it was and adds 1 to *refusals (once per caller's row).  A shared row gets the
+// same verdict in every group, so the table changes as a whole or not at all.
+struct FinMask {
+  unsigned long long lo[2], hi[2];   // elements 0..63, 64..127
+};
+__global__ void k_set_bounds_rows(double* __restrict__ zmin, double* __restrict__ zmax, const double* __restrict__ src_lo,
+                                  const double* __restrict__ src_hi, FinMask fin, int nz, int stride, int rows, int B,
+                                  int per_instance, unsigned long long* __restrict__ refusals) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t row = t / 16;
+  const int lane = (int)(t % 16);
+  const bool live = row < (size_t)rows;      // (every lane of the wave takes part in the shuffles)
+  const size_t ib = live ? row : 0;
+  const size_t src = per_instance ? (ib < (size_t)B ? ib : (size_t)B - 1) : 0;
+  int bad = 0;
+  for (int j = lane; j < nz; j += 16) {
+    const double lo = src_lo[src * nz + j], hi = src_hi[src * nz + j];
+    const bool lf = (fin.lo[j >> 6] >> (j & 63)) & 1ull, hf = (fin.hi[j >> 6] >> (j & 63)) & 1ull;
+    if (lo != lo || hi != hi || lo > hi || (lo > -1e300) != lf || (hi < 1e300) != hf) bad = 1;
+  }
+  for (int s = 8; s > 0; s >>= 1) bad |= __shfl_xor(bad, s, 16);
+  if (!live) return;
+  if (bad) {
+    if (lane == 0 && (per_instance ? ib < (size_t)B : ib == 0)) atomicAdd(refusals, 1ull);
+    return;
+  }
+  for (int j = lane; j < stride; j += 16) {
+    const bool lf = j < nz && ((fin.lo[j >> 6] >> (j & 63)) & 1ull), hf = j < nz && ((fin.hi[j >> 6] >> (j & 63)) & 1ull);
+    zmin[ib * stride + j] = lf ? src_lo[src * nz + j] : -INFINITY;
+    zmax[ib * stride + j] = hf ? src_hi[src * nz + j] : INFINITY;
+  }
+}
+// rows 1 .. rows - 1 of a [rows][len] table <- row 0 (a shared row of bounds becomes one row per instance)
+__global__ void k_fan_row0(double* __restrict__ tab, int len, int rows) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (size_t)rows * len || t < (size_t)len) return;
+  tab[t] = tab[t % len];
+}
 
 // altro_batch_get_first_knot_dev, 16-lane backend: Zp holds [Bp] blocks of (2N + 1) knots x 16 lanes, two planes of N knots;
 // lanes 0..n-1 of a knot are its state, n..n+m-1 its control.  One thread per (instance, lane) reads plane cur[inst]:

@@ -170,11 +170,13 @@ struct WideBackend {
     bool soc = false;
     bool per_instance = false;
     std::vector<double> A, b;  // row-major p x nz blocks: [instance if per_instance][knot of the range if per_knot]
+    bool stale = false;        // update_constraint_data_dev wrote the device rows: A, b are refreshed before use
   };
   std::vector<Block> blocks;
   int Pn = 0, ncon = 0, ncone = 0;
   bool con_dirty = false, con_locked = false, con_per_instance = false;
   size_t acon_elems = (size_t)-1;
+  unsigned long long* refusals = nullptr;   // device counter: rows set_bounds_dev refused since create
 
   int np() const { return pad16(d.n); }
   int mp() const { return pad16(d.m); }
@@ -226,7 +228,7 @@ struct WideBackend {
     DA_(Jtrace, B * ALTRO_TRACE_LEN); DA_(ctrace, B * ALTRO_TRACE_LEN); DA_(atrace, B * ALTRO_TRACE_LEN);
     DA_(n_backward, B); DA_(n_rollout, B); DA_(n_trials, B); DA_(n_solves, B); DA_(n_iters, B); DA_(n_ok, B); DA_(n_gconf, B); DA_(n_gs, B);
     DA_(noise_w, kMaxN); DA_(noise_grp, kMaxN);
-    DA_(Lc, 1); DA_(AconT, 1); DA_(bcon, 1); DA_(ctype, 1); DA_(rowk0, 1); DA_(rowk1, 1); DA_(rowc0, 1); DA_(rowcp, 1);
+    DA_(Lc, 1); DA_(AconT, 1); DA_(bcon, 1); DA_(ctype, 1); DA_(rowk0, 1); DA_(rowk1, 1); DA_(rowc0, 1); DA_(rowcp, 1); DA_(refusals, 1);
 #undef DA_
     {
       std::vector<double> inf(z, INFINITY), ninf(z, -INFINITY), w(kMaxN, 0.01), m0(B, 1.0);
@@ -245,7 +247,7 @@ struct WideBackend {
     void* ptrs[] = {A, Bm, f, wd, wf, zmin, zmax, x0, Xref, Uref, X, U, Lb, Lc, mu, Kg, dg, trash, AconT, bcon, stage, cur, ctype,
                     rowk0, rowk1, rowc0, rowcp, iters, iters_outer, status, noise_grp, cost, cmax, Jtrace, ctrace, atrace, noise, noise_w,
                     n_backward, n_rollout, n_trials, n_solves, n_iters, n_ok, Xsave, Usave, Qz, n_gconf, n_gs, fac, bwst, aset,
-                    pn_ran, pn_failed, pn_dfail, pn_res, pn_dres0, pn_dres, pnE, pndv, pnLd, pnLo, pnvec, pntz, pnblk, pnnb, pnnst, pnrinfo, mlog};
+                    pn_ran, pn_failed, pn_dfail, pn_res, pn_dres0, pn_dres, pnE, pndv, pnLd, pnLo, pnvec, pntz, pnblk, pnnb, pnnst, pnrinfo, mlog, refusals};
     for (void* p : ptrs)
       if (p) hipFree(p);
     ring.destroy();
@@ -430,6 +432,8 @@ struct WideBackend {
     if (kind == ALTRO_CON_SOC && (p < 2 || p > 4)) WFAIL(ALTRO_ERR_UNSUPPORTED, "second-order cones of dimension 2..4 only");
     if (kind == ALTRO_CON_LINEAR && sense != ALTRO_SENSE_EQ && sense != ALTRO_SENSE_INEQ) return ALTRO_ERR_INVALID_ARG;
     if (Pn + p > kMaxP) WFAIL(ALTRO_ERR_UNSUPPORTED, "more than 64 linear constraint rows");
+    // (rows a `_dev` update wrote come back while the tables still have the row count Pn they were packed with)
+    if (int rcm = refresh_block_mirrors()) return rcm;
     Block bl;
     bl.id = ncon++;
     bl.soc = kind == ALTRO_CON_SOC;
@@ -451,10 +455,110 @@ struct WideBackend {
     return nullptr;
   }
 
+  // Host mirrors after update_constraint_data_dev: the rows a `_dev` call wrote exist on the device only.  Before anything
+  // reads Block::A / b the device tables are read back and the stale blocks are taken out of them (the inverse of
+  // pack_constraints).  The tables are decoded with the Pn and con_per_instance they were packed with: add_constraint
+  // refreshes BEFORE it changes Pn.  Synchronises; its callers (a host update, a repack, add_constraint) do anyway.
+  int refresh_block_mirrors() {
+    bool any = false;
+    for (const auto& bl : blocks) any = any || bl.stale;
+    if (!any) return ALTRO_OK;
+    WCHK(hipSetDevice(device));
+    const size_t N = d.N, z = nz(), P = Pn, B = d.batch;
+    const size_t ninst = con_per_instance ? B : 1;
+    std::vector<double> At(ninst * N * z * P), bc(ninst * N * P);
+    WCHK(hipStreamSynchronize(stream));
+    WCHK(hipMemcpy(At.data(), AconT, At.size() * sizeof(double), hipMemcpyDeviceToHost));
+    WCHK(hipMemcpy(bc.data(), bcon, bc.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (auto& bl : blocks) {
+      if (!bl.stale) continue;
+      const size_t nk = bl.per_knot ? (size_t)(bl.k1 - bl.k0 + 1) : 1;
+      for (size_t ib = 0; ib < (bl.per_instance ? B : 1); ++ib)
+        for (size_t kk = 0; kk < nk; ++kk)
+          for (int r = 0; r < bl.p; ++r) {
+            const size_t blk = ib * nk + kk, e = ib * N + (size_t)bl.k0 + kk, row = (size_t)bl.r0 + r;
+            bl.b[blk * bl.p + r] = bc[e * P + row];
+            for (size_t j = 0; j < z; ++j) bl.A[(blk * bl.p + r) * z + j] = At[(e * z + j) * P + row];
+          }
+      bl.stale = false;
+    }
+    return ALTRO_OK;
+  }
+
+  // altro_batch_update_constraint_data_dev (pointers validated by the caller): the rows go straight into AconT / bcon on the
+  // stream.  While the tables do not exist yet (con_dirty: before the first solve, or after a host update) this one call packs
+  // them on the host first, which synchronises once.  bl: the constraint's block (find(), looked up by the caller).
+  int update_constraint_data_dev(Block* bl, const double* A_, const double* b_) {
+    WCHK(hipSetDevice(device));
+    if (con_dirty) {
+      WCHK(hipStreamSynchronize(stream));   // a solve in flight may still be reading the tables the repack frees or overwrites
+      const int rc = pack_constraints();
+      if (rc) return rc;
+    }
+    const int nk = bl->k1 - bl->k0 + 1;
+    const size_t ninst = con_per_instance ? (size_t)d.batch : 1;
+    const size_t total = ninst * nk * bl->p * (size_t)nz();
+    hipLaunchKernelGGL(altro::k_pack_con_rows_wide, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, AconT, bcon, A_, b_, (int)ninst,
+                       d.N, nz(), Pn, bl->r0, bl->k0, nk, bl->p, bl->per_knot, bl->per_instance ? 1 : 0);
+    WCHK(hipGetLastError());
+    gains_valid = false;
+    bl->stale = true;
+    return ALTRO_OK;
+  }
+
+  // altro_batch_set_bounds_dev (pointers validated by the caller): rows checked and written on the device
+  // (device_io.h: k_set_bounds_rows).  A shared row written while the table holds one row per instance goes to every row, and the
+  // table keeps that shape.  The first per-instance call on a table of one row gives it B rows: it allocates and synchronises
+  // once, and every row starts as the shared one.  (The caller has checked that the id is the BOX's.)
+  int set_bounds_dev(const double* lo, const double* hi, int per_instance) {
+    WCHK(hipSetDevice(device));
+    const size_t B = d.batch, z = nz();
+    if (per_instance && !b_pi && B > 1) {
+      if (!b_big) {
+        WCHK(hipStreamSynchronize(stream));
+        double *nlo = nullptr, *nhi = nullptr;
+        int rc;
+        if ((rc = dalloc(&nlo, B * z, false))) return rc;
+        if ((rc = dalloc(&nhi, B * z, false))) { hipFree(nlo); return rc; }
+        WCHK(hipMemcpyAsync(nlo, zmin, z * sizeof(double), hipMemcpyDeviceToDevice, stream));
+        WCHK(hipMemcpyAsync(nhi, zmax, z * sizeof(double), hipMemcpyDeviceToDevice, stream));
+        WCHK(hipStreamSynchronize(stream));
+        WCHK(hipFree(zmin)); zmin = nlo;
+        WCHK(hipFree(zmax)); zmax = nhi;
+        b_big = true;
+      }
+      const dim3 g((unsigned)((B * z + 255) / 256));
+      hipLaunchKernelGGL(altro::k_fan_row0, g, dim3(256), 0, stream, zmin, (int)z, (int)B);
+      hipLaunchKernelGGL(altro::k_fan_row0, g, dim3(256), 0, stream, zmax, (int)z, (int)B);
+      WCHK(hipGetLastError());
+      b_pi = 1;
+    }
+    altro::FinMask fin{};
+    for (size_t j = 0; j < z; ++j) {
+      if (box_lo_fin[j]) fin.lo[j >> 6] |= 1ull << (j & 63);
+      if (box_hi_fin[j]) fin.hi[j >> 6] |= 1ull << (j & 63);
+    }
+    const size_t rows = b_pi ? B : 1;
+    hipLaunchKernelGGL(altro::k_set_bounds_rows, dim3((unsigned)((rows * 16 + 255) / 256)), dim3(256), 0, stream, zmin, zmax, lo, hi, fin, (int)z,
+                       (int)z, (int)rows, (int)B, per_instance ? 1 : 0, refusals);
+    WCHK(hipGetLastError());
+    gains_valid = false;
+    return ALTRO_OK;
+  }
+  int get_dev_refusals(int64_t* rows) {
+    WCHK(hipSetDevice(device));
+    WCHK(hipStreamSynchronize(stream));
+    unsigned long long v = 0;
+    WCHK(hipMemcpy(&v, refusals, sizeof(v), hipMemcpyDeviceToHost));
+    *rows = (int64_t)v;
+    return ALTRO_OK;
+  }
+
   int update_constraint_data(int con_id, const double* A_, const double* b_) {
     gains_valid = false;
     Block* bl = find(con_id);
     if (!bl) WFAIL(ALTRO_ERR_INVALID_ARG, "no such LINEAR constraint");
+    if (int rcm = refresh_block_mirrors()) return rcm;   // (a `_dev` update before this one: its rows come back first)
     const size_t nb = (bl->per_knot ? (size_t)(bl->k1 - bl->k0 + 1) : 1) * (bl->per_instance ? (size_t)d.batch : 1);
     if (A_) bl->A.assign(A_, A_ + nb * bl->p * nz());
     if (b_) bl->b.assign(b_, b_ + nb * bl->p);
@@ -465,6 +569,7 @@ struct WideBackend {
   // per-knot tables of the generic rows (transposed: AconT[k][j][r])
   int pack_constraints() {
     if (!con_dirty) return ALTRO_OK;
+    if (int rcm = refresh_block_mirrors()) return rcm;
     WCHK(hipSetDevice(device));
     const size_t N = d.N, z = nz(), P = Pn;
     // one table per instance as soon as any block carries per-instance data (grasp_mpc_helpers.jl:46-55 mutates each

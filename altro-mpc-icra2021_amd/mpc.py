@@ -249,7 +249,8 @@ class ExternalMPC:
         self.shift = bool(shift)
         self.i = 0
 
-    def tick(self, x0, Xref=None, Uref=None, dynamics=None, out=None, active=None, restart=None, U_restart=None):
+    def tick(self, x0, Xref=None, Uref=None, dynamics=None, out=None, active=None, restart=None, U_restart=None,
+             constraint_data=None, bounds=None):
         """x0 (B, n); Xref (B, N, n) and Uref (B, N-1, m): the new reference window (both or neither); dynamics: an
         api.LinearModel of column-major-stored tensors (api module docstring) -- all GPU tensors on the solver's device.
         active (B,) int32: the instances this tick shifts and solves; it stays set as the solver's mask (api.set_active).
@@ -257,6 +258,10 @@ class ExternalMPC:
         (B, N-1, m; default Uref) -- they are not shifted, and are solved if active.  With neither, a mask the solver holds
         stays in force; restart without active means every instance is active, and leaves no mask set.  For an inactive
         instance the tensors returned hold its last values.
+        constraint_data {con: (A, b)}: new data of LINEAR / SOC constraints (index into the problem's constraint list; A or b
+        may be None), bounds (zmin, zmax): new rows of the BOX -- GPU tensors (api.update_constraint_data / api.set_bounds),
+        applied after the primal shift and before the dual shift, the order of the reference's grasp loop
+        (grasp_mpc.jl:60-75).
         Returns (u0, x1, status, iterations) as api.first_knot does (out: tensors to write into)."""
         s = self.solver
         if not api._on_gpu(x0):
@@ -288,7 +293,14 @@ class ExternalMPC:
                     api._set_active_dev(s, shift_mask)
                 elif active is not None:
                     api._set_active_dev(s, active)
-                api.shift_fill(s, True, True)
+                if constraint_data or bounds is not None:
+                    api.shift_fill(s, True, False)
+                    self._constraints_dev(constraint_data, bounds)
+                    api.shift_fill(s, False, True)
+                else:
+                    api.shift_fill(s, True, True)
+            else:
+                self._constraints_dev(constraint_data, bounds)
             if active is not None:
                 api._set_active_dev(s, active)
             elif shift_mask is not None:     # no mask given: the shift's was this tick's own
@@ -299,6 +311,16 @@ class ExternalMPC:
             api.signal_stream(s)
         self.i += 1
         return res
+
+    def _constraints_dev(self, constraint_data, bounds):
+        s = self.solver
+        for con, (A, b) in (constraint_data or {}).items():
+            api._update_constraint_data_dev(s, con, A, b)
+        if bounds is not None:
+            box = [k for k, (c, _, _) in enumerate(s.prob.constraints.items) if isinstance(c, api.BoundConstraint)]
+            if not box:
+                raise ValueError("tick: bounds given, but the problem has no BoundConstraint")
+            api._set_bounds_dev(s, box[0], *bounds)
 
 
 def _add_specs(cons, specs, n, m):

@@ -445,7 +445,7 @@ int32_t altro_batch_get_stream(altro_handle* h, void** stream);
  * that is too short, NULL where it is not allowed, a NULL handle -- the call returns ALTRO_ERR_INVALID_ARG with a message in
  * altro_last_error (of the handle; of NULL for a NULL handle), nothing is launched and the handle is unchanged and usable.
  * A setter leaves the handle in the byte-identical device state its host twin would, a getter writes byte-identical values.
- * Not covered, on purpose (set once, or packed on the host): constraint tables, cost weights, bounds, duals, gains, traces,
+ * Not covered, on purpose (set once, or packed on the host): cost weights, duals, gains, traces,
  * altro_mpc_set_track / _noise / _dynamics_track and the MPC log. */
 
 /* altro_batch_set_initial_state with x0 [batch][n] on the device */
@@ -471,6 +471,33 @@ int32_t altro_batch_get_initial_state_dev(altro_handle* h, double* x0);
  * altro_batch_get_stats reports them.  Any pointer may be NULL (skipped).  For an instance that is inactive
  * (altro_batch_set_active) these are its LAST values: those of the last solve it took part in. */
 int32_t altro_batch_get_first_knot_dev(altro_handle* h, double* u0, double* x1, int32_t* status, int32_t* iterations);
+
+/* ---- constraint data and box bounds from device pointers: the grasp loop (grasp_mpc_helpers.jl:46-55 rewrites the torque
+ * balance, the grasp-force rows and both friction cones of the shifted window on every step) and per-tick actuator limits,
+ * under the rules of the device-pointer block above.
+ * altro_batch_update_constraint_data_dev: A, b on the device in the layout the constraint was added with
+ * ([batch][knots][p][n+m] / [batch][knots][p] when it was added with per-instance data); either may be NULL (unchanged), not
+ * both.  A kernel writes the rows straight into the constraint's place in the device tables; lane assignment, knot ranges and
+ * duals are untouched, the stored gains are dropped stream-ordered.  On the one-wave-per-instance kernel the tables are packed
+ * on the host before the first solve and after a host altro_batch_update_constraint_data: a `_dev` call that finds them
+ * unpacked packs them once, which synchronises the stream.
+ * altro_batch_set_bounds_dev: zmin, zmax on the device, [n+m] (per_instance = 0) or [batch][n+m].  What
+ * altro_batch_set_bounds checks on the host is checked on the DEVICE, row by row: no NaN, zmin <= zmax, the pattern of finite
+ * sides that of the BOX as it was added.  A row that passes is written (the infinities of absent sides regenerated); a row that
+ * fails leaves that instance's bounds exactly as they were -- with per_instance = 0 the whole table -- and adds 1 to a counter
+ * on the device; the call still returns ALTRO_OK.  altro_batch_get_dev_refusals: the count since create; synchronises.
+ * The first per-instance call on a handle whose bounds are one shared row changes the shape of the tables: that one call
+ * reallocates and synchronises the stream once (every instance starts from the shared row).  A shared row given while the
+ * tables hold one row per instance goes to every row.
+ * Host and device calls may be mixed in any order and give what host calls alone give: the host copies the library keeps of
+ * these tables are marked stale by a `_dev` write and read back from the device before a host call next needs them.
+ * ALTRO_ERR_INVALID_ARG (nothing launched, the handle unchanged): NULL handle; unknown con_id; a BOX id given to
+ * update_constraint_data_dev, a LINEAR / SOC id to set_bounds_dev; A and b both NULL; get_dev_refusals: NULL rows; what the
+ * device-pointer block refuses. */
+int32_t altro_batch_update_constraint_data_dev(altro_handle* h, int32_t con_id, const double* A, const double* b);
+int32_t altro_batch_set_bounds_dev(altro_handle* h, int32_t con_id, const double* zmin, const double* zmax,
+                                   int32_t per_instance);
+int32_t altro_batch_get_dev_refusals(altro_handle* h, int64_t* rows);
 
 /* ---- per-instance active mask and cold restart: ragged batches of closed loops.
  * The reference runs one problem per loop, and a loop that ends simply stops calling solve! (simple_rocket.jl:137-205); in a

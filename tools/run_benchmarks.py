@@ -2,8 +2,8 @@
 Usage: python tools/run_benchmarks.py [--launch-steps K] [--device-io] [random_linear|sweeps|rocket|grasp|quadruped|all] [batch] [results.npz | outdir/]
 --launch-steps K > 1: random_linear and rocket run K MPC steps per launch (altro_mpc_run_async) and take every step's
 iterations / status from the device log; "time" is then per launch (the other benchmarks rewrite data between steps).
---device-io: the quadruped loop keeps every per-tick array in GPU memory (torch tensors, mpc.ExternalMPC): no per-tick device
-times then ("time" is NaN), iterations and status as before.
+--device-io: the quadruped and grasp loops keep every per-tick array in GPU memory (torch tensors, mpc.ExternalMPC; the grasp
+loop's constraint tables too): no per-tick device times then ("time" is NaN), iterations and status as before.
 The optional .npz holds, per benchmark, the reference's result Dict entries (random_linear_problem.jl:188)
 as arrays: "<name>/time" (ms per MPC step for the batch) and "<name>/iter" (steps x instances).  With a
 directory instead, the three sweeps are written as horizon_comp.h5, state_dim_comp.h5, control_dim_comp.h5 in
@@ -41,7 +41,7 @@ if which in ("all", "rocket"):
     r = Bm.run_rocket(batch=B, launch_steps=K); raw["rocket N_mpc=21"] = r
     out["rocket N_mpc=21"] = Bm.summarise(r)
 if which in ("all", "grasp"):
-    r = Bm.run_grasp(batch=min(B, 64), N_cold=101, tf=10.0); raw["grasp N_mpc=21"] = r
+    r = Bm.run_grasp(batch=min(B, 64), N_cold=101, tf=10.0, device_io=DEVICE_IO); raw["grasp N_mpc=21"] = r
     out["grasp N_mpc=21"] = Bm.summarise(r)
 if which in ("all", "quadruped"):
     for nm, lin in (("quadruped N=15 pyramids", True), ("quadruped N=15 cones", False)):
