@@ -88,8 +88,8 @@ struct altro_handle {
   // scheduling switches (altro_debug_set; the defaults are the product's behaviour)
   bool d_in_kd = false;  // the last solve launch's kernel keeps d in the gain rows (altro::kd_holds_d), not in Dff
   int reuse = 1;  // gain reuse (solve_dpp16.h fosweep); "no_reuse" switches it off (tests)
-  int lone = 1;  // backward_lone (solve_dpp16.h); "no_lone" switches it off (tests: lone == four-row pass bit for bit)
-  int pair = 1;  // backward_pair (two rows need a pass); "no_pair" keeps the four-row form for them
+  int lone = 1;  // backward_split<4> (solve_dpp16.h); "no_lone" switches it off (tests: lone == four-row pass bit for bit)
+  int pair = 1;  // backward_split<2> (two rows need a pass); "no_pair" keeps the four-row form for them
   int group_max_steps = 32;  // fused launches of more steps are not grouped ("group_max_steps": diagnostic)
   int shadow = 1;  // "no_shadow": rows that sit a phase out keep their own instance (solve_dpp16.h shadow_enter)
   int useqz = 1;   // "no_qz_pass": backward passes always recompute their cost / box expansion (solve_dpp16.h backward QV)

@@ -155,8 +155,8 @@ struct SolveParams {
   int resync;            // 1: rows wait a turn to stay in step with their wave-mates (run(), phase A)
   int reuse;             // 1: gain reuse (fosweep) allowed; ALTRO_NO_REUSE=1 at create time switches it off
   int shadow;  // rows that sit a phase out take the identity of a row that takes part (Solver::shadow_enter)
-  int pair;              // 1: a backward pass that exactly two rows of a wave need runs two DPP rows per instance (backward_pair)
-  int lone;              // 1: a backward pass that only one row of a wave needs runs spread over the four DPP rows (backward_lone)
+  int pair;              // 1: a backward pass that exactly two rows of a wave need runs two DPP rows per instance (backward_split<2>)
+  int lone;              // 1: a backward pass that only one row of a wave needs runs spread over the four DPP rows (backward_split<4>)
   int useqz;             // 1: a backward pass over a trajectory a rollout has just produced reads its expansion back from Qz (backward QV)
   // generic affine constraints (LINEAR eq/ineq, SOC): up to 16 constraint rows per knot, row r
   // on lane r, organised in 4 quads of 4 lanes; a quad is one cone (SOC of dimension <= 4, or
@@ -457,8 +457,8 @@ struct Solver {
   unsigned* simd_row = nullptr;  // this wave's SIMD in P.simd_tab (16 wave slots), or null
   unsigned wave_slot = 0;
   int turns = 0;           // turns of the wave loop so far
-  int n_pair = 0;          // backward passes of this launch that ran as backward_pair (altro_batch_get_wave_passes [0])
-  int n_lone = 0;          // backward passes of this launch that ran as backward_lone (diagnostic, wave_cycles[7])
+  int n_pair = 0;          // backward passes of this launch that ran as backward_split<2> (altro_batch_get_wave_passes [0])
+  int n_lone = 0;          // backward passes of this launch that ran as backward_split<4> (diagnostic, wave_cycles[7])
   ASet* ah;    // this lane's active set of the backward pass that left the gains in KD (LDS; kept in P.ahash between launches)
   ASet* qhs;   // this lane's active set of the trajectory in Qz (LDS)
   ASet* atr;   // this lane's trash set: where a row that sits a phase out accumulates
@@ -1404,6 +1404,111 @@ struct Solver {
     code = ((bh & ahi) ? 1u : 0u) | ((bl & alo) ? 2u : 0u);
   }
 
+  // Expansion of the cost (weight w) and box terms of this lane's element at knot k: gradient qz, Hessian diagonal hz; the
+  // sides that entered the Hessian go into the active set ta.  lanes: the lanes that have box terms at this knot (the
+  // terminal knot: the states).  QV (see backward()): zr carries the knot's Qz, and z, lhi, llo are not read.
+  template <bool QV>
+  __device__ __forceinline__ void expand_knot(const LaneConst& lc, double mu, double w, int k, bool lanes, double z, double zr,
+                                              double lhi, double llo, ASet* ta, double& qz, double& hz) const {
+    if constexpr (QV) {
+      qz = zr;
+      hz = hz_of(w, mu, aset_get(qhs, k));
+    } else {
+      qz = w * (z - zr);
+      hz = w;
+      unsigned code;
+      box_expand(lc, mu, z, lhi, llo, box_at(k) & lanes, qz, hz, code);
+      aset_add(ta, code, k);
+    }
+  }
+
+  // The part of a knot every form of the backward pass shares (backward, backward_split): from gz (Qx[j] on x lanes, Qu[a]
+  // on u lanes) and hq[a] (row NX + a of H: [Qux Quu]) the factors L, 1 / D of Quu + rho I, the right-hand sides r, the gains
+  // and feedforward terms kd, the new vector s; adds the knot's terms to dV and ORs into fail (a pivot not positive) and
+  // dbig (a feedforward term above rounding level against the control z it would change).
+  template <bool RHO>
+  __device__ __forceinline__ void knot_gains(double gz, const double (&hq)[NU], double rho, double z, double (&kd)[NU],
+                                             double (&L)[NU][NU], double (&dinv)[NU], double (&r)[NU], double& snew,
+                                             double& dV1, double& dV2, bool& fail, bool& dbig) const {
+    // gather Quu (lower triangle) and Qu to every lane
+    double quu[NU][NU];
+    double qu[NU];
+    sfor<0, NU>([&](auto a) {
+      constexpr int A = decltype(a)::value;
+      qu[A] = bcast<NX + A>(gz);
+      sfor<0, A + 1>([&](auto b) {
+        constexpr int Bq = decltype(b)::value;
+        quu[A][Bq] = bcast<NX + Bq>(hq[A]);
+      });
+    });
+    // L D L' of Quu + rho I (redundantly on every lane); Ld[i][k] = L[i][k]*D[k]
+    double Ld[NU][NU];
+    sfor<0, NU>([&](auto jc) {
+      constexpr int Jc = decltype(jc)::value;
+      double dd = RHO ? quu[Jc][Jc] + rho : quu[Jc][Jc];
+      sfor<0, Jc>([&](auto kk) {
+        constexpr int Kk = decltype(kk)::value;
+        dd -= L[Jc][Kk] * Ld[Jc][Kk];
+      });
+      fail = fail | !(dd > 0.0);
+      dinv[Jc] = rcp_nr(dd);
+      sfor<Jc + 1, NU>([&](auto ii) {
+        constexpr int I = decltype(ii)::value;
+        double v = quu[I][Jc];
+        sfor<0, Jc>([&](auto kk) {
+          constexpr int Kk = decltype(kk)::value;
+          v -= L[I][Kk] * Ld[Jc][Kk];
+        });
+        Ld[I][Jc] = v;
+        L[I][Jc] = v * dinv[Jc];
+      });
+    });
+    // right-hand side: x lanes Qux(:,j), u lanes Qu  -> kd = -Quu_reg^{-1} rhs
+    sfor<0, NU>([&](auto a) {
+      constexpr int A = decltype(a)::value;
+      r[A] = is_x ? hq[A] : qu[A];
+    });
+    {
+      double y[NU];
+      sfor<0, NU>([&](auto ii) {
+        constexpr int I = decltype(ii)::value;
+        double v = r[I];
+        sfor<0, I>([&](auto kk) { v -= L[I][decltype(kk)::value] * y[decltype(kk)::value]; });
+        y[I] = v;
+      });
+      sfor<0, NU>([&](auto ir) {
+        constexpr int I = NU - 1 - decltype(ir)::value;
+        double v = y[I] * dinv[I];
+        sfor<I + 1, NU>([&](auto kk) { v -= L[decltype(kk)::value][I] * kd[decltype(kk)::value]; });
+        kd[I] = v;
+      });
+      sfor<0, NU>([&](auto a) { kd[decltype(a)::value] = -kd[decltype(a)::value]; });
+    }
+    {  // feedforward magnitude against the control it would change (u lanes hold every d[a] in kd[])
+      double dm = fabs(kd[0]);
+      sfor<1, NU>([&](auto a) { dm = fmax(dm, fabs(kd[decltype(a)::value])); });
+      dbig = dbig | (is_u & !(dm <= 1e-9 * (1.0 + fabs(z))));
+    }
+    // d to every lane (from the first u lane)
+    double dd_[NU];
+    sfor<0, NU>([&](auto a) { dd_[decltype(a)::value] = bcast<NX>(kd[decltype(a)::value]); });
+    // s = Qx + Qux'd - rho K'd ;  dV += (d'Qu, -1/2 d'Qu - 1/2 rho d'd)
+    snew = gz;
+    double t1 = 0.0, dtd = 0.0, ktd = 0.0;
+    sfor<0, NU>([&](auto a) {
+      constexpr int A = decltype(a)::value;
+      snew += r[A] * dd_[A];
+      t1 += dd_[A] * qu[A];
+      if constexpr (RHO) {
+        dtd += dd_[A] * dd_[A];
+        ktd += kd[A] * dd_[A];
+      }
+    });
+    if constexpr (RHO) snew -= rho * ktd;
+    dV1 += t1;
+    dV2 += RHO ? (-0.5 * t1 - 0.5 * rho * dtd) : (-0.5 * t1);
+  }
+
   // backwardpass! (SURVEY A.3 / oracle backward_pass): Riccati recursion over plane `cur`,
   // writes the gain blocks KD, returns dV and whether any Quu pivot was not positive.
   //
@@ -1467,21 +1572,13 @@ struct Solver {
     double Sx[NX + 1];
     {
       const int k = N - 1;
-      double qz, hz;
-      double z = 0.0;
-      if constexpr (QV) {
-        qz = ldg(P.Qz, qat(k));
-        hz = hz_of(lc.wf, mu, aset_get(qhs, k));
-      } else {
-        z = ldg(P.Z, zs + zat(k));
-        const double zr = ldg(P.Zref, rat(kref + k));
-        const double lhi = ldg(P.Lb, lb_at(k, 0)), llo = ldg(P.Lb, lb_at(k, 1));
-        qz = lc.wf * (z - zr);
-        hz = lc.wf;
-        unsigned codeT;
-        box_expand(lc, mu, z, lhi, llo, box_at(k) & is_x, qz, hz, codeT);
-        aset_add(ta, codeT, k);
+      const double z = QV ? 0.0 : ldg(P.Z, zs + zat(k)), zr = QV ? ldg(P.Qz, qat(k)) : ldg(P.Zref, rat(kref + k));   // QV: zr carries Qz
+      double lhi = 0.0, llo = 0.0, qz, hz;
+      if constexpr (!QV) {
+        lhi = ldg(P.Lb, lb_at(k, 0));
+        llo = ldg(P.Lb, lb_at(k, 1));
       }
+      expand_knot<QV>(lc, mu, lc.wf, k, is_x, z, zr, lhi, llo, ta, qz, hz);
       if constexpr (CONES) {
         double hT[NZ];
         sfor<0, NZ>([&](auto c) {
@@ -1544,16 +1641,7 @@ struct Solver {
       double lcn = 0.0;
       if constexpr (CONES) lcn = ldg(P.Lc, qat(km));
       double qz, hz;
-      if constexpr (QV) {
-        qz = zr;
-        hz = hz_of(lc.wd, mu, aset_get(qhs, k));
-      } else {
-        qz = lc.wd * (z - zr);
-        hz = lc.wd;
-        unsigned code;
-        box_expand(lc, mu, z, lhi, llo, box_at(k), qz, hz, code);
-        aset_add(ta, code, k);
-      }
+      expand_knot<QV>(lc, mu, lc.wd, k, true, z, zr, lhi, llo, ta, qz, hz);
       // W = [S; s'] * G   (w[NX] = (G's)[lane])
       double w[NX + 1];
       sfor<0, NX + 1>([&](auto c) { w[decltype(c)::value] = 0.0; });
@@ -1571,83 +1659,10 @@ struct Solver {
       }
       Blk<NX, NU>::GtW(h, g, w);
       const double gz = qz + w[NX];  // Qx[j] on x lanes, Qu[a] on u lanes
-      // gather Quu (lower triangle) and Qu to every lane
-      double quu[NU][NU];
-      double qu[NU];
-      sfor<0, NU>([&](auto a) {
-        constexpr int A = decltype(a)::value;
-        qu[A] = bcast<NX + A>(gz);
-        sfor<0, A + 1>([&](auto b) {
-          constexpr int Bq = decltype(b)::value;
-          quu[A][Bq] = bcast<NX + Bq>(h[NX + A]);
-        });
-      });
-      // L D L' of Quu + rho I (redundantly on every lane); Ld[i][k] = L[i][k]*D[k]
-      double L[NU][NU], Ld[NU][NU], dinv[NU];
-      sfor<0, NU>([&](auto jc) {
-        constexpr int Jc = decltype(jc)::value;
-        double dd = RHO ? quu[Jc][Jc] + rho : quu[Jc][Jc];
-        sfor<0, Jc>([&](auto kk) {
-          constexpr int Kk = decltype(kk)::value;
-          dd -= L[Jc][Kk] * Ld[Jc][Kk];
-        });
-        fail = fail | !(dd > 0.0);
-        dinv[Jc] = rcp_nr(dd);
-        sfor<Jc + 1, NU>([&](auto ii) {
-          constexpr int I = decltype(ii)::value;
-          double v = quu[I][Jc];
-          sfor<0, Jc>([&](auto kk) {
-            constexpr int Kk = decltype(kk)::value;
-            v -= L[I][Kk] * Ld[Jc][Kk];
-          });
-          Ld[I][Jc] = v;
-          L[I][Jc] = v * dinv[Jc];
-        });
-      });
-      // right-hand side: x lanes Qux(:,j), u lanes Qu  -> kd = -Quu_reg^{-1} rhs
-      double r[NU], kd[NU];
-      sfor<0, NU>([&](auto a) {
-        constexpr int A = decltype(a)::value;
-        r[A] = is_x ? h[NX + A] : qu[A];
-      });
-      {
-        double y[NU];
-        sfor<0, NU>([&](auto ii) {
-          constexpr int I = decltype(ii)::value;
-          double v = r[I];
-          sfor<0, I>([&](auto kk) { v -= L[I][decltype(kk)::value] * y[decltype(kk)::value]; });
-          y[I] = v;
-        });
-        sfor<0, NU>([&](auto ir) {
-          constexpr int I = NU - 1 - decltype(ir)::value;
-          double v = y[I] * dinv[I];
-          sfor<I + 1, NU>([&](auto kk) { v -= L[decltype(kk)::value][I] * kd[decltype(kk)::value]; });
-          kd[I] = v;
-        });
-        sfor<0, NU>([&](auto a) { kd[decltype(a)::value] = -kd[decltype(a)::value]; });
-      }
-      {  // feedforward magnitude against the control it would change (u lanes hold every d[a] in kd[])
-        double dm = fabs(kd[0]);
-        sfor<1, NU>([&](auto a) { dm = fmax(dm, fabs(kd[decltype(a)::value])); });
-        dbig = dbig | (is_u & !(dm <= 1e-9 * (1.0 + fabs(z))));
-      }
-      // d to every lane (from the first u lane)
-      double dd_[NU];
-      sfor<0, NU>([&](auto a) { dd_[decltype(a)::value] = bcast<NX>(kd[decltype(a)::value]); });
-      // s = Qx + Qux'd - rho K'd ;  dV += (d'Qu, -1/2 d'Qu - 1/2 rho d'd)
-      double snew = gz, t1 = 0.0, dtd = 0.0, ktd = 0.0;
-      sfor<0, NU>([&](auto a) {
-        constexpr int A = decltype(a)::value;
-        snew += r[A] * dd_[A];
-        t1 += dd_[A] * qu[A];
-        if constexpr (RHO) {
-          dtd += dd_[A] * dd_[A];
-          ktd += kd[A] * dd_[A];
-        }
-      });
-      if constexpr (RHO) snew -= rho * ktd;
-      dV1 += t1;
-      dV2 += RHO ? (-0.5 * t1 - 0.5 * rho * dtd) : (-0.5 * t1);
+      // gains, feedforward terms, s and dV of the knot from Qu (in gz) and the rows of [Qux Quu]
+      double hq[NU], L[NU][NU], dinv[NU], r[NU], kd[NU], snew;
+      sfor<0, NU>([&](auto a) { hq[decltype(a)::value] = h[NX + decltype(a)::value]; });
+      knot_gains<RHO>(gz, hq, rho, z, kd, L, dinv, r, snew, dV1, dV2, fail, dbig);
       store_gains(live ? k : N - 1, live ? k : N, kd, L, dinv);
       // S = Qxx + Qux'K - rho K'K   (in place on h[0..NX-1]), then S = (S + S')/2
       if constexpr (RHO) {
@@ -1837,38 +1852,56 @@ struct Solver {
     prio_base();
   }
 
-  // ---- lone-row backward pass ---------------------------------------------------------------------------
+  // ---- split backward pass: one instance on R = 4 or R = 2 DPP rows ----------------------------------------
   // When exactly one row of the wave needs a backward pass (the tail of a launch, where single hard instances walk
   // their serial chains, and every turn of a wave whose rows are out of step), the wave's other three DPP rows
-  // would execute the pass's 396 FMAs per knot on operands nobody reads.  backward_lone() spreads the ONE instance
-  // over all four rows instead: row r owns rows r*RL .. r*RL + RL-1 of S, W = S [A B] and Qxx (row 0 also the
-  // vector s), and rows NX + r*RQ.. of [Qux Quu]; lane j is column j in every row, as before.  The rows trade their
-  // slices of W and of [Qux Quu] with v_permlane32_swap / v_permlane16_swap (gfx950), everything that is not a
-  // product (box expansion, L D L', gain solves, dV) runs redundantly on all four.  153 product / exchange
-  // instructions per knot instead of 396.  Every output element is the same chain of FMAs in the same order as in
-  // backward<false, SYM>, so the two passes agree bit for bit (tests: ALTRO_NO_LONE=1 against the default).
-  // The caller points inst / rowoff / rs / ah of ALL lanes at the lone row before the call.  rho == 0 only.
-  static __device__ __forceinline__ void rows_gather(double v, double (&o)[4]) {
-    // o[q] = v of the same lane of DPP row q
+  // would execute the pass's 396 FMAs per knot on operands nobody reads; when exactly two need it, two rows would.
+  // backward_split<R>() spreads an instance over R DPP rows instead.  R = 4 (the lone form): the ONE instance on all
+  // four rows.  R = 2 (the pair form): DPP rows 0-1 work for the first row that needs the pass, rows 2-3 for the
+  // second.  Row r of the R owns rows r*RL .. r*RL + RL-1 of S, W = S [A B] and Qxx (row 0 also the vector s), and
+  // rows NX + r*RQ.. of [Qux Quu]; lane j is column j in every row, as before.  The rows trade their slices of W and
+  // of [Qux Quu] with v_permlane32_swap / v_permlane16_swap (gfx950) -- R = 2 needs only the v_permlane16_swap level,
+  // the pairs never trade with each other -- and everything that is not a product (box expansion, L D L', gain
+  // solves, dV) runs redundantly on all R.  R = 4: 153 product / exchange instructions per knot instead of 396.
+  // Every output element is the same chain of FMAs in the same order as in backward<false, SYM>, so the passes agree
+  // bit for bit (tests: no_lone and no_pair against the default).  The caller points inst / rowoff / rs / sm / ah /
+  // qhs of the lanes at the row they work for before the call (lone_enter, pair_enter).  rho == 0 only.
+  template <int R>
+  static __device__ __forceinline__ void rows_gather(double v, double (&o)[R]) {
+    // o[q] = v of the same lane of DPP row q of the R rows that share an instance
     const int lo = __double2loint(v), hi = __double2hiint(v);
-    const auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);  // [0] = rows 0,1 | 0,1   [1] = rows 2,3 | 2,3
-    const auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-    const auto a0 = __builtin_amdgcn_permlane16_swap(a[0], a[0], false, false);  // [0] = row 0 everywhere, [1] = row 1
-    const auto b0 = __builtin_amdgcn_permlane16_swap(b[0], b[0], false, false);
-    const auto a1 = __builtin_amdgcn_permlane16_swap(a[1], a[1], false, false);  // [0] = row 2, [1] = row 3
-    const auto b1 = __builtin_amdgcn_permlane16_swap(b[1], b[1], false, false);
-    o[0] = __hiloint2double(b0[0], a0[0]);
-    o[1] = __hiloint2double(b0[1], a0[1]);
-    o[2] = __hiloint2double(b1[0], a1[0]);
-    o[3] = __hiloint2double(b1[1], a1[1]);
+    if constexpr (R == 4) {
+      const auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);  // [0] = rows 0,1 | 0,1   [1] = rows 2,3 | 2,3
+      const auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+      const auto a0 = __builtin_amdgcn_permlane16_swap(a[0], a[0], false, false);  // [0] = row 0 everywhere, [1] = row 1
+      const auto b0 = __builtin_amdgcn_permlane16_swap(b[0], b[0], false, false);
+      const auto a1 = __builtin_amdgcn_permlane16_swap(a[1], a[1], false, false);  // [0] = row 2, [1] = row 3
+      const auto b1 = __builtin_amdgcn_permlane16_swap(b[1], b[1], false, false);
+      o[0] = __hiloint2double(b0[0], a0[0]);
+      o[1] = __hiloint2double(b0[1], a0[1]);
+      o[2] = __hiloint2double(b1[0], a1[0]);
+      o[3] = __hiloint2double(b1[1], a1[1]);
+    } else {
+      const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);  // [0] = rows 0,0 | 2,2   [1] = rows 1,1 | 3,3
+      const auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+      o[0] = __hiloint2double(b[0], a[0]);
+      o[1] = __hiloint2double(b[1], a[1]);
+    }
   }
-  static __device__ __forceinline__ double rows_gather0(double v) {  // v of the same lane of DPP row 0
+  template <int R>
+  static __device__ __forceinline__ double rows_gather0(double v) {  // v of the same lane of the first of the R DPP rows
     const int lo = __double2loint(v), hi = __double2hiint(v);
-    const auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-    const auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-    const auto a0 = __builtin_amdgcn_permlane16_swap(a[0], a[0], false, false);
-    const auto b0 = __builtin_amdgcn_permlane16_swap(b[0], b[0], false, false);
-    return __hiloint2double(b0[0], a0[0]);
+    if constexpr (R == 4) {
+      const auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+      const auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+      const auto a0 = __builtin_amdgcn_permlane16_swap(a[0], a[0], false, false);
+      const auto b0 = __builtin_amdgcn_permlane16_swap(b[0], b[0], false, false);
+      return __hiloint2double(b0[0], a0[0]);
+    } else {
+      const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+      const auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+      return __hiloint2double(b[0], a[0]);
+    }
   }
   static __device__ __forceinline__ double lane_gather(double v, int src_lane) {  // v of lane src_lane (ds_bpermute)
     const int lo = __builtin_amdgcn_ds_bpermute(src_lane << 2, __double2loint(v));
@@ -1885,14 +1918,19 @@ struct Solver {
     ASet* ah;
     ASet* qhs;
   };
-  __device__ __forceinline__ LoneCtx lone_enter(int lrow) {
-    LoneCtx c{inst, rowoff, rs, sm, ah, qhs};
-    inst = __builtin_amdgcn_readlane(inst, lrow * LW);
+  // points rowoff / rs / sm / ah / qhs of this lane at row lrow of the wave, whose instance `inst` already names (c: the
+  // lane's own identity).  shadow_enter spells the same five out: there each is a per-lane select.
+  __device__ __forceinline__ void to_row(const LoneCtx& c, int lrow) {
     rowoff = (unsigned)inst * LW + j;
     rs = c.rs - (lane >> 4) + lrow;
     sm = c.sm - (lane >> 4) * (LW * (LW + 1)) + lrow * (LW * (LW + 1));
     ah = c.ah - lane + lrow * LW + j;
     qhs = c.qhs - lane + lrow * LW + j;
+  }
+  __device__ __forceinline__ LoneCtx lone_enter(int lrow) {
+    LoneCtx c{inst, rowoff, rs, sm, ah, qhs};
+    inst = __builtin_amdgcn_readlane(inst, lrow * LW);
+    to_row(c, lrow);
     return c;
   }
   __device__ __forceinline__ void lone_leave(const LoneCtx& c) {
@@ -1902,6 +1940,15 @@ struct Solver {
     sm = c.sm;
     ah = c.ah;
     qhs = c.qhs;
+  }
+  // Pair phases: DPP rows 0-1 take the identity of row ra of the wave, DPP rows 2-3 that of row rb (both wave-uniform)
+  __device__ __forceinline__ LoneCtx pair_enter(int ra, int rb) {
+    LoneCtx c{inst, rowoff, rs, sm, ah, qhs};
+    const int ia = __builtin_amdgcn_readlane(inst, ra * LW), ib = __builtin_amdgcn_readlane(inst, rb * LW);
+    const int lrow = (lane < 32) ? ra : rb;
+    inst = (lane < 32) ? ia : ib;
+    to_row(c, lrow);
+    return c;
   }
   // Shadow rows.  The four rows of a wave run every phase together, and a row that sits a phase out used to run it on its
   // own instance: real loads of operands nobody needs (a fifth of the kernel's HBM traffic).  It now takes the identity of a
@@ -1939,12 +1986,13 @@ struct Solver {
     return __hiloint2double(hi, lo);
   }
 
-  template <bool SYM, bool QV = false>   // QV: the expansion read back from Qz and the trajectory's active set (see backward())
-  __device__ void backward_lone(double& dV1, double& dV2, bool& fail, bool& dtiny) {
-    using BK = Blk<NX, NU>;
+  template <int R, bool SYM, bool QV = false>   // QV: the expansion read back from Qz and the trajectory's active set (see backward())
+  __device__ void backward_split(double& dV1, double& dV2, bool& fail, bool& dtiny) {
+    static_assert(R == 4 || R == 2, "an instance on all four DPP rows or on a pair of them");
+    using BK = std::conditional_t<R == 4, typename Blk<NX, NU>::Split4, typename Blk<NX, NU>::Split2>;
     constexpr int RL = BK::RL, RQ = BK::RQ;
     phase_begin();
-    const int rr = lane >> 4;  // the quarter of the instance this DPP row owns
+    const int rr = (R == 4) ? (lane >> 4) : ((lane >> 4) & 1);  // which quarter (R = 4) or half (R = 2) of its instance this DPP row owns
     const LaneConst lc = consts();
     const double mu = rs->mu;
     const int kref = rs->kref;
@@ -1975,26 +2023,19 @@ struct Solver {
       diag_u[U] = (rr * RQ + U < NU) & (j == NX + rr * RQ + U);
     });
     const int psrc = (lane & 48) + ((rr * RL + j) & 15);  // lane whose [Qux] entry slot j of this row's S rows needs
-    ASet* const ta = ah;   // (lone_enter has pointed it at the lone row's set; every DPP row ORs the same bits)
+    ASet* const ta = ah;   // (the caller has pointed it at the instance's set; all its DPP rows OR the same bits)
     if constexpr (QV) aset_copy(ta, qhs);
     else aset_clear(ta);
     double Sl[RL + 1];
     {
       const int k = N - 1;
-      double qz, hz;
-      if constexpr (QV) {
-        qz = ldg(P.Qz, qat(k));
-        hz = hz_of(lc.wf, mu, aset_get(qhs, k));
-      } else {
-        const double z = ldg(P.Z, zs + zat(k));
-        const double zr = ldg(P.Zref, rat(kref + k));
-        const double lhi = ldg(P.Lb, lb_at(k, 0)), llo = ldg(P.Lb, lb_at(k, 1));
-        qz = lc.wf * (z - zr);
-        hz = lc.wf;
-        unsigned codeT;
-        box_expand(lc, mu, z, lhi, llo, box_at(k) & is_x, qz, hz, codeT);
-        aset_add(ta, codeT, k);
+      const double z = QV ? 0.0 : ldg(P.Z, zs + zat(k)), zr = QV ? ldg(P.Qz, qat(k)) : ldg(P.Zref, rat(kref + k));   // QV: zr carries Qz
+      double lhi = 0.0, llo = 0.0, qz, hz;
+      if constexpr (!QV) {
+        lhi = ldg(P.Lb, lb_at(k, 0));
+        llo = ldg(P.Lb, lb_at(k, 1));
       }
+      expand_knot<QV>(lc, mu, lc.wf, k, is_x, z, zr, lhi, llo, ta, qz, hz);
       sfor<0, RL>([&](auto t) { Sl[decltype(t)::value] = diag_x[decltype(t)::value] ? hz : 0.0; });
       Sl[RL] = (is_x & (rr == 0)) ? qz : 0.0;
     }
@@ -2021,45 +2062,36 @@ struct Solver {
         llon = ldg(P.Lb, lb_at(km, 1));
       }
       double qz, hz;
-      if constexpr (QV) {
-        qz = zr;
-        hz = hz_of(lc.wd, mu, aset_get(qhs, k));
-      } else {
-        qz = lc.wd * (z - zr);
-        hz = lc.wd;
-        unsigned code;
-        box_expand(lc, mu, z, lhi, llo, box_at(k), qz, hz, code);
-        aset_add(ta, code, k);
-      }
+      expand_knot<QV>(lc, mu, lc.wd, k, true, z, zr, lhi, llo, ta, qz, hz);
       // this row's rows of W = [S; s'] G
       double wl[RL + 1];
       sfor<0, RL + 1>([&](auto t) { wl[decltype(t)::value] = 0.0; });
-      BK::SGL(wl, Sl, g);
-      // all rows of W to every DPP row
+      BK::SG(wl, Sl, g);
+      // all rows of W to every DPP row of the instance
       double wa[NX + 1];
       sfor<0, RL>([&](auto t) {
         constexpr int Tt = decltype(t)::value;
-        double o[4];
+        double o[R];
         rows_gather(wl[Tt], o);
-        sfor<0, 4>([&](auto q) {
+        sfor<0, R>([&](auto q) {
           constexpr int Q = decltype(q)::value;
           if constexpr (Q * RL + Tt < NX) wa[Q * RL + Tt] = o[Q];
         });
       });
-      wa[NX] = rows_gather0(wl[RL]);
+      wa[NX] = rows_gather0<R>(wl[RL]);
       // this row's rows of H = G' W + diag(lzz): RL rows of Qxx, RQ rows of [Qux Quu]
       double hl[RL + RQ];
       sfor<0, RL>([&](auto t) { hl[decltype(t)::value] = diag_x[decltype(t)::value] ? hz : 0.0; });
       sfor<0, RQ>([&](auto u) { hl[RL + decltype(u)::value] = diag_u[decltype(u)::value] ? hz : 0.0; });
-      BK::GTWL(hl, gp, wa);
+      BK::GTW(hl, gp, wa);
       const double gz = qz + wa[NX];  // Qx[j] on x lanes, Qu[a] on u lanes
-      // rows of [Qux Quu] to every DPP row: hq[a] = what backward() calls h[NX + a]
+      // rows of [Qux Quu] to every DPP row of the instance: hq[a] = what backward() calls h[NX + a]
       double hq[NU];
       sfor<0, RQ>([&](auto u) {
         constexpr int U = decltype(u)::value;
-        double o[4];
+        double o[R];
         rows_gather(hl[RL + U], o);
-        sfor<0, 4>([&](auto q) {
+        sfor<0, R>([&](auto q) {
           constexpr int Q = decltype(q)::value;
           if constexpr (Q * RQ + U < NU) hq[Q * RQ + U] = o[Q];
         });
@@ -2068,335 +2100,10 @@ struct Solver {
       // (requested here: the ds_bpermute round trip hides behind the factorisation)
       double rp[NU];
       sfor<0, NU>([&](auto a) { rp[decltype(a)::value] = lane_gather(hq[decltype(a)::value], psrc); });
-      double quu[NU][NU];
-      double qu[NU];
-      sfor<0, NU>([&](auto a) {
-        constexpr int A = decltype(a)::value;
-        qu[A] = bcast<NX + A>(gz);
-        sfor<0, A + 1>([&](auto b) {
-          constexpr int Bq = decltype(b)::value;
-          quu[A][Bq] = bcast<NX + Bq>(hq[A]);
-        });
-      });
-      double L[NU][NU], Ld[NU][NU], dinv[NU];
-      sfor<0, NU>([&](auto jc) {
-        constexpr int Jc = decltype(jc)::value;
-        double dd = quu[Jc][Jc];
-        sfor<0, Jc>([&](auto kk) {
-          constexpr int Kk = decltype(kk)::value;
-          dd -= L[Jc][Kk] * Ld[Jc][Kk];
-        });
-        fail = fail | !(dd > 0.0);
-        dinv[Jc] = rcp_nr(dd);
-        sfor<Jc + 1, NU>([&](auto ii) {
-          constexpr int I = decltype(ii)::value;
-          double v = quu[I][Jc];
-          sfor<0, Jc>([&](auto kk) {
-            constexpr int Kk = decltype(kk)::value;
-            v -= L[I][Kk] * Ld[Jc][Kk];
-          });
-          Ld[I][Jc] = v;
-          L[I][Jc] = v * dinv[Jc];
-        });
-      });
-      double r[NU], kd[NU];
-      sfor<0, NU>([&](auto a) {
-        constexpr int A = decltype(a)::value;
-        r[A] = is_x ? hq[A] : qu[A];
-      });
-      {
-        double y[NU];
-        sfor<0, NU>([&](auto ii) {
-          constexpr int I = decltype(ii)::value;
-          double v = r[I];
-          sfor<0, I>([&](auto kk) { v -= L[I][decltype(kk)::value] * y[decltype(kk)::value]; });
-          y[I] = v;
-        });
-        sfor<0, NU>([&](auto ir) {
-          constexpr int I = NU - 1 - decltype(ir)::value;
-          double v = y[I] * dinv[I];
-          sfor<I + 1, NU>([&](auto kk) { v -= L[decltype(kk)::value][I] * kd[decltype(kk)::value]; });
-          kd[I] = v;
-        });
-        sfor<0, NU>([&](auto a) { kd[decltype(a)::value] = -kd[decltype(a)::value]; });
-      }
-      {
-        double dm = fabs(kd[0]);
-        sfor<1, NU>([&](auto a) { dm = fmax(dm, fabs(kd[decltype(a)::value])); });
-        dbig = dbig | (is_u & !(dm <= 1e-9 * (1.0 + fabs(z))));
-      }
-      double dd_[NU];
-      sfor<0, NU>([&](auto a) { dd_[decltype(a)::value] = bcast<NX>(kd[decltype(a)::value]); });
-      double snew = gz, t1 = 0.0;
-      sfor<0, NU>([&](auto a) {
-        constexpr int A = decltype(a)::value;
-        snew += r[A] * dd_[A];
-        t1 += dd_[A] * qu[A];
-      });
-      dV1 += t1;
-      dV2 += -0.5 * t1;
-      store_gains((rr == 0) ? k : N - 1, (rr == 0) ? k : N, kd, L, dinv);  // one row stores; the others hit the trash slots
-      BK::CTGL0(hl, kd, rp);  // S = Qxx + Qux'K on this row's rows
-      if constexpr (SYM) {
-        sfor<0, RL>([&](auto t) {
-          constexpr int Tt = decltype(t)::value;
-          my[(rr * RL + Tt) * (LW + 1) + j] = hl[Tt];  // rows >= NX of the tile are never read by a state lane
-        });
-        __builtin_amdgcn_wave_barrier();
-        sfor<0, RL>([&](auto t) {
-          constexpr int Tt = decltype(t)::value;
-          const double st = my[j * (LW + 1) + ((rr * RL + Tt) & 15)];
-          Sl[Tt] = 0.5 * (hl[Tt] + st);
-        });
-        __builtin_amdgcn_wave_barrier();
-      } else {
-        sfor<0, RL>([&](auto t) { Sl[decltype(t)::value] = hl[decltype(t)::value]; });
-      }
-      Sl[RL] = (rr == 0) ? snew : 0.0;
-      z = zn;
-      zr = zrn;
-      lhi = lhin;
-      llo = llon;
-    }
-    dtiny = !row_any(dbig, lane);
-  }
-
-  // ---- pair backward pass ---------------------------------------------------------------------------------
-  // When exactly two rows of the wave need a backward pass, the four-row form runs two DPP rows on operands nobody
-  // reads.  backward_pair() gives each of the two instances two adjacent DPP rows: DPP rows 0-1 work for the first row
-  // that needs the pass, rows 2-3 for the second.  Row r of a pair owns rows r*RLP .. r*RLP + RLP-1 of S, W = S [A B] and
-  // Qxx (row 0 also the vector s) and rows NX + r*RQP.. of [Qux Quu] -- backward_lone's split with two owners, its
-  // all-gather cut to the one v_permlane16_swap level (the pairs never trade with each other); box expansion, L D L',
-  // the gain solves and dV run redundantly in both rows.  Same chains of FMAs in the same order as backward<false, SYM>:
-  // bit-identical (tests: no_pair against the default).  The caller points inst / rowoff / rs / sm / ah / qhs of the
-  // lanes at their pair's row before the call (pair_enter).  rho == 0 only.
-  static __device__ __forceinline__ void pair_gather(double v, double (&o)[2]) {
-    // o[q] = v of the same lane of DPP row q of this lane's pair
-    const int lo = __double2loint(v), hi = __double2hiint(v);
-    const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);  // [0] = rows 0,0 | 2,2   [1] = rows 1,1 | 3,3
-    const auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-    o[0] = __hiloint2double(b[0], a[0]);
-    o[1] = __hiloint2double(b[1], a[1]);
-  }
-  static __device__ __forceinline__ double pair_gather0(double v) {  // v of the same lane of the pair's first DPP row
-    const int lo = __double2loint(v), hi = __double2hiint(v);
-    const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-    const auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-    return __hiloint2double(b[0], a[0]);
-  }
-  // Pair phases: DPP rows 0-1 take the identity of row ra of the wave, DPP rows 2-3 that of row rb (both wave-uniform)
-  __device__ __forceinline__ LoneCtx pair_enter(int ra, int rb) {
-    LoneCtx c{inst, rowoff, rs, sm, ah, qhs};
-    const int ia = __builtin_amdgcn_readlane(inst, ra * LW), ib = __builtin_amdgcn_readlane(inst, rb * LW);
-    const int lrow = (lane < 32) ? ra : rb;
-    inst = (lane < 32) ? ia : ib;
-    rowoff = (unsigned)inst * LW + j;
-    rs = c.rs - (lane >> 4) + lrow;
-    sm = c.sm - (lane >> 4) * (LW * (LW + 1)) + lrow * (LW * (LW + 1));
-    ah = c.ah - lane + lrow * LW + j;
-    qhs = c.qhs - lane + lrow * LW + j;
-    return c;
-  }
-  __device__ __forceinline__ void pair_leave(const LoneCtx& c) { lone_leave(c); }
-
-  template <bool SYM, bool QV = false>   // QV: the expansion read back from Qz and the trajectory's active set (see backward())
-  __device__ void backward_pair(double& dV1, double& dV2, bool& fail, bool& dtiny) {
-    using BK = Blk<NX, NU>;
-    constexpr int RL = BK::RLP, RQ = BK::RQP;
-    phase_begin();
-    const int rr = (lane >> 4) & 1;  // the half of its instance this DPP row owns
-    const LaneConst lc = consts();
-    const double mu = rs->mu;
-    const int kref = rs->kref;
-    const unsigned zs = plane(rs->cur);
-    // g: [A B] by columns as in backward(); gp: the columns this row's own output rows need as broadcast operands,
-    // moved to lanes 0..: lane t < RL holds column rr*RL + t, lane RL + u holds control column NX + rr*RQ + u
-    double g[NX], gp[NX];
-    {
-      const int pc = (j < RL) ? rr * RL + j : NX + rr * RQ + (j - RL);
-      const bool pv = (j < RL) ? (rr * RL + j < NX) : ((j - RL < RQ) && (rr * RQ + (j - RL) < NU));
-      sfor<0, NX>([&](auto c) {
-        constexpr int C = decltype(c)::value;
-        g[C] = ldg(P.Gcol, ((unsigned)inst * NX + C) * LW + j);
-        const double v = ldg(P.Gcol, ((unsigned)inst * NX + C) * LW + (pv ? pc : 0));
-        gp[C] = pv ? v : 0.0;
-      });
-    }
-    const int N = P.N;
-    // which global row of S / Qxx a local slot of this DPP row holds, and whether this lane is its diagonal
-    bool diag_x[RL], own_x[RL], diag_u[RQ];
-    sfor<0, RL>([&](auto t) {
-      constexpr int Tt = decltype(t)::value;
-      own_x[Tt] = rr * RL + Tt < NX;
-      diag_x[Tt] = own_x[Tt] & (j == rr * RL + Tt);
-    });
-    sfor<0, RQ>([&](auto u) {
-      constexpr int U = decltype(u)::value;
-      diag_u[U] = (rr * RQ + U < NU) & (j == NX + rr * RQ + U);
-    });
-    const int psrc = (lane & 48) + ((rr * RL + j) & 15);  // lane whose [Qux] entry slot j of this row's S rows needs
-    ASet* const ta = ah;   // (pair_enter has pointed it at the instance's set; both DPP rows OR the same bits)
-    if constexpr (QV) aset_copy(ta, qhs);
-    else aset_clear(ta);
-    double Sl[RL + 1];
-    {
-      const int k = N - 1;
-      double qz, hz;
-      if constexpr (QV) {
-        qz = ldg(P.Qz, qat(k));
-        hz = hz_of(lc.wf, mu, aset_get(qhs, k));
-      } else {
-        const double z = ldg(P.Z, zs + zat(k));
-        const double zr = ldg(P.Zref, rat(kref + k));
-        const double lhi = ldg(P.Lb, lb_at(k, 0)), llo = ldg(P.Lb, lb_at(k, 1));
-        qz = lc.wf * (z - zr);
-        hz = lc.wf;
-        unsigned codeT;
-        box_expand(lc, mu, z, lhi, llo, box_at(k) & is_x, qz, hz, codeT);
-        aset_add(ta, codeT, k);
-      }
-      sfor<0, RL>([&](auto t) { Sl[decltype(t)::value] = diag_x[decltype(t)::value] ? hz : 0.0; });
-      Sl[RL] = (is_x & (rr == 0)) ? qz : 0.0;
-    }
-    dV1 = 0.0;
-    dV2 = 0.0;
-    fail = false;
-    bool dbig = false;
-    double* my = sm;
-    double z = ldg(P.Z, zs + zat(N - 2)), zr = QV ? ldg(P.Qz, qat(N - 2)) : ldg(P.Zref, rat(kref + N - 2));   // QV: zr carries Qz
-    double lhi = 0.0, llo = 0.0;
-    if constexpr (!QV) {
-      lhi = ldg(P.Lb, lb_at(N - 2, 0));
-      llo = ldg(P.Lb, lb_at(N - 2, 1));
-    }
-    asm volatile("" : "+v"(z), "+v"(zr));  // waited for once, outside the loop: see backward()
-    if constexpr (!QV) asm volatile("" : "+v"(lhi), "+v"(llo));
-    for (int k = N - 2; k >= 0; --k) {  // body: one basic block
-      const int km = imax(k - 1, 0);
-      const double zn = ldg(P.Z, zs + zat(km));
-      const double zrn = QV ? ldg(P.Qz, qat(km)) : ldg(P.Zref, rat(kref + km));
-      double lhin = 0.0, llon = 0.0;
-      if constexpr (!QV) {
-        lhin = ldg(P.Lb, lb_at(km, 0));
-        llon = ldg(P.Lb, lb_at(km, 1));
-      }
-      double qz, hz;
-      if constexpr (QV) {
-        qz = zr;
-        hz = hz_of(lc.wd, mu, aset_get(qhs, k));
-      } else {
-        qz = lc.wd * (z - zr);
-        hz = lc.wd;
-        unsigned code;
-        box_expand(lc, mu, z, lhi, llo, box_at(k), qz, hz, code);
-        aset_add(ta, code, k);
-      }
-      // this row's rows of W = [S; s'] G
-      double wl[RL + 1];
-      sfor<0, RL + 1>([&](auto t) { wl[decltype(t)::value] = 0.0; });
-      BK::SGP(wl, Sl, g);
-      // all rows of W to both DPP rows of the pair
-      double wa[NX + 1];
-      sfor<0, RL>([&](auto t) {
-        constexpr int Tt = decltype(t)::value;
-        double o[2];
-        pair_gather(wl[Tt], o);
-        sfor<0, 2>([&](auto q) {
-          constexpr int Q = decltype(q)::value;
-          if constexpr (Q * RL + Tt < NX) wa[Q * RL + Tt] = o[Q];
-        });
-      });
-      wa[NX] = pair_gather0(wl[RL]);
-      // this row's rows of H = G' W + diag(lzz): RL rows of Qxx, RQ rows of [Qux Quu]
-      double hl[RL + RQ];
-      sfor<0, RL>([&](auto t) { hl[decltype(t)::value] = diag_x[decltype(t)::value] ? hz : 0.0; });
-      sfor<0, RQ>([&](auto u) { hl[RL + decltype(u)::value] = diag_u[decltype(u)::value] ? hz : 0.0; });
-      BK::GTWP(hl, gp, wa);
-      const double gz = qz + wa[NX];  // Qx[j] on x lanes, Qu[a] on u lanes
-      // rows of [Qux Quu] to both DPP rows: hq[a] = what backward() calls h[NX + a]
-      double hq[NU];
-      sfor<0, RQ>([&](auto u) {
-        constexpr int U = decltype(u)::value;
-        double o[2];
-        pair_gather(hl[RL + U], o);
-        sfor<0, 2>([&](auto q) {
-          constexpr int Q = decltype(q)::value;
-          if constexpr (Q * RQ + U < NU) hq[Q * RQ + U] = o[Q];
-        });
-      });
-      // the broadcast operand of S = Qxx + Qux'K on this row's rows: Qux[a][i] of row i = rr*RL + t sits on lane i
-      // (requested here: the ds_bpermute round trip hides behind the factorisation)
-      double rp[NU];
-      sfor<0, NU>([&](auto a) { rp[decltype(a)::value] = lane_gather(hq[decltype(a)::value], psrc); });
-      double quu[NU][NU];
-      double qu[NU];
-      sfor<0, NU>([&](auto a) {
-        constexpr int A = decltype(a)::value;
-        qu[A] = bcast<NX + A>(gz);
-        sfor<0, A + 1>([&](auto b) {
-          constexpr int Bq = decltype(b)::value;
-          quu[A][Bq] = bcast<NX + Bq>(hq[A]);
-        });
-      });
-      double L[NU][NU], Ld[NU][NU], dinv[NU];
-      sfor<0, NU>([&](auto jc) {
-        constexpr int Jc = decltype(jc)::value;
-        double dd = quu[Jc][Jc];
-        sfor<0, Jc>([&](auto kk) {
-          constexpr int Kk = decltype(kk)::value;
-          dd -= L[Jc][Kk] * Ld[Jc][Kk];
-        });
-        fail = fail | !(dd > 0.0);
-        dinv[Jc] = rcp_nr(dd);
-        sfor<Jc + 1, NU>([&](auto ii) {
-          constexpr int I = decltype(ii)::value;
-          double v = quu[I][Jc];
-          sfor<0, Jc>([&](auto kk) {
-            constexpr int Kk = decltype(kk)::value;
-            v -= L[I][Kk] * Ld[Jc][Kk];
-          });
-          Ld[I][Jc] = v;
-          L[I][Jc] = v * dinv[Jc];
-        });
-      });
-      double r[NU], kd[NU];
-      sfor<0, NU>([&](auto a) {
-        constexpr int A = decltype(a)::value;
-        r[A] = is_x ? hq[A] : qu[A];
-      });
-      {
-        double y[NU];
-        sfor<0, NU>([&](auto ii) {
-          constexpr int I = decltype(ii)::value;
-          double v = r[I];
-          sfor<0, I>([&](auto kk) { v -= L[I][decltype(kk)::value] * y[decltype(kk)::value]; });
-          y[I] = v;
-        });
-        sfor<0, NU>([&](auto ir) {
-          constexpr int I = NU - 1 - decltype(ir)::value;
-          double v = y[I] * dinv[I];
-          sfor<I + 1, NU>([&](auto kk) { v -= L[decltype(kk)::value][I] * kd[decltype(kk)::value]; });
-          kd[I] = v;
-        });
-        sfor<0, NU>([&](auto a) { kd[decltype(a)::value] = -kd[decltype(a)::value]; });
-      }
-      {
-        double dm = fabs(kd[0]);
-        sfor<1, NU>([&](auto a) { dm = fmax(dm, fabs(kd[decltype(a)::value])); });
-        dbig = dbig | (is_u & !(dm <= 1e-9 * (1.0 + fabs(z))));
-      }
-      double dd_[NU];
-      sfor<0, NU>([&](auto a) { dd_[decltype(a)::value] = bcast<NX>(kd[decltype(a)::value]); });
-      double snew = gz, t1 = 0.0;
-      sfor<0, NU>([&](auto a) {
-        constexpr int A = decltype(a)::value;
-        snew += r[A] * dd_[A];
-        t1 += dd_[A] * qu[A];
-      });
-      dV1 += t1;
-      dV2 += -0.5 * t1;
-      store_gains((rr == 0) ? k : N - 1, (rr == 0) ? k : N, kd, L, dinv);  // one row of each pair stores; the other hits the trash slots
-      BK::CTGP0(hl, kd, rp);  // S = Qxx + Qux'K on this row's rows
+      double L[NU][NU], dinv[NU], r[NU], kd[NU], snew;
+      knot_gains<false>(gz, hq, 0.0, z, kd, L, dinv, r, snew, dV1, dV2, fail, dbig);
+      store_gains((rr == 0) ? k : N - 1, (rr == 0) ? k : N, kd, L, dinv);  // one row per instance stores; the others hit the trash slots
+      BK::CTG0(hl, kd, rp);  // S = Qxx + Qux'K on this row's rows
       if constexpr (SYM) {
         sfor<0, RL>([&](auto t) {
           constexpr int Tt = decltype(t)::value;
@@ -2795,14 +2502,14 @@ struct Solver {
             ALTRO_STAMP(int took = 0;)   // 1: lone form, 2: pair form
             if (!CONES && P.lone && !with_rho && nbwr == 1) {
               ALTRO_STAMP(took = 1;)
-              // exactly one row needs the pass: all four DPP rows work on that row's instance (backward_lone)
+              // exactly one row needs the pass: all four DPP rows work on that row's instance (backward_split<4>)
               const LoneCtx ctx = lone_enter(first_row(bm));
               double a1, a2;
               bool dt;
               if constexpr (!CONES) {
                 const bool useq = (P.useqz != 0) && (rs->qvalid != 0) && (P.N <= ASET_MAXN);   // (all lanes: the lone row's state)
-                if (o.strict) { if (useq) backward_lone<true, true>(a1, a2, fail, dt); else backward_lone<true, false>(a1, a2, fail, dt); }
-                else { if (useq) backward_lone<false, true>(a1, a2, fail, dt); else backward_lone<false, false>(a1, a2, fail, dt); }
+                if (o.strict) { if (useq) backward_split<4, true, true>(a1, a2, fail, dt); else backward_split<4, true, false>(a1, a2, fail, dt); }
+                else { if (useq) backward_split<4, false, true>(a1, a2, fail, dt); else backward_split<4, false, false>(a1, a2, fail, dt); }
               }
               lone_leave(ctx);
               if (bwrow) {
@@ -2813,7 +2520,7 @@ struct Solver {
               n_lone++;
             } else if (ALTRO_PAIR_PASS && NX == 12 && !CONES && P.lone && P.pair && !with_rho && nbwr == 2) {
               ALTRO_STAMP(took = 2;)
-              // exactly two rows need the pass: two DPP rows for each of their instances (backward_pair)
+              // exactly two rows need the pass: two DPP rows for each of their instances (backward_split<2>)
               if constexpr (ALTRO_PAIR_PASS && NX == 12 && !CONES) {
                 const int ra = (bm & 1ull) ? 0 : (((bm >> 16) & 1ull) ? 1 : 2);
                 const int rb = ((bm >> 48) & 1ull) ? 3 : (((bm >> 32) & 1ull) ? 2 : 1);
@@ -2822,9 +2529,9 @@ struct Solver {
                 const LoneCtx ctx = pair_enter(ra, rb);
                 double a1, a2;
                 bool pf, dt;
-                if (o.strict) { if (useq) backward_pair<true, true>(a1, a2, pf, dt); else backward_pair<true, false>(a1, a2, pf, dt); }
-                else { if (useq) backward_pair<false, true>(a1, a2, pf, dt); else backward_pair<false, false>(a1, a2, pf, dt); }
-                pair_leave(ctx);
+                if (o.strict) { if (useq) backward_split<2, true, true>(a1, a2, pf, dt); else backward_split<2, true, false>(a1, a2, pf, dt); }
+                else { if (useq) backward_split<2, false, true>(a1, a2, pf, dt); else backward_split<2, false, false>(a1, a2, pf, dt); }
+                lone_leave(ctx);
                 // each row of the wave takes the outputs of the DPP rows that worked for it
                 const unsigned long long fb = __ballot(pf), tb = __ballot(dt);
                 const bool second = (lane >> 4) == rb;

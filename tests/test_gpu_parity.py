@@ -735,7 +735,7 @@ def test_fused_multi_step_launch_is_bit_identical_to_single_steps(n, m, N):
 @pytest.mark.parametrize("n,m,N,strict", [(12, 4, 50, 0), (12, 4, 50, 1), (8, 4, 21, 0), (6, 3, 21, 0), (6, 6, 31, 0), (12, 3, 31, 1)])
 def test_lone_row_backward_pass_is_bit_identical_to_the_four_row_pass(monkeypatch, n, m, N, strict):
     """A backward pass that only one row of a wave needs runs with the instance spread over the wave's four DPP rows
-    (solve_dpp16.h backward_lone).  ALTRO_NO_LONE=1 (read at create time) keeps the four-row pass: every output of a
+    (solve_dpp16.h backward_split<4>).  ALTRO_NO_LONE=1 (read at create time) keeps the four-row pass: every output of a
     desynchronised multi-step launch must be the same bit for bit, and the lone form must actually have run."""
     B, S = 23, 12
     pb = altro.problems.gen_random_linear_batch(B, n=n, m=m, N=N, steps=S, seed=29)

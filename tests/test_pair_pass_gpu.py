@@ -1,4 +1,4 @@
-"""Pair backward pass (solve_dpp16.h backward_pair): when exactly two rows of a wave need a backward pass, each of the two
+"""Pair backward pass (solve_dpp16.h backward_split<2>): when exactly two rows of a wave need a backward pass, each of the two
 instances runs on two DPP rows.  Every element is the same chain of FMAs as in the four-row pass, so a run with the pass
 and a run with `no_pair` must agree bit for bit.
 
