@@ -22,7 +22,8 @@ Arrays are numpy, instance-major: X (B, N, n), U (B, N-1, m), A (B, n, n) in nat
 Device-resident I/O: set_initial_state, update_trajectory, initial_controls, set_dynamics, update_constraint_data and
 set_bounds also take torch tensors that
 live on the solver's GPU (the altro_*_dev entry points: nothing crosses PCIe, nothing synchronises), and states, controls
-and first_knot write into such tensors.  A GPU tensor is never copied, cast or moved behind the caller's back: float64,
+and first_knot write into such tensors; eval_policy (the feedback policy between two ticks) and get_gains_dev read and write
+them.  A GPU tensor is never copied, cast or moved behind the caller's back: float64,
 contiguous, on the solver's device and of the exact shape, or ValueError.  Matrices keep their natural (row, col) indexing;
 since the C-ABI reads column-major blocks, a dynamics tensor must be STORED column-major, i.e. `At.transpose(-1, -2)` of a
 contiguous tensor At that holds the transposed blocks.  Every tensor call is ordered against torch's current stream
@@ -898,3 +899,65 @@ def gain_factors(solver):
     F = np.empty((solver.B, solver.N - 1, solver.m, solver.m))
     solver._chk(solver._L.altro_batch_get_gain_factors(solver.h, _p(F)))
     return F
+
+
+def _eval_policy_dev(solver, x, knot=None, clamp=True, out=None, fb=None):
+    import torch
+    dev = torch.device("cuda", solver.device)
+    check_device_tensor(x, (solver.B, solver.n), solver.device, "x")
+    if knot is not None:
+        check_device_tensor(knot, (solver.B,), solver.device, "knot", dtype="torch.int32")
+    if out is None:
+        out = torch.empty((solver.B, solver.m), dtype=torch.float64, device=dev)
+    check_device_tensor(out, (solver.B, solver.m), solver.device, "out")
+    if fb is not None:
+        check_device_tensor(fb, (solver.B,), solver.device, "fb", dtype="torch.int32")
+    solver._chk(solver._L.altro_batch_eval_policy_dev(solver.h, _addr(x), _addr(knot), int(bool(clamp)), _addr(out), _addr(fb)))
+    return out
+
+
+def eval_policy(solver, x, knot=None, clamp=True, out=None, fb=None):
+    """The feedback policy of the last solve, u = u_k + K_k (x - x_k), saturated at the BOX when clamp (altro_batch_eval_policy
+    / _dev): what drives the plant between two solver ticks.  x (B, n) measured states, knot (B,) the knot of the current
+    horizon each instance is at (None: knot 0).  With GPU tensors (x float64, knot int32) the call is stream-ordered behind
+    the solve and nothing synchronises; out (B, m) and fb (B,) int32 are tensors to write into (out defaults to a new one).
+    With numpy the host twin runs (the same bytes), and fb may be a (B,) int32 array to fill.  fb: 1 feedback applied, 0 no
+    valid stored gains (u = u_k), -1 knot outside 0 .. N-2 (device path only: the row of u is left as it was; the host path
+    raises).  Returns u."""
+    if _on_gpu(x):
+        if not ((knot is None or _on_gpu(knot)) and (out is None or _on_gpu(out)) and (fb is None or _on_gpu(fb))):
+            raise ValueError("eval_policy: x, knot, out and fb must all be GPU tensors (or None), or none of them")
+        with _bracket(solver):
+            return _eval_policy_dev(solver, x, knot, clamp, out, fb)
+    if _on_gpu(knot) or _on_gpu(out) or _on_gpu(fb):
+        raise ValueError("eval_policy: x, knot, out and fb must all be GPU tensors (or None), or none of them")
+    x = _c(x)
+    assert x.shape == (solver.B, solver.n)
+    kn = None if knot is None else _clock_i32(knot, solver.B, "knot")
+    if out is None:
+        out = np.empty((solver.B, solver.m))
+    if not (isinstance(out, np.ndarray) and out.dtype == np.float64 and out.flags.c_contiguous and out.shape == (solver.B, solver.m)):
+        raise ValueError(f"eval_policy: out must be a C-contiguous float64 array of shape ({solver.B}, {solver.m})")
+    if fb is not None and not (isinstance(fb, np.ndarray) and fb.dtype == np.int32 and fb.flags.c_contiguous and fb.shape == (solver.B,)):
+        raise ValueError(f"eval_policy: fb must be a C-contiguous int32 array of shape ({solver.B},)")
+    solver._chk(solver._L.altro_batch_eval_policy(solver.h, _p(x), None if kn is None else kn.ctypes.data_as(_IP), int(bool(clamp)),
+                                                  _p(out), None if fb is None else fb.ctypes.data_as(_IP)))
+    return out
+
+
+def get_gains_dev(solver, K=None, d=None):
+    """altro_batch_get_gains into GPU tensors, stream-ordered and without a host synchronisation: K (B, N-1, m, n) in natural
+    (row, col) indexing, i.e. STORED column-major like a dynamics tensor (the transpose(-1, -2) of a contiguous (B, N-1, n, m)
+    tensor), d (B, N-1, m).  With neither given both are allocated; with one given only that one is written.  Returns (K, d)."""
+    import torch
+    if K is None and d is None:
+        dev = torch.device("cuda", solver.device)
+        K = torch.empty((solver.B, solver.N - 1, solver.n, solver.m), dtype=torch.float64, device=dev).transpose(-1, -2)
+        d = torch.empty((solver.B, solver.N - 1, solver.m), dtype=torch.float64, device=dev)
+    if K is not None:
+        check_device_tensor(K, (solver.B, solver.N - 1, solver.m, solver.n), solver.device, "K", colmajor=True)
+    if d is not None:
+        check_device_tensor(d, (solver.B, solver.N - 1, solver.m), solver.device, "d")
+    with _bracket(solver):
+        solver._chk(solver._L.altro_batch_get_gains_dev(solver.h, _addr(K), _addr(d)))
+    return K, d

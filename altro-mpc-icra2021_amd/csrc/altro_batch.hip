@@ -17,6 +17,7 @@
 #include "device_io.h"
 #include "launch_ring.h"
 #include "pn_polish.h"
+#include "policy.h"
 #include "solve_dpp16.h"
 // The one-wave-per-instance kernels are compiled in translation units of their own (wide_inst.hip, _lib.build) and only
 // declared here; -DALTRO_WIDE_SINGLE_TU (and the development builds) instantiate them in this unit as before.
@@ -2517,6 +2518,81 @@ int32_t altro_batch_get_dev_refusals(altro_handle* h, int64_t* rows) {
     unsigned long long v = 0;
     HIPCHK(h, hipMemcpy(&v, h->refusals, sizeof(v), hipMemcpyDeviceToHost));
     *rows = (int64_t)v;
+    return ALTRO_OK;
+  });
+}
+
+// ---- feedback policy on the device (kernels in policy.h)
+// x, knot, u, fb: device arrays (the caller's, validated; or the staged copies of the host twin).  Enqueues one kernel.
+static int eval_policy_launch(altro_handle* h, const double* x, const int32_t* knot, int32_t clamp, double* u, int32_t* fb) {
+  if (h->wide) {
+    const int rc = h->wide->eval_policy_dev(x, knot, clamp, u, fb);
+    if (rc) h->err = h->wide->err;
+    return rc;
+  }
+  hipLaunchKernelGGL(altro::k_eval_policy, grid_for((size_t)h->Bp * LW), dim3(256), 0, h->stream, u, fb, x, knot, h->Z, h->cur, h->KD, h->kmu,
+                     h->zmin, h->zmax, tab_imask(h), (size_t)h->d.N * LW, h->Bp, h->d.batch, h->d.N, h->d.n, h->d.m, clamp ? 1 : 0, h->box_k0,
+                     h->box_k1);
+  HIPCHK(h, hipGetLastError());
+  return ALTRO_OK;
+}
+
+int32_t altro_batch_eval_policy_dev(altro_handle* h, const double* x, const int32_t* knot, int32_t clamp, double* u, int32_t* fb) {
+  return guard(h, [&]() -> int32_t {
+    DEV_ENTER(h, "altro_batch_eval_policy_dev");
+    DEV_ARG(h, "x", x, B_ * n_, double, false);
+    DEV_ARG(h, "knot", knot, B_, int32_t, true);
+    DEV_ARG(h, "u", u, B_ * m_, double, false);
+    DEV_ARG(h, "fb", fb, B_, int32_t, true);
+    return eval_policy_launch(h, x, knot, clamp, u, fb);
+  });
+}
+
+// The host twin: knot is checked here, then x and knot go through the staging buffer, the SAME kernel runs on the staged
+// copies and u, fb come back -- the bytes are those of the `_dev` call by construction.
+int32_t altro_batch_eval_policy(altro_handle* h, const double* x, const int32_t* knot, int32_t clamp, double* u, int32_t* fb) {
+  return guard(h, [&]() -> int32_t {
+    if (!h) return dev_null_handle("altro_batch_eval_policy");
+    if (!x || !u) FAIL(h, ALTRO_ERR_INVALID_ARG, "altro_batch_eval_policy: x and u are required");
+    const size_t B = h->d.batch, N = h->d.N, n = h->d.n, m = h->d.m;
+    for (size_t b = 0; knot && b < B; ++b)
+      if (knot[b] < 0 || knot[b] > (int32_t)N - 2)
+        FAIL(h, ALTRO_ERR_INVALID_ARG, "altro_batch_eval_policy: knot[" + std::to_string(b) + "] = " + std::to_string(knot[b]) + " is outside 0 .. N-2");
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t bytes = B * (n + m) * sizeof(double) + 2 * B * sizeof(int32_t);
+    if (int rc = h->wide ? h->wide->ensure_stage(bytes) : ensure_stage(h, bytes)) {
+      if (h->wide) h->err = h->wide->err;
+      return rc;
+    }
+    const hipStream_t st = h->wide ? h->wide->stream : h->stream;
+    double* sx = h->wide ? h->wide->stage : h->stage;
+    double* su = sx + B * n;
+    int32_t* sk = reinterpret_cast<int32_t*>(su + B * m);
+    int32_t* sf = sk + B;
+    HIPCHK(h, hipMemcpyAsync(sx, x, B * n * sizeof(double), hipMemcpyHostToDevice, st));
+    if (knot) HIPCHK(h, hipMemcpyAsync(sk, knot, B * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (int rc = eval_policy_launch(h, sx, knot ? sk : nullptr, clamp, su, fb ? sf : nullptr)) return rc;
+    HIPCHK(h, hipMemcpyAsync(u, su, B * m * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (fb) HIPCHK(h, hipMemcpyAsync(fb, sf, B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    return ALTRO_OK;
+  });
+}
+
+// altro_batch_get_gains on the device: the unpack of KD / Dff that the host call does in a loop (k_unpack_gains), resp. two
+// device-to-device copies of Kg / dg
+int32_t altro_batch_get_gains_dev(altro_handle* h, double* K, double* d) {
+  return guard(h, [&]() -> int32_t {
+    DEV_ENTER(h, "altro_batch_get_gains_dev");
+    if (!K && !d) FAIL(h, ALTRO_ERR_INVALID_ARG, std::string(fn_) + ": K and d are both null");
+    DEV_ARG(h, "K", K, B_ * (N_ - 1) * n_ * m_, double, true);
+    DEV_ARG(h, "d", d, B_ * (N_ - 1) * m_, double, true);
+    DEV_WIDE(h, get_gains_dev(K, d));
+    altro::DSlots at{};
+    for (int a = 0; a < (int)m_; ++a) { at.row[a] = altro::kd_drow(a); at.col[a] = altro::kd_dcol(a, (int)m_); }
+    hipLaunchKernelGGL(altro::k_unpack_gains, grid_for(B_ * (N_ - 1) * m_ * LW), dim3(256), 0, h->stream, K, d, h->KD, h->Dff, h->dzero,
+                       h->d_in_kd ? 1 : 0, at, (int)B_, (int)N_, (int)n_, (int)m_);
+    HIPCHK(h, hipGetLastError());
     return ALTRO_OK;
   });
 }

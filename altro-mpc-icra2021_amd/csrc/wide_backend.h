@@ -12,6 +12,7 @@
 #include "../../include/altro_batch.h"
 #include "device_io.h"
 #include "launch_ring.h"
+#include "policy.h"
 #include "solve_wide.h"
 #include "pn_wide.h"
 
@@ -750,6 +751,23 @@ struct WideBackend {
     hipLaunchKernelGGL(altro::k_first_knot_wide, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, stream, u0d, x1d, st, it, X, U, cur,
                        status, iters, d.batch, d.N, d.n, d.m);
     WCHK(hipGetLastError());
+    return ALTRO_OK;
+  }
+  // altro_batch_eval_policy_dev (pointers validated by the caller; the host twin passes staged copies): one kernel on the
+  // current planes, Kg, the reuse state and the bounds rows (policy.h)
+  int eval_policy_dev(const double* xd, const int32_t* knot, int clamp, double* ud, int32_t* fb) {
+    WCHK(hipSetDevice(device));
+    const size_t thr = (size_t)d.batch * d.m;
+    hipLaunchKernelGGL(altro::k_eval_policy_wide, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, stream, ud, fb, xd, knot, X, U, cur, Kg, bwst,
+                       (gains_valid || debug_keep_gains) ? 1 : 0, zmin, zmax, b_pi, d.batch, d.N, d.n, d.m, clamp ? 1 : 0, box_k0, box_k1);
+    WCHK(hipGetLastError());
+    return ALTRO_OK;
+  }
+  // altro_batch_get_gains_dev: Kg and dg are kept in the ABI's layout
+  int get_gains_dev(double* Kd, double* dd) {
+    WCHK(hipSetDevice(device));
+    if (Kd) WCHK(hipMemcpyAsync(Kd, Kg, (size_t)d.batch * (d.N - 1) * d.n * d.m * sizeof(double), hipMemcpyDeviceToDevice, stream));
+    if (dd) WCHK(hipMemcpyAsync(dd, dg, (size_t)d.batch * (d.N - 1) * d.m * sizeof(double), hipMemcpyDeviceToDevice, stream));
     return ALTRO_OK;
   }
   int get_planes(double* Xh, double* Uh) {

@@ -242,7 +242,19 @@ class ExternalMPC:
     set x0 [, new reference window] [, new dynamics]; primal + dual shift_fill; solve; read the first knot -- enqueued on
     the solver's stream between one wait_stream and one signal_stream against torch's current stream, with no host
     synchronisation and no copy over PCIe.  The tensors returned are ready in torch's stream order.  The solver must hold
-    a solution to shift (api.solve once before the loop), as in the reference."""
+    a solution to shift (api.solve once before the loop), as in the reference.
+
+    Two rates: the solver ticks slowly, and between two ticks the plant is driven by the feedback policy the last solve
+    holds, u = u_k + K_k (x - x_k) saturated at the BOX (`policy`, altro_batch_eval_policy_dev), also without the host:
+
+        loop = ExternalMPC(solver)
+        for i in range(ticks):
+            u, *_ = loop.tick(x, Xref[i], Uref[i])                 # 50-100 Hz
+            for s in range(S):                                     # 1 kHz: S plant substeps per tick
+                x = plant(x, u)
+                u = loop.policy(x, out=u)                          # knot 0: the tick period is one knot
+
+    (A loop whose ticks are several knots apart passes the knot each instance is at as an int32 tensor, `knot=`.)"""
 
     def __init__(self, solver, shift=True):
         self.solver = solver
@@ -311,6 +323,15 @@ class ExternalMPC:
             api.signal_stream(s)
         self.i += 1
         return res
+
+    def policy(self, x, knot=None, clamp=True, out=None):
+        """u (B, m) = u_k + K_k (x - x_k) of the trajectory and gains the solver holds once its stream reaches this point,
+        saturated at the BOX when clamp (api.eval_policy, device form): x (B, n) float64 and knot (B,) int32 GPU tensors
+        (knot None: knot 0), out: a tensor to write into.  Ordered against torch's current stream like tick; no host
+        synchronisation."""
+        if not api._on_gpu(x):
+            raise ValueError("ExternalMPC.policy takes GPU tensors; the numpy form is api.eval_policy")
+        return api.eval_policy(self.solver, x, knot=knot, clamp=clamp, out=out)
 
     def _constraints_dev(self, constraint_data, bounds):
         s = self.solver

@@ -445,8 +445,8 @@ int32_t altro_batch_get_stream(altro_handle* h, void** stream);
  * that is too short, NULL where it is not allowed, a NULL handle -- the call returns ALTRO_ERR_INVALID_ARG with a message in
  * altro_last_error (of the handle; of NULL for a NULL handle), nothing is launched and the handle is unchanged and usable.
  * A setter leaves the handle in the byte-identical device state its host twin would, a getter writes byte-identical values.
- * Not covered, on purpose (set once, or packed on the host): cost weights, duals, gains, traces,
- * altro_mpc_set_track / _noise / _dynamics_track and the MPC log. */
+ * Not covered, on purpose (set once, or packed on the host): cost weights, duals, traces,
+ * altro_mpc_set_track / _noise / _dynamics_track and the MPC log.  (Gains: altro_batch_get_gains_dev, below.) */
 
 /* altro_batch_set_initial_state with x0 [batch][n] on the device */
 int32_t altro_batch_set_initial_state_dev(altro_handle* h, const double* x0);
@@ -498,6 +498,39 @@ int32_t altro_batch_update_constraint_data_dev(altro_handle* h, int32_t con_id, 
 int32_t altro_batch_set_bounds_dev(altro_handle* h, int32_t con_id, const double* zmin, const double* zmax,
                                    int32_t per_instance);
 int32_t altro_batch_get_dev_refusals(altro_handle* h, int64_t* rows);
+
+/* ---- feedback policy on the device: the second rate of a two-rate controller.  The reference's quadruped loop solves at
+ * 50-100 Hz (Woofer/MPCControl/altro_solver.jl) while the plant runs at 1 kHz; between two solver ticks it is driven by the
+ * policy the last solve already holds, u = u_k + K_k (x - x_k), saturated at the actuator limits.
+ * altro_batch_eval_policy_dev: x [batch][n] measured states, knot [batch] the knot of the current horizon each instance is
+ * at (NULL: knot 0 for every instance), u [batch][m] output, fb [batch] output (may be NULL), all on the device under the rules
+ * of the device-pointer block (validated before anything is enqueued, stream-ordered behind the solve that wrote the gains, no
+ * host synchronisation, no allocation; NULL x or u is refused).  For instance b at k = knot[b], for every control a
+ *     u[b][a] = u_k[a] + sum_j K_k[a][j] (x[b][j] - x_k[j])
+ * with (x_k, u_k) the trajectory the handle holds (altro_batch_get_states / _get_controls: the polished one when
+ * projected_newton = 1) and K_k the matrix altro_batch_get_gains returns.  The feedforward term d is NOT applied: the
+ * trajectory already contains the accepted step.  The order of the sum over j is fixed per backend (16-lane kernels: the
+ * products sit on their state lanes and are added by an xor butterfly over the 16 lanes, strides 8, 4, 2, 1; one-wave-per-
+ * instance kernels: fused multiply-adds for j = 0 .. n-1 in turn) and the nominal control is added last, so x = x_k returns
+ * u_k bit for bit.
+ * clamp = 1 on a handle with a BOX, k inside the BOX's knot range: u[b][a] <- min(max(u[b][a], zmin[n+a]), zmax[n+a]) with
+ * instance b's row of bounds as the solve kernels see it at that point of the stream (altro_batch_set_bounds(_dev) included);
+ * infinite sides do nothing.  clamp = 0: no saturation.
+ * fb[b] = 1: feedback was applied.  0: instance b holds no valid stored gains -- before its first solve, after any setter
+ * that drops the stored gains, after altro_batch_restart_instances, or when its last backward pass was regularised or failed
+ * -- and u[b] = u_k (clamped if asked).  -1: knot[b] is outside 0 .. N-2; row u[b] is not written (nothing is counted in
+ * altro_batch_get_dev_refusals).  The call is not masked: an instance the active mask or the clock leaves out answers from its
+ * last solve, as in altro_batch_get_first_knot_dev.
+ * altro_batch_eval_policy: the same with host arrays, through the handle's staging buffer; synchronises; writes the bytes the
+ * `_dev` call writes.  An out-of-range knot is found on the host instead: ALTRO_ERR_INVALID_ARG, nothing enqueued.
+ * altro_batch_get_gains_dev: altro_batch_get_gains into device arrays K [batch][N-1] blocks of m x n (column-major),
+ * d [batch][N-1][m], byte-identical to the host call (d = 0 after a costate-sweep confirmation included); either may be NULL,
+ * not both.
+ * ALTRO_ERR_INVALID_ARG (nothing enqueued, the handle unchanged): NULL handle, NULL x or u, K and d both NULL; _dev: what the
+ * device-pointer block refuses. */
+int32_t altro_batch_eval_policy_dev(altro_handle* h, const double* x, const int32_t* knot, int32_t clamp, double* u, int32_t* fb);
+int32_t altro_batch_eval_policy(altro_handle* h, const double* x, const int32_t* knot, int32_t clamp, double* u, int32_t* fb);
+int32_t altro_batch_get_gains_dev(altro_handle* h, double* K, double* d);
 
 /* ---- per-instance active mask and cold restart: ragged batches of closed loops.
  * The reference runs one problem per loop, and a loop that ends simply stops calling solve! (simple_rocket.jl:137-205); in a
