@@ -22,8 +22,8 @@ Arrays are numpy, instance-major: X (B, N, n), U (B, N-1, m), A (B, n, n) in nat
 Device-resident I/O: set_initial_state, update_trajectory, initial_controls, set_dynamics, update_constraint_data and
 set_bounds also take torch tensors that
 live on the solver's GPU (the altro_*_dev entry points: nothing crosses PCIe, nothing synchronises), and states, controls
-and first_knot write into such tensors; eval_policy (the feedback policy between two ticks) and get_gains_dev read and write
-them.  A GPU tensor is never copied, cast or moved behind the caller's back: float64,
+and first_knot write into such tensors; eval_policy (the feedback policy between two ticks), get_gains_dev, evaluate and
+rollout (candidate trajectories scored against the next solve's problem) read and write them.  A GPU tensor is never copied, cast or moved behind the caller's back: float64,
 contiguous, on the solver's device and of the exact shape, or ValueError.  Matrices keep their natural (row, col) indexing;
 since the C-ABI reads column-major blocks, a dynamics tensor must be STORED column-major, i.e. `At.transpose(-1, -2)` of a
 contiguous tensor At that holds the transposed blocks.  Every tensor call is ordered against torch's current stream
@@ -961,3 +961,114 @@ def get_gains_dev(solver, K=None, d=None):
     with _bracket(solver):
         solver._chk(solver._L.altro_batch_get_gains_dev(solver.h, _addr(K), _addr(d)))
     return K, d
+
+
+def _evaluate_shapes(solver, U, X, x0, name):
+    """(ncand, shape of the outputs, shape U / X / x0 must have): U (B, N-1, m) is one candidate per instance with (B,) outputs,
+    U (B, ncand, N-1, m) gives (B, ncand); U None (the solver's own trajectory) is one candidate"""
+    B, N, n, m = solver.B, solver.N, solver.n, solver.m
+    if U is None:
+        if X is not None or x0 is not None:
+            raise ValueError(f"{name}: X and x0 need U (U None scores the solver's own trajectory)")
+        return 1, (B,), None, None, None
+    shp = tuple(int(k) for k in U.shape)
+    if len(shp) == 3:
+        ncand, lead = 1, (B,)
+    elif len(shp) == 4 and shp[1] >= 1:
+        ncand, lead = shp[1], (B, shp[1])
+    else:
+        raise ValueError(f"{name}: U: shape {shp}, expected ({B}, {N - 1}, {m}) or ({B}, ncand, {N - 1}, {m})")
+    if X is not None and x0 is not None:
+        raise ValueError(f"{name}: x0 belongs to the rollout form: it must be None when X is given")
+    return ncand, lead, lead + (N - 1, m), lead + (N, n), (B, n)
+
+
+def _evaluate_dev(solver, U=None, X=None, x0=None, out=None, Xout=None):
+    """device form of evaluate: every tensor is validated (shape, dtype, strides, device) before the library is called"""
+    import torch
+    dev = torch.device("cuda", solver.device)
+    ncand, lead, su, sx, s0 = _evaluate_shapes(solver, U, X, x0, "evaluate")
+    if U is not None:
+        check_device_tensor(U, su, solver.device, "U")
+    if X is not None:
+        check_device_tensor(X, sx, solver.device, "X")
+        if Xout is not None:
+            raise ValueError("evaluate: Xout belongs to the rollout form: it must be None when X is given")
+    if x0 is not None:
+        check_device_tensor(x0, s0, solver.device, "x0")
+    if Xout is not None:
+        if U is None:
+            raise ValueError("evaluate: Xout needs U")
+        check_device_tensor(Xout, sx, solver.device, "Xout")
+    if out is None:
+        out = tuple(torch.empty(lead, dtype=torch.float64, device=dev) for _ in range(3))
+    out = tuple(out)
+    if len(out) != 3 or all(o is None for o in out):
+        raise ValueError("evaluate: out is (J, c_max, defect); any may be None, not all")
+    for o, nm in zip(out, ("J", "c_max", "defect")):
+        if o is not None:
+            check_device_tensor(o, lead, solver.device, nm)
+    solver._chk(solver._L.altro_batch_evaluate_dev(solver.h, ncand, _addr(U), _addr(X), _addr(x0), _addr(out[0]), _addr(out[1]),
+                                                   _addr(out[2]), _addr(Xout)))
+    return out
+
+
+def evaluate(solver, U=None, X=None, x0=None, out=None, Xout=None):
+    """Score trajectories the solver did not make against the problem its next solve would see (altro_batch_evaluate / _dev):
+    returns (J, c_max, defect) -- the plain tracking cost without augmented-Lagrangian terms, the maximum constraint violation
+    and the dynamics defect max_k |A x_k + B u_k + f - x_{k+1}|_inf.
+    U (B, N-1, m): one candidate per instance, outputs (B,); U (B, ncand, N-1, m): outputs (B, ncand).  With X None the states
+    are rolled out from x0 (B, n) (None: the solver's initial state), written to Xout (shape of U with (N, n)) when given, and
+    defect is +0; with X (the shape of Xout) the pair is scored as it is.  U None: the solver's own trajectory.
+    With GPU tensors (float64, contiguous) the call is stream-ordered and nothing synchronises; out = (J, c_max, defect) are
+    tensors to write into (any may be None, not all; default: three new ones).  With numpy the host twin runs: the same bytes."""
+    args = (U, X, x0, Xout) + (tuple(out) if out is not None else ())
+    if any(_on_gpu(a) for a in args):
+        if not all(a is None or _on_gpu(a) for a in args):
+            raise ValueError("evaluate: U, X, x0, Xout and out must all be GPU tensors (or None), or none of them")
+        with _bracket(solver):
+            return _evaluate_dev(solver, U, X, x0, out, Xout)
+    U = None if U is None else _c(U)
+    X = None if X is None else _c(X)
+    x0 = None if x0 is None else _c(x0)
+    ncand, lead, su, sx, s0 = _evaluate_shapes(solver, U, X, x0, "evaluate")
+    for a, shp, nm in ((U, su, "U"), (X, sx, "X"), (x0, s0, "x0")):
+        if a is not None and a.shape != shp:
+            raise ValueError(f"evaluate: {nm}: shape {a.shape}, expected {shp}")
+    if Xout is not None and (U is None or X is not None):
+        raise ValueError("evaluate: Xout belongs to the rollout form (U given, X None)")
+    if out is None:
+        out = tuple(np.empty(lead) for _ in range(3))
+    out = tuple(out)
+    if len(out) != 3 or all(o is None for o in out):
+        raise ValueError("evaluate: out is (J, c_max, defect); any may be None, not all")
+    for o, shp, nm in tuple(zip(out, (lead,) * 3, ("J", "c_max", "defect"))) + ((Xout, sx, "Xout"),):
+        if o is not None and not (isinstance(o, np.ndarray) and o.dtype == np.float64 and o.flags.c_contiguous and o.shape == shp):
+            raise ValueError(f"evaluate: {nm} must be a C-contiguous float64 array of shape {shp}")
+    solver._chk(solver._L.altro_batch_evaluate(solver.h, ncand, _p(U), _p(X), _p(x0), _p(out[0]), _p(out[1]), _p(out[2]), _p(Xout)))
+    return out
+
+
+def rollout(solver, U, x0=None, out=None):
+    """rollout!(prob): the states of the model under the controls U from x0 (None: the solver's initial state), on the device
+    (the rollout form of altro_batch_evaluate).  U (B, N-1, m) -> X (B, N, n); U (B, ncand, N-1, m) -> X (B, ncand, N, n).  GPU
+    tensors: stream-ordered, out is the tensor to write into; numpy: the host twin."""
+    if U is None:
+        raise ValueError("rollout: U is required")
+    shp = tuple(int(k) for k in U.shape)[:-2] + (solver.N, solver.n)
+    # (the C-ABI wants one of J, c_max, defect: c_max goes to a scratch array kept with the solver, so that a rollout per tick
+    #  allocates nothing but `out` when the caller does not pass it)
+    if _on_gpu(U):
+        import torch
+        dev = torch.device("cuda", solver.device)
+        if out is None:
+            out = torch.empty(shp, dtype=torch.float64, device=dev)
+        c = getattr(solver, "_rollout_scratch", None)
+        if c is None or not _on_gpu(c) or tuple(c.shape) != shp[:-2]:
+            c = solver._rollout_scratch = torch.empty(shp[:-2], dtype=torch.float64, device=dev)
+        evaluate(solver, U, x0=x0, out=(None, c, None), Xout=out)
+        return out
+    if out is None:
+        out = np.empty(shp)
+    evaluate(solver, U, x0=x0, out=(None, np.empty(shp[:-2]), None), Xout=out)
+    return out

@@ -15,6 +15,7 @@
 
 #include "../../include/altro_batch.h"
 #include "device_io.h"
+#include "evaluate.h"
 #include "launch_ring.h"
 #include "pn_polish.h"
 #include "policy.h"
@@ -106,6 +107,8 @@ struct altro_handle {
   int *iters = nullptr, *iters_outer = nullptr, *status = nullptr;
   double *cost = nullptr, *cmax = nullptr, *Jtrace = nullptr, *ctrace = nullptr, *atrace = nullptr;
   double* stage = nullptr;  // device staging buffer for host<->device layout conversion
+  double* eval_ws = nullptr;   // altro_batch_evaluate(_dev): states of a rollout without Xout, or the gathered own trajectory (grow-only)
+  size_t eval_ws_elems = 0;
   altro::StreamLink link;   // events of altro_batch_wait_stream / altro_batch_signal_stream (device_io.h)
   altro::InstanceFlags flags;  // active mask and restart selection of a 16-lane handle, [Bp] (device_io.h; a wide handle's live in its backend)
   altro::EpisodeClock clock;   // per-instance episode clock of a 16-lane handle, [Bp] (device_io.h; a wide handle's lives in its backend)
@@ -1047,10 +1050,11 @@ static void free_dpp_backend(altro_handle* h) {
                    (void**)&h->n_ok, (void**)&h->n_trials, (void**)&h->Zsave, (void**)&h->n_gconf, (void**)&h->dzero, (void**)&h->Qz,
                    (void**)&h->Dff, (void**)&h->ahash, (void**)&h->kmu, (void**)&h->n_fo, (void**)&h->perm, (void**)&h->gscore,
                    (void**)&h->pn_ran, (void**)&h->pn_failed, (void**)&h->pn_res, (void**)&h->pn_dfail, (void**)&h->pn_dres0, (void**)&h->pn_dres, (void**)&h->pnE, (void**)&h->pndv, (void**)&h->pnLd, (void**)&h->pnLo,
-                   (void**)&h->pnvec, (void**)&h->pntz, (void**)&h->pnnb, (void**)&h->pnnst, (void**)&h->pnrinfo, (void**)&h->mlog, (void**)&h->refusals};
+                   (void**)&h->pnvec, (void**)&h->pntz, (void**)&h->pnnb, (void**)&h->pnnst, (void**)&h->pnrinfo, (void**)&h->mlog, (void**)&h->refusals, (void**)&h->eval_ws};
   for (void** p : ptrs)
     if (*p) { hipFree(*p); *p = nullptr; }
   h->stage_bytes = 0;
+  h->eval_ws_elems = 0;
   h->mlog_cap = 0;
   h->ring.destroy();
   if (h->bev0) { hipEventDestroy(h->bev0); h->bev0 = nullptr; }
@@ -2593,6 +2597,118 @@ int32_t altro_batch_get_gains_dev(altro_handle* h, double* K, double* d) {
     hipLaunchKernelGGL(altro::k_unpack_gains, grid_for(B_ * (N_ - 1) * m_ * LW), dim3(256), 0, h->stream, K, d, h->KD, h->Dff, h->dzero,
                        h->d_in_kd ? 1 : 0, at, (int)B_, (int)N_, (int)n_, (int)m_);
     HIPCHK(h, hipGetLastError());
+    return ALTRO_OK;
+  });
+}
+
+// ---- caller-supplied trajectories scored on the device (kernels in evaluate.h)
+// the argument rules both forms share, checked before anything else
+static int evaluate_rules(altro_handle* h, const char* fn, int32_t ncand, const double* U, const double* X, const double* x0, double* J,
+                          double* c_max, double* defect, double* Xout) {
+  const std::string f(fn);
+  if (ncand < 1) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": ncand must be at least 1");
+  if (!U && ncand != 1) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": the handle's own trajectory (U null) is one candidate: ncand must be 1");
+  if (!U && (X || x0 || Xout)) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": X, x0 and Xout must be null when U is null");
+  if (X && (x0 || Xout)) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": x0 and Xout belong to the rollout form: they must be null when X is given");
+  if (!J && !c_max && !defect) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": J, c_max and defect are all null");
+  return ALTRO_OK;
+}
+
+// U, X, x0, J, c_max, defect, Xout: device arrays (the caller's, validated; or the staged copies of the host twin).  Enqueues
+// the rollout kernel when there is no X, then the scoring kernel; allocates only when the workspace has to grow.
+static int evaluate_launch(altro_handle* h, int32_t ncand, const double* U, const double* X, const double* x0, double* J, double* c_max,
+                           double* defect, double* Xout) {
+  if (h->wide) {
+    const int rc = h->wide->evaluate_dev(ncand, U, X, x0, J, c_max, defect, Xout);
+    if (rc) h->err = h->wide->err;
+    return rc;
+  }
+  int rc = check_ready(h);
+  if (rc) return rc;
+  if (!h->clock.on && h->kref + h->d.N > h->Nt) FAIL(h, ALTRO_ERR_STATE, "reference window runs past the end of the stored trajectory");
+  if ((rc = pack_constraints(h))) return rc;   // (what the next solve would do first; a no-op once the tables are packed)
+  const size_t B = h->d.batch, N = h->d.N, n = h->d.n, m = h->d.m;
+  const size_t R = B * (size_t)ncand, lx = N * n, lu = (N - 1) * m;
+  const size_t need = !U ? R * (lx + lu) : (!X && !Xout) ? R * lx : 0;
+  if (need > h->eval_ws_elems) {
+    if (h->eval_ws) HIPCHK(h, hipFree(h->eval_ws));
+    h->eval_ws = nullptr;
+    h->eval_ws_elems = 0;
+    HIPCHK(h, hipMalloc(&h->eval_ws, need * sizeof(double)));
+    h->eval_ws_elems = need;
+  }
+  altro::Eval16 p{};
+  p.Grow = h->Grow; p.fvec = h->fvec; p.wd = h->wd; p.wf = h->wf; p.zmin = h->zmin; p.zmax = h->zmax; p.Zref = h->Zref;
+  p.Acon = h->Acon; p.bcon = h->bcon; p.cmeta = h->cmeta; p.window = h->clock.args().window; p.imask = tab_imask(h);
+  p.con_istride = h->con_per_instance ? N * LW * LW : 0; p.ncrows = h->ncrows;
+  p.N = (int)N; p.Nt = h->Nt; p.n = (int)n; p.m = (int)m; p.kref = h->kref; p.box_k0 = h->box_k0; p.box_k1 = h->box_k1;
+  const size_t rows = (R + 3) & ~(size_t)3;   // whole waves of four rows
+  int given = 1;
+  if (!U) {   // own trajectory: the current plane, unpacked into the workspace in the caller's layout
+    if ((rc = get_traj(h, h->eval_ws, h->eval_ws + R * lx, true))) return rc;
+    X = h->eval_ws;
+    U = h->eval_ws + R * lx;
+  } else if (!X) {
+    double* Xw = Xout ? Xout : h->eval_ws;
+    hipLaunchKernelGGL(altro::k_eval_rollout16, grid_for(rows * LW), dim3(256), 0, h->stream, Xw, U, x0 ? x0 : h->x0, x0 ? (int)n : LW, p, (int)ncand, R, rows);
+    HIPCHK(h, hipGetLastError());
+    X = Xw;
+    given = 0;
+  }
+  hipLaunchKernelGGL(altro::k_eval_score16, grid_for(rows * LW), dim3(256), 0, h->stream, J, c_max, defect, X, U, p, (int)ncand, R, rows, given);
+  HIPCHK(h, hipGetLastError());
+  return ALTRO_OK;
+}
+
+int32_t altro_batch_evaluate_dev(altro_handle* h, int32_t ncand, const double* U, const double* X, const double* x0, double* J, double* c_max,
+                                 double* defect, double* Xout) {
+  return guard(h, [&]() -> int32_t {
+    DEV_ENTER(h, "altro_batch_evaluate_dev");
+    if (int rc = evaluate_rules(h, fn_, ncand, U, X, x0, J, c_max, defect, Xout)) return rc;
+    const size_t R = B_ * (size_t)ncand;
+    DEV_ARG(h, "U", U, R * (N_ - 1) * m_, double, true);
+    DEV_ARG(h, "X", X, R * N_ * n_, double, true);
+    DEV_ARG(h, "x0", x0, B_ * n_, double, true);
+    DEV_ARG(h, "J", J, R, double, true);
+    DEV_ARG(h, "c_max", c_max, R, double, true);
+    DEV_ARG(h, "defect", defect, R, double, true);
+    DEV_ARG(h, "Xout", Xout, R * N_ * n_, double, true);
+    return evaluate_launch(h, ncand, U, X, x0, J, c_max, defect, Xout);
+  });
+}
+
+// The host twin: the arrays go through the staging buffer, the SAME kernels run on the staged copies and the outputs come
+// back -- the bytes are those of the `_dev` call by construction.
+int32_t altro_batch_evaluate(altro_handle* h, int32_t ncand, const double* U, const double* X, const double* x0, double* J, double* c_max,
+                             double* defect, double* Xout) {
+  return guard(h, [&]() -> int32_t {
+    if (!h) return dev_null_handle("altro_batch_evaluate");
+    if (int rc = evaluate_rules(h, "altro_batch_evaluate", ncand, U, X, x0, J, c_max, defect, Xout)) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t B = h->d.batch, N = h->d.N, n = h->d.n, m = h->d.m;
+    const size_t R = B * (size_t)ncand, cu = R * (N - 1) * m, cx = R * N * n;
+    const size_t elems = 3 * R + (U ? cu : 0) + (X ? cx : 0) + (x0 ? B * n : 0) + (Xout ? cx : 0);
+    if (int rc = h->wide ? h->wide->ensure_stage(elems * sizeof(double)) : ensure_stage(h, elems * sizeof(double))) {
+      if (h->wide) h->err = h->wide->err;
+      return rc;
+    }
+    const hipStream_t st = h->wide ? h->wide->stream : h->stream;
+    double* s = h->wide ? h->wide->stage : h->stage;
+    double *sJ = s, *sc = s + R, *sd = s + 2 * R;
+    s += 3 * R;
+    double* sU = U ? s : nullptr; s += U ? cu : 0;
+    double* sX = X ? s : nullptr; s += X ? cx : 0;
+    double* sx0 = x0 ? s : nullptr; s += x0 ? B * n : 0;
+    double* sXo = Xout ? s : nullptr;
+    if (U) HIPCHK(h, hipMemcpyAsync(sU, U, cu * sizeof(double), hipMemcpyHostToDevice, st));
+    if (X) HIPCHK(h, hipMemcpyAsync(sX, X, cx * sizeof(double), hipMemcpyHostToDevice, st));
+    if (x0) HIPCHK(h, hipMemcpyAsync(sx0, x0, B * n * sizeof(double), hipMemcpyHostToDevice, st));
+    if (int rc = evaluate_launch(h, ncand, sU, sX, sx0, J ? sJ : nullptr, c_max ? sc : nullptr, defect ? sd : nullptr, sXo)) return rc;
+    if (J) HIPCHK(h, hipMemcpyAsync(J, sJ, R * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (c_max) HIPCHK(h, hipMemcpyAsync(c_max, sc, R * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (defect) HIPCHK(h, hipMemcpyAsync(defect, sd, R * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (Xout) HIPCHK(h, hipMemcpyAsync(Xout, sXo, cx * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));
     return ALTRO_OK;
   });
 }

@@ -1,0 +1,391 @@
+// evaluate.h -- caller-supplied trajectories scored on the device (altro_batch_evaluate(_dev); include/altro_batch.h,
+// DESIGN.md 7h): rollout x_{k+1} = A_k x_k + B_k u_k + f_k, the plain tracking cost J, the maximum constraint violation c_max
+// and the dynamics defect, against the problem the next solve would see at that point of the stream.
+// Two kernels per backend.  The ROLLOUT kernel writes the states to memory ([rows][N][n], rows = batch * ncand, the caller's
+// layout); the SCORING kernel reads states and controls from memory in every form, so a rollout followed by a scoring of what
+// it wrote gives the bytes a direct scoring of the same arrays gives.  The kernels read the tables the solve kernels read --
+// dynamics, cost rows, bounds rows, reference window, constraint rows -- and write nothing the library owns.  No
+// synchronisation between waves; LDS only as a wave-private copy of time-invariant dynamics on the one-wave-per-instance backend.  Contraction is off in every function of this file and each fused multiply-add is written out, so the
+// order of every sum is the one stated here:
+//   dynamics / constraint row   acc = f_i (b_r); acc = fma(coefficient_j, z_j, acc) for j = 0, 1, ..., n + m - 1 in turn
+//   cost                        every lane adds its own w e^2 (product e * e rounded, then w * (e e), then the addition) knot
+//                               after knot, k = 0 .. N-1; the lanes are then added by an xor butterfly (strides 8, 4, 2, 1, and
+//                               32, 16 first on the one-wave-per-instance backend); J = 0.5 * that sum
+//   c_max, defect               maxima (exact in any order); a NaN stays a NaN
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "solve_dpp16.h"
+
+namespace altro {
+
+// max that keeps a NaN once it has seen one (fmax would drop it: an overflowed rollout must not look feasible)
+__device__ __forceinline__ double eval_max(double acc, double v) { return (v > acc || v != v) ? v : acc; }
+
+// |Proj(v) - v| of element `pos` of a second-order cone of dimension p (2..4) whose values are v[0..p-1] (v[q] = 0 for
+// q >= p): the oracle's soc_project / con_violation.  Inside the cone 0, in the polar cone |v_pos|, otherwise the distance to
+// the boundary point c (s, |s|), c = (1 + t / |s|) / 2.
+__device__ __forceinline__ double soc_row_violation(const double (&v)[4], int p, int pos) {
+#pragma clang fp contract(off)
+  const int pt = p - 1;
+  double n2 = 0.0, t = 0.0, mine = 0.0;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    n2 = q < pt ? n2 + v[q] * v[q] : n2;
+    t = q == pt ? v[q] : t;
+    mine = q == pos ? v[q] : mine;
+  }
+  const double nv = sqrt(n2);
+  if (nv <= t) return 0.0;
+  if (nv <= -t) return fabs(mine);
+  const double c = 0.5 * (1.0 + t / nv);
+  const double proj = pos == pt ? c * nv : c * mine;
+  return fabs(proj - mine);   // (a NaN anywhere in the cone fails both tests above and comes out here)
+}
+
+// ------------------------------------------------------------------ 16-lane backend (SolveParams layout)
+// One 16-lane row per (instance, candidate), four per wave.  rows = batch * ncand padded to whole waves; rows >= R compute on
+// row 0 and store nothing, so EXEC is all ones wherever a DPP move reads another lane.  Lane j < n holds x_j, lane n + a holds
+// u_a (0 at the terminal knot), lanes >= n + m hold 0.
+struct Eval16 {
+  const double *Grow, *fvec;              // [Bp][16][16] Grow[b][c][i] = [A B][i][c]; [Bp][16]
+  const double *wd, *wf, *zmin, *zmax;    // element (b * 16 + lane) & imask
+  const double* Zref;                     // [Bp][Nt][16]
+  const double *Acon, *bcon;              // [N][16][16] row-major, [N][16]; + b * con_istride, b * con_istride / 16
+  const int* cmeta;                       // [N][16][4]: type, k0, k1, p
+  const int* window;                      // [Bp] per-instance reference window (episode clock), or null: kref
+  unsigned imask;
+  size_t con_istride;
+  int ncrows, N, Nt, n, m, kref, box_k0, box_k1;
+};
+
+// acc + sum_c g[c] * z_c over the 16 lanes of the row, c = 0 .. 15 in turn; g[c] is 0 for c >= n + m, where z_c is 0 too
+__device__ __forceinline__ double row_affine(const double (&g)[16], double acc, double z) {
+  sfor<0, 16>([&](auto c) {
+    constexpr int C = decltype(c)::value;
+    acc = __builtin_fma(g[C], bcast<C>(z), acc);
+  });
+  return acc;
+}
+
+__device__ __forceinline__ int eval_window(const int* window, int kref, size_t b, int N, int Nt) {
+  int w = window != nullptr ? window[b] : kref;
+  w = w + N > Nt ? Nt - N : w;   // (the host and the tick rule keep every window inside the track: this never moves one)
+  return w < 0 ? 0 : w;
+}
+
+// lane i's column of [A B | f] of instance b: g[c] = [A B][i][c]
+__device__ __forceinline__ void eval16_dyn(const Eval16& P, size_t b, int lane, double (&g)[16], double& fv) {
+  const int nz = P.n + P.m;
+  const double* G = P.Grow + b * 256 + lane;
+#pragma unroll
+  for (int c = 0; c < 16; ++c) g[c] = (c < nz && lane < P.n) ? G[c * 16] : 0.0;
+  fv = lane < P.n ? P.fvec[b * 16 + lane] : 0.0;
+}
+
+// Rollout: Xw [R][N][n] <- x_0 = x0[b] (x0s = its row stride: n for a caller's array, 16 for the handle's own), then the
+// recursion under U [R][N-1][m].
+__global__ void k_eval_rollout16(double* __restrict__ Xw, const double* __restrict__ U, const double* __restrict__ x0, int x0s, Eval16 P,
+                                 int ncand, size_t R, size_t rows) {
+#pragma clang fp contract(off)
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t row = t / 16;
+  const int lane = (int)(t % 16);
+  if (row >= rows) return;   // (whole waves only)
+  const bool live = row < R;
+  const size_t r = live ? row : 0, b = r / (size_t)ncand;
+  const int n = P.n, m = P.m, N = P.N;
+  const bool isx = lane < n, isu = lane >= n && lane < n + m;
+  double g[16], fv;
+  eval16_dyn(P, b, lane, g, fv);
+  double* Xr = Xw + r * (size_t)N * n;
+  const double* Ur = U + r * (size_t)(N - 1) * m;
+  double x = isx ? x0[b * (size_t)x0s + lane] : 0.0;
+  for (int k = 0;; ++k) {
+    if (live && isx) Xr[(size_t)k * n + lane] = x;
+    if (k == N - 1) break;
+    const double z = isx ? x : (isu ? Ur[(size_t)k * m + (lane - n)] : 0.0);
+    const double nx = row_affine(g, fv, z);
+    x = isx ? nx : 0.0;
+  }
+}
+
+// Scoring of (X [R][N][n], U [R][N-1][m]); J, cmax, defect [R], any may be null.  given = 0: defect <- +0 (the rollout form).
+__global__ void k_eval_score16(double* __restrict__ J, double* __restrict__ cmax, double* __restrict__ defect, const double* __restrict__ X,
+                               const double* __restrict__ U, Eval16 P, int ncand, size_t R, size_t rows, int given) {
+#pragma clang fp contract(off)
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t row = t / 16;
+  const int lane = (int)(t % 16);
+  if (row >= rows) return;
+  const bool live = row < R;
+  const size_t r = live ? row : 0, b = r / (size_t)ncand;
+  const int n = P.n, m = P.m, N = P.N;
+  const bool isx = lane < n, isu = lane >= n && lane < n + m;
+  const bool want_defect = defect != nullptr && given != 0;
+  const int kref = eval_window(P.window, P.kref, b, N, P.Nt);
+  const unsigned e = ((unsigned)b * 16u + (unsigned)lane) & P.imask;
+  const double wd = P.wd[e], wf = P.wf[e], zlo = P.zmin[e], zhi = P.zmax[e];
+  const bool has_hi = zhi < 1e300, has_lo = zlo > -1e300;   // (the solve kernels' test for a finite side)
+  double g[16], fv = 0.0;
+#pragma unroll
+  for (int c = 0; c < 16; ++c) g[c] = 0.0;
+  if (want_defect) eval16_dyn(P, b, lane, g, fv);
+  const double* Xr = X + r * (size_t)N * n;
+  const double* Ur = U + r * (size_t)(N - 1) * m;
+  const double* Zr = P.Zref + (b * (size_t)P.Nt + (size_t)kref) * 16 + lane;
+  const double* Ac = P.Acon + b * P.con_istride + (size_t)lane * 16;
+  const double* bc = P.bcon + b * (P.con_istride / 16) + lane;
+  const int pos = lane & 3;
+  double cost = 0.0, viol = 0.0, dfc = 0.0;
+  for (int k = 0; k < N; ++k) {
+    const bool term = k == N - 1;
+    const bool on = isx || (isu && !term);
+    const double z = isx ? Xr[(size_t)k * n + lane] : (on ? Ur[(size_t)k * m + (lane - n)] : 0.0);
+    {
+      const double d = z - Zr[(size_t)k * 16];
+      double q = d * d;
+      q = (term ? wf : wd) * q;
+      cost = on ? cost + q : cost;
+    }
+    if (on && k >= P.box_k0 && k <= P.box_k1) {
+      if (has_hi) viol = eval_max(viol, z - zhi);
+      if (has_lo) viol = eval_max(viol, zlo - z);
+    }
+    if (want_defect && !term) {
+      const double pred = row_affine(g, fv, z);
+      if (isx) dfc = eval_max(dfc, fabs(pred - Xr[(size_t)(k + 1) * n + lane]));
+    }
+    if (P.ncrows > 0) {   // lane r owns constraint row r of the knot's table
+      const int* cm = P.cmeta + ((size_t)k * 16 + lane) * 4;
+      const int type = cm[0], p = cm[3];
+      const bool act = type != CT_NONE && k >= cm[1] && k <= cm[2];
+      double a[16], v = 0.0;
+#pragma unroll
+      for (int c = 0; c < 16; ++c) a[c] = 0.0;
+      if (act) {
+        const double* ar = Ac + (size_t)k * 256;
+#pragma unroll
+        for (int c = 0; c < 16; ++c) a[c] = c < n + m ? ar[c] : 0.0;
+        v = bc[(size_t)k * 16];
+      }
+      v = row_affine(a, v, z);
+      const bool is_soc = type == CT_SOC;
+      const bool row_on = act && (!is_soc || pos < p);   // (a linear row may sit in a spare lane of a cone's quad)
+      const double vv = (row_on && is_soc) ? v : 0.0;
+      double vq[4];
+      vq[0] = quad_bcast<0>(vv); vq[1] = quad_bcast<1>(vv); vq[2] = quad_bcast<2>(vv); vq[3] = quad_bcast<3>(vv);
+      const double cv = is_soc ? soc_row_violation(vq, p, pos) : (type == CT_EQ ? fabs(v) : v);
+      if (row_on) viol = eval_max(viol, cv);
+    }
+  }
+  for (int s = 8; s > 0; s >>= 1) {
+    cost += __shfl_xor(cost, s, 16);
+    viol = eval_max(viol, __shfl_xor(viol, s, 16));
+    dfc = eval_max(dfc, __shfl_xor(dfc, s, 16));
+  }
+  if (!live || lane != 0) return;
+  if (J != nullptr) J[r] = 0.5 * cost;
+  if (cmax != nullptr) cmax[r] = viol;
+  if (defect != nullptr) defect[r] = dfc;   // (+0 in the rollout form)
+}
+
+// ------------------------------------------------------------------ one-wave-per-instance backend (wide::Params layout)
+// One wave per (instance, candidate).  Lane T < n owns x_T, lane T < m owns u_T, lane T < Pn owns constraint row T.  A, Bm
+// are column-major and AconT has the rows of a knot's table as columns, so the loads of one term of a sum are consecutive
+// addresses over the lanes; x_j / u_j come from lane j by v_readlane (j is uniform).
+struct EvalW {
+  const double *A, *Bm, *f;               // column-major blocks, block arithmetic of solve_wide.h dynblk()
+  const double *wd, *wf, *zmin, *zmax;    // rows b * w_pi resp. b * b_pi
+  const double *Xref, *Uref;              // [B][Nt][n], [B][Nt-1][m]
+  const double *AconT, *bcon;             // [N][n+m][Pn], [N][Pn]; + b * con_istride, b * bcon_istride
+  const int *ctype, *rowc0, *rowcp;       // [N][Pn], [Pn], [Pn]
+  const int* window;
+  size_t con_istride, bcon_istride;
+  int w_pi, b_pi, ltv, dyn_pi, dyn_blocks, dyn_stride, Pn, N, Nt, n, m, kref, box_k0, box_k1;
+  int lds_dyn;   // 1: time-invariant dynamics whose [A | B] block fits: every wave keeps its instance's block in its slice of LDS
+};
+
+// LDS doubles a wave needs for lds_dyn, and the rule for it: four waves of a 256-thread block inside the 64 KB a kernel gets
+// without asking for more (n (n + m) <= 2048: up to (32, 32), (40, 11), ...).  Larger blocks are read from memory at every knot.
+__host__ __device__ inline size_t evalw_lds_doubles(int n, int m) { return (size_t)n * (n + m); }
+__host__ __device__ inline bool evalw_lds_fits(int n, int m, int ltv) { return !ltv && 4 * evalw_lds_doubles(n, m) * sizeof(double) <= 65536; }
+
+__device__ __forceinline__ double eval_readlane(double v, int j) {
+  const int lo = __builtin_amdgcn_readlane(__double2loint(v), j), hi = __builtin_amdgcn_readlane(__double2hiint(v), j);
+  return __hiloint2double(hi, lo);
+}
+
+__device__ __forceinline__ size_t evalw_block(const EvalW& P, size_t b, int kref, int k) {
+  size_t kb = 0;
+  if (P.ltv) {
+    kb = (size_t)kref * P.dyn_stride + k;
+    kb = kb < (size_t)P.dyn_blocks ? kb : (size_t)P.dyn_blocks - 1;   // (never taken: the host checks that the window's blocks exist)
+  }
+  return (P.dyn_pi ? b : 0) * (size_t)(P.ltv ? P.dyn_blocks : 1) + kb;
+}
+
+// acc + sum_j col[j * stride] * v_j, j = 0 .. cnt-1 in turn, v_j = lane j's v.  The loads go out eight at a time (a plain
+// accumulate loop would wait a memory round trip per term); `on` = false: the lane owns no row, its coefficients are 0.
+__device__ __forceinline__ double evalw_dot(const double* col, size_t stride, double v, int cnt, double acc, bool on) {
+  for (int j0 = 0; j0 < cnt; j0 += 8) {
+    double a[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) a[u] = on ? col[(size_t)(j0 + u < cnt ? j0 + u : cnt - 1) * stride] : 0.0;
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      if (j0 + u < cnt) acc = __builtin_fma(a[u], eval_readlane(v, j0 + u), acc);
+  }
+  return acc;
+}
+
+// row Tn of A x + B u + f0: Acol / Bcol point at element Tn of the first column; xs / us are the lane's own elements
+__device__ __forceinline__ double evalw_step(const double* Acol, const double* Bcol, double f0, int n, int m, double xs, double us) {
+  const double acc = evalw_dot(Acol, (size_t)n, xs, n, f0, true);
+  return evalw_dot(Bcol, (size_t)n, us, m, acc, true);
+}
+
+// The dynamics of instance b as one wave reads them at knot k.  Time-invariant blocks that fit (lds_dyn) are copied once into
+// the wave's own slice of LDS -- every knot of every candidate would otherwise read the same n (n + m) doubles from memory
+// again, and at (32, 16), batch 8192, ncand 8 that traffic (12 KB per knot and wave) was the whole run time.  The slice is
+// written and read by the same wave only: LDS instructions of a wave execute in order, so the hand-over needs a wave-level
+// fence for the compiler and no barrier.  The values and the order of every sum are the same either way.
+struct EvalWDyn {
+  const EvalW& P;
+  size_t b;
+  int kref, Tn;
+  const double* lds;   // the wave's [A | B] in LDS, or null
+  double f0;
+  __device__ __forceinline__ EvalWDyn(const EvalW& p, size_t b_, int kref_, int T, int Tn_, double* slice, bool wanted)
+      : P(p), b(b_), kref(kref_), Tn(Tn_), lds(nullptr), f0(0.0) {
+    if (!wanted || !P.lds_dyn) return;
+    const size_t blk = evalw_block(P, b, kref, 0);
+    const int na = P.n * P.n, nb = P.n * P.m;
+    for (int e = T; e < na; e += 64) slice[e] = P.A[blk * na + e];
+    for (int e = T; e < nb; e += 64) slice[na + e] = P.Bm[blk * nb + e];
+    f0 = P.f != nullptr ? P.f[blk * P.n + Tn] : 0.0;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    lds = slice;
+  }
+  __device__ __forceinline__ double step(int k, double xs, double us) const {
+    const int n = P.n, m = P.m;
+    if (lds != nullptr) return evalw_step(lds + Tn, lds + n * n + Tn, f0, n, m, xs, us);
+    const size_t blk = evalw_block(P, b, kref, k);
+    return evalw_step(P.A + blk * n * n + Tn, P.Bm + blk * n * m + Tn, P.f != nullptr ? P.f[blk * n + Tn] : 0.0, n, m, xs, us);
+  }
+};
+
+__global__ void k_eval_rollout_wide(double* __restrict__ Xw, const double* __restrict__ U, const double* __restrict__ x0, EvalW P, int ncand,
+                                    size_t R) {
+#pragma clang fp contract(off)
+  const size_t r = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) / 64;
+  const int T = (int)(threadIdx.x & 63);
+  if (r >= R) return;   // (whole waves)
+  const size_t b = r / (size_t)ncand;
+  const int n = P.n, m = P.m, N = P.N;
+  const bool isx = T < n, isu = T < m;
+  const int Tn = isx ? T : n - 1;
+  const int kref = eval_window(P.window, P.kref, b, N, P.Nt);
+  double* Xr = Xw + r * (size_t)N * n;
+  const double* Ur = U + r * (size_t)(N - 1) * m;
+  extern __shared__ double eval_lds[];
+  const EvalWDyn dyn(P, b, kref, T, Tn, eval_lds + (threadIdx.x >> 6) * evalw_lds_doubles(n, m), true);
+  double x = isx ? x0[b * (size_t)n + T] : 0.0;
+  for (int k = 0;; ++k) {
+    if (isx) Xr[(size_t)k * n + T] = x;
+    if (k == N - 1) break;
+    const double u = isu ? Ur[(size_t)k * m + T] : 0.0;
+    const double nx = dyn.step(k, x, u);
+    x = isx ? nx : 0.0;
+  }
+}
+
+__global__ void k_eval_score_wide(double* __restrict__ J, double* __restrict__ cmax, double* __restrict__ defect, const double* __restrict__ X,
+                                  const double* __restrict__ U, EvalW P, int ncand, size_t R, int given) {
+#pragma clang fp contract(off)
+  const size_t r = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) / 64;
+  const int T = (int)(threadIdx.x & 63);
+  if (r >= R) return;
+  const size_t b = r / (size_t)ncand;
+  const int n = P.n, m = P.m, N = P.N, nz = P.n + P.m, Pn = P.Pn;
+  const bool isx = T < n, isu = T < m, isr = T < Pn;
+  const int Tn = isx ? T : n - 1, Tm = isu ? T : m - 1;
+  const bool want_defect = defect != nullptr && given != 0;
+  const int kref = eval_window(P.window, P.kref, b, N, P.Nt);
+  const double* wdi = P.wd + b * (size_t)P.w_pi * nz;
+  const double* wfi = P.wf + b * (size_t)P.w_pi * n;
+  const double* zlo = P.zmin + b * (size_t)P.b_pi * nz;
+  const double* zhi = P.zmax + b * (size_t)P.b_pi * nz;
+  const double wx = wdi[Tn], wfx = wfi[Tn], wu = wdi[n + Tm];
+  const double xlo = zlo[Tn], xhi = zhi[Tn], ulo = zlo[n + Tm], uhi = zhi[n + Tm];
+  const double* Xr = X + r * (size_t)N * n;
+  const double* Ur = U + r * (size_t)(N - 1) * m;
+  const double* Xf = P.Xref + (b * (size_t)P.Nt + (size_t)kref) * n;
+  const double* Uf = P.Uref + (b * (size_t)(P.Nt - 1) + (size_t)kref) * m;
+  const double* At = P.AconT + b * P.con_istride + (isr ? T : 0);
+  const double* bc = P.bcon + b * P.bcon_istride + (isr ? T : 0);
+  const int c0 = isr ? P.rowc0[T] : 0, cp = isr ? P.rowcp[T] : 0;
+  extern __shared__ double eval_lds[];
+  const EvalWDyn dyn(P, b, kref, T, Tn, eval_lds + (threadIdx.x >> 6) * evalw_lds_doubles(n, m), want_defect);
+  double cost = 0.0, viol = 0.0, dfc = 0.0;
+  for (int k = 0; k < N; ++k) {
+    const bool term = k == N - 1;
+    const bool uon = isu && !term;
+    const double x = isx ? Xr[(size_t)k * n + T] : 0.0;
+    const double u = uon ? Ur[(size_t)k * m + T] : 0.0;
+    if (isx) {
+      const double d = x - Xf[(size_t)k * n + T];
+      double q = d * d;
+      q = (term ? wfx : wx) * q;
+      cost += q;
+    }
+    if (uon) {
+      const double d = u - Uf[(size_t)k * m + T];
+      double q = d * d;
+      q = wu * q;
+      cost += q;
+    }
+    if (k >= P.box_k0 && k <= P.box_k1) {
+      if (isx && xhi < 1e300) viol = eval_max(viol, x - xhi);
+      if (isx && xlo > -1e300) viol = eval_max(viol, xlo - x);
+      if (uon && uhi < 1e300) viol = eval_max(viol, u - uhi);
+      if (uon && ulo > -1e300) viol = eval_max(viol, ulo - u);
+    }
+    if (want_defect && !term) {
+      const double pred = dyn.step(k, x, u);
+      if (isx) dfc = eval_max(dfc, fabs(pred - Xr[(size_t)(k + 1) * n + T]));
+    }
+    if (Pn > 0) {
+      const int ct = isr ? P.ctype[(size_t)k * Pn + T] : 0;
+      const bool on = ct != 0;
+      const double* Ak = At + (size_t)k * nz * Pn;
+      double v = on ? bc[(size_t)k * Pn] : 0.0;
+      v = evalw_dot(Ak, (size_t)Pn, x, n, v, on);
+      if (!term) v = evalw_dot(Ak + (size_t)n * Pn, (size_t)Pn, u, m, v, on);
+      double vq[4];   // (every lane of the wave is here: the shuffles read live lanes)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const double s = __shfl(v, (c0 + q) & 63, 64);
+        vq[q] = q < cp ? s : 0.0;
+      }
+      const double cv = ct == 3 ? soc_row_violation(vq, cp, T - c0) : (ct == 1 ? fabs(v) : v);
+      if (on) viol = eval_max(viol, cv);
+    }
+  }
+  for (int s = 32; s > 0; s >>= 1) {
+    cost += __shfl_xor(cost, s, 64);
+    viol = eval_max(viol, __shfl_xor(viol, s, 64));
+    dfc = eval_max(dfc, __shfl_xor(dfc, s, 64));
+  }
+  if (T != 0) return;
+  if (J != nullptr) J[r] = 0.5 * cost;
+  if (cmax != nullptr) cmax[r] = viol;
+  if (defect != nullptr) defect[r] = dfc;
+}
+
+}  // namespace altro

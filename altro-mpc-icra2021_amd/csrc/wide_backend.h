@@ -11,6 +11,7 @@
 
 #include "../../include/altro_batch.h"
 #include "device_io.h"
+#include "evaluate.h"
 #include "launch_ring.h"
 #include "policy.h"
 #include "solve_wide.h"
@@ -156,6 +157,8 @@ struct WideBackend {
   long long *n_backward = nullptr, *n_rollout = nullptr, *n_trials = nullptr, *n_solves = nullptr, *n_iters = nullptr,
             *n_ok = nullptr, *n_gconf = nullptr, *n_gs = nullptr;
   size_t stage_bytes = 0;
+  double* eval_ws = nullptr;   // altro_batch_evaluate(_dev): states of a rollout without Xout, or the gathered own trajectory (grow-only)
+  size_t eval_ws_elems = 0;
   int Nt = 0, kref = 0, noise_steps = 0, noise_mode = 0, mpc_shift = 1;
   double* mlog = nullptr;  // per-step log of the MPC loop (mpc_log.h): [mlog_cap][B][n + m + MLOG_TAIL]; null: off
   int mlog_cap = 0;
@@ -248,7 +251,7 @@ struct WideBackend {
     void* ptrs[] = {A, Bm, f, wd, wf, zmin, zmax, x0, Xref, Uref, X, U, Lb, Lc, mu, Kg, dg, trash, AconT, bcon, stage, cur, ctype,
                     rowk0, rowk1, rowc0, rowcp, iters, iters_outer, status, noise_grp, cost, cmax, Jtrace, ctrace, atrace, noise, noise_w,
                     n_backward, n_rollout, n_trials, n_solves, n_iters, n_ok, Xsave, Usave, Qz, n_gconf, n_gs, fac, bwst, aset,
-                    pn_ran, pn_failed, pn_dfail, pn_res, pn_dres0, pn_dres, pnE, pndv, pnLd, pnLo, pnvec, pntz, pnblk, pnnb, pnnst, pnrinfo, mlog, refusals};
+                    pn_ran, pn_failed, pn_dfail, pn_res, pn_dres0, pn_dres, pnE, pndv, pnLd, pnLo, pnvec, pntz, pnblk, pnnb, pnnst, pnrinfo, mlog, refusals, eval_ws};
     for (void* p : ptrs)
       if (p) hipFree(p);
     ring.destroy();
@@ -760,6 +763,52 @@ struct WideBackend {
     const size_t thr = (size_t)d.batch * d.m;
     hipLaunchKernelGGL(altro::k_eval_policy_wide, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, stream, ud, fb, xd, knot, X, U, cur, Kg, bwst,
                        (gains_valid || debug_keep_gains) ? 1 : 0, zmin, zmax, b_pi, d.batch, d.N, d.n, d.m, clamp ? 1 : 0, box_k0, box_k1);
+    WCHK(hipGetLastError());
+    return ALTRO_OK;
+  }
+  // altro_batch_evaluate_dev (evaluate.h; pointers and argument rules checked by the caller, the host twin passes staged
+  // copies): the rollout kernel when there is no X, then the scoring kernel on states and controls in memory.  Reads what the
+  // next solve would read; writes the caller's outputs and eval_ws only.
+  int evaluate_dev(int ncand, const double* Ud, const double* Xd, const double* x0d, double* Jd, double* cd, double* dd, double* Xout) {
+    WCHK(hipSetDevice(device));
+    if (!have_dyn) WFAIL(ALTRO_ERR_STATE, "altro_batch_set_dynamics has not been called");
+    if (!have_cost) WFAIL(ALTRO_ERR_STATE, "altro_batch_set_tracking_cost has not been called");
+    if (!have_ref) WFAIL(ALTRO_ERR_STATE, "no reference trajectory (altro_batch_set_reference / altro_mpc_set_track)");
+    if (!clock.on && kref + d.N > Nt) WFAIL(ALTRO_ERR_STATE, "reference window runs past the end of the stored trajectory");
+    if (!clock.on && !dyn_covers(kref)) WFAIL(ALTRO_ERR_STATE, "the dynamics track ends before the window");
+    if (int rc = pack_constraints()) return rc;   // (what the next solve would do first; a no-op once the tables are packed)
+    const size_t R = (size_t)d.batch * ncand, lx = (size_t)d.N * d.n, lu = (size_t)(d.N - 1) * d.m;
+    const size_t need = !Ud ? R * (lx + lu) : (!Xd && !Xout) ? R * lx : 0;
+    if (need > eval_ws_elems) {
+      if (eval_ws) WCHK(hipFree(eval_ws));
+      eval_ws = nullptr;
+      eval_ws_elems = 0;
+      WCHK(hipMalloc(&eval_ws, need * sizeof(double)));
+      eval_ws_elems = need;
+    }
+    altro::EvalW p{};
+    p.A = A; p.Bm = Bm; p.f = f; p.wd = wd; p.wf = wf; p.zmin = zmin; p.zmax = zmax; p.Xref = Xref; p.Uref = Uref;
+    p.AconT = AconT; p.bcon = bcon; p.ctype = ctype; p.rowc0 = rowc0; p.rowcp = rowcp; p.window = clock.args().window;
+    p.con_istride = con_per_instance ? (size_t)d.N * nz() * Pn : 0;
+    p.bcon_istride = con_per_instance ? (size_t)d.N * Pn : 0;
+    p.w_pi = w_pi; p.b_pi = b_pi; p.ltv = ltv; p.dyn_pi = dyn_per_instance; p.dyn_blocks = dyn_blocks; p.dyn_stride = dyn_step_stride;
+    p.Pn = Pn; p.N = d.N; p.Nt = Nt; p.n = d.n; p.m = d.m; p.kref = kref; p.box_k0 = box_k0; p.box_k1 = box_k1;
+    p.lds_dyn = altro::evalw_lds_fits(d.n, d.m, ltv) ? 1 : 0;
+    const size_t lds = p.lds_dyn ? 4 * altro::evalw_lds_doubles(d.n, d.m) * sizeof(double) : 0;
+    const dim3 grid((unsigned)((R * 64 + 255) / 256)), block(256);
+    int given = 1;
+    if (!Ud) {   // own trajectory: the current planes, gathered into the workspace in the caller's layout
+      if (int rc = get_planes_dev(eval_ws, eval_ws + R * lx)) return rc;
+      Xd = eval_ws;
+      Ud = eval_ws + R * lx;
+    } else if (!Xd) {
+      double* Xw = Xout ? Xout : eval_ws;
+      hipLaunchKernelGGL(altro::k_eval_rollout_wide, grid, block, lds, stream, Xw, Ud, x0d ? x0d : x0, p, ncand, R);
+      WCHK(hipGetLastError());
+      Xd = Xw;
+      given = 0;
+    }
+    hipLaunchKernelGGL(altro::k_eval_score_wide, grid, block, (dd && given) ? lds : 0, stream, Jd, cd, dd, Xd, Ud, p, ncand, R, given);
     WCHK(hipGetLastError());
     return ALTRO_OK;
   }

@@ -333,6 +333,11 @@ class ExternalMPC:
             raise ValueError("ExternalMPC.policy takes GPU tensors; the numpy form is api.eval_policy")
         return api.eval_policy(self.solver, x, knot=knot, clamp=clamp, out=out)
 
+    def evaluate(self, U=None, X=None, x0=None, out=None, Xout=None):
+        """(J, c_max, defect) of candidate trajectories against the problem the next tick's solve would see once the solver's
+        stream reaches this point (api.evaluate): a pass-through, GPU tensors or numpy."""
+        return api.evaluate(self.solver, U, X=X, x0=x0, out=out, Xout=Xout)
+
     def _constraints_dev(self, constraint_data, bounds):
         s = self.solver
         for con, (A, b) in (constraint_data or {}).items():

@@ -532,6 +532,54 @@ int32_t altro_batch_eval_policy_dev(altro_handle* h, const double* x, const int3
 int32_t altro_batch_eval_policy(altro_handle* h, const double* x, const int32_t* knot, int32_t clamp, double* u, int32_t* fb);
 int32_t altro_batch_get_gains_dev(altro_handle* h, double* K, double* d);
 
+/* ---- caller-supplied trajectories scored on the device: rollout!(prob) (random_linear_problem.jl:30,
+ * rocket_landing_problem.jl:183, run_simple_rocket.jl:63,87, grasp_problem.jl:104), cost(prob_mpc) / cost(prob_mpc.obj, Z)
+ * (simple_rocket.jl:198-200: the plain objective, of the solver's trajectory and of ECOS's), max_violation(...) and
+ * dynamics_violation(prob, X, U) (simple_rocket.jl:191,208-216).  A caller that holds several candidate control sequences per
+ * instance -- the shifted previous solution, the reference controls, a learned guess -- has them scored against the problem
+ * the next altro_batch_solve would see at that point of the stream, takes an argmin and installs the winner with
+ * altro_batch_set_initial_trajectory_dev.
+ * altro_batch_evaluate_dev: every pointer is a device pointer under the rules of the device-pointer block (validated before
+ * anything is enqueued, stream-ordered, no host synchronisation, no caller pointer kept).  ncand >= 1 candidates per instance:
+ *   U      [batch][ncand][N-1][m]
+ *   J, c_max, defect   [batch][ncand] outputs; any may be NULL, not all
+ * Rollout form (X == NULL): x_0 = x0[b] (x0 [batch][n]; NULL: the initial state the handle holds), x_{k+1} = A_k x_k + B_k u_k
+ *   + f_k; Xout [batch][ncand][N][n] (may be NULL) receives the states; defect receives +0.0.  With Xout == NULL the states go
+ *   to a grow-only workspace of the handle: the one allocation, on the first call or when batch * ncand grows.
+ * Given form (X [batch][ncand][N][n] not NULL): (X, U) are scored as they are; x0 and Xout must be NULL;
+ *   defect[b][c] = max_k max_i |A_k x_k + B_k u_k + f_k - x_{k+1}|_i, the maximum over ALL knots.  (The reference's
+ *   dynamics_violation overwrites its `err` in every pass of the loop and so returns the last knot's value only; the maximum
+ *   is what it evidently means.)
+ * Own trajectory (U == NULL): ncand must be 1 and X, x0, Xout NULL; the given form on the trajectory the handle holds
+ *   (altro_batch_get_states / _get_controls): cost(prob_mpc) and max_violation(solver) without the augmented-Lagrangian terms.
+ * J = sum_{k<N-1} dt (1/2 dx' Q dx + 1/2 du' R du) + 1/2 dx_N' Qf dx_N with dx, du the distance to the reference window the
+ *   handle holds (under an episode clock: the instance's own window) and the instance's own weights when they are per
+ *   instance; no AL terms.  The dynamics are the blocks of that window (altro_mpc_set_dynamics_track: kref * step_stride + k).
+ * c_max = the maximum over every constraint and every knot of its range of the violation (the oracle's con_violation): BOX
+ *   max(0, z - zmax, zmin - z) over finite sides, state columns only at knot N-1; LINEAR |v| for an equality row, max(0, v)
+ *   for an inequality row; SOC ||Proj(v) - v||_inf.  The data is the device tables as the solve kernels address them, with
+ *   whatever altro_batch_set_bounds(_dev) / altro_batch_update_constraint_data(_dev) wrote earlier on the stream.
+ * No masking, no clamping, no status: an instance the active mask or the clock leaves out is scored like any other; a
+ * rollout that overflows puts Inf or NaN into its own outputs and nothing else.  Nothing the library owns changes: every later
+ * solve, MPC step, counter and log record is bit-identical to a handle that never made the call (the stored gains stay).
+ * Results are a function of the call's inputs: candidate c of instance b gets the bytes it would get alone (ncand = 1) or on a
+ * batch-1 handle holding instance b's data, and the rollout form with Xout followed by the given form on (Xout, U) returns the
+ * same bytes of J and c_max (one scoring kernel reads states from memory in both forms).  Summation orders: csrc/evaluate.h.
+ * One caveat to "no host synchronisation, no allocation": like a solve, the call first packs constraint tables that a HOST
+ * altro_batch_add_constraint / altro_batch_update_constraint_data has left unpacked -- host copies, and before the first solve a
+ * reallocation of the tables and of the (still zero) duals of the constraint rows.  It is exactly what the next solve would do
+ * first, it happens only after such a host-side edit, and it is a no-op otherwise (the `_dev` setters never leave tables unpacked).
+ * altro_batch_evaluate: the same with host arrays, through the handle's staging buffer (grown if needed); synchronises; writes
+ * the bytes the `_dev` call writes.
+ * ALTRO_ERR_INVALID_ARG (nothing enqueued, the handle unchanged and usable): NULL handle; ncand < 1; U == NULL with ncand != 1
+ * or with X, x0 or Xout; X together with x0 or Xout; J, c_max and defect all NULL; _dev: what the device-pointer block
+ * refuses.  ALTRO_ERR_STATE: dynamics, cost or reference not set, or the window runs past the stored reference.  All indexing
+ * is size_t: the 4 GiB rule of the handle's own arrays does not apply to the caller's. */
+int32_t altro_batch_evaluate_dev(altro_handle* h, int32_t ncand, const double* U, const double* X, const double* x0, double* J,
+                                 double* c_max, double* defect, double* Xout);
+int32_t altro_batch_evaluate(altro_handle* h, int32_t ncand, const double* U, const double* X, const double* x0, double* J,
+                             double* c_max, double* defect, double* Xout);
+
 /* ---- per-instance active mask and cold restart: ragged batches of closed loops.
  * The reference runs one problem per loop, and a loop that ends simply stops calling solve! (simple_rocket.jl:137-205); in a
  * batch the instance whose rocket has landed, or whose episode has ended and is re-spawned, sits among others that go on.
