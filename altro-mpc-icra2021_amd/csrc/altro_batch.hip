@@ -15,6 +15,7 @@
 
 #include "../../include/altro_batch.h"
 #include "device_io.h"
+#include "device_pool.h"
 #include "evaluate.h"
 #include "launch_ring.h"
 #include "pn_polish.h"
@@ -39,15 +40,42 @@ struct DebugSwitches {
   int lone = 1, pair = 1, shadow = 1, resync = 1, reuse = 1, useqz = 1, mate = 1;
   int group = 1;             // 0 off, 1 sorted, 2-4: other slot orders (k_group_rank)
   int group_max_steps = 32;
-  int trace_wave = -1;       // -DALTRO_PHASE_STAMPS builds
+  int dbg_wave = -1;         // "trace_wave": -DALTRO_PHASE_STAMPS builds
   int force_wide = 0;        // every (n, m) on the one-wave-per-instance backend
-  int keep_gains = 0;        // -DALTRO_DEBUG builds only
+  int keep_gains = 0;        // -DALTRO_DEBUG builds only: the setters do NOT drop the stored gains (exists to show that the
+                             // tests notice stale gains)
   int wide_compact = -1, wide_coop = -1, wide_static_mask = -1;   // -1: the backend's default
 };
 static thread_local DebugSwitches g_dbg;
+// key -> member.  negate: a "no_x" key switches the feature x off; at_create: read when a handle is created, refused on one
+struct SwitchKey {
+  const char* key;
+  int DebugSwitches::*member;
+  bool negate, at_create;
+};
+static const SwitchKey kSwitchKeys[] = {
+    {"no_lone", &DebugSwitches::lone, true, false},        // backward_split<4> (tests: lone == four-row pass bit for bit)
+    {"no_pair", &DebugSwitches::pair, true, false},        // backward_split<2>: two rows need a pass
+    {"no_qz_pass", &DebugSwitches::useqz, true, false},    // backward passes always recompute their cost / box expansion
+    {"no_shadow", &DebugSwitches::shadow, true, false},    // rows that sit a phase out keep their own instance
+    {"no_resync", &DebugSwitches::resync, true, false},    // rows never wait for their wave-mates
+    {"no_mate_rank", &DebugSwitches::mate, true, false},   // issue priority from the row's own state only
+    {"no_reuse", &DebugSwitches::reuse, true, false},      // gain reuse (solve_dpp16.h fosweep)
+    {"no_group", &DebugSwitches::group, true, false},      // fused MPC launches run in instance order
+    {"group_mode", &DebugSwitches::group, false, false},
+    {"group_max_steps", &DebugSwitches::group_max_steps, false, false},   // fused launches of more steps are not grouped
+    {"trace_wave", &DebugSwitches::dbg_wave, false, false},
+    {"keep_gains", &DebugSwitches::keep_gains, false, false},
+    {"force_wide", &DebugSwitches::force_wide, false, true},
+    {"wide_compact", &DebugSwitches::wide_compact, false, true},
+    {"wide_coop", &DebugSwitches::wide_coop, false, true},
+    {"wide_static_mask", &DebugSwitches::wide_static_mask, false, true},
+};
 
 struct altro_handle {
   altro_wide::WideBackend* wide = nullptr;  // set: this handle runs on the one-wave-per-instance kernel
+  altro::DevicePool pool;                   // owns every device array below (device_pool.h); the members stay plain pointers
+  DebugSwitches sw;                         // the switches as they were when the handle was created, then altro_debug_set(h, ..)
   altro_dims d{};
   altro_opts o{};
   int device = 0;
@@ -87,22 +115,9 @@ struct altro_handle {
   int mpc_shift = 1;
   double* mlog = nullptr;  // per-step log of the MPC loop (mpc_log.h): [mlog_cap][batch][16 + MLOG_TAIL]; null: off
   int mlog_cap = 0;        // steps it holds
-  // scheduling switches (altro_debug_set; the defaults are the product's behaviour)
   bool d_in_kd = false;  // the last solve launch's kernel keeps d in the gain rows (altro::kd_holds_d), not in Dff
-  int reuse = 1;  // gain reuse (solve_dpp16.h fosweep); "no_reuse" switches it off (tests)
-  int lone = 1;  // backward_split<4> (solve_dpp16.h); "no_lone" switches it off (tests: lone == four-row pass bit for bit)
-  int pair = 1;  // backward_split<2> (two rows need a pass); "no_pair" keeps the four-row form for them
-  int group_max_steps = 32;  // fused launches of more steps are not grouped ("group_max_steps": diagnostic)
-  int shadow = 1;  // "no_shadow": rows that sit a phase out keep their own instance (solve_dpp16.h shadow_enter)
-  int useqz = 1;   // "no_qz_pass": backward passes always recompute their cost / box expansion (solve_dpp16.h backward QV)
   int* cur = nullptr;
   int *perm = nullptr, *gscore = nullptr;  // [Bp] wave slot -> instance of a grouped MPC launch, and its sort key
-  bool debug_keep_gains = false;           // "keep_gains" (-DALTRO_DEBUG builds only): the setters do NOT drop the stored gains
-                                           // (exists to show that the tests notice stale gains)
-  int group = 1;                           // "no_group": identity; "group_mode": other slot orders
-  int dbg_wave = -1;                       // "trace_wave" (diagnostic builds only)
-  int resync = 1;                          // "no_resync": rows never wait for their wave-mates
-  int mate = 1;                            // "no_mate_rank": issue priority from the row's own state only, not from its SIMD mates'
   unsigned* simd_tab = nullptr;            // [65536][16], zero between launches
   int *iters = nullptr, *iters_outer = nullptr, *status = nullptr;
   double *cost = nullptr, *cmax = nullptr, *Jtrace = nullptr, *ctrace = nullptr, *atrace = nullptr;
@@ -163,7 +178,7 @@ struct altro_handle {
     return (code);         \
   } while (0)
 
-// forward an entry point to the wide backend when the handle runs on it
+// forward an entry point to the wide backend when the handle runs on it (the device-pointer entry points: after the validation)
 #define WIDE_FWD(h, call)                           \
   do {                                              \
     if ((h) && (h)->wide) {                         \
@@ -174,12 +189,7 @@ struct altro_handle {
   } while (0)
 
 static int ensure_stage(altro_handle* h, size_t bytes) {
-  if (bytes <= h->stage_bytes) return ALTRO_OK;
-  if (h->stage) HIPCHK(h, hipFree(h->stage));
-  h->stage = nullptr;
-  h->stage_bytes = 0;
-  HIPCHK(h, hipMalloc(&h->stage, bytes));
-  h->stage_bytes = bytes;
+  HIPCHK(h, h->pool.reserve(reinterpret_cast<char**>(&h->stage), &h->stage_bytes, bytes));
   return ALTRO_OK;
 }
 
@@ -586,13 +596,8 @@ static int upload_tables(altro_handle* h) {
   const bool pi = h->cost_pi || h->bnd_pi;
   const size_t rows = pi ? (size_t)h->Bp : 1;
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  if ((int)rows > h->tab_cap) {
-    double** tabs[] = {&h->wd, &h->wf, &h->zmin, &h->zmax};
-    for (double** t : tabs) {
-      HIPCHK(h, hipFree(*t));
-      *t = nullptr;
-    }
-    for (double** t : tabs) HIPCHK(h, hipMalloc(t, rows * LW * sizeof(double)));
+  if ((int)rows > h->tab_cap || !h->wd || !h->wf || !h->zmin || !h->zmax) {
+    for (double** t : {&h->wd, &h->wf, &h->zmin, &h->zmax}) HIPCHK(h, h->pool.alloc(t, rows * LW, h->stream, false));
     h->tab_cap = (int)rows;
   }
   const std::vector<double>* src[] = {&h->wd_h, &h->wf_h, &h->zmin_h, &h->zmax_h};
@@ -620,7 +625,7 @@ static int launch_solve(altro_handle* h, int first_step, int nsteps, int prepare
   p.Gcol = h->Gcol; p.Grow = h->Grow; p.fvec = h->fvec;
   p.wd = h->wd; p.wf = h->wf; p.zmin = h->zmin; p.zmax = h->zmax; p.imask = tab_imask(h);
   p.x0 = h->x0; p.Zref = h->Zref; p.Z = h->Z; p.cur = h->cur;
-  p.Lb = h->Lb; p.bslot = h->bslot; p.nbp = h->nbp; p.mu = h->mu; p.lone = h->lone; p.pair = h->pair; p.useqz = h->useqz; p.shadow = h->shadow; p.reuse = h->reuse; p.resync = h->resync; p.dbg_wave = h->dbg_wave;
+  p.Lb = h->Lb; p.bslot = h->bslot; p.nbp = h->nbp; p.mu = h->mu; p.lone = h->sw.lone; p.pair = h->sw.pair; p.useqz = h->sw.useqz; p.shadow = h->sw.shadow; p.reuse = h->sw.reuse; p.resync = h->sw.resync; p.dbg_wave = h->sw.dbg_wave;
   p.Dff = h->Dff; p.ahash = h->ahash; p.kmu = h->kmu; p.n_fo = h->n_fo;
   p.Qz = h->Qz;
   p.Acon = h->Acon; p.bcon = h->bcon; p.cmeta = h->cmeta; p.ckn = h->ckn; p.con_inv = h->con_inv;
@@ -628,7 +633,7 @@ static int launch_solve(altro_handle* h, int first_step, int nsteps, int prepare
   p.iters = h->iters; p.iters_outer = h->iters_outer; p.status = h->status;
   p.cost = h->cost; p.cmax = h->cmax; p.Jtrace = h->Jtrace; p.ctrace = h->ctrace; p.atrace = h->atrace;
   p.n_backward = h->n_backward; p.n_rollout = h->n_rollout; p.wave_cycles = h->wave_cycles;
-  p.simd_tab = h->mate ? h->simd_tab : nullptr;
+  p.simd_tab = h->sw.mate ? h->simd_tab : nullptr;
   p.n_solves = h->n_solves; p.n_iters = h->n_iters; p.n_ok = h->n_ok; p.n_trials = h->n_trials;
   p.n_gconf = h->n_gconf; p.dzero = h->dzero;
   p.mlog = (nsteps > 0 && !prepare_only) ? h->mlog : nullptr;  // MPC steps only (altro_mpc_run_async checked the capacity)
@@ -645,10 +650,10 @@ static int launch_solve(altro_handle* h, int first_step, int nsteps, int prepare
   // (short launches only: over 100 steps nearly every window meets a bound at some point, the score stops separating the
   //  instances and clustering the pass-heavy rows -- they are also the ones with the hard solves -- lengthens the tail:
   //  measured 20 steps +2 %, 100 steps -3 %, tools/gpu_ab.py)
-  if (h->group && h->reuse && !h->o.strict && nsteps >= 4 && nsteps <= h->group_max_steps && !prepare_only && h->ncrows == 0 && h->box_k1 >= h->box_k0 && h->Bp <= 32768) {
+  if (h->sw.group && h->sw.reuse && !h->o.strict && nsteps >= 4 && nsteps <= h->sw.group_max_steps && !prepare_only && h->ncrows == 0 && h->box_k1 >= h->box_k0 && h->Bp <= 32768) {
     hipLaunchKernelGGL(k_group_score, grid_for((size_t)h->Bp * LW), dim3(256), 0, h->stream, h->Zref, h->zmin, h->zmax, tab_imask(h), h->gscore, h->Bp, h->Nt,
                        first_step, nsteps, h->box_k0, h->box_k1, h->d.n + h->d.m, h->flags.mask(), h->clock.args(), h->d.N);
-    hipLaunchKernelGGL(k_group_rank, dim3(1), dim3(256), 0, h->stream, h->gscore, h->perm, h->Bp, h->group);
+    hipLaunchKernelGGL(k_group_rank, dim3(1), dim3(256), 0, h->stream, h->gscore, h->perm, h->Bp, h->sw.group);
     p.perm = h->perm;
   }
   const dim3 grid(h->Bp / IPW), block(64);
@@ -680,7 +685,7 @@ static int launch_solve(altro_handle* h, int first_step, int nsteps, int prepare
 // elements and the options: every setter of those drops them (kmu < 0: no valid gains).  Trajectories, duals and
 // reference windows need no such care: the active set they produce is hashed and compared at every use.
 static int drop_gains(altro_handle* h) {
-  if (h->kmu && !h->debug_keep_gains) {
+  if (h->kmu && !h->sw.keep_gains) {
     hipLaunchKernelGGL(k_fill, grid_for((size_t)h->Bp), dim3(256), 0, h->stream, h->kmu, -1.0, (size_t)h->Bp);
     HIPCHK(h, hipGetLastError());
   }
@@ -737,9 +742,7 @@ int32_t altro_debug_set(altro_handle* h, const char* key, int32_t value) {
     };
     if (k == "keep_gains") {
 #ifdef ALTRO_DEBUG
-      if (h) { if (h->wide) h->wide->debug_keep_gains = value != 0; else h->debug_keep_gains = value != 0; }
-      else g_dbg.keep_gains = value != 0;
-      return ALTRO_OK;
+      if (h && h->wide) { h->wide->debug_keep_gains = value != 0; return ALTRO_OK; }
 #else
       if (value == 0) return ALTRO_OK;
       return bad(ALTRO_ERR_UNSUPPORTED, "keep_gains exists in -DALTRO_DEBUG builds of the library only");
@@ -750,37 +753,17 @@ int32_t altro_debug_set(altro_handle* h, const char* key, int32_t value) {
       h->dev_via_stage = value != 0;
       return ALTRO_OK;
     }
+    const SwitchKey* sk = nullptr;
+    for (const SwitchKey& c : kSwitchKeys)
+      if (k == c.key) sk = &c;
+    if (!sk) return bad(ALTRO_ERR_INVALID_ARG, "unknown switch");
     // create-time switches: which backend, and the LDS carve-up of the one-wave-per-instance backend
-    int* pre = k == "force_wide" ? &g_dbg.force_wide : k == "wide_compact" ? &g_dbg.wide_compact : k == "wide_coop" ? &g_dbg.wide_coop
-             : k == "wide_static_mask" ? &g_dbg.wide_static_mask : nullptr;
-    if (pre) {
-      if (h) return bad(ALTRO_ERR_STATE, "this switch is read when a handle is created: pass a null handle before altro_batch_create");
-      *pre = value;
-      return ALTRO_OK;
-    }
-    DebugSwitches tmp;
-    DebugSwitches& d = h ? tmp : g_dbg;
-    if (h) { tmp.mate = h->mate; tmp.lone = h->lone; tmp.pair = h->pair; tmp.useqz = h->useqz; tmp.shadow = h->shadow; tmp.resync = h->resync; tmp.reuse = h->reuse; tmp.group = h->group;
-             tmp.group_max_steps = h->group_max_steps; tmp.trace_wave = h->dbg_wave; }
-    if (k == "no_lone") d.lone = value ? 0 : 1;
-    else if (k == "no_pair") d.pair = value ? 0 : 1;
-    else if (k == "no_qz_pass") d.useqz = value ? 0 : 1;
-    else if (k == "no_shadow") d.shadow = value ? 0 : 1;
-    else if (k == "no_resync") d.resync = value ? 0 : 1;
-    else if (k == "no_mate_rank") d.mate = value ? 0 : 1;
-    else if (k == "no_reuse") d.reuse = value ? 0 : 1;
-    else if (k == "no_group") d.group = value ? 0 : 1;
-    else if (k == "group_mode") { if (value < 0 || value > 4) return bad(ALTRO_ERR_INVALID_ARG, "group_mode is 0..4"); d.group = value; }
-    else if (k == "group_max_steps") d.group_max_steps = value;
-    else if (k == "trace_wave") d.trace_wave = value;
-    else return bad(ALTRO_ERR_INVALID_ARG, "unknown switch");
-    if (h && !h->wide) {
-      const bool reuse_changed = h->reuse != tmp.reuse;
-      h->mate = tmp.mate;
-      h->lone = tmp.lone; h->pair = tmp.pair; h->useqz = tmp.useqz; h->shadow = tmp.shadow; h->resync = tmp.resync; h->reuse = tmp.reuse; h->group = tmp.group;
-      h->group_max_steps = tmp.group_max_steps; h->dbg_wave = tmp.trace_wave;
-      if (reuse_changed) { HIPCHK(h, hipSetDevice(h->device)); return drop_gains(h); }
-    }
+    if (sk->at_create && h) return bad(ALTRO_ERR_STATE, "this switch is read when a handle is created: pass a null handle before altro_batch_create");
+    if (k == "group_mode" && (value < 0 || value > 4)) return bad(ALTRO_ERR_INVALID_ARG, "group_mode is 0..4");
+    DebugSwitches& d = h ? h->sw : g_dbg;   // (a wide handle keeps its copy too: its backend reads none of the scheduling switches)
+    const int reuse_was = d.reuse;
+    d.*(sk->member) = sk->negate ? (value ? 0 : 1) : value;
+    if (h && !h->wide && d.reuse != reuse_was) { HIPCHK(h, hipSetDevice(h->device)); return drop_gains(h); }
     return ALTRO_OK;
   });
 }
@@ -886,9 +869,7 @@ int32_t altro_batch_create(const altro_dims* dims, const altro_opts* opts, int32
     h->d = *dims;
     if (opts) h->o = *opts; else altro_default_opts(&h->o);
     h->device = device;
-    h->mate = g_dbg.mate;
-    h->lone = g_dbg.lone; h->pair = g_dbg.pair; h->useqz = g_dbg.useqz; h->shadow = g_dbg.shadow; h->resync = g_dbg.resync; h->reuse = g_dbg.reuse; h->group = g_dbg.group;
-    h->group_max_steps = g_dbg.group_max_steps; h->dbg_wave = g_dbg.trace_wave; h->debug_keep_gains = g_dbg.keep_gains != 0;
+    h->sw = g_dbg;
     h->Bp = (dims->batch + IPW - 1) / IPW * IPW;
     auto fail = [&](const char* what, hipError_t er) {
       g_create_err = std::string(what) + ": " + hipGetErrorString(er);
@@ -909,126 +890,42 @@ int32_t altro_batch_create(const altro_dims* dims, const altro_opts* opts, int32
       g_create_err = "batch * N too large for one handle (arrays must stay below 4 GiB); split the batch";
       return ALTRO_ERR_UNSUPPORTED;
     }
-    CCHK(hipMalloc(&h->Gcol, Bp * n * LW * sizeof(double)));
-    CCHK(hipMalloc(&h->Grow, Bp * LW * LW * sizeof(double)));
-    CCHK(hipMalloc(&h->fvec, row * sizeof(double)));
-    CCHK(hipMalloc(&h->wd, LW * sizeof(double)));
-    CCHK(hipMalloc(&h->wf, LW * sizeof(double)));
-    CCHK(hipMalloc(&h->zmin, LW * sizeof(double)));
-    CCHK(hipMalloc(&h->zmax, LW * sizeof(double)));
-    CCHK(hipMalloc(&h->x0, row * sizeof(double)));
-    // + one trash row at the end of each (stores of rows that sit out a phase land there)
-    CCHK(hipMalloc(&h->Z, (2 * N + 1) * row * sizeof(double)));
     for (int j = 0; j < LW; ++j) h->bslot_h[j] = -1;
-    h->nbp = 1;
-    CCHK(hipMalloc(&h->Lb, (N + 1) * Bp * 2 * h->nbp * sizeof(double)));
-    CCHK(hipMalloc(&h->bslot, LW * sizeof(int)));
-    CCHK(hipMalloc(&h->Acon, N * LW * LW * sizeof(double)));
-    CCHK(hipMalloc(&h->bcon, N * LW * sizeof(double)));
-    CCHK(hipMalloc(&h->cmeta, N * LW * 4 * sizeof(int)));
-    CCHK(hipMalloc(&h->ckn, LW * sizeof(int)));
-    CCHK(hipMemsetAsync(h->ckn, 0, LW * sizeof(int), h->stream));
-    CCHK(hipMalloc(&h->lanebuf, LW * sizeof(int)));
-    CCHK(hipMalloc(&h->noise_w, LW * sizeof(double)));
-    CCHK(hipMalloc(&h->noise_grp, LW * sizeof(int)));
-    {
-      std::vector<double> w(LW, 0.01);  // 1 % of ||x0||_inf (random_linear_problem.jl:129)
-      std::vector<int> g(LW, 0);
-      CCHK(hipMemcpyAsync(h->noise_w, w.data(), LW * sizeof(double), hipMemcpyHostToDevice, h->stream));
-      CCHK(hipMemcpyAsync(h->noise_grp, g.data(), LW * sizeof(int), hipMemcpyHostToDevice, h->stream));
-      CCHK(hipStreamSynchronize(h->stream));
-    }
-    CCHK(hipMalloc(&h->Lc, (N + 1) * row * sizeof(double)));
+    // every device array of the backend: (member, elements), zero-filled on the stream
+  #define DA(member, count) CCHK(h->pool.alloc(&h->member, (count), h->stream))
+    DA(Gcol, Bp * n * LW); DA(Grow, Bp * LW * LW); DA(fvec, row);
+    DA(wd, LW); DA(wf, LW); DA(zmin, LW); DA(zmax, LW);
+    DA(x0, row);
+    DA(Z, (2 * N + 1) * row);    // + one trash row at the end of each (stores of rows that sit out a phase land there)
+    DA(Lb, (N + 1) * Bp * 2 * h->nbp); DA(bslot, LW); DA(Lc, (N + 1) * row);
+    DA(Acon, N * LW * LW); DA(bcon, N * LW); DA(cmeta, N * LW * 4); DA(ckn, LW); DA(lanebuf, LW);
+    DA(noise_w, LW); DA(noise_grp, LW);
+    DA(mu, Bp); DA(kmu, Bp); DA(ahash, row); DA(dzero, Bp);
+    DA(KD, N * Bp * m * LW);     // N-1 gain blocks + a trash slot
+    DA(Qz, (N + 1) * row); DA(Dff, (N + 1) * row);
+    DA(pn_ran, Bp); DA(pn_failed, Bp); DA(pn_dfail, Bp); DA(pn_res, Bp); DA(pn_dres0, Bp); DA(pn_dres, Bp);
+    DA(cur, Bp); DA(perm, Bp); DA(gscore, Bp); DA(refusals, 1);
+    DA(iters, Bp); DA(iters_outer, Bp); DA(status, Bp); DA(cost, Bp); DA(cmax, Bp);
+    DA(Jtrace, Bp * ALTRO_TRACE_LEN); DA(ctrace, Bp * ALTRO_TRACE_LEN); DA(atrace, Bp * ALTRO_TRACE_LEN);
+    DA(n_backward, Bp); DA(n_rollout, Bp); DA(n_solves, Bp); DA(n_iters, Bp); DA(n_ok, Bp); DA(n_trials, Bp); DA(n_gconf, Bp); DA(n_fo, Bp);
+    DA(wave_cycles, Bp * 6 + 4096); DA(simd_tab, (size_t)65536 * 16);
+  #undef DA
+    // what does not start at zero: no bounds until a BOX constraint is added, no bounded element, no constraint row on any
+    // lane, 1 % of ||x0||_inf of plant noise (random_linear_problem.jl:129), penalty 1, no gains yet
+    h->zmin_h.assign(LW, -INFINITY); h->zmax_h.assign(LW, INFINITY);
+    h->wd_h.assign(LW, 0.0); h->wf_h.assign(LW, 0.0);
     h->Acon_h.assign(N * LW * LW, 0.0);
     h->bcon_h.assign(N * LW, 0.0);
     h->cmeta_h.assign(N * LW * 4, 0);
     for (size_t e = 0; e < N * LW; ++e) h->cmeta_h[4 * e + 2] = -1;
-    CCHK(hipMemcpyAsync(h->Acon, h->Acon_h.data(), h->Acon_h.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    CCHK(hipMemcpyAsync(h->bcon, h->bcon_h.data(), h->bcon_h.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     CCHK(hipMemcpyAsync(h->cmeta, h->cmeta_h.data(), h->cmeta_h.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    CCHK(hipMemsetAsync(h->Lc, 0, (N + 1) * row * sizeof(double), h->stream));
     CCHK(hipMemcpyAsync(h->bslot, h->bslot_h, LW * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    CCHK(hipMalloc(&h->mu, Bp * sizeof(double)));
-    CCHK(hipMalloc(&h->KD, N * Bp * m * LW * sizeof(double)));  // N-1 gain blocks + a trash slot
-    CCHK(hipMalloc(&h->Qz, (N + 1) * row * sizeof(double)));
-    CCHK(hipMalloc(&h->Dff, (N + 1) * row * sizeof(double)));
-    CCHK(hipMemsetAsync(h->Dff, 0, (N + 1) * row * sizeof(double), h->stream));
-    CCHK(hipMalloc(&h->ahash, row * sizeof(altro::ASet)));
-    CCHK(hipMemsetAsync(h->ahash, 0, row * sizeof(altro::ASet), h->stream));
-    CCHK(hipMalloc(&h->kmu, Bp * sizeof(double)));
-    CCHK(hipMalloc(&h->n_fo, Bp * sizeof(long long)));
-    CCHK(hipMalloc(&h->pn_ran, Bp * sizeof(int)));
-    CCHK(hipMalloc(&h->pn_failed, Bp * sizeof(int)));
-    CCHK(hipMalloc(&h->pn_res, Bp * sizeof(double)));
-    CCHK(hipMalloc(&h->pn_dfail, Bp * sizeof(int)));
-    CCHK(hipMalloc(&h->pn_dres0, Bp * sizeof(double)));
-    CCHK(hipMalloc(&h->pn_dres, Bp * sizeof(double)));
-    CCHK(hipMemsetAsync(h->pn_dfail, 0, Bp * sizeof(int), h->stream));
-    CCHK(hipMemsetAsync(h->pn_dres0, 0, Bp * sizeof(double), h->stream));
-    CCHK(hipMemsetAsync(h->pn_dres, 0, Bp * sizeof(double), h->stream));
-    CCHK(hipMemsetAsync(h->pn_ran, 0, Bp * sizeof(int), h->stream));
-    CCHK(hipMemsetAsync(h->pn_failed, 0, Bp * sizeof(int), h->stream));
-    CCHK(hipMemsetAsync(h->pn_res, 0, Bp * sizeof(double), h->stream));
-    CCHK(hipMemsetAsync(h->n_fo, 0, Bp * sizeof(long long), h->stream));
-    CCHK(hipMemsetAsync(h->Qz, 0, (N + 1) * row * sizeof(double), h->stream));
-    CCHK(hipMalloc(&h->cur, Bp * sizeof(int)));
-    CCHK(hipMalloc(&h->refusals, sizeof(unsigned long long)));
-    CCHK(hipMemsetAsync(h->refusals, 0, sizeof(unsigned long long), h->stream));
-    CCHK(hipMalloc(&h->perm, Bp * sizeof(int)));
-    CCHK(hipMalloc(&h->gscore, Bp * sizeof(int)));
-    CCHK(hipMalloc(&h->iters, Bp * sizeof(int)));
-    CCHK(hipMalloc(&h->iters_outer, Bp * sizeof(int)));
-    CCHK(hipMalloc(&h->status, Bp * sizeof(int)));
-    CCHK(hipMalloc(&h->cost, Bp * sizeof(double)));
-    CCHK(hipMalloc(&h->cmax, Bp * sizeof(double)));
-    CCHK(hipMalloc(&h->Jtrace, Bp * ALTRO_TRACE_LEN * sizeof(double)));
-    CCHK(hipMalloc(&h->ctrace, Bp * ALTRO_TRACE_LEN * sizeof(double)));
-    CCHK(hipMalloc(&h->atrace, Bp * ALTRO_TRACE_LEN * sizeof(double)));
-    CCHK(hipMemsetAsync(h->atrace, 0, Bp * ALTRO_TRACE_LEN * sizeof(double), h->stream));
-    CCHK(hipMalloc(&h->n_backward, Bp * sizeof(long long)));
-    CCHK(hipMalloc(&h->n_rollout, Bp * sizeof(long long)));
-    CCHK(hipMalloc(&h->wave_cycles, (Bp * 6 + 4096) * sizeof(long long)));
-    CCHK(hipMalloc(&h->simd_tab, (size_t)65536 * 16 * sizeof(unsigned)));
-    CCHK(hipMemsetAsync(h->simd_tab, 0, (size_t)65536 * 16 * sizeof(unsigned), h->stream));
-    CCHK(hipMalloc(&h->n_solves, Bp * sizeof(long long)));
-    CCHK(hipMalloc(&h->n_iters, Bp * sizeof(long long)));
-    CCHK(hipMalloc(&h->n_ok, Bp * sizeof(long long)));
-    CCHK(hipMalloc(&h->n_trials, Bp * sizeof(long long)));
-    CCHK(hipMemsetAsync(h->n_trials, 0, Bp * sizeof(long long), h->stream));
-    CCHK(hipMalloc(&h->n_gconf, Bp * sizeof(long long)));
-    CCHK(hipMemsetAsync(h->n_gconf, 0, Bp * sizeof(long long), h->stream));
-    CCHK(hipMalloc(&h->dzero, Bp * sizeof(int)));
-    CCHK(hipMemsetAsync(h->dzero, 0, Bp * sizeof(int), h->stream));
-    CCHK(hipMemsetAsync(h->n_solves, 0, Bp * sizeof(long long), h->stream));
-    CCHK(hipMemsetAsync(h->n_iters, 0, Bp * sizeof(long long), h->stream));
-    CCHK(hipMemsetAsync(h->n_ok, 0, Bp * sizeof(long long), h->stream));
-    CCHK(hipMemsetAsync(h->wave_cycles, 0, (Bp * 6 + 4096) * sizeof(long long), h->stream));
-    CCHK(hipMemsetAsync(h->n_backward, 0, Bp * sizeof(long long), h->stream));
-    CCHK(hipMemsetAsync(h->n_rollout, 0, Bp * sizeof(long long), h->stream));
-    CCHK(hipMemsetAsync(h->Z, 0, (2 * N + 1) * row * sizeof(double), h->stream));
-    CCHK(hipMemsetAsync(h->Lb, 0, (N + 1) * Bp * 2 * h->nbp * sizeof(double), h->stream));
-    CCHK(hipMemsetAsync(h->KD, 0, N * Bp * m * LW * sizeof(double), h->stream));
-    CCHK(hipMemsetAsync(h->cur, 0, Bp * sizeof(int), h->stream));
-    CCHK(hipMemsetAsync(h->iters, 0, Bp * sizeof(int), h->stream));
-    CCHK(hipMemsetAsync(h->iters_outer, 0, Bp * sizeof(int), h->stream));
-    CCHK(hipMemsetAsync(h->status, 0, Bp * sizeof(int), h->stream));
-    CCHK(hipMemsetAsync(h->cost, 0, Bp * sizeof(double), h->stream));
-    CCHK(hipMemsetAsync(h->cmax, 0, Bp * sizeof(double), h->stream));
-    CCHK(hipMemsetAsync(h->Jtrace, 0, Bp * ALTRO_TRACE_LEN * sizeof(double), h->stream));
-    CCHK(hipMemsetAsync(h->ctrace, 0, Bp * ALTRO_TRACE_LEN * sizeof(double), h->stream));
-    CCHK(hipMemsetAsync(h->x0, 0, row * sizeof(double), h->stream));
-    CCHK(hipMemsetAsync(h->fvec, 0, row * sizeof(double), h->stream));
-    {
-      // no bounds until a BOX constraint is added
-      std::vector<double> lo(LW, -INFINITY), hi(LW, INFINITY);
-      h->zmin_h = lo; h->zmax_h = hi;
-      h->wd_h.assign(LW, 0.0); h->wf_h.assign(LW, 0.0);
-      CCHK(hipMemcpyAsync(h->zmin, lo.data(), LW * sizeof(double), hipMemcpyHostToDevice, h->stream));
-      CCHK(hipMemcpyAsync(h->zmax, hi.data(), LW * sizeof(double), hipMemcpyHostToDevice, h->stream));
-      CCHK(hipStreamSynchronize(h->stream));
-    }
+    hipLaunchKernelGGL(k_fill, dim3(1), dim3(256), 0, h->stream, h->zmin, -INFINITY, (size_t)LW);
+    hipLaunchKernelGGL(k_fill, dim3(1), dim3(256), 0, h->stream, h->zmax, INFINITY, (size_t)LW);
+    hipLaunchKernelGGL(k_fill, dim3(1), dim3(256), 0, h->stream, h->noise_w, 0.01, (size_t)LW);
     hipLaunchKernelGGL(k_fill, grid_for(Bp), dim3(256), 0, h->stream, h->mu, 1.0, (size_t)Bp);
-    hipLaunchKernelGGL(k_fill, grid_for(Bp), dim3(256), 0, h->stream, h->kmu, -1.0, (size_t)Bp);  // no gains yet
+    hipLaunchKernelGGL(k_fill, grid_for(Bp), dim3(256), 0, h->stream, h->kmu, -1.0, (size_t)Bp);
+    CCHK(hipGetLastError());
     CCHK(hipStreamSynchronize(h->stream));
   #undef CCHK
     owner.p = nullptr;
@@ -1041,21 +938,11 @@ int32_t altro_batch_create(const altro_dims* dims, const altro_opts* opts, int32
 static void free_dpp_backend(altro_handle* h) {
   hipSetDevice(h->device);
   if (h->stream) hipStreamSynchronize(h->stream);
-  void** ptrs[] = {(void**)&h->Gcol, (void**)&h->Grow, (void**)&h->fvec, (void**)&h->wd, (void**)&h->wf, (void**)&h->zmin, (void**)&h->zmax,
-                   (void**)&h->x0, (void**)&h->Zref, (void**)&h->Z, (void**)&h->Lb, (void**)&h->bslot, (void**)&h->Acon, (void**)&h->bcon,
-                   (void**)&h->cmeta, (void**)&h->ckn, (void**)&h->Lc, (void**)&h->lanebuf, (void**)&h->noise_w, (void**)&h->noise_grp, (void**)&h->mu,
-                   (void**)&h->KD, (void**)&h->noise, (void**)&h->cur, (void**)&h->iters, (void**)&h->iters_outer, (void**)&h->status,
-                   (void**)&h->cost, (void**)&h->cmax, (void**)&h->Jtrace, (void**)&h->ctrace, (void**)&h->atrace, (void**)&h->stage,
-                   (void**)&h->n_backward, (void**)&h->n_rollout, (void**)&h->wave_cycles, (void**)&h->simd_tab, (void**)&h->n_solves, (void**)&h->n_iters,
-                   (void**)&h->n_ok, (void**)&h->n_trials, (void**)&h->Zsave, (void**)&h->n_gconf, (void**)&h->dzero, (void**)&h->Qz,
-                   (void**)&h->Dff, (void**)&h->ahash, (void**)&h->kmu, (void**)&h->n_fo, (void**)&h->perm, (void**)&h->gscore,
-                   (void**)&h->pn_ran, (void**)&h->pn_failed, (void**)&h->pn_res, (void**)&h->pn_dfail, (void**)&h->pn_dres0, (void**)&h->pn_dres, (void**)&h->pnE, (void**)&h->pndv, (void**)&h->pnLd, (void**)&h->pnLo,
-                   (void**)&h->pnvec, (void**)&h->pntz, (void**)&h->pnnb, (void**)&h->pnnst, (void**)&h->pnrinfo, (void**)&h->mlog, (void**)&h->refusals, (void**)&h->eval_ws};
-  for (void** p : ptrs)
-    if (*p) { hipFree(*p); *p = nullptr; }
+  h->pool.release_all();
   h->stage_bytes = 0;
   h->eval_ws_elems = 0;
   h->mlog_cap = 0;
+  h->pn_bm = 0;
   h->ring.destroy();
   if (h->bev0) { hipEventDestroy(h->bev0); h->bev0 = nullptr; }
   if (h->bev1) { hipEventDestroy(h->bev1); h->bev1 = nullptr; }
@@ -1089,7 +976,7 @@ int32_t altro_batch_destroy(altro_handle* h) {
 static int migrate_to_wide(altro_handle* h) {
   if (h->have_cost || h->have_ref || h->have_dyn || h->ncon > 0 || h->timed)
     FAIL(h, ALTRO_ERR_UNSUPPORTED, "per-knot dynamics on an (n, m) of the 16-lane kernel set: call altro_batch_set_dynamics "
-                                   "first after altro_batch_create (or set ALTRO_FORCE_WIDE=1)");
+                                   "first after altro_batch_create (or altro_debug_set(NULL, \"force_wide\", 1) before it)");
   altro_wide::WideBackend* wb = new (std::nothrow) altro_wide::WideBackend();
   if (!wb) FAIL(h, ALTRO_ERR_INTERNAL, "out of host memory");
   apply_wide_switches(wb);
@@ -1323,13 +1210,10 @@ static int pack_constraints(altro_handle* h) {
       for (int i = 0; i < 4; ++i) h->cmeta_h[4 * ((size_t)k * LW + 4 * q + i) + 3] = pdim;
     }
   h->ncrows = h->cons.empty() ? 0 : LW;
-  if (h->Acon_h.size() != h->acon_elems) {  // the table changed shape (per-instance data arrived): reallocate
+  if (h->Acon_h.size() != h->acon_elems || !h->Acon || !h->bcon) {  // the table changed shape (per-instance data arrived): reallocate
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->Acon) HIPCHK(h, hipFree(h->Acon));
-    if (h->bcon) HIPCHK(h, hipFree(h->bcon));
-    h->Acon = h->bcon = nullptr;
-    HIPCHK(h, hipMalloc(&h->Acon, h->Acon_h.size() * sizeof(double)));
-    HIPCHK(h, hipMalloc(&h->bcon, h->bcon_h.size() * sizeof(double)));
+    HIPCHK(h, h->pool.alloc(&h->Acon, h->Acon_h.size(), h->stream, false));
+    HIPCHK(h, h->pool.alloc(&h->bcon, h->bcon_h.size(), h->stream, false));
     h->acon_elems = h->Acon_h.size();
   }
   HIPCHK(h, hipMemcpyAsync(h->Acon, h->Acon_h.data(), h->Acon_h.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -1414,13 +1298,7 @@ int32_t altro_batch_add_constraint(altro_handle* h, int32_t kind, int32_t sense,
     h->nbp = nb > 0 ? nb : 1;
     HIPCHK(h, hipMemcpyAsync(h->bslot, h->bslot_h, LW * sizeof(int), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipFree(h->Lb));
-    h->Lb = nullptr;
-    {
-      const size_t lbytes = (size_t)(h->d.N + 1) * h->Bp * 2 * h->nbp * sizeof(double);
-      HIPCHK(h, hipMalloc(&h->Lb, lbytes));
-      HIPCHK(h, hipMemsetAsync(h->Lb, 0, lbytes, h->stream));
-    }
+    HIPCHK(h, h->pool.alloc(&h->Lb, (size_t)(h->d.N + 1) * h->Bp * 2 * h->nbp, h->stream));
     if (int rcd = drop_gains(h)) return rcd;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->box_k0 = k_first;
@@ -1541,10 +1419,10 @@ static int set_ref_common(altro_handle* h, const double* Xref, const double* Ure
   int rc = staged ? ensure_stage(h, (cx + cu) * sizeof(double)) : ALTRO_OK;
   if (rc) return rc;
   if ((size_t)Nt * h->Bp * LW * sizeof(double) >= (1ull << 32)) FAIL(h, ALTRO_ERR_UNSUPPORTED, "reference trajectory too large for one handle (below 4 GiB)");
-  if (h->Nt != Nt) {
-    if (h->Zref) HIPCHK(h, hipFree(h->Zref));
-    h->Zref = nullptr;
-    HIPCHK(h, hipMalloc(&h->Zref, (size_t)Nt * h->Bp * LW * sizeof(double)));
+  if (h->Nt != Nt || !h->Zref) {
+    h->Nt = 0;   // (no reference while the array does not exist: a failure below leaves a handle that says so)
+    h->have_ref = false;
+    HIPCHK(h, h->pool.alloc(&h->Zref, (size_t)Nt * h->Bp * LW, h->stream, false));
     h->Nt = Nt;
   }
   if (staged) {
@@ -1640,18 +1518,18 @@ static int prepare_polish(altro_handle* h) {
   const int bm = 2 * h->d.n + (h->box_k1 >= h->box_k0 ? 2 * nbounded : 0) + (h->ncrows > 0 ? LW : 0);
   if (bm > altro_pn::BMAX) FAIL(h, ALTRO_ERR_UNSUPPORTED, "projected_newton: more rows per knot than pn_polish.h holds");
   if (h->pn_bm != bm || !h->pnE) {
-    void** ws[] = {(void**)&h->pnE, (void**)&h->pndv, (void**)&h->pnLd, (void**)&h->pnLo, (void**)&h->pnvec, (void**)&h->pntz,
-                   (void**)&h->pnnb, (void**)&h->pnnst, (void**)&h->pnrinfo};
-    for (void** q : ws) if (*q) { HIPCHK(h, hipFree(*q)); *q = nullptr; }
-    HIPCHK(h, hipMalloc(&h->pnE, Bp * N * bm * LW * sizeof(double)));
-    HIPCHK(h, hipMalloc(&h->pndv, Bp * N * bm * sizeof(double)));
-    HIPCHK(h, hipMalloc(&h->pnLd, Bp * N * bm * bm * sizeof(double)));
-    HIPCHK(h, hipMalloc(&h->pnLo, Bp * N * bm * bm * sizeof(double)));
-    HIPCHK(h, hipMalloc(&h->pnvec, Bp * 6 * N * bm * sizeof(double)));
-    HIPCHK(h, hipMalloc(&h->pntz, Bp * 3 * N * LW * sizeof(double)));
-    HIPCHK(h, hipMalloc(&h->pnnb, Bp * N * sizeof(int)));
-    HIPCHK(h, hipMalloc(&h->pnnst, Bp * N * sizeof(int)));
-    HIPCHK(h, hipMalloc(&h->pnrinfo, Bp * N * bm * sizeof(int)));
+    h->pn_bm = 0;   // (until every array of the workspace exists)
+    altro::DevicePool& pl = h->pool;
+    const hipStream_t st = h->stream;
+    HIPCHK(h, pl.alloc(&h->pnE, Bp * N * bm * LW, st, false));
+    HIPCHK(h, pl.alloc(&h->pndv, Bp * N * bm, st, false));
+    HIPCHK(h, pl.alloc(&h->pnLd, Bp * N * bm * bm, st, false));
+    HIPCHK(h, pl.alloc(&h->pnLo, Bp * N * bm * bm, st, false));
+    HIPCHK(h, pl.alloc(&h->pnvec, Bp * 6 * N * bm, st, false));
+    HIPCHK(h, pl.alloc(&h->pntz, Bp * 3 * N * LW, st, false));
+    HIPCHK(h, pl.alloc(&h->pnnb, Bp * N, st, false));
+    HIPCHK(h, pl.alloc(&h->pnnst, Bp * N, st, false));
+    HIPCHK(h, pl.alloc(&h->pnrinfo, Bp * N * bm, st, false));
     h->pn_bm = bm;
   }
   return ALTRO_OK;
@@ -2140,10 +2018,8 @@ int32_t altro_mpc_set_noise(altro_handle* h, const double* noise, int32_t steps)
     WIDE_FWD(h, mpc_set_noise(noise, steps));
     if (!h || !noise || steps < 1) return ALTRO_ERR_INVALID_ARG;
     HIPCHK(h, hipSetDevice(h->device));
-    if (h->noise) HIPCHK(h, hipFree(h->noise));
-    h->noise = nullptr;
     const size_t cnt = (size_t)steps * h->d.batch * h->d.n;
-    HIPCHK(h, hipMalloc(&h->noise, cnt * sizeof(double)));
+    HIPCHK(h, h->pool.alloc(&h->noise, cnt, h->stream, false));
     HIPCHK(h, hipMemcpy(h->noise, noise, cnt * sizeof(double), hipMemcpyHostToDevice));
     h->noise_steps = steps;
     return ALTRO_OK;
@@ -2201,13 +2077,12 @@ int32_t altro_mpc_set_log(altro_handle* h, int32_t capacity_steps) {
     if (capacity_steps < 0) FAIL(h, ALTRO_ERR_INVALID_ARG, "negative log capacity");
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));  // a launch in flight may still be writing the old log
-    if (h->mlog) HIPCHK(h, hipFree(h->mlog));
-    h->mlog = nullptr;
     h->mlog_cap = 0;
+    HIPCHK(h, h->pool.release(&h->mlog));
     if (capacity_steps == 0) return ALTRO_OK;
-    const size_t bytes = (size_t)capacity_steps * (size_t)h->d.batch * (LW + altro::MLOG_TAIL) * sizeof(double);
-    HIPCHK(h, hipMalloc(&h->mlog, bytes));
-    HIPCHK(h, hipMemsetAsync(h->mlog, 0xFF, bytes, h->stream));  // never written: -1 / NaN
+    const size_t elems = (size_t)capacity_steps * (size_t)h->d.batch * (LW + altro::MLOG_TAIL);
+    HIPCHK(h, h->pool.alloc(&h->mlog, elems, h->stream, false));
+    HIPCHK(h, hipMemsetAsync(h->mlog, 0xFF, elems * sizeof(double), h->stream));  // never written: -1 / NaN
     h->mlog_cap = capacity_steps;
     return ALTRO_OK;
   });
@@ -2268,7 +2143,7 @@ int32_t altro_batch_benchmark_solve(altro_handle* h, int32_t samples, int32_t ev
     if (h->clock.on) FAIL(h, ALTRO_ERR_STATE, "altro_batch_benchmark_solve restores and repeats whole batches: clear the episode clock first");
     HIPCHK(h, hipSetDevice(h->device));
     const size_t plane = (size_t)h->d.N * LW;
-    if (!h->Zsave) HIPCHK(h, hipMalloc(&h->Zsave, plane * h->Bp * sizeof(double)));
+    if (!h->Zsave) HIPCHK(h, h->pool.alloc(&h->Zsave, plane * h->Bp, h->stream, false));
     const dim3 grid = grid_for((size_t)h->Bp * LW);
     // Z0 = deepcopy(get_trajectory(solver))
     hipLaunchKernelGGL(k_plane_copy, grid, dim3(256), 0, h->stream, h->Z, h->Zsave, h->cur, plane, h->Bp, h->d.N, 1);
@@ -2320,21 +2195,12 @@ static int dev_arg(altro_handle* h, const char* fn, const char* what, const void
   do {                                                                                      \
     if (int rc_ = dev_arg(h, fn_, what, p, (size_t)(count) * sizeof(type), optional)) return rc_; \
   } while (0)
-// forward to the wide backend when the handle runs on it (after the validation)
-#define DEV_WIDE(h, call)                  \
-  do {                                     \
-    if ((h)->wide) {                       \
-      const int rc_ = (h)->wide->call;     \
-      if (rc_) (h)->err = (h)->wide->err;  \
-      return rc_;                          \
-    }                                      \
-  } while (0)
 
 int32_t altro_batch_set_initial_state_dev(altro_handle* h, const double* x0) {
   return guard(h, [&]() -> int32_t {
     DEV_ENTER(h, "altro_batch_set_initial_state_dev");
     DEV_ARG(h, "x0", x0, B_ * n_, double, false);
-    DEV_WIDE(h, set_initial_state_dev(x0));
+    WIDE_FWD(h, set_initial_state_dev(x0));
     return set_x0_16(h, x0, true);
   });
 }
@@ -2343,7 +2209,7 @@ int32_t altro_batch_get_initial_state_dev(altro_handle* h, double* x0) {
   return guard(h, [&]() -> int32_t {
     DEV_ENTER(h, "altro_batch_get_initial_state_dev");
     DEV_ARG(h, "x0", x0, B_ * n_, double, false);
-    DEV_WIDE(h, get_initial_state_dev(x0));
+    WIDE_FWD(h, get_initial_state_dev(x0));
     return get_x0_16(h, x0, true);
   });
 }
@@ -2353,7 +2219,7 @@ int32_t altro_batch_set_reference_dev(altro_handle* h, const double* Xref, const
     DEV_ENTER(h, "altro_batch_set_reference_dev");
     DEV_ARG(h, "Xref", Xref, B_ * N_ * n_, double, false);
     DEV_ARG(h, "Uref", Uref, B_ * (N_ - 1) * m_, double, false);
-    DEV_WIDE(h, set_reference_dev(Xref, Uref));
+    WIDE_FWD(h, set_reference_dev(Xref, Uref));
     return set_ref_common(h, Xref, Uref, h->d.N, true);
   });
 }
@@ -2363,7 +2229,7 @@ int32_t altro_batch_set_initial_trajectory_dev(altro_handle* h, const double* X,
     DEV_ENTER(h, "altro_batch_set_initial_trajectory_dev");
     DEV_ARG(h, "X", X, B_ * N_ * n_, double, true);
     DEV_ARG(h, "U", U, B_ * (N_ - 1) * m_, double, false);
-    DEV_WIDE(h, set_initial_trajectory_dev(X, U));
+    WIDE_FWD(h, set_initial_trajectory_dev(X, U));
     return set_traj_16(h, X, U, true);
   });
 }
@@ -2376,7 +2242,7 @@ int32_t altro_batch_set_dynamics_dev(altro_handle* h, const double* A, const dou
     DEV_ARG(h, "A", A, nb * n_ * n_, double, false);
     DEV_ARG(h, "B", B, nb * n_ * m_, double, false);
     DEV_ARG(h, "f", f, nb * n_, double, true);
-    DEV_WIDE(h, set_dynamics_dev(A, B, f, per_knot, per_instance));
+    WIDE_FWD(h, set_dynamics_dev(A, B, f, per_knot, per_instance));
     if (per_knot) {  // the first call on an (n, m) of the 16-lane set: the handle moves to the one-wave-per-instance kernel
       const int rc = migrate_to_wide(h);
       if (rc) return rc;
@@ -2392,7 +2258,7 @@ int32_t altro_batch_get_states_dev(altro_handle* h, double* X) {
   return guard(h, [&]() -> int32_t {
     DEV_ENTER(h, "altro_batch_get_states_dev");
     DEV_ARG(h, "X", X, B_ * N_ * n_, double, false);
-    DEV_WIDE(h, get_planes_dev(X, nullptr));
+    WIDE_FWD(h, get_planes_dev(X, nullptr));
     return get_traj(h, X, nullptr, true);
   });
 }
@@ -2401,7 +2267,7 @@ int32_t altro_batch_get_controls_dev(altro_handle* h, double* U) {
   return guard(h, [&]() -> int32_t {
     DEV_ENTER(h, "altro_batch_get_controls_dev");
     DEV_ARG(h, "U", U, B_ * (N_ - 1) * m_, double, false);
-    DEV_WIDE(h, get_planes_dev(nullptr, U));
+    WIDE_FWD(h, get_planes_dev(nullptr, U));
     return get_traj(h, nullptr, U, true);
   });
 }
@@ -2414,7 +2280,7 @@ int32_t altro_batch_get_first_knot_dev(altro_handle* h, double* u0, double* x1, 
     DEV_ARG(h, "status", status, B_, int32_t, true);
     DEV_ARG(h, "iterations", iterations, B_, int32_t, true);
     if (!u0 && !x1 && !status && !iterations) return ALTRO_OK;
-    DEV_WIDE(h, get_first_knot_dev(u0, x1, status, iterations));
+    WIDE_FWD(h, get_first_knot_dev(u0, x1, status, iterations));
     hipLaunchKernelGGL(altro::k_first_knot, grid_for(B_ * LW), dim3(256), 0, h->stream, u0, x1, status, iterations, h->Z, h->cur,
                        h->status, h->iters, N_ * (size_t)LW, (int)B_, (int)N_, (int)n_, (int)m_);
     HIPCHK(h, hipGetLastError());
@@ -2451,7 +2317,7 @@ int32_t altro_batch_update_constraint_data_dev(altro_handle* h, int32_t con_id, 
     if (!A && !b) FAIL(h, ALTRO_ERR_INVALID_ARG, std::string(fn_) + ": A and b are both null");
     DEV_ARG(h, "A", A, nblk * p * (n_ + m_), double, true);
     DEV_ARG(h, "b", b, nblk * p, double, true);
-    DEV_WIDE(h, update_constraint_data_dev(bl, A, b));
+    WIDE_FWD(h, update_constraint_data_dev(bl, A, b));
     if (h->con_dirty) {   // (only after a packing that failed: the tables are rebuilt on the host first)
       if (int rc = pack_constraints(h)) return rc;
     }
@@ -2480,7 +2346,7 @@ int32_t altro_batch_set_bounds_dev(altro_handle* h, int32_t con_id, const double
     const size_t rows = per_instance ? B_ : 1;
     DEV_ARG(h, "zmin", zmin, rows * (n_ + m_), double, false);
     DEV_ARG(h, "zmax", zmax, rows * (n_ + m_), double, false);
-    DEV_WIDE(h, set_bounds_dev(zmin, zmax, per_instance));
+    WIDE_FWD(h, set_bounds_dev(zmin, zmax, per_instance));
     if (per_instance && !h->bnd_pi) {
       if (int rc = refresh_bounds_mirror(h)) return rc;
       std::vector<double> lo(B_ * LW), hi(B_ * LW);
@@ -2516,7 +2382,7 @@ int32_t altro_batch_get_dev_refusals(altro_handle* h, int64_t* rows) {
   return guard(h, [&]() -> int32_t {
     if (!h) return dev_null_handle("altro_batch_get_dev_refusals");
     if (!rows) FAIL(h, ALTRO_ERR_INVALID_ARG, "altro_batch_get_dev_refusals: null pointer");
-    DEV_WIDE(h, get_dev_refusals(rows));
+    WIDE_FWD(h, get_dev_refusals(rows));
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     unsigned long long v = 0;
@@ -2591,7 +2457,7 @@ int32_t altro_batch_get_gains_dev(altro_handle* h, double* K, double* d) {
     if (!K && !d) FAIL(h, ALTRO_ERR_INVALID_ARG, std::string(fn_) + ": K and d are both null");
     DEV_ARG(h, "K", K, B_ * (N_ - 1) * n_ * m_, double, true);
     DEV_ARG(h, "d", d, B_ * (N_ - 1) * m_, double, true);
-    DEV_WIDE(h, get_gains_dev(K, d));
+    WIDE_FWD(h, get_gains_dev(K, d));
     altro::DSlots at{};
     for (int a = 0; a < (int)m_; ++a) { at.row[a] = altro::kd_drow(a); at.col[a] = altro::kd_dcol(a, (int)m_); }
     hipLaunchKernelGGL(altro::k_unpack_gains, grid_for(B_ * (N_ - 1) * m_ * LW), dim3(256), 0, h->stream, K, d, h->KD, h->Dff, h->dzero,
@@ -2630,13 +2496,7 @@ static int evaluate_launch(altro_handle* h, int32_t ncand, const double* U, cons
   const size_t B = h->d.batch, N = h->d.N, n = h->d.n, m = h->d.m;
   const size_t R = B * (size_t)ncand, lx = N * n, lu = (N - 1) * m;
   const size_t need = !U ? R * (lx + lu) : (!X && !Xout) ? R * lx : 0;
-  if (need > h->eval_ws_elems) {
-    if (h->eval_ws) HIPCHK(h, hipFree(h->eval_ws));
-    h->eval_ws = nullptr;
-    h->eval_ws_elems = 0;
-    HIPCHK(h, hipMalloc(&h->eval_ws, need * sizeof(double)));
-    h->eval_ws_elems = need;
-  }
+  if (need) HIPCHK(h, h->pool.reserve(&h->eval_ws, &h->eval_ws_elems, need));
   altro::Eval16 p{};
   p.Grow = h->Grow; p.fvec = h->fvec; p.wd = h->wd; p.wf = h->wf; p.zmin = h->zmin; p.zmax = h->zmax; p.Zref = h->Zref;
   p.Acon = h->Acon; p.bcon = h->bcon; p.cmeta = h->cmeta; p.window = h->clock.args().window; p.imask = tab_imask(h);
@@ -2780,7 +2640,7 @@ int32_t altro_batch_restart_instances(altro_handle* h, const int32_t* which, con
     if (!h) return dev_null_handle("altro_batch_restart_instances");
     if (!which || !U) FAIL(h, ALTRO_ERR_INVALID_ARG, "altro_batch_restart_instances: which and U are required");
     HIPCHK(h, hipSetDevice(h->device));
-    DEV_WIDE(h, restart(which, X, U, false));
+    WIDE_FWD(h, restart(which, X, U, false));
     return restart_16(h, which, X, U, false);
   });
 }
@@ -2791,7 +2651,7 @@ int32_t altro_batch_restart_instances_dev(altro_handle* h, const int32_t* which,
     DEV_ARG(h, "which", which, B_, int32_t, false);
     DEV_ARG(h, "X", X, B_ * N_ * n_, double, true);
     DEV_ARG(h, "U", U, B_ * (N_ - 1) * m_, double, false);
-    DEV_WIDE(h, restart(which, X, U, true));
+    WIDE_FWD(h, restart(which, X, U, true));
     return restart_16(h, which, X, U, true);
   });
 }
@@ -2879,7 +2739,6 @@ int32_t altro_batch_signal_stream(altro_handle* h, void* consumer) {
 }
 #undef DEV_ENTER
 #undef DEV_ARG
-#undef DEV_WIDE
 
 int32_t altro_batch_get_stream(altro_handle* h, void** stream) {
   return guard(h, [&]() -> int32_t {

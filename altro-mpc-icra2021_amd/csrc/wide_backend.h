@@ -11,6 +11,7 @@
 
 #include "../../include/altro_batch.h"
 #include "device_io.h"
+#include "device_pool.h"
 #include "evaluate.h"
 #include "launch_ring.h"
 #include "policy.h"
@@ -132,6 +133,7 @@ struct WideBackend {
   altro::InstanceFlags flags;  // active mask and restart selection, [batch] (device_io.h)
   altro::EpisodeClock clock;   // per-instance episode clock, [batch] (device_io.h)
   std::string err;
+  altro::DevicePool pool;   // owns every device array below (device_pool.h); the members stay plain pointers
   // device
   double *A = nullptr, *Bm = nullptr, *f = nullptr, *wd = nullptr, *wf = nullptr, *zmin = nullptr, *zmax = nullptr;
   double *x0 = nullptr, *Xref = nullptr, *Uref = nullptr, *X = nullptr, *U = nullptr, *Lb = nullptr, *Lc = nullptr,
@@ -189,19 +191,7 @@ struct WideBackend {
   static bool supports(int n, int m) { return n >= 1 && m >= 1 && n <= kMaxN && m <= kMaxM; }
 
   int ensure_stage(size_t bytes) {
-    if (bytes <= stage_bytes) return ALTRO_OK;
-    if (stage) WCHK(hipFree(stage));
-    stage = nullptr;
-    stage_bytes = 0;
-    WCHK(hipMalloc(&stage, bytes));
-    stage_bytes = bytes;
-    return ALTRO_OK;
-  }
-
-  template <typename Tp>
-  int dalloc(Tp** p, size_t count, bool zero = true) {
-    WCHK(hipMalloc(p, (count ? count : 1) * sizeof(Tp)));
-    if (zero) WCHK(hipMemsetAsync(*p, 0, (count ? count : 1) * sizeof(Tp), stream));
+    WCHK(pool.reserve(reinterpret_cast<char**>(&stage), &stage_bytes, bytes));
     return ALTRO_OK;
   }
 
@@ -223,17 +213,21 @@ struct WideBackend {
     bench_ev.reserve(2);
     const size_t B = d.batch, N = d.N, n = d.n, m = d.m, z = n + m;
     if (B * 3 * N * 64 >= (1ull << 32)) WFAIL(ALTRO_ERR_UNSUPPORTED, "batch x horizon too large for one handle (active-set planes are addressed with 32-bit offsets): split the batch");
-    int rc;
-#define DA_(p, c) if ((rc = dalloc(&p, (c)))) return rc
-    DA_(wd, z); DA_(wf, n); DA_(zmin, z); DA_(zmax, z);
-    DA_(x0, B * n); DA_(X, B * 2 * N * n); DA_(U, B * 2 * (N - 1) * m); DA_(cur, B);
-    DA_(Lb, B * N * 2 * z); DA_(mu, B); DA_(Kg, B * (N - 1) * n * m); DA_(dg, B * (N - 1) * m); DA_(trash, B * 64); DA_(Qz, B * N * z); DA_(fac, m <= 16 ? B * N * wide_fac_size(m) : 1); DA_(bwst, B * 136); DA_(aset, B * 3 * N * 64);
-    DA_(iters, B); DA_(iters_outer, B); DA_(status, B); DA_(cost, B); DA_(cmax, B);
-    DA_(Jtrace, B * ALTRO_TRACE_LEN); DA_(ctrace, B * ALTRO_TRACE_LEN); DA_(atrace, B * ALTRO_TRACE_LEN);
-    DA_(n_backward, B); DA_(n_rollout, B); DA_(n_trials, B); DA_(n_solves, B); DA_(n_iters, B); DA_(n_ok, B); DA_(n_gconf, B); DA_(n_gs, B);
-    DA_(noise_w, kMaxN); DA_(noise_grp, kMaxN);
-    DA_(Lc, 1); DA_(AconT, 1); DA_(bcon, 1); DA_(ctype, 1); DA_(rowk0, 1); DA_(rowk1, 1); DA_(rowc0, 1); DA_(rowcp, 1); DA_(refusals, 1);
-#undef DA_
+    // every device array of the backend: (member, elements), zero-filled on the stream
+    const size_t T = ALTRO_TRACE_LEN;
+    const std::pair<double**, size_t> dbl[] = {
+        {&wd, z}, {&wf, n}, {&zmin, z}, {&zmax, z}, {&x0, B * n}, {&X, B * 2 * N * n}, {&U, B * 2 * (N - 1) * m}, {&Lb, B * N * 2 * z},
+        {&mu, B}, {&Kg, B * (N - 1) * n * m}, {&dg, B * (N - 1) * m}, {&trash, B * 64}, {&Qz, B * N * z},
+        {&fac, m <= 16 ? B * N * wide_fac_size(m) : 1}, {&cost, B}, {&cmax, B}, {&Jtrace, B * T}, {&ctrace, B * T}, {&atrace, B * T},
+        {&noise_w, kMaxN}, {&Lc, 1}, {&AconT, 1}, {&bcon, 1}};
+    const std::pair<int**, size_t> ints[] = {{&cur, B}, {&iters, B}, {&iters_outer, B}, {&status, B}, {&noise_grp, kMaxN},
+                                             {&ctype, 1}, {&rowk0, 1}, {&rowk1, 1}, {&rowc0, 1}, {&rowcp, 1}};
+    for (const auto& a : dbl) WCHK(pool.alloc(a.first, a.second, stream));
+    for (const auto& a : ints) WCHK(pool.alloc(a.first, a.second, stream));
+    for (long long** c : {&n_backward, &n_rollout, &n_trials, &n_solves, &n_iters, &n_ok, &n_gconf, &n_gs}) WCHK(pool.alloc(c, B, stream));
+    WCHK(pool.alloc(&bwst, B * 136, stream));
+    WCHK(pool.alloc(&aset, B * 3 * N * 64, stream));
+    WCHK(pool.alloc(&refusals, 1, stream));
     {
       std::vector<double> inf(z, INFINITY), ninf(z, -INFINITY), w(kMaxN, 0.01), m0(B, 1.0);
       WCHK(hipMemcpyAsync(zmax, inf.data(), z * sizeof(double), hipMemcpyHostToDevice, stream));
@@ -248,12 +242,7 @@ struct WideBackend {
   void destroy() {
     hipSetDevice(device);
     if (stream) hipStreamSynchronize(stream);
-    void* ptrs[] = {A, Bm, f, wd, wf, zmin, zmax, x0, Xref, Uref, X, U, Lb, Lc, mu, Kg, dg, trash, AconT, bcon, stage, cur, ctype,
-                    rowk0, rowk1, rowc0, rowcp, iters, iters_outer, status, noise_grp, cost, cmax, Jtrace, ctrace, atrace, noise, noise_w,
-                    n_backward, n_rollout, n_trials, n_solves, n_iters, n_ok, Xsave, Usave, Qz, n_gconf, n_gs, fac, bwst, aset,
-                    pn_ran, pn_failed, pn_dfail, pn_res, pn_dres0, pn_dres, pnE, pndv, pnLd, pnLo, pnvec, pntz, pnblk, pnnb, pnnst, pnrinfo, mlog, refusals, eval_ws};
-    for (void* p : ptrs)
-      if (p) hipFree(p);
+    pool.release_all();
     ring.destroy();
     flags.destroy();
     clock.destroy();
@@ -264,6 +253,16 @@ struct WideBackend {
     if (stream) hipStreamDestroy(stream);
   }
 
+  // tables A, Bm, f with room for `blocks_` blocks (the caller has synchronised the stream)
+  int alloc_dynamics(size_t blocks_) {
+    const size_t n = d.n, m = d.m;
+    dyn_table_blocks = 0;
+    WCHK(pool.alloc(&A, blocks_ * n * n, stream, false));
+    WCHK(pool.alloc(&Bm, blocks_ * n * m, stream, false));
+    WCHK(pool.alloc(&f, blocks_ * n, stream, false));
+    dyn_table_blocks = blocks_;
+    return ALTRO_OK;
+  }
   // blocks_per_instance knot blocks per instance (1: time-invariant)
   int upload_dynamics(const double* A_, const double* B_, const double* f_, size_t blocks_per_instance, int per_instance) {
     if (!A_ || !B_) return ALTRO_ERR_INVALID_ARG;
@@ -271,16 +270,11 @@ struct WideBackend {
     WCHK(hipStreamSynchronize(stream));
     const size_t n = d.n, m = d.m;
     const size_t blocks_ = (per_instance ? (size_t)d.batch : 1) * blocks_per_instance;
-    for (double** p : {&A, &Bm, &f})
-      if (*p) { WCHK(hipFree(*p)); *p = nullptr; }
-    WCHK(hipMalloc(&A, blocks_ * n * n * sizeof(double)));
-    WCHK(hipMalloc(&Bm, blocks_ * n * m * sizeof(double)));
-    WCHK(hipMalloc(&f, blocks_ * n * sizeof(double)));
+    if (int rc = alloc_dynamics(blocks_)) return rc;
     WCHK(hipMemcpy(A, A_, blocks_ * n * n * sizeof(double), hipMemcpyHostToDevice));
     WCHK(hipMemcpy(Bm, B_, blocks_ * n * m * sizeof(double), hipMemcpyHostToDevice));
     if (f_) WCHK(hipMemcpy(f, f_, blocks_ * n * sizeof(double), hipMemcpyHostToDevice));
     else WCHK(hipMemset(f, 0, blocks_ * n * sizeof(double)));
-    dyn_table_blocks = blocks_;
     dyn_per_instance = per_instance != 0;
     have_dyn = true;
     return ALTRO_OK;
@@ -294,13 +288,7 @@ struct WideBackend {
     const size_t blocks_ = (per_instance ? (size_t)d.batch : 1) * blocks_per_instance;
     if (blocks_ != dyn_table_blocks || !A || !Bm || !f) {
       WCHK(hipStreamSynchronize(stream));
-      for (double** p : {&A, &Bm, &f})
-        if (*p) { WCHK(hipFree(*p)); *p = nullptr; }
-      dyn_table_blocks = 0;
-      WCHK(hipMalloc(&A, blocks_ * n * n * sizeof(double)));
-      WCHK(hipMalloc(&Bm, blocks_ * n * m * sizeof(double)));
-      WCHK(hipMalloc(&f, blocks_ * n * sizeof(double)));
-      dyn_table_blocks = blocks_;
+      if (int rc = alloc_dynamics(blocks_)) return rc;
     }
     WCHK(hipMemcpyAsync(A, A_, blocks_ * n * n * sizeof(double), hipMemcpyDeviceToDevice, stream));
     WCHK(hipMemcpyAsync(Bm, B_, blocks_ * n * m * sizeof(double), hipMemcpyDeviceToDevice, stream));
@@ -365,13 +353,11 @@ struct WideBackend {
     if (!Qd || !Rd || !Qfd || !(dt > 0.0)) return ALTRO_ERR_INVALID_ARG;
     WCHK(hipSetDevice(device));
     const size_t n = d.n, m = d.m, z = nz();
-    if (rows > 1 && !w_big) {   // the shared arrays hold one row: room for B rows from now on
+    if ((rows > 1 && !w_big) || !wd || !wf) {   // the shared arrays hold one row: room for B rows from now on
       WCHK(hipStreamSynchronize(stream));
-      WCHK(hipFree(wd)); wd = nullptr;
-      WCHK(hipFree(wf)); wf = nullptr;
-      int rc;
-      if ((rc = dalloc(&wd, rows * z)) || (rc = dalloc(&wf, rows * n))) return rc;
-      w_big = true;
+      WCHK(pool.alloc(&wd, rows * z, stream));
+      WCHK(pool.alloc(&wf, rows * n, stream));
+      w_big = rows > 1;
     }
     std::vector<double> w(rows * z);
     for (size_t r = 0; r < rows; ++r) {
@@ -397,13 +383,11 @@ struct WideBackend {
     }
     gains_valid = false;
     WCHK(hipSetDevice(device));
-    if (rows > 1 && !b_big) {
+    if ((rows > 1 && !b_big) || !zmin || !zmax) {
       WCHK(hipStreamSynchronize(stream));
-      WCHK(hipFree(zmin)); zmin = nullptr;
-      WCHK(hipFree(zmax)); zmax = nullptr;
-      int rc;
-      if ((rc = dalloc(&zmin, rows * z)) || (rc = dalloc(&zmax, rows * z))) return rc;
-      b_big = true;
+      WCHK(pool.alloc(&zmin, rows * z, stream));
+      WCHK(pool.alloc(&zmax, rows * z, stream));
+      b_big = rows > 1;
     }
     WCHK(hipStreamSynchronize(stream));
     WCHK(hipMemcpy(zmin, zmin_, rows * z * sizeof(double), hipMemcpyHostToDevice));
@@ -518,17 +502,15 @@ struct WideBackend {
     WCHK(hipSetDevice(device));
     const size_t B = d.batch, z = nz();
     if (per_instance && !b_pi && B > 1) {
-      if (!b_big) {
+      if (!b_big) {   // the shared row goes through the host while the tables are replaced by ones of B rows
+        std::vector<double> r0(2 * z);
         WCHK(hipStreamSynchronize(stream));
-        double *nlo = nullptr, *nhi = nullptr;
-        int rc;
-        if ((rc = dalloc(&nlo, B * z, false))) return rc;
-        if ((rc = dalloc(&nhi, B * z, false))) { hipFree(nlo); return rc; }
-        WCHK(hipMemcpyAsync(nlo, zmin, z * sizeof(double), hipMemcpyDeviceToDevice, stream));
-        WCHK(hipMemcpyAsync(nhi, zmax, z * sizeof(double), hipMemcpyDeviceToDevice, stream));
-        WCHK(hipStreamSynchronize(stream));
-        WCHK(hipFree(zmin)); zmin = nlo;
-        WCHK(hipFree(zmax)); zmax = nhi;
+        WCHK(hipMemcpy(r0.data(), zmin, z * sizeof(double), hipMemcpyDeviceToHost));
+        WCHK(hipMemcpy(r0.data() + z, zmax, z * sizeof(double), hipMemcpyDeviceToHost));
+        WCHK(pool.alloc(&zmin, B * z, stream, false));
+        WCHK(pool.alloc(&zmax, B * z, stream, false));
+        WCHK(hipMemcpy(zmin, r0.data(), z * sizeof(double), hipMemcpyHostToDevice));
+        WCHK(hipMemcpy(zmax, r0.data() + z, z * sizeof(double), hipMemcpyHostToDevice));
         b_big = true;
       }
       const dim3 g((unsigned)((B * z + 255) / 256));
@@ -602,25 +584,15 @@ struct WideBackend {
           }
         }
       }
-    if (At.size() != acon_elems) {  // the table changed shape (a block with per-instance data arrived): reallocate
-      for (double** p : {&AconT, &bcon})
-        if (*p) { WCHK(hipFree(*p)); *p = nullptr; }
-      WCHK(hipMalloc(&AconT, (At.size() ? At.size() : 1) * sizeof(double)));
-      WCHK(hipMalloc(&bcon, (bc.size() ? bc.size() : 1) * sizeof(double)));
+    if (At.size() != acon_elems || !AconT || !bcon) {  // the table changed shape (a block with per-instance data arrived): reallocate
+      WCHK(pool.alloc(&AconT, At.size(), stream, false));
+      WCHK(pool.alloc(&bcon, bc.size(), stream, false));
       acon_elems = At.size();
     }
     if (!con_locked) {
-      for (void* p : {(void*)ctype, (void*)rowk0, (void*)rowk1, (void*)rowc0, (void*)rowcp, (void*)Lc})
-        if (p) WCHK(hipFree(p));
-      Lc = nullptr;
-      ctype = rowk0 = rowk1 = rowc0 = rowcp = nullptr;
-      WCHK(hipMalloc(&ctype, ct.size() * sizeof(int)));
-      WCHK(hipMalloc(&rowk0, P * sizeof(int)));
-      WCHK(hipMalloc(&rowk1, P * sizeof(int)));
-      WCHK(hipMalloc(&rowc0, P * sizeof(int)));
-      WCHK(hipMalloc(&rowcp, P * sizeof(int)));
-      WCHK(hipMalloc(&Lc, (size_t)d.batch * N * P * sizeof(double)));
-      WCHK(hipMemset(Lc, 0, (size_t)d.batch * N * P * sizeof(double)));
+      WCHK(pool.alloc(&ctype, ct.size(), stream, false));
+      for (int** p : {&rowk0, &rowk1, &rowc0, &rowcp}) WCHK(pool.alloc(p, P, stream, false));
+      WCHK(pool.alloc(&Lc, (size_t)d.batch * N * P, stream));
     }
     WCHK(hipMemcpy(AconT, At.data(), At.size() * sizeof(double), hipMemcpyHostToDevice));
     WCHK(hipMemcpy(bcon, bc.data(), bc.size() * sizeof(double), hipMemcpyHostToDevice));
@@ -659,17 +631,21 @@ struct WideBackend {
     WCHK(hipMemcpyAsync(x, x0, (size_t)d.batch * d.n * sizeof(double), hipMemcpyDeviceToDevice, stream));
     return ALTRO_OK;
   }
+  // Xref, Uref for a track of Nt_ knots (the caller has synchronised the stream); no reference while they do not exist
+  int alloc_reference(int Nt_) {
+    Nt = 0;
+    have_ref = false;
+    WCHK(pool.alloc(&Xref, (size_t)d.batch * Nt_ * d.n, stream, false));
+    WCHK(pool.alloc(&Uref, (size_t)d.batch * (Nt_ - 1) * d.m, stream, false));
+    Nt = Nt_;
+    return ALTRO_OK;
+  }
   int set_reference_dev(const double* Xr, const double* Ur) {
     WCHK(hipSetDevice(device));
     const int Nt_ = d.N;
-    if (Nt_ != Nt || !Xref) {   // another window length than the stored one: reallocate, as the host call does
+    if (Nt_ != Nt || !Xref || !Uref) {   // another window length than the stored one: reallocate, as the host call does
       WCHK(hipStreamSynchronize(stream));
-      if (Xref) WCHK(hipFree(Xref));
-      if (Uref) WCHK(hipFree(Uref));
-      Xref = Uref = nullptr;
-      WCHK(hipMalloc(&Xref, (size_t)d.batch * Nt_ * d.n * sizeof(double)));
-      WCHK(hipMalloc(&Uref, (size_t)d.batch * (Nt_ - 1) * d.m * sizeof(double)));
-      Nt = Nt_;
+      if (int rc = alloc_reference(Nt_)) return rc;
     }
     WCHK(hipMemcpyAsync(Xref, Xr, (size_t)d.batch * Nt * d.n * sizeof(double), hipMemcpyDeviceToDevice, stream));
     WCHK(hipMemcpyAsync(Uref, Ur, (size_t)d.batch * (Nt - 1) * d.m * sizeof(double), hipMemcpyDeviceToDevice, stream));
@@ -685,13 +661,8 @@ struct WideBackend {
   int set_ref_common(const double* Xr, const double* Ur, int Nt_) {
     WCHK(hipSetDevice(device));
     WCHK(hipStreamSynchronize(stream));
-    if (Nt_ != Nt || !Xref) {
-      if (Xref) WCHK(hipFree(Xref));
-      if (Uref) WCHK(hipFree(Uref));
-      Xref = Uref = nullptr;
-      WCHK(hipMalloc(&Xref, (size_t)d.batch * Nt_ * d.n * sizeof(double)));
-      WCHK(hipMalloc(&Uref, (size_t)d.batch * (Nt_ - 1) * d.m * sizeof(double)));
-      Nt = Nt_;
+    if (Nt_ != Nt || !Xref || !Uref) {
+      if (int rc = alloc_reference(Nt_)) return rc;
     }
     WCHK(hipMemcpy(Xref, Xr, (size_t)d.batch * Nt * d.n * sizeof(double), hipMemcpyHostToDevice));
     WCHK(hipMemcpy(Uref, Ur, (size_t)d.batch * (Nt - 1) * d.m * sizeof(double), hipMemcpyHostToDevice));
@@ -779,13 +750,7 @@ struct WideBackend {
     if (int rc = pack_constraints()) return rc;   // (what the next solve would do first; a no-op once the tables are packed)
     const size_t R = (size_t)d.batch * ncand, lx = (size_t)d.N * d.n, lu = (size_t)(d.N - 1) * d.m;
     const size_t need = !Ud ? R * (lx + lu) : (!Xd && !Xout) ? R * lx : 0;
-    if (need > eval_ws_elems) {
-      if (eval_ws) WCHK(hipFree(eval_ws));
-      eval_ws = nullptr;
-      eval_ws_elems = 0;
-      WCHK(hipMalloc(&eval_ws, need * sizeof(double)));
-      eval_ws_elems = need;
-    }
+    if (need) WCHK(pool.reserve(&eval_ws, &eval_ws_elems, need));
     altro::EvalW p{};
     p.A = A; p.Bm = Bm; p.f = f; p.wd = wd; p.wf = wf; p.zmin = zmin; p.zmax = zmax; p.Xref = Xref; p.Uref = Uref;
     p.AconT = AconT; p.bcon = bcon; p.ctype = ctype; p.rowc0 = rowc0; p.rowcp = rowcp; p.window = clock.args().window;
@@ -872,10 +837,9 @@ struct WideBackend {
   // its slot of the timing ring
   int polish_prepare() {
     const size_t B = d.batch, N = d.N, z = nz();
-    if (!pn_ran) {
-      int rc;
-      if ((rc = dalloc(&pn_ran, B)) || (rc = dalloc(&pn_failed, B)) || (rc = dalloc(&pn_dfail, B)) || (rc = dalloc(&pn_res, B)) ||
-          (rc = dalloc(&pn_dres0, B)) || (rc = dalloc(&pn_dres, B))) return rc;
+    if (!pn_ran) {   // (pn_ran last: it exists only once the other five do)
+      for (int** p : {&pn_failed, &pn_dfail, &pn_ran}) WCHK(pool.alloc(p, B, stream));
+      for (double** p : {&pn_res, &pn_dres0, &pn_dres}) WCHK(pool.alloc(p, B, stream));
     }
     int sides = 0;   // from the host copy of the BOX's finite sides (common to every instance)
     if (box_k1 >= box_k0)
@@ -883,20 +847,18 @@ struct WideBackend {
     const int bm = 2 * d.n + sides + Pn;
     const int slots = (int)(B < 64 ? B : 64);
     if (bm != pn_bm || slots != pn_slots || !pnE) {
-      void** ws[] = {(void**)&pnE, (void**)&pndv, (void**)&pnLd, (void**)&pnLo, (void**)&pnvec, (void**)&pntz, (void**)&pnblk,
-                     (void**)&pnnb, (void**)&pnnst, (void**)&pnrinfo};
-      for (void** q : ws) if (*q) { WCHK(hipFree(*q)); *q = nullptr; }
       const size_t S = slots, b = bm;
-      WCHK(hipMalloc(&pnE, S * N * b * z * sizeof(double)));
-      WCHK(hipMalloc(&pndv, S * N * b * sizeof(double)));
-      WCHK(hipMalloc(&pnLd, S * N * b * b * sizeof(double)));
-      WCHK(hipMalloc(&pnLo, S * N * b * b * sizeof(double)));
-      WCHK(hipMalloc(&pnvec, S * 6 * N * b * sizeof(double)));
-      WCHK(hipMalloc(&pntz, S * 3 * N * z * sizeof(double)));
-      WCHK(hipMalloc(&pnblk, S * (2 * b * (b + 1) + 4 * b) * sizeof(double)));
-      WCHK(hipMalloc(&pnnb, S * N * sizeof(int)));
-      WCHK(hipMalloc(&pnnst, S * N * sizeof(int)));
-      WCHK(hipMalloc(&pnrinfo, S * N * b * sizeof(int)));
+      pn_bm = pn_slots = 0;   // (until every array of the workspace exists)
+      WCHK(pool.alloc(&pnE, S * N * b * z, stream, false));
+      WCHK(pool.alloc(&pndv, S * N * b, stream, false));
+      WCHK(pool.alloc(&pnLd, S * N * b * b, stream, false));
+      WCHK(pool.alloc(&pnLo, S * N * b * b, stream, false));
+      WCHK(pool.alloc(&pnvec, S * 6 * N * b, stream, false));
+      WCHK(pool.alloc(&pntz, S * 3 * N * z, stream, false));
+      WCHK(pool.alloc(&pnblk, S * (2 * b * (b + 1) + 4 * b), stream, false));
+      WCHK(pool.alloc(&pnnb, S * N, stream, false));
+      WCHK(pool.alloc(&pnnst, S * N, stream, false));
+      WCHK(pool.alloc(&pnrinfo, S * N * b, stream, false));
       pn_bm = bm;
       pn_slots = slots;
     }
@@ -1048,8 +1010,8 @@ struct WideBackend {
     if (clock.on) WFAIL(ALTRO_ERR_STATE, "altro_batch_benchmark_solve restores and repeats whole batches: clear the episode clock first");
     WCHK(hipSetDevice(device));
     const size_t B = d.batch, lx = (size_t)d.N * d.n, lu = (size_t)(d.N - 1) * d.m;
-    if (!Xsave) WCHK(hipMalloc(&Xsave, B * lx * sizeof(double)));
-    if (!Usave) WCHK(hipMalloc(&Usave, B * lu * sizeof(double)));
+    if (!Xsave) WCHK(pool.alloc(&Xsave, B * lx, stream, false));
+    if (!Usave) WCHK(pool.alloc(&Usave, B * lu, stream, false));
     while (bench_ev.size() < 2) {
       hipEvent_t e;
       WCHK(hipEventCreate(&e));
@@ -1214,10 +1176,8 @@ struct WideBackend {
   int mpc_set_noise(const double* nzv, int steps) {
     if (!nzv || steps < 1) return ALTRO_ERR_INVALID_ARG;
     WCHK(hipSetDevice(device));
-    if (noise) WCHK(hipFree(noise));
-    noise = nullptr;
     const size_t cnt = (size_t)steps * d.batch * d.n;
-    WCHK(hipMalloc(&noise, cnt * sizeof(double)));
+    WCHK(pool.alloc(&noise, cnt, stream, false));
     WCHK(hipMemcpy(noise, nzv, cnt * sizeof(double), hipMemcpyHostToDevice));
     noise_steps = steps;
     return ALTRO_OK;
@@ -1242,13 +1202,12 @@ struct WideBackend {
     if (capacity_steps < 0) WFAIL(ALTRO_ERR_INVALID_ARG, "negative log capacity");
     WCHK(hipSetDevice(device));
     WCHK(hipStreamSynchronize(stream));  // a launch in flight may still be writing the old log
-    if (mlog) WCHK(hipFree(mlog));
-    mlog = nullptr;
     mlog_cap = 0;
+    WCHK(pool.release(&mlog));
     if (capacity_steps == 0) return ALTRO_OK;
-    const size_t bytes = (size_t)capacity_steps * (size_t)d.batch * mlog_rec() * sizeof(double);
-    WCHK(hipMalloc(&mlog, bytes));
-    WCHK(hipMemsetAsync(mlog, 0xFF, bytes, stream));  // never written: -1 / NaN
+    const size_t elems = (size_t)capacity_steps * (size_t)d.batch * mlog_rec();
+    WCHK(pool.alloc(&mlog, elems, stream, false));
+    WCHK(hipMemsetAsync(mlog, 0xFF, elems * sizeof(double), stream));  // never written: -1 / NaN
     mlog_cap = capacity_steps;
     return ALTRO_OK;
   }
