@@ -23,7 +23,8 @@ Device-resident I/O: set_initial_state, update_trajectory, initial_controls, set
 set_bounds also take torch tensors that
 live on the solver's GPU (the altro_*_dev entry points: nothing crosses PCIe, nothing synchronises), and states, controls
 and first_knot write into such tensors; eval_policy (the feedback policy between two ticks), get_gains_dev, evaluate and
-rollout (candidate trajectories scored against the next solve's problem) read and write them.  A GPU tensor is never copied, cast or moved behind the caller's back: float64,
+rollout (candidate trajectories scored against the next solve's problem) read and write them.  warm_start scores candidate
+controls the same way and installs the best as the next solve's initial trajectory.  A GPU tensor is never copied, cast or moved behind the caller's back: float64,
 contiguous, on the solver's device and of the exact shape, or ValueError.  Matrices keep their natural (row, col) indexing;
 since the C-ABI reads column-major blocks, a dynamics tensor must be STORED column-major, i.e. `At.transpose(-1, -2)` of a
 contiguous tensor At that holds the transposed blocks.  Every tensor call is ordered against torch's current stream
@@ -1071,4 +1072,81 @@ def rollout(solver, U, x0=None, out=None):
     if out is None:
         out = np.empty(shp)
     evaluate(solver, U, x0=x0, out=(None, np.empty(shp[:-2]), None), Xout=out)
+    return out
+
+
+def _warm_start_args(solver, U, rho, include_current):
+    """(ncand, shape U must have as (B, ncand, N-1, m) or (B, N-1, m), shape of J / c_max); refuses a bad rho here: the library
+    is not called with one"""
+    B, N, m = solver.B, solver.N, solver.m
+    if U is None:
+        raise ValueError("warm_start: U is required")
+    rho = float(rho)
+    if not (rho >= 0.0) or rho == float("inf"):
+        raise ValueError(f"warm_start: rho = {rho}: it must be finite and not negative")
+    shp = tuple(int(k) for k in U.shape)
+    if len(shp) == 3:
+        ncand = 1
+    elif len(shp) == 4 and shp[1] >= 1:
+        ncand = shp[1]
+    else:
+        raise ValueError(f"warm_start: U: shape {shp}, expected ({B}, {N - 1}, {m}) or ({B}, ncand, {N - 1}, {m})")
+    want = (B, N - 1, m) if len(shp) == 3 else (B, ncand, N - 1, m)
+    return ncand, want, (B, ncand + (1 if include_current else 0)), rho
+
+
+def _warm_start_dev(solver, U, rho=0.0, include_current=True, out=None):
+    """device form of warm_start: every tensor is validated (shape, dtype, strides, device) before the library is called"""
+    ncand, su, lead, rho = _warm_start_args(solver, U, rho, include_current)
+    check_device_tensor(U, su, solver.device, "U")
+    if out is None:
+        import torch
+        dev = torch.device("cuda", solver.device)
+        out = (torch.empty((solver.B,), dtype=torch.int32, device=dev),) + tuple(torch.empty(lead, dtype=torch.float64, device=dev) for _ in range(2))
+    out = tuple(out)
+    if len(out) != 3:
+        raise ValueError("warm_start: out is (chosen, J, c_max); any may be None")
+    if out[0] is not None:
+        check_device_tensor(out[0], (solver.B,), solver.device, "chosen", dtype="torch.int32")
+    for o, nm in zip(out[1:], ("J", "c_max")):
+        if o is not None:
+            check_device_tensor(o, lead, solver.device, nm)
+    solver._chk(solver._L.altro_batch_warm_start_dev(solver.h, ncand, _addr(U), rho, 1 if include_current else 0, _addr(out[0]), _addr(out[1]),
+                                                     _addr(out[2])))
+    return out
+
+
+def warm_start(solver, U, rho=0.0, include_current=True, out=None):
+    """Warm start from the best of several candidates (altro_batch_warm_start / _dev): every candidate control sequence is rolled
+    out from the solver's initial state and scored as evaluate's rollout form scores it, merit = fma(rho, c_max, J); per
+    instance the lowest merit wins -- the trajectory the solver holds competes as the incumbent when include_current (last
+    column, wins ties; among candidates the lowest index wins ties; NaN / Inf never win) -- and the winner's controls and
+    rolled-out states become the initial trajectory of the next solve, as initial_controls / set_initial_trajectory would
+    leave them.  Duals, penalties, statistics and stored gains stay.  While a mask is set (set_active) inactive instances
+    are scored but left as they are.
+    U (B, ncand, N-1, m), or (B, N-1, m) for one candidate.  Returns (chosen, J, c_max): chosen (B,) int32 -- 0 .. ncand-1 that
+    candidate, ncand the incumbent, -1 nothing had a finite merit (instance untouched), -2 inactive; J, c_max
+    (B, ncand + include_current).  With GPU tensors (float64, contiguous; chosen int32) the call is stream-ordered and nothing
+    synchronises; out = (chosen, J, c_max) are tensors to write into (any may be None; default: three new ones).  With numpy
+    the host twin runs: the same bytes."""
+    args = (U,) + (tuple(out) if out is not None else ())
+    if any(_on_gpu(a) for a in args):
+        if not all(a is None or _on_gpu(a) for a in args):
+            raise ValueError("warm_start: U and out must all be GPU tensors (or None), or none of them")
+        with _bracket(solver):
+            return _warm_start_dev(solver, U, rho, include_current, out)
+    U = None if U is None else _c(U)
+    ncand, su, lead, rho = _warm_start_args(solver, U, rho, include_current)
+    if U.shape != su:
+        raise ValueError(f"warm_start: U: shape {U.shape}, expected {su}")
+    if out is None:
+        out = (np.empty(solver.B, dtype=np.int32), np.empty(lead), np.empty(lead))
+    out = tuple(out)
+    if len(out) != 3:
+        raise ValueError("warm_start: out is (chosen, J, c_max); any may be None")
+    for o, shp, dt, nm in zip(out, ((solver.B,), lead, lead), (np.int32, np.float64, np.float64), ("chosen", "J", "c_max")):
+        if o is not None and not (isinstance(o, np.ndarray) and o.dtype == dt and o.flags.c_contiguous and o.shape == shp):
+            raise ValueError(f"warm_start: {nm} must be a C-contiguous {np.dtype(dt).name} array of shape {shp}")
+    ch = None if out[0] is None else out[0].ctypes.data_as(_IP)
+    solver._chk(solver._L.altro_batch_warm_start(solver.h, ncand, _p(U), rho, 1 if include_current else 0, ch, _p(out[1]), _p(out[2])))
     return out

@@ -21,6 +21,7 @@
 #include "pn_polish.h"
 #include "policy.h"
 #include "solve_dpp16.h"
+#include "warm_start.h"
 // The one-wave-per-instance kernels are compiled in translation units of their own (wide_inst.hip, _lib.build) and only
 // declared here; -DALTRO_WIDE_SINGLE_TU (and the development builds) instantiate them in this unit as before.
 #if !defined(ALTRO_WIDE_SINGLE_TU) && !defined(ALTRO_DEV_HEADLINE_ONLY)
@@ -124,6 +125,8 @@ struct altro_handle {
   double* stage = nullptr;  // device staging buffer for host<->device layout conversion
   double* eval_ws = nullptr;   // altro_batch_evaluate(_dev): states of a rollout without Xout, or the gathered own trajectory (grow-only)
   size_t eval_ws_elems = 0;
+  double* ws_merit = nullptr;  // altro_batch_warm_start(_dev): J, c_max [batch * (ncand + 1)] each when the caller passes none (grow-only)
+  size_t ws_merit_elems = 0;
   altro::StreamLink link;   // events of altro_batch_wait_stream / altro_batch_signal_stream (device_io.h)
   altro::InstanceFlags flags;  // active mask and restart selection of a 16-lane handle, [Bp] (device_io.h; a wide handle's live in its backend)
   altro::EpisodeClock clock;   // per-instance episode clock of a 16-lane handle, [Bp] (device_io.h; a wide handle's lives in its backend)
@@ -2568,6 +2571,97 @@ int32_t altro_batch_evaluate(altro_handle* h, int32_t ncand, const double* U, co
     if (c_max) HIPCHK(h, hipMemcpyAsync(c_max, sc, R * sizeof(double), hipMemcpyDeviceToHost, st));
     if (defect) HIPCHK(h, hipMemcpyAsync(defect, sd, R * sizeof(double), hipMemcpyDeviceToHost, st));
     if (Xout) HIPCHK(h, hipMemcpyAsync(Xout, sXo, cx * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    return ALTRO_OK;
+  });
+}
+
+// ---- warm start from the best of several candidates (kernels in warm_start.h)
+// the argument rules both forms share, checked before anything else
+static int warm_start_rules(altro_handle* h, const char* fn, int32_t ncand, const double* U, double rho, int32_t include_current) {
+  const std::string f(fn);
+  if (!U) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": U is required");
+  if (ncand < 1) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": ncand must be at least 1");
+  if (!(rho >= 0.0) || std::isinf(rho)) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": rho must be finite and not negative");
+  if (include_current != 0 && include_current != 1) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": include_current must be 0 or 1");
+  return ALTRO_OK;
+}
+
+// U, chosen, J, c_max: device arrays (the caller's, validated; or the staged copies of the host twin).  Enqueues the scoring
+// kernel, then the select-and-install kernel; allocates only when J or c_max is null and the merit workspace has to grow.
+static int warm_start_launch(altro_handle* h, int32_t ncand, const double* U, double rho, int32_t inc, int32_t* chosen, double* J,
+                             double* c_max) {
+  if (h->wide) {
+    const int rc = h->wide->warm_start_dev(ncand, U, rho, inc, chosen, J, c_max);
+    if (rc) h->err = h->wide->err;
+    return rc;
+  }
+  int rc = check_ready(h);
+  if (rc) return rc;
+  if (!h->clock.on && h->kref + h->d.N > h->Nt) FAIL(h, ALTRO_ERR_STATE, "reference window runs past the end of the stored trajectory");
+  if ((rc = pack_constraints(h))) return rc;   // (what the next solve would do first; a no-op once the tables are packed)
+  const size_t B = h->d.batch, N = h->d.N, n = h->d.n, m = h->d.m;
+  const size_t R = B * (size_t)(ncand + inc);
+  if (!J || !c_max) {
+    HIPCHK(h, h->pool.reserve(&h->ws_merit, &h->ws_merit_elems, 2 * R));
+    if (!J) J = h->ws_merit;
+    if (!c_max) c_max = h->ws_merit + R;
+  }
+  altro::Eval16 p{};
+  p.Grow = h->Grow; p.fvec = h->fvec; p.wd = h->wd; p.wf = h->wf; p.zmin = h->zmin; p.zmax = h->zmax; p.Zref = h->Zref;
+  p.Acon = h->Acon; p.bcon = h->bcon; p.cmeta = h->cmeta; p.window = h->clock.args().window; p.imask = tab_imask(h);
+  p.con_istride = h->con_per_instance ? N * LW * LW : 0; p.ncrows = h->ncrows;
+  p.N = (int)N; p.Nt = h->Nt; p.n = (int)n; p.m = (int)m; p.kref = h->kref; p.box_k0 = h->box_k0; p.box_k1 = h->box_k1;
+  const size_t plane = N * (size_t)LW;
+  const size_t rows = (R + 3) & ~(size_t)3;   // whole waves of four rows
+  hipLaunchKernelGGL(altro::k_ws_score16, grid_for(rows * LW), dim3(256), 0, h->stream, J, c_max, U, h->Z, h->cur, plane, h->x0, p, (int)ncand,
+                     (int)inc, R, rows);
+  HIPCHK(h, hipGetLastError());
+  const size_t slots = ((size_t)h->Bp + 3) & ~(size_t)3;
+  hipLaunchKernelGGL(altro::k_ws_install16, grid_for(slots * LW), dim3(256), 0, h->stream, chosen, J, c_max, U, h->Z, h->cur, plane, h->x0,
+                     h->flags.mask(), p, (int)ncand, (int)inc, rho, (int)B, h->Bp, slots);
+  HIPCHK(h, hipGetLastError());
+  return ALTRO_OK;
+}
+
+int32_t altro_batch_warm_start_dev(altro_handle* h, int32_t ncand, const double* U, double rho, int32_t include_current, int32_t* chosen,
+                                   double* J, double* c_max) {
+  return guard(h, [&]() -> int32_t {
+    DEV_ENTER(h, "altro_batch_warm_start_dev");
+    if (int rc = warm_start_rules(h, fn_, ncand, U, rho, include_current)) return rc;
+    const size_t R1 = B_ * (size_t)(ncand + include_current);
+    DEV_ARG(h, "U", U, B_ * (size_t)ncand * (N_ - 1) * m_, double, false);
+    DEV_ARG(h, "chosen", chosen, B_, int32_t, true);
+    DEV_ARG(h, "J", J, R1, double, true);
+    DEV_ARG(h, "c_max", c_max, R1, double, true);
+    return warm_start_launch(h, ncand, U, rho, include_current, chosen, J, c_max);
+  });
+}
+
+// The host twin: U goes through the staging buffer, the SAME kernels run on the staged copies and the outputs come back --
+// the bytes are those of the `_dev` call by construction.
+int32_t altro_batch_warm_start(altro_handle* h, int32_t ncand, const double* U, double rho, int32_t include_current, int32_t* chosen,
+                               double* J, double* c_max) {
+  return guard(h, [&]() -> int32_t {
+    if (!h) return dev_null_handle("altro_batch_warm_start");
+    if (int rc = warm_start_rules(h, "altro_batch_warm_start", ncand, U, rho, include_current)) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t B = h->d.batch, N = h->d.N, m = h->d.m;
+    const size_t R1 = B * (size_t)(ncand + include_current), cu = B * (size_t)ncand * (N - 1) * m;
+    const size_t bytes = (2 * R1 + cu) * sizeof(double) + B * sizeof(int32_t);
+    if (int rc = h->wide ? h->wide->ensure_stage(bytes) : ensure_stage(h, bytes)) {
+      if (h->wide) h->err = h->wide->err;
+      return rc;
+    }
+    const hipStream_t st = h->wide ? h->wide->stream : h->stream;
+    double* sJ = h->wide ? h->wide->stage : h->stage;
+    double *sc = sJ + R1, *sU = sc + R1;
+    int32_t* sw = reinterpret_cast<int32_t*>(sU + cu);
+    HIPCHK(h, hipMemcpyAsync(sU, U, cu * sizeof(double), hipMemcpyHostToDevice, st));
+    if (int rc = warm_start_launch(h, ncand, sU, rho, include_current, sw, sJ, sc)) return rc;
+    if (chosen) HIPCHK(h, hipMemcpyAsync(chosen, sw, B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (J) HIPCHK(h, hipMemcpyAsync(J, sJ, R1 * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (c_max) HIPCHK(h, hipMemcpyAsync(c_max, sc, R1 * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipStreamSynchronize(st));
     return ALTRO_OK;
   });

@@ -13,6 +13,7 @@
 #include "device_io.h"
 #include "device_pool.h"
 #include "evaluate.h"
+#include "warm_start.h"
 #include "launch_ring.h"
 #include "policy.h"
 #include "solve_wide.h"
@@ -161,6 +162,8 @@ struct WideBackend {
   size_t stage_bytes = 0;
   double* eval_ws = nullptr;   // altro_batch_evaluate(_dev): states of a rollout without Xout, or the gathered own trajectory (grow-only)
   size_t eval_ws_elems = 0;
+  double* ws_merit = nullptr;  // altro_batch_warm_start(_dev): J, c_max [batch * (ncand + 1)] each when the caller passes none (grow-only)
+  size_t ws_merit_elems = 0;
   int Nt = 0, kref = 0, noise_steps = 0, noise_mode = 0, mpc_shift = 1;
   double* mlog = nullptr;  // per-step log of the MPC loop (mpc_log.h): [mlog_cap][B][n + m + MLOG_TAIL]; null: off
   int mlog_cap = 0;
@@ -774,6 +777,39 @@ struct WideBackend {
       given = 0;
     }
     hipLaunchKernelGGL(altro::k_eval_score_wide, grid, block, (dd && given) ? lds : 0, stream, Jd, cd, dd, Xd, Ud, p, ncand, R, given);
+    WCHK(hipGetLastError());
+    return ALTRO_OK;
+  }
+  // altro_batch_warm_start_dev (warm_start.h; pointers and argument rules checked by the caller, the host twin passes staged
+  // copies): the fused rollout-and-score kernel over batch * (ncand + inc) waves, then select-and-install over batch waves.
+  // Reads what the next solve would read; writes the caller's outputs, ws_merit and plane cur[b] of X / U.
+  int warm_start_dev(int ncand, const double* Ud, double rho, int inc, int32_t* chosen, double* Jd, double* cd) {
+    WCHK(hipSetDevice(device));
+    if (!have_dyn) WFAIL(ALTRO_ERR_STATE, "altro_batch_set_dynamics has not been called");
+    if (!have_cost) WFAIL(ALTRO_ERR_STATE, "altro_batch_set_tracking_cost has not been called");
+    if (!have_ref) WFAIL(ALTRO_ERR_STATE, "no reference trajectory (altro_batch_set_reference / altro_mpc_set_track)");
+    if (!clock.on && kref + d.N > Nt) WFAIL(ALTRO_ERR_STATE, "reference window runs past the end of the stored trajectory");
+    if (!clock.on && !dyn_covers(kref)) WFAIL(ALTRO_ERR_STATE, "the dynamics track ends before the window");
+    if (int rc = pack_constraints()) return rc;   // (what the next solve would do first; a no-op once the tables are packed)
+    const size_t R = (size_t)d.batch * (size_t)(ncand + inc);
+    if (!Jd || !cd) {
+      WCHK(pool.reserve(&ws_merit, &ws_merit_elems, 2 * R));
+      if (!Jd) Jd = ws_merit;
+      if (!cd) cd = ws_merit + R;
+    }
+    altro::EvalW p{};
+    p.A = A; p.Bm = Bm; p.f = f; p.wd = wd; p.wf = wf; p.zmin = zmin; p.zmax = zmax; p.Xref = Xref; p.Uref = Uref;
+    p.AconT = AconT; p.bcon = bcon; p.ctype = ctype; p.rowc0 = rowc0; p.rowcp = rowcp; p.window = clock.args().window;
+    p.con_istride = con_per_instance ? (size_t)d.N * nz() * Pn : 0;
+    p.bcon_istride = con_per_instance ? (size_t)d.N * Pn : 0;
+    p.w_pi = w_pi; p.b_pi = b_pi; p.ltv = ltv; p.dyn_pi = dyn_per_instance; p.dyn_blocks = dyn_blocks; p.dyn_stride = dyn_step_stride;
+    p.Pn = Pn; p.N = d.N; p.Nt = Nt; p.n = d.n; p.m = d.m; p.kref = kref; p.box_k0 = box_k0; p.box_k1 = box_k1;
+    p.lds_dyn = altro::evalw_lds_fits(d.n, d.m, ltv) ? 1 : 0;
+    const size_t lds = p.lds_dyn ? 4 * altro::evalw_lds_doubles(d.n, d.m) * sizeof(double) : 0;
+    hipLaunchKernelGGL(altro::k_ws_score_wide, dim3((unsigned)((R * 64 + 255) / 256)), dim3(256), lds, stream, Jd, cd, Ud, U, cur, x0, p, ncand, inc, R);
+    WCHK(hipGetLastError());
+    hipLaunchKernelGGL(altro::k_ws_install_wide, dim3((unsigned)(((size_t)d.batch * 64 + 255) / 256)), dim3(256), lds, stream, chosen, Jd, cd, Ud, X, U,
+                       cur, x0, flags.mask(), p, ncand, inc, rho, (size_t)d.batch);
     WCHK(hipGetLastError());
     return ALTRO_OK;
   }

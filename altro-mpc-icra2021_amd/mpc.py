@@ -262,7 +262,7 @@ class ExternalMPC:
         self.i = 0
 
     def tick(self, x0, Xref=None, Uref=None, dynamics=None, out=None, active=None, restart=None, U_restart=None,
-             constraint_data=None, bounds=None):
+             constraint_data=None, bounds=None, candidates=None, candidate_rho=0.0):
         """x0 (B, n); Xref (B, N, n) and Uref (B, N-1, m): the new reference window (both or neither); dynamics: an
         api.LinearModel of column-major-stored tensors (api module docstring) -- all GPU tensors on the solver's device.
         active (B,) int32: the instances this tick shifts and solves; it stays set as the solver's mask (api.set_active).
@@ -274,12 +274,18 @@ class ExternalMPC:
         may be None), bounds (zmin, zmax): new rows of the BOX -- GPU tensors (api.update_constraint_data / api.set_bounds),
         applied after the primal shift and before the dual shift, the order of the reference's grasp loop
         (grasp_mpc.jl:60-75).
+        candidates (B, ncand, N-1, m) or (B, N-1, m): control sequences that compete with the shifted solution for this tick's
+        warm start under merit = J + candidate_rho * c_max (api.warm_start with the incumbent included, so a tick never starts
+        worse than the shifted solution under that merit) -- after this tick's setters, shift, constraint data and final
+        mask, immediately before the solve.
         Returns (u0, x1, status, iterations) as api.first_knot does (out: tensors to write into)."""
         s = self.solver
         if not api._on_gpu(x0):
             raise ValueError("ExternalMPC.tick takes GPU tensors; the numpy loop is api.set_initial_state / shift_fill / solve")
         if (Xref is None) != (Uref is None):
             raise ValueError("tick: give Xref and Uref together")
+        if candidates is not None:   # refused before anything of this tick is enqueued
+            api.check_device_tensor(candidates, api._warm_start_args(s, candidates, candidate_rho, True)[1], s.device, "candidates")
         shift_mask = None
         if restart is not None:
             if U_restart is None:
@@ -317,6 +323,8 @@ class ExternalMPC:
                 api._set_active_dev(s, active)
             elif shift_mask is not None:     # no mask given: the shift's was this tick's own
                 api.set_active(s, None)
+            if candidates is not None:
+                api._warm_start_dev(s, candidates, candidate_rho, True, (None, None, None))
             api.solve_async(s)
             res = api._first_knot_dev(s, out)
         finally:
@@ -337,6 +345,12 @@ class ExternalMPC:
         """(J, c_max, defect) of candidate trajectories against the problem the next tick's solve would see once the solver's
         stream reaches this point (api.evaluate): a pass-through, GPU tensors or numpy."""
         return api.evaluate(self.solver, U, X=X, x0=x0, out=out, Xout=Xout)
+
+    def warm_start(self, U, rho=0.0, include_current=True, out=None):
+        """(chosen, J, c_max) of api.warm_start: the best of the candidates U (and the trajectory held, when include_current)
+        becomes the initial trajectory of the next tick's solve once the solver's stream reaches this point: a pass-through,
+        GPU tensors or numpy."""
+        return api.warm_start(self.solver, U, rho=rho, include_current=include_current, out=out)
 
     def _constraints_dev(self, constraint_data, bounds):
         s = self.solver

@@ -537,8 +537,8 @@ int32_t altro_batch_get_gains_dev(altro_handle* h, double* K, double* d);
  * (simple_rocket.jl:198-200: the plain objective, of the solver's trajectory and of ECOS's), max_violation(...) and
  * dynamics_violation(prob, X, U) (simple_rocket.jl:191,208-216).  A caller that holds several candidate control sequences per
  * instance -- the shifted previous solution, the reference controls, a learned guess -- has them scored against the problem
- * the next altro_batch_solve would see at that point of the stream, takes an argmin and installs the winner with
- * altro_batch_set_initial_trajectory_dev.
+ * the next altro_batch_solve would see at that point of the stream.  (To have the best of them chosen and installed as the
+ * warm start in the same call, use altro_batch_warm_start_dev below: it scores with the arithmetic of this call.)
  * altro_batch_evaluate_dev: every pointer is a device pointer under the rules of the device-pointer block (validated before
  * anything is enqueued, stream-ordered, no host synchronisation, no caller pointer kept).  ncand >= 1 candidates per instance:
  *   U      [batch][ncand][N-1][m]
@@ -579,6 +579,49 @@ int32_t altro_batch_evaluate_dev(altro_handle* h, int32_t ncand, const double* U
                                  double* c_max, double* defect, double* Xout);
 int32_t altro_batch_evaluate(altro_handle* h, int32_t ncand, const double* U, const double* X, const double* x0, double* J,
                              double* c_max, double* defect, double* Xout);
+
+/* ---- warm start from the best of several candidates, chosen on the device.  The closed loops of the reference start every
+ * solve from ONE guess (the shifted previous solution: random_linear_problem.jl:136, simple_rocket.jl:160); a loop that also
+ * holds the reference controls and a learned or sampled guess wants the best of them, and the 20-step launch lasts as long as
+ * its hardest instance.  One call rolls out and scores every candidate, chooses per instance and installs the winner as the
+ * initial trajectory of the next solve.
+ * altro_batch_warm_start_dev: every pointer is a device pointer under the rules of the device-pointer block (validated before
+ * anything is enqueued, stream-ordered on the handle's stream, no host synchronisation, no caller pointer kept).
+ *   U        [batch][ncand][N-1][m], ncand >= 1
+ *   rho      >= 0, finite
+ *   include_current   0 or 1: the controls the handle holds (altro_batch_get_controls) compete as one more candidate, the
+ *            incumbent, in the LAST column (index ncand)
+ *   chosen   [batch] int32 output, may be NULL
+ *   J, c_max [batch][ncand + include_current] outputs, may be NULL
+ * Scoring: every candidate is rolled out from the initial state the handle holds at that point of the stream (there is no x0
+ *   argument: the plane installed must be consistent with the handle) and scored exactly as the rollout form of
+ *   altro_batch_evaluate_dev scores it -- the same window (kref, or the instance's own under an episode clock), dynamics
+ *   blocks, weights, device tables and summation orders: J[b][c] and c_max[b][c] are the bytes that call writes for the same
+ *   U, and the incumbent's are those of altro_batch_evaluate_dev on the output of altro_batch_get_controls_dev.  The states
+ *   never reach memory (csrc/warm_start.h): no workspace grows with ncand * N * n; with J or c_max NULL the merits go to a
+ *   grow-only workspace of 2 * batch * (ncand + include_current) doubles, the one allocation.
+ * Choice: merit = fma(rho, c_max, J), one rounding (rho = 0: the plain cost).  best = +Inf, chosen = -1; the incumbent is
+ *   visited first if included, then c = 0 .. ncand-1 in turn, and a candidate takes over only if merit < best.  Hence the
+ *   incumbent wins ties, among candidates the lowest index wins ties, and a NaN or +Inf merit never wins.
+ *   chosen[b] = 0 .. ncand-1: that candidate; ncand: the incumbent; -1: nothing had a finite merit, nothing of instance b is
+ *   written; -2: the active mask leaves instance b out.
+ * Install: plane cur[b] receives the winner's controls and its rolled-out states and is then byte-identical to what
+ *   altro_batch_set_initial_trajectory_dev(X_w, U_w) leaves, X_w the Xout of altro_batch_evaluate_dev for that candidate --
+ *   also when the incumbent wins (its states are re-rolled from the handle's x0, its controls stay).  Nothing else the
+ *   library owns changes: duals, penalty, statistics, counters, log, clocks and the stored gains with their validity stay.
+ * Mask: the call transforms the trajectory like altro_batch_shift_fill and is masked like it: while altro_batch_set_active is
+ *   in force nothing the library owns changes for an inactive instance and chosen[b] = -2; its rows of J / c_max are still
+ *   written (scoring is not masked, as in altro_batch_evaluate_dev).  The episode clock only selects the window.
+ * Like a solve and like altro_batch_evaluate_dev the call first packs constraint tables a HOST edit has left unpacked.
+ * altro_batch_warm_start: the same with host arrays, through the handle's staging buffer (grown if needed); synchronises;
+ * writes the bytes the `_dev` call writes.
+ * ALTRO_ERR_INVALID_ARG (nothing enqueued, the handle unchanged and usable): NULL handle or NULL U; ncand < 1; rho negative,
+ * NaN or infinite; include_current not 0 or 1; _dev: what the device-pointer block refuses.  ALTRO_ERR_STATE: dynamics, cost
+ * or reference not set, or the window runs past the stored reference.  Caller arrays are indexed with size_t. */
+int32_t altro_batch_warm_start_dev(altro_handle* h, int32_t ncand, const double* U, double rho, int32_t include_current,
+                                   int32_t* chosen, double* J, double* c_max);
+int32_t altro_batch_warm_start(altro_handle* h, int32_t ncand, const double* U, double rho, int32_t include_current,
+                               int32_t* chosen, double* J, double* c_max);
 
 /* ---- per-instance active mask and cold restart: ragged batches of closed loops.
  * The reference runs one problem per loop, and a loop that ends simply stops calling solve! (simple_rocket.jl:137-205); in a
