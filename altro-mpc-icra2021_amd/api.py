@@ -24,7 +24,8 @@ set_bounds also take torch tensors that
 live on the solver's GPU (the altro_*_dev entry points: nothing crosses PCIe, nothing synchronises), and states, controls
 and first_knot write into such tensors; eval_policy (the feedback policy between two ticks), get_gains_dev, evaluate and
 rollout (candidate trajectories scored against the next solve's problem) read and write them.  warm_start scores candidate
-controls the same way and installs the best as the next solve's initial trajectory.  A GPU tensor is never copied, cast or moved behind the caller's back: float64,
+controls the same way and installs the best as the next solve's initial trajectory; simulate_policy runs the policy the last
+solve holds in closed loop on the model, many disturbed samples per instance.  A GPU tensor is never copied, cast or moved behind the caller's back: float64,
 contiguous, on the solver's device and of the exact shape, or ValueError.  Matrices keep their natural (row, col) indexing;
 since the C-ABI reads column-major blocks, a dynamics tensor must be STORED column-major, i.e. `At.transpose(-1, -2)` of a
 contiguous tensor At that holds the transposed blocks.  Every tensor call is ordered against torch's current stream
@@ -1072,6 +1073,101 @@ def rollout(solver, U, x0=None, out=None):
     if out is None:
         out = np.empty(shp)
     evaluate(solver, U, x0=x0, out=(None, np.empty(shp[:-2]), None), Xout=out)
+    return out
+
+
+def _simulate_shapes(solver, x0, w, nsamp):
+    """(nsamp, shape x0 / w / the per-sample outputs / Xout / Uout must have); nsamp comes from x0 (B, nsamp, n) or
+    w (B, nsamp, N-1, n) when given, and what is given must agree"""
+    B, N, n, m = solver.B, solver.N, solver.n, solver.m
+    seen = []
+    if x0 is not None:
+        shp = tuple(int(k) for k in x0.shape)
+        if len(shp) != 3 or shp[1] < 1:
+            raise ValueError(f"simulate_policy: x0: shape {shp}, expected ({B}, nsamp, {n})")
+        seen.append(shp[1])
+    if w is not None:
+        shp = tuple(int(k) for k in w.shape)
+        if len(shp) != 4 or shp[1] < 1:
+            raise ValueError(f"simulate_policy: w: shape {shp}, expected ({B}, nsamp, {N - 1}, {n})")
+        seen.append(shp[1])
+    if nsamp is not None:
+        if int(nsamp) != nsamp or int(nsamp) < 1:
+            raise ValueError(f"simulate_policy: nsamp = {nsamp}: it must be an integer >= 1")
+        seen.append(int(nsamp))
+    if any(k != seen[0] for k in seen):
+        raise ValueError(f"simulate_policy: x0, w and nsamp disagree on the number of samples: {seen}")
+    ns = seen[0] if seen else 1
+    return ns, (B, ns, n), (B, ns, N - 1, n), (B, ns), (B, ns, N, n), (B, ns, N - 1, m)
+
+
+def _simulate_policy_dev(solver, x0=None, w=None, nsamp=None, clamp=True, out=None, fb=None, Xout=None, Uout=None):
+    """device form of simulate_policy: every tensor is validated (shape, dtype, strides, device) before the library is called"""
+    ns, s0, sw, lead, sx, su = _simulate_shapes(solver, x0, w, nsamp)
+    if x0 is not None:
+        check_device_tensor(x0, s0, solver.device, "x0")
+    if w is not None:
+        check_device_tensor(w, sw, solver.device, "w")
+    if out is None:
+        import torch
+        dev = torch.device("cuda", solver.device)
+        out = tuple(torch.empty(lead, dtype=torch.float64, device=dev) for _ in range(3))
+    out = tuple(out)
+    if len(out) != 3:
+        raise ValueError("simulate_policy: out is (J, c_max, dx_max); any may be None")
+    if all(o is None for o in out + (fb, Xout, Uout)):
+        raise ValueError("simulate_policy: J, c_max, dx_max, fb, Xout and Uout are all None")
+    for o, nm in zip(out, ("J", "c_max", "dx_max")):
+        if o is not None:
+            check_device_tensor(o, lead, solver.device, nm)
+    if fb is not None:
+        check_device_tensor(fb, (solver.B,), solver.device, "fb", dtype="torch.int32")
+    if Xout is not None:
+        check_device_tensor(Xout, sx, solver.device, "Xout")
+    if Uout is not None:
+        check_device_tensor(Uout, su, solver.device, "Uout")
+    solver._chk(solver._L.altro_batch_simulate_policy_dev(solver.h, ns, _addr(x0), _addr(w), int(bool(clamp)), _addr(out[0]), _addr(out[1]),
+                                                          _addr(out[2]), _addr(fb), _addr(Xout), _addr(Uout)))
+    return out
+
+
+def simulate_policy(solver, x0=None, w=None, nsamp=None, clamp=True, out=None, fb=None, Xout=None, Uout=None):
+    """The stored policy of the last solve run in closed loop on the model, nsamp samples per instance
+    (altro_batch_simulate_policy / _dev): from x_0 = x0[b, s] (None: the solver's initial state), u_k = eval_policy(x_k, knot k,
+    clamp), x_{k+1} = the model's step (+ w[b, s, k] when w is given), over the whole horizon in one kernel.  Returns
+    (J, c_max, dx_max), each (B, nsamp): the plain tracking cost and the maximum constraint violation as evaluate gives them
+    for the simulated pair, and max_k |x_k - xbar_k|_inf, the largest excursion from the trajectory the solver holds.
+    x0 (B, nsamp, n), w (B, nsamp, N-1, n); nsamp is inferred from them when given (default 1).  fb (B,) int32 receives 1 where
+    the stored gains are valid, 0 where they are not and the loop is open (u_k = ubar_k); Xout (B, nsamp, N, n) and Uout
+    (B, nsamp, N-1, m) receive the simulated states and controls.  Nothing the solver owns changes.
+    With GPU tensors (float64, contiguous; fb int32) the call is stream-ordered and nothing synchronises; out = (J, c_max,
+    dx_max) are tensors to write into (any may be None; default: three new ones).  With numpy -- or with no array at all --
+    the host twin runs: the same bytes."""
+    args = (x0, w, fb, Xout, Uout) + (tuple(out) if out is not None else ())
+    if any(_on_gpu(a) for a in args):
+        if not all(a is None or _on_gpu(a) for a in args):
+            raise ValueError("simulate_policy: x0, w, out, fb, Xout and Uout must all be GPU tensors (or None), or none of them")
+        with _bracket(solver):
+            return _simulate_policy_dev(solver, x0, w, nsamp, clamp, out, fb, Xout, Uout)
+    x0 = None if x0 is None else _c(x0)
+    w = None if w is None else _c(w)
+    ns, s0, sw, lead, sx, su = _simulate_shapes(solver, x0, w, nsamp)
+    for a, shp, nm in ((x0, s0, "x0"), (w, sw, "w")):
+        if a is not None and a.shape != shp:
+            raise ValueError(f"simulate_policy: {nm}: shape {a.shape}, expected {shp}")
+    if out is None:
+        out = tuple(np.empty(lead) for _ in range(3))
+    out = tuple(out)
+    if len(out) != 3:
+        raise ValueError("simulate_policy: out is (J, c_max, dx_max); any may be None")
+    if all(o is None for o in out + (fb, Xout, Uout)):
+        raise ValueError("simulate_policy: J, c_max, dx_max, fb, Xout and Uout are all None")
+    for o, shp, dt, nm in zip(out + (fb, Xout, Uout), (lead,) * 3 + ((solver.B,), sx, su), (np.float64,) * 3 + (np.int32, np.float64, np.float64),
+                              ("J", "c_max", "dx_max", "fb", "Xout", "Uout")):
+        if o is not None and not (isinstance(o, np.ndarray) and o.dtype == dt and o.flags.c_contiguous and o.shape == shp):
+            raise ValueError(f"simulate_policy: {nm} must be a C-contiguous {np.dtype(dt).name} array of shape {shp}")
+    solver._chk(solver._L.altro_batch_simulate_policy(solver.h, ns, _p(x0), _p(w), int(bool(clamp)), _p(out[0]), _p(out[1]), _p(out[2]),
+                                                      None if fb is None else fb.ctypes.data_as(_IP), _p(Xout), _p(Uout)))
     return out
 
 

@@ -22,6 +22,7 @@
 #include "policy.h"
 #include "solve_dpp16.h"
 #include "warm_start.h"
+#include "simulate.h"
 // The one-wave-per-instance kernels are compiled in translation units of their own (wide_inst.hip, _lib.build) and only
 // declared here; -DALTRO_WIDE_SINGLE_TU (and the development builds) instantiate them in this unit as before.
 #if !defined(ALTRO_WIDE_SINGLE_TU) && !defined(ALTRO_DEV_HEADLINE_ONLY)
@@ -2471,6 +2472,17 @@ int32_t altro_batch_get_gains_dev(altro_handle* h, double* K, double* d) {
 }
 
 // ---- caller-supplied trajectories scored on the device (kernels in evaluate.h)
+// the tables a scoring kernel of evaluate.h / warm_start.h / simulate.h reads, as the solve kernels address them now
+static altro::Eval16 eval16_params(altro_handle* h) {
+  const size_t N = h->d.N;
+  altro::Eval16 p{};
+  p.Grow = h->Grow; p.fvec = h->fvec; p.wd = h->wd; p.wf = h->wf; p.zmin = h->zmin; p.zmax = h->zmax; p.Zref = h->Zref;
+  p.Acon = h->Acon; p.bcon = h->bcon; p.cmeta = h->cmeta; p.window = h->clock.args().window; p.imask = tab_imask(h);
+  p.con_istride = h->con_per_instance ? N * LW * LW : 0; p.ncrows = h->ncrows;
+  p.N = (int)N; p.Nt = h->Nt; p.n = h->d.n; p.m = h->d.m; p.kref = h->kref; p.box_k0 = h->box_k0; p.box_k1 = h->box_k1;
+  return p;
+}
+
 // the argument rules both forms share, checked before anything else
 static int evaluate_rules(altro_handle* h, const char* fn, int32_t ncand, const double* U, const double* X, const double* x0, double* J,
                           double* c_max, double* defect, double* Xout) {
@@ -2500,11 +2512,7 @@ static int evaluate_launch(altro_handle* h, int32_t ncand, const double* U, cons
   const size_t R = B * (size_t)ncand, lx = N * n, lu = (N - 1) * m;
   const size_t need = !U ? R * (lx + lu) : (!X && !Xout) ? R * lx : 0;
   if (need) HIPCHK(h, h->pool.reserve(&h->eval_ws, &h->eval_ws_elems, need));
-  altro::Eval16 p{};
-  p.Grow = h->Grow; p.fvec = h->fvec; p.wd = h->wd; p.wf = h->wf; p.zmin = h->zmin; p.zmax = h->zmax; p.Zref = h->Zref;
-  p.Acon = h->Acon; p.bcon = h->bcon; p.cmeta = h->cmeta; p.window = h->clock.args().window; p.imask = tab_imask(h);
-  p.con_istride = h->con_per_instance ? N * LW * LW : 0; p.ncrows = h->ncrows;
-  p.N = (int)N; p.Nt = h->Nt; p.n = (int)n; p.m = (int)m; p.kref = h->kref; p.box_k0 = h->box_k0; p.box_k1 = h->box_k1;
+  const altro::Eval16 p = eval16_params(h);
   const size_t rows = (R + 3) & ~(size_t)3;   // whole waves of four rows
   int given = 1;
   if (!U) {   // own trajectory: the current plane, unpacked into the workspace in the caller's layout
@@ -2607,11 +2615,7 @@ static int warm_start_launch(altro_handle* h, int32_t ncand, const double* U, do
     if (!J) J = h->ws_merit;
     if (!c_max) c_max = h->ws_merit + R;
   }
-  altro::Eval16 p{};
-  p.Grow = h->Grow; p.fvec = h->fvec; p.wd = h->wd; p.wf = h->wf; p.zmin = h->zmin; p.zmax = h->zmax; p.Zref = h->Zref;
-  p.Acon = h->Acon; p.bcon = h->bcon; p.cmeta = h->cmeta; p.window = h->clock.args().window; p.imask = tab_imask(h);
-  p.con_istride = h->con_per_instance ? N * LW * LW : 0; p.ncrows = h->ncrows;
-  p.N = (int)N; p.Nt = h->Nt; p.n = (int)n; p.m = (int)m; p.kref = h->kref; p.box_k0 = h->box_k0; p.box_k1 = h->box_k1;
+  const altro::Eval16 p = eval16_params(h);
   const size_t plane = N * (size_t)LW;
   const size_t rows = (R + 3) & ~(size_t)3;   // whole waves of four rows
   hipLaunchKernelGGL(altro::k_ws_score16, grid_for(rows * LW), dim3(256), 0, h->stream, J, c_max, U, h->Z, h->cur, plane, h->x0, p, (int)ncand,
@@ -2662,6 +2666,96 @@ int32_t altro_batch_warm_start(altro_handle* h, int32_t ncand, const double* U, 
     if (chosen) HIPCHK(h, hipMemcpyAsync(chosen, sw, B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     if (J) HIPCHK(h, hipMemcpyAsync(J, sJ, R1 * sizeof(double), hipMemcpyDeviceToHost, st));
     if (c_max) HIPCHK(h, hipMemcpyAsync(c_max, sc, R1 * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    return ALTRO_OK;
+  });
+}
+
+// ---- closed-loop simulation of the stored policy under disturbances (kernels in simulate.h)
+// the argument rules both forms share, checked before anything else
+static int simulate_rules(altro_handle* h, const char* fn, int32_t nsamp, int32_t clamp, const altro::SimIO& io) {
+  const std::string f(fn);
+  if (nsamp < 1) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": nsamp must be at least 1");
+  if (clamp != 0 && clamp != 1) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": clamp must be 0 or 1");
+  if (!io.J && !io.cmax && !io.dxmax && !io.fb && !io.Xout && !io.Uout)
+    FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": J, c_max, dx_max, fb, Xout and Uout are all null");
+  return ALTRO_OK;
+}
+
+// io: device arrays (the caller's, validated; or the staged copies of the host twin).  Enqueues one kernel, allocates nothing.
+static int simulate_launch(altro_handle* h, int32_t nsamp, int32_t clamp, const altro::SimIO& io) {
+  if (h->wide) {
+    const int rc = h->wide->simulate_policy_dev(nsamp, clamp, io);
+    if (rc) h->err = h->wide->err;
+    return rc;
+  }
+  int rc = check_ready(h);
+  if (rc) return rc;
+  if (!h->clock.on && h->kref + h->d.N > h->Nt) FAIL(h, ALTRO_ERR_STATE, "reference window runs past the end of the stored trajectory");
+  if ((rc = pack_constraints(h))) return rc;   // (what the next solve would do first; a no-op once the tables are packed)
+  const size_t R = (size_t)h->d.batch * (size_t)nsamp;
+  const altro::Eval16 p = eval16_params(h);
+  const size_t rows = (R + 3) & ~(size_t)3;   // whole waves of four rows
+  hipLaunchKernelGGL(altro::k_sim16, grid_for(rows * LW), dim3(256), 0, h->stream, io, h->Z, h->cur, (size_t)h->d.N * LW, h->KD, h->kmu, h->x0, p,
+                     (int)nsamp, clamp ? 1 : 0, R, rows);
+  HIPCHK(h, hipGetLastError());
+  return ALTRO_OK;
+}
+
+int32_t altro_batch_simulate_policy_dev(altro_handle* h, int32_t nsamp, const double* x0, const double* w, int32_t clamp, double* J,
+                                        double* c_max, double* dx_max, int32_t* fb, double* Xout, double* Uout) {
+  return guard(h, [&]() -> int32_t {
+    DEV_ENTER(h, "altro_batch_simulate_policy_dev");
+    const altro::SimIO io{x0, w, J, c_max, dx_max, fb, Xout, Uout};
+    if (int rc = simulate_rules(h, fn_, nsamp, clamp, io)) return rc;
+    const size_t R = B_ * (size_t)nsamp;
+    DEV_ARG(h, "x0", x0, R * n_, double, true);
+    DEV_ARG(h, "w", w, R * (N_ - 1) * n_, double, true);
+    DEV_ARG(h, "J", J, R, double, true);
+    DEV_ARG(h, "c_max", c_max, R, double, true);
+    DEV_ARG(h, "dx_max", dx_max, R, double, true);
+    DEV_ARG(h, "fb", fb, B_, int32_t, true);
+    DEV_ARG(h, "Xout", Xout, R * N_ * n_, double, true);
+    DEV_ARG(h, "Uout", Uout, R * (N_ - 1) * m_, double, true);
+    return simulate_launch(h, nsamp, clamp, io);
+  });
+}
+
+// The host twin: x0 and w go through the staging buffer, the SAME kernel runs on the staged copies and the outputs come back
+// -- the bytes are those of the `_dev` call by construction.
+int32_t altro_batch_simulate_policy(altro_handle* h, int32_t nsamp, const double* x0, const double* w, int32_t clamp, double* J,
+                                    double* c_max, double* dx_max, int32_t* fb, double* Xout, double* Uout) {
+  return guard(h, [&]() -> int32_t {
+    if (!h) return dev_null_handle("altro_batch_simulate_policy");
+    if (int rc = simulate_rules(h, "altro_batch_simulate_policy", nsamp, clamp, altro::SimIO{x0, w, J, c_max, dx_max, fb, Xout, Uout})) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t B = h->d.batch, N = h->d.N, n = h->d.n, m = h->d.m;
+    const size_t R = B * (size_t)nsamp, c0 = R * n, cw = R * (N - 1) * n, cx = R * N * n, cu = R * (N - 1) * m;
+    const size_t elems = 3 * R + (x0 ? c0 : 0) + (w ? cw : 0) + (Xout ? cx : 0) + (Uout ? cu : 0);
+    const size_t bytes = elems * sizeof(double) + B * sizeof(int32_t);
+    if (int rc = h->wide ? h->wide->ensure_stage(bytes) : ensure_stage(h, bytes)) {
+      if (h->wide) h->err = h->wide->err;
+      return rc;
+    }
+    const hipStream_t st = h->wide ? h->wide->stream : h->stream;
+    double* s = h->wide ? h->wide->stage : h->stage;
+    double *sJ = s, *sc = s + R, *sd = s + 2 * R;
+    s += 3 * R;
+    double* sx0 = x0 ? s : nullptr; s += x0 ? c0 : 0;
+    double* sw = w ? s : nullptr; s += w ? cw : 0;
+    double* sX = Xout ? s : nullptr; s += Xout ? cx : 0;
+    double* sU = Uout ? s : nullptr; s += Uout ? cu : 0;
+    int32_t* sf = reinterpret_cast<int32_t*>(s);
+    if (x0) HIPCHK(h, hipMemcpyAsync(sx0, x0, c0 * sizeof(double), hipMemcpyHostToDevice, st));
+    if (w) HIPCHK(h, hipMemcpyAsync(sw, w, cw * sizeof(double), hipMemcpyHostToDevice, st));
+    const altro::SimIO io{sx0, sw, J ? sJ : nullptr, c_max ? sc : nullptr, dx_max ? sd : nullptr, fb ? sf : nullptr, sX, sU};
+    if (int rc = simulate_launch(h, nsamp, clamp, io)) return rc;
+    if (J) HIPCHK(h, hipMemcpyAsync(J, sJ, R * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (c_max) HIPCHK(h, hipMemcpyAsync(c_max, sc, R * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (dx_max) HIPCHK(h, hipMemcpyAsync(dx_max, sd, R * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (fb) HIPCHK(h, hipMemcpyAsync(fb, sf, B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (Xout) HIPCHK(h, hipMemcpyAsync(Xout, sX, cx * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (Uout) HIPCHK(h, hipMemcpyAsync(Uout, sU, cu * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipStreamSynchronize(st));
     return ALTRO_OK;
   });

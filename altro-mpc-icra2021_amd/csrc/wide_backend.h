@@ -14,6 +14,7 @@
 #include "device_pool.h"
 #include "evaluate.h"
 #include "warm_start.h"
+#include "simulate.h"
 #include "launch_ring.h"
 #include "policy.h"
 #include "solve_wide.h"
@@ -740,20 +741,18 @@ struct WideBackend {
     WCHK(hipGetLastError());
     return ALTRO_OK;
   }
-  // altro_batch_evaluate_dev (evaluate.h; pointers and argument rules checked by the caller, the host twin passes staged
-  // copies): the rollout kernel when there is no X, then the scoring kernel on states and controls in memory.  Reads what the
-  // next solve would read; writes the caller's outputs and eval_ws only.
-  int evaluate_dev(int ncand, const double* Ud, const double* Xd, const double* x0d, double* Jd, double* cd, double* dd, double* Xout) {
-    WCHK(hipSetDevice(device));
+  // what evaluate_dev, warm_start_dev and simulate_policy_dev check first ...
+  int eval_ready() {
     if (!have_dyn) WFAIL(ALTRO_ERR_STATE, "altro_batch_set_dynamics has not been called");
     if (!have_cost) WFAIL(ALTRO_ERR_STATE, "altro_batch_set_tracking_cost has not been called");
     if (!have_ref) WFAIL(ALTRO_ERR_STATE, "no reference trajectory (altro_batch_set_reference / altro_mpc_set_track)");
     if (!clock.on && kref + d.N > Nt) WFAIL(ALTRO_ERR_STATE, "reference window runs past the end of the stored trajectory");
     if (!clock.on && !dyn_covers(kref)) WFAIL(ALTRO_ERR_STATE, "the dynamics track ends before the window");
     if (int rc = pack_constraints()) return rc;   // (what the next solve would do first; a no-op once the tables are packed)
-    const size_t R = (size_t)d.batch * ncand, lx = (size_t)d.N * d.n, lu = (size_t)(d.N - 1) * d.m;
-    const size_t need = !Ud ? R * (lx + lu) : (!Xd && !Xout) ? R * lx : 0;
-    if (need) WCHK(pool.reserve(&eval_ws, &eval_ws_elems, need));
+    return ALTRO_OK;
+  }
+  // ... and the tables their kernels read, as the solve kernels address them now
+  altro::EvalW eval_params() const {
     altro::EvalW p{};
     p.A = A; p.Bm = Bm; p.f = f; p.wd = wd; p.wf = wf; p.zmin = zmin; p.zmax = zmax; p.Xref = Xref; p.Uref = Uref;
     p.AconT = AconT; p.bcon = bcon; p.ctype = ctype; p.rowc0 = rowc0; p.rowcp = rowcp; p.window = clock.args().window;
@@ -762,6 +761,18 @@ struct WideBackend {
     p.w_pi = w_pi; p.b_pi = b_pi; p.ltv = ltv; p.dyn_pi = dyn_per_instance; p.dyn_blocks = dyn_blocks; p.dyn_stride = dyn_step_stride;
     p.Pn = Pn; p.N = d.N; p.Nt = Nt; p.n = d.n; p.m = d.m; p.kref = kref; p.box_k0 = box_k0; p.box_k1 = box_k1;
     p.lds_dyn = altro::evalw_lds_fits(d.n, d.m, ltv) ? 1 : 0;
+    return p;
+  }
+  // altro_batch_evaluate_dev (evaluate.h; pointers and argument rules checked by the caller, the host twin passes staged
+  // copies): the rollout kernel when there is no X, then the scoring kernel on states and controls in memory.  Reads what the
+  // next solve would read; writes the caller's outputs and eval_ws only.
+  int evaluate_dev(int ncand, const double* Ud, const double* Xd, const double* x0d, double* Jd, double* cd, double* dd, double* Xout) {
+    WCHK(hipSetDevice(device));
+    if (int rc = eval_ready()) return rc;
+    const size_t R = (size_t)d.batch * ncand, lx = (size_t)d.N * d.n, lu = (size_t)(d.N - 1) * d.m;
+    const size_t need = !Ud ? R * (lx + lu) : (!Xd && !Xout) ? R * lx : 0;
+    if (need) WCHK(pool.reserve(&eval_ws, &eval_ws_elems, need));
+    const altro::EvalW p = eval_params();
     const size_t lds = p.lds_dyn ? 4 * altro::evalw_lds_doubles(d.n, d.m) * sizeof(double) : 0;
     const dim3 grid((unsigned)((R * 64 + 255) / 256)), block(256);
     int given = 1;
@@ -785,31 +796,33 @@ struct WideBackend {
   // Reads what the next solve would read; writes the caller's outputs, ws_merit and plane cur[b] of X / U.
   int warm_start_dev(int ncand, const double* Ud, double rho, int inc, int32_t* chosen, double* Jd, double* cd) {
     WCHK(hipSetDevice(device));
-    if (!have_dyn) WFAIL(ALTRO_ERR_STATE, "altro_batch_set_dynamics has not been called");
-    if (!have_cost) WFAIL(ALTRO_ERR_STATE, "altro_batch_set_tracking_cost has not been called");
-    if (!have_ref) WFAIL(ALTRO_ERR_STATE, "no reference trajectory (altro_batch_set_reference / altro_mpc_set_track)");
-    if (!clock.on && kref + d.N > Nt) WFAIL(ALTRO_ERR_STATE, "reference window runs past the end of the stored trajectory");
-    if (!clock.on && !dyn_covers(kref)) WFAIL(ALTRO_ERR_STATE, "the dynamics track ends before the window");
-    if (int rc = pack_constraints()) return rc;   // (what the next solve would do first; a no-op once the tables are packed)
+    if (int rc = eval_ready()) return rc;
     const size_t R = (size_t)d.batch * (size_t)(ncand + inc);
     if (!Jd || !cd) {
       WCHK(pool.reserve(&ws_merit, &ws_merit_elems, 2 * R));
       if (!Jd) Jd = ws_merit;
       if (!cd) cd = ws_merit + R;
     }
-    altro::EvalW p{};
-    p.A = A; p.Bm = Bm; p.f = f; p.wd = wd; p.wf = wf; p.zmin = zmin; p.zmax = zmax; p.Xref = Xref; p.Uref = Uref;
-    p.AconT = AconT; p.bcon = bcon; p.ctype = ctype; p.rowc0 = rowc0; p.rowcp = rowcp; p.window = clock.args().window;
-    p.con_istride = con_per_instance ? (size_t)d.N * nz() * Pn : 0;
-    p.bcon_istride = con_per_instance ? (size_t)d.N * Pn : 0;
-    p.w_pi = w_pi; p.b_pi = b_pi; p.ltv = ltv; p.dyn_pi = dyn_per_instance; p.dyn_blocks = dyn_blocks; p.dyn_stride = dyn_step_stride;
-    p.Pn = Pn; p.N = d.N; p.Nt = Nt; p.n = d.n; p.m = d.m; p.kref = kref; p.box_k0 = box_k0; p.box_k1 = box_k1;
-    p.lds_dyn = altro::evalw_lds_fits(d.n, d.m, ltv) ? 1 : 0;
+    const altro::EvalW p = eval_params();
     const size_t lds = p.lds_dyn ? 4 * altro::evalw_lds_doubles(d.n, d.m) * sizeof(double) : 0;
     hipLaunchKernelGGL(altro::k_ws_score_wide, dim3((unsigned)((R * 64 + 255) / 256)), dim3(256), lds, stream, Jd, cd, Ud, U, cur, x0, p, ncand, inc, R);
     WCHK(hipGetLastError());
     hipLaunchKernelGGL(altro::k_ws_install_wide, dim3((unsigned)(((size_t)d.batch * 64 + 255) / 256)), dim3(256), lds, stream, chosen, Jd, cd, Ud, X, U,
                        cur, x0, flags.mask(), p, ncand, inc, rho, (size_t)d.batch);
+    WCHK(hipGetLastError());
+    return ALTRO_OK;
+  }
+  // altro_batch_simulate_policy_dev (simulate.h; pointers and argument rules checked by the caller, the host twin passes staged
+  // copies): one fused kernel over batch * nsamp waves.  Reads what the next solve and eval_policy_dev would read; writes the
+  // caller's outputs only.
+  int simulate_policy_dev(int nsamp, int clamp, const altro::SimIO& io) {
+    WCHK(hipSetDevice(device));
+    if (int rc = eval_ready()) return rc;
+    const size_t R = (size_t)d.batch * (size_t)nsamp;
+    const altro::EvalW p = eval_params();
+    const size_t lds = p.lds_dyn ? 4 * altro::evalw_lds_doubles(d.n, d.m) * sizeof(double) : 0;
+    hipLaunchKernelGGL(altro::k_sim_wide, dim3((unsigned)((R * 64 + 255) / 256)), dim3(256), lds, stream, io, X, U, cur, Kg, bwst,
+                       (gains_valid || debug_keep_gains) ? 1 : 0, x0, p, nsamp, clamp ? 1 : 0, R);
     WCHK(hipGetLastError());
     return ALTRO_OK;
   }

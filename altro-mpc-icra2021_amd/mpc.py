@@ -352,6 +352,12 @@ class ExternalMPC:
         GPU tensors or numpy."""
         return api.warm_start(self.solver, U, rho=rho, include_current=include_current, out=out)
 
+    def simulate(self, x0=None, w=None, nsamp=None, clamp=True, out=None, fb=None, Xout=None, Uout=None):
+        """(J, c_max, dx_max) of api.simulate_policy: the policy the solver holds once its stream reaches this point, run in
+        closed loop on the model from the start states x0 (B, nsamp, n) under the disturbances w (B, nsamp, N-1, n) -- what the
+        last solve is worth if the state estimate is off or the plant is pushed: a pass-through, GPU tensors or numpy."""
+        return api.simulate_policy(self.solver, x0=x0, w=w, nsamp=nsamp, clamp=clamp, out=out, fb=fb, Xout=Xout, Uout=Uout)
+
     def _constraints_dev(self, constraint_data, bounds):
         s = self.solver
         for con, (A, b) in (constraint_data or {}).items():

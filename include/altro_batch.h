@@ -623,6 +623,42 @@ int32_t altro_batch_warm_start_dev(altro_handle* h, int32_t ncand, const double*
 int32_t altro_batch_warm_start(altro_handle* h, int32_t ncand, const double* U, double rho, int32_t include_current,
                                int32_t* chosen, double* J, double* c_max);
 
+/* ---- closed-loop simulation of the stored policy under disturbances.  Every closed loop of the reference perturbs the plant
+ * state on every tick (random_linear_problem.jl:129, simple_rocket.jl:65-71, flexible_sat_mpc.jl:266); what the policy a
+ * handle holds is worth under such perturbations -- before it is trusted between two ticks, to size a constraint back-off, to
+ * decide whether an instance needs a re-solve -- is a Monte-Carlo study with many samples per instance.  One call runs it.
+ * altro_batch_simulate_policy_dev: every pointer is a device pointer under the rules of the device-pointer block (validated
+ * before anything is enqueued, stream-ordered on the handle's stream, no host synchronisation, no caller pointer kept).
+ *   nsamp    >= 1 samples per instance
+ *   x0       [batch][nsamp][n] start states; NULL: every sample starts from the initial state the handle holds
+ *   w        [batch][nsamp][N-1][n] additive disturbances; NULL: none, and no addition is performed at all
+ *   clamp    0 or 1: saturate every control at the BOX, as altro_batch_eval_policy_dev does
+ *   J, c_max, dx_max   [batch][nsamp] outputs;  fb [batch] int32 output
+ *   Xout     [batch][nsamp][N][n],  Uout [batch][nsamp][N-1][m]   optional outputs
+ *   Any output may be NULL, not all six of them.
+ * For sample s of instance b, with (xbar, ubar) the trajectory the handle holds and K the gains altro_batch_get_gains returns:
+ *   x_0     = x0[b][s]
+ *   u_k     = the bytes altro_batch_eval_policy_dev writes for x = x_k, knot = k, clamp          k = 0 .. N-2
+ *   x_{k+1} = the rollout arithmetic of altro_batch_evaluate_dev on (x_k, u_k); with w one more rounded addition of
+ *             w[b][s][k], performed last
+ *   J, c_max = what the given form of altro_batch_evaluate_dev returns for (X, U) = the simulated pair
+ *   dx_max  = max over k = 0 .. N-1 and i of |x_k[i] - xbar_k[i]| (the subtraction the policy makes; a NaN stays)
+ *   fb[b]   = 1 / 0 as altro_batch_eval_policy_dev reports the validity of the stored gains; with 0 the loop is open:
+ *             u_k = ubar_k, clamped if asked
+ * The window, the dynamics blocks, the weights, the bounds and the device tables are those altro_batch_evaluate_dev sees at
+ * that point of the stream (under an episode clock the instance's own window).  One fused kernel (csrc/simulate.h): the states
+ * stay in registers, no workspace grows with nsamp * N * n, and nothing the library owns changes -- the stored gains stay.
+ * There is no masking and no status.  Like a solve the call first packs constraint tables a HOST edit has left unpacked.
+ * altro_batch_simulate_policy: the same with host arrays, through the handle's staging buffer (grown if needed);
+ * synchronises; writes the bytes the `_dev` call writes.
+ * ALTRO_ERR_INVALID_ARG (nothing enqueued, the handle unchanged and usable): NULL handle; nsamp < 1; clamp not 0 or 1; every
+ * output NULL; _dev: what the device-pointer block refuses.  ALTRO_ERR_STATE: dynamics, cost or reference not set, or the
+ * window runs past the stored reference.  Caller arrays are indexed with size_t. */
+int32_t altro_batch_simulate_policy_dev(altro_handle* h, int32_t nsamp, const double* x0, const double* w, int32_t clamp,
+                                        double* J, double* c_max, double* dx_max, int32_t* fb, double* Xout, double* Uout);
+int32_t altro_batch_simulate_policy(altro_handle* h, int32_t nsamp, const double* x0, const double* w, int32_t clamp, double* J,
+                                    double* c_max, double* dx_max, int32_t* fb, double* Xout, double* Uout);
+
 /* ---- per-instance active mask and cold restart: ragged batches of closed loops.
  * The reference runs one problem per loop, and a loop that ends simply stops calling solve! (simple_rocket.jl:137-205); in a
  * batch the instance whose rocket has landed, or whose episode has ended and is re-spawned, sits among others that go on.
