@@ -21,6 +21,7 @@
 #include "pn_polish.h"
 #include "policy.h"
 #include "solve_dpp16.h"
+#include "stage_layout.h"
 #include "warm_start.h"
 #include "simulate.h"
 // The one-wave-per-instance kernels are compiled in translation units of their own (wide_inst.hip, _lib.build) and only
@@ -2483,6 +2484,44 @@ static altro::Eval16 eval16_params(altro_handle* h) {
   return p;
 }
 
+// what evaluate_launch, warm_start_launch and simulate_launch check first on the 16-lane path (the one-wave-per-instance
+// backend has WideBackend::eval_ready)
+static int score_ready(altro_handle* h) {
+  if (int rc = check_ready(h)) return rc;
+  if (!h->clock.on && h->kref + h->d.N > h->Nt) FAIL(h, ALTRO_ERR_STATE, "reference window runs past the end of the stored trajectory");
+  return pack_constraints(h);   // (what the next solve would do first; a no-op once the tables are packed)
+}
+
+// The arrays of a host twin in the staging buffer of whichever backend the handle runs on (their layout: stage_layout.h).
+// open() makes room and copies in what the caller passed, f64() / i32() are what the launch gets, close() copies the outputs back and
+// synchronises once: the SAME kernels run on the staged copies, so the bytes are those of the `_dev` call by construction.
+struct StageCursor : altro::StageLayout {
+  altro_handle* h;
+  hipStream_t st = nullptr;
+  char* base = nullptr;
+  explicit StageCursor(altro_handle* h_) : h(h_) {}
+  int open() {
+    if (int rc = h->wide ? h->wide->ensure_stage(bytes) : ensure_stage(h, bytes)) {
+      if (h->wide) h->err = h->wide->err;
+      return rc;
+    }
+    st = h->wide ? h->wide->stream : h->stream;
+    base = reinterpret_cast<char*>(h->wide ? h->wide->stage : h->stage);
+    for (int i = 0; i < nslots; ++i)
+      if (slot[i].in) HIPCHK(h, hipMemcpyAsync(base + slot[i].off, slot[i].in, slot[i].bytes, hipMemcpyHostToDevice, st));
+    return ALTRO_OK;
+  }
+  void* dev(int i) const { return slot[i].dev ? base + slot[i].off : nullptr; }
+  double* f64(int i) const { return static_cast<double*>(dev(i)); }
+  int32_t* i32(int i) const { return static_cast<int32_t*>(dev(i)); }
+  int close() {
+    for (int i = 0; i < nslots; ++i)
+      if (slot[i].out) HIPCHK(h, hipMemcpyAsync(slot[i].out, base + slot[i].off, slot[i].bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    return ALTRO_OK;
+  }
+};
+
 // the argument rules both forms share, checked before anything else
 static int evaluate_rules(altro_handle* h, const char* fn, int32_t ncand, const double* U, const double* X, const double* x0, double* J,
                           double* c_max, double* defect, double* Xout) {
@@ -2504,10 +2543,8 @@ static int evaluate_launch(altro_handle* h, int32_t ncand, const double* U, cons
     if (rc) h->err = h->wide->err;
     return rc;
   }
-  int rc = check_ready(h);
+  int rc = score_ready(h);
   if (rc) return rc;
-  if (!h->clock.on && h->kref + h->d.N > h->Nt) FAIL(h, ALTRO_ERR_STATE, "reference window runs past the end of the stored trajectory");
-  if ((rc = pack_constraints(h))) return rc;   // (what the next solve would do first; a no-op once the tables are packed)
   const size_t B = h->d.batch, N = h->d.N, n = h->d.n, m = h->d.m;
   const size_t R = B * (size_t)ncand, lx = N * n, lu = (N - 1) * m;
   const size_t need = !U ? R * (lx + lu) : (!X && !Xout) ? R * lx : 0;
@@ -2548,39 +2585,21 @@ int32_t altro_batch_evaluate_dev(altro_handle* h, int32_t ncand, const double* U
   });
 }
 
-// The host twin: the arrays go through the staging buffer, the SAME kernels run on the staged copies and the outputs come
-// back -- the bytes are those of the `_dev` call by construction.
+// The host twin (StageCursor)
 int32_t altro_batch_evaluate(altro_handle* h, int32_t ncand, const double* U, const double* X, const double* x0, double* J, double* c_max,
                              double* defect, double* Xout) {
   return guard(h, [&]() -> int32_t {
     if (!h) return dev_null_handle("altro_batch_evaluate");
     if (int rc = evaluate_rules(h, "altro_batch_evaluate", ncand, U, X, x0, J, c_max, defect, Xout)) return rc;
     HIPCHK(h, hipSetDevice(h->device));
-    const size_t B = h->d.batch, N = h->d.N, n = h->d.n, m = h->d.m;
-    const size_t R = B * (size_t)ncand, cu = R * (N - 1) * m, cx = R * N * n;
-    const size_t elems = 3 * R + (U ? cu : 0) + (X ? cx : 0) + (x0 ? B * n : 0) + (Xout ? cx : 0);
-    if (int rc = h->wide ? h->wide->ensure_stage(elems * sizeof(double)) : ensure_stage(h, elems * sizeof(double))) {
-      if (h->wide) h->err = h->wide->err;
+    StageCursor sc(h);
+    altro::stage_evaluate(sc, h->d.batch, h->d.N, h->d.n, h->d.m, ncand, U, X, x0, J, c_max, defect, Xout);
+    if (int rc = sc.open()) return rc;
+    if (int rc = evaluate_launch(h, ncand, sc.f64(altro::EV_U), sc.f64(altro::EV_X), sc.f64(altro::EV_X0),
+                                 sc.f64(altro::EV_J), sc.f64(altro::EV_CMAX), sc.f64(altro::EV_DEFECT),
+                                 sc.f64(altro::EV_XOUT)))
       return rc;
-    }
-    const hipStream_t st = h->wide ? h->wide->stream : h->stream;
-    double* s = h->wide ? h->wide->stage : h->stage;
-    double *sJ = s, *sc = s + R, *sd = s + 2 * R;
-    s += 3 * R;
-    double* sU = U ? s : nullptr; s += U ? cu : 0;
-    double* sX = X ? s : nullptr; s += X ? cx : 0;
-    double* sx0 = x0 ? s : nullptr; s += x0 ? B * n : 0;
-    double* sXo = Xout ? s : nullptr;
-    if (U) HIPCHK(h, hipMemcpyAsync(sU, U, cu * sizeof(double), hipMemcpyHostToDevice, st));
-    if (X) HIPCHK(h, hipMemcpyAsync(sX, X, cx * sizeof(double), hipMemcpyHostToDevice, st));
-    if (x0) HIPCHK(h, hipMemcpyAsync(sx0, x0, B * n * sizeof(double), hipMemcpyHostToDevice, st));
-    if (int rc = evaluate_launch(h, ncand, sU, sX, sx0, J ? sJ : nullptr, c_max ? sc : nullptr, defect ? sd : nullptr, sXo)) return rc;
-    if (J) HIPCHK(h, hipMemcpyAsync(J, sJ, R * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (c_max) HIPCHK(h, hipMemcpyAsync(c_max, sc, R * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (defect) HIPCHK(h, hipMemcpyAsync(defect, sd, R * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (Xout) HIPCHK(h, hipMemcpyAsync(Xout, sXo, cx * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    return ALTRO_OK;
+    return sc.close();
   });
 }
 
@@ -2604,10 +2623,7 @@ static int warm_start_launch(altro_handle* h, int32_t ncand, const double* U, do
     if (rc) h->err = h->wide->err;
     return rc;
   }
-  int rc = check_ready(h);
-  if (rc) return rc;
-  if (!h->clock.on && h->kref + h->d.N > h->Nt) FAIL(h, ALTRO_ERR_STATE, "reference window runs past the end of the stored trajectory");
-  if ((rc = pack_constraints(h))) return rc;   // (what the next solve would do first; a no-op once the tables are packed)
+  if (int rc = score_ready(h)) return rc;
   const size_t B = h->d.batch, N = h->d.N, n = h->d.n, m = h->d.m;
   const size_t R = B * (size_t)(ncand + inc);
   if (!J || !c_max) {
@@ -2642,32 +2658,20 @@ int32_t altro_batch_warm_start_dev(altro_handle* h, int32_t ncand, const double*
   });
 }
 
-// The host twin: U goes through the staging buffer, the SAME kernels run on the staged copies and the outputs come back --
-// the bytes are those of the `_dev` call by construction.
+// The host twin (StageCursor)
 int32_t altro_batch_warm_start(altro_handle* h, int32_t ncand, const double* U, double rho, int32_t include_current, int32_t* chosen,
                                double* J, double* c_max) {
   return guard(h, [&]() -> int32_t {
     if (!h) return dev_null_handle("altro_batch_warm_start");
     if (int rc = warm_start_rules(h, "altro_batch_warm_start", ncand, U, rho, include_current)) return rc;
     HIPCHK(h, hipSetDevice(h->device));
-    const size_t B = h->d.batch, N = h->d.N, m = h->d.m;
-    const size_t R1 = B * (size_t)(ncand + include_current), cu = B * (size_t)ncand * (N - 1) * m;
-    const size_t bytes = (2 * R1 + cu) * sizeof(double) + B * sizeof(int32_t);
-    if (int rc = h->wide ? h->wide->ensure_stage(bytes) : ensure_stage(h, bytes)) {
-      if (h->wide) h->err = h->wide->err;
+    StageCursor sc(h);
+    altro::stage_warm_start(sc, h->d.batch, h->d.N, h->d.m, ncand, include_current, U, chosen, J, c_max);
+    if (int rc = sc.open()) return rc;
+    if (int rc = warm_start_launch(h, ncand, sc.f64(altro::WS_U), rho, include_current, sc.i32(altro::WS_CHOSEN),
+                                   sc.f64(altro::WS_J), sc.f64(altro::WS_CMAX)))
       return rc;
-    }
-    const hipStream_t st = h->wide ? h->wide->stream : h->stream;
-    double* sJ = h->wide ? h->wide->stage : h->stage;
-    double *sc = sJ + R1, *sU = sc + R1;
-    int32_t* sw = reinterpret_cast<int32_t*>(sU + cu);
-    HIPCHK(h, hipMemcpyAsync(sU, U, cu * sizeof(double), hipMemcpyHostToDevice, st));
-    if (int rc = warm_start_launch(h, ncand, sU, rho, include_current, sw, sJ, sc)) return rc;
-    if (chosen) HIPCHK(h, hipMemcpyAsync(chosen, sw, B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    if (J) HIPCHK(h, hipMemcpyAsync(J, sJ, R1 * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (c_max) HIPCHK(h, hipMemcpyAsync(c_max, sc, R1 * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    return ALTRO_OK;
+    return sc.close();
   });
 }
 
@@ -2689,10 +2693,7 @@ static int simulate_launch(altro_handle* h, int32_t nsamp, int32_t clamp, const 
     if (rc) h->err = h->wide->err;
     return rc;
   }
-  int rc = check_ready(h);
-  if (rc) return rc;
-  if (!h->clock.on && h->kref + h->d.N > h->Nt) FAIL(h, ALTRO_ERR_STATE, "reference window runs past the end of the stored trajectory");
-  if ((rc = pack_constraints(h))) return rc;   // (what the next solve would do first; a no-op once the tables are packed)
+  if (int rc = score_ready(h)) return rc;
   const size_t R = (size_t)h->d.batch * (size_t)nsamp;
   const altro::Eval16 p = eval16_params(h);
   const size_t rows = (R + 3) & ~(size_t)3;   // whole waves of four rows
@@ -2721,43 +2722,20 @@ int32_t altro_batch_simulate_policy_dev(altro_handle* h, int32_t nsamp, const do
   });
 }
 
-// The host twin: x0 and w go through the staging buffer, the SAME kernel runs on the staged copies and the outputs come back
-// -- the bytes are those of the `_dev` call by construction.
+// The host twin (StageCursor)
 int32_t altro_batch_simulate_policy(altro_handle* h, int32_t nsamp, const double* x0, const double* w, int32_t clamp, double* J,
                                     double* c_max, double* dx_max, int32_t* fb, double* Xout, double* Uout) {
   return guard(h, [&]() -> int32_t {
     if (!h) return dev_null_handle("altro_batch_simulate_policy");
     if (int rc = simulate_rules(h, "altro_batch_simulate_policy", nsamp, clamp, altro::SimIO{x0, w, J, c_max, dx_max, fb, Xout, Uout})) return rc;
     HIPCHK(h, hipSetDevice(h->device));
-    const size_t B = h->d.batch, N = h->d.N, n = h->d.n, m = h->d.m;
-    const size_t R = B * (size_t)nsamp, c0 = R * n, cw = R * (N - 1) * n, cx = R * N * n, cu = R * (N - 1) * m;
-    const size_t elems = 3 * R + (x0 ? c0 : 0) + (w ? cw : 0) + (Xout ? cx : 0) + (Uout ? cu : 0);
-    const size_t bytes = elems * sizeof(double) + B * sizeof(int32_t);
-    if (int rc = h->wide ? h->wide->ensure_stage(bytes) : ensure_stage(h, bytes)) {
-      if (h->wide) h->err = h->wide->err;
-      return rc;
-    }
-    const hipStream_t st = h->wide ? h->wide->stream : h->stream;
-    double* s = h->wide ? h->wide->stage : h->stage;
-    double *sJ = s, *sc = s + R, *sd = s + 2 * R;
-    s += 3 * R;
-    double* sx0 = x0 ? s : nullptr; s += x0 ? c0 : 0;
-    double* sw = w ? s : nullptr; s += w ? cw : 0;
-    double* sX = Xout ? s : nullptr; s += Xout ? cx : 0;
-    double* sU = Uout ? s : nullptr; s += Uout ? cu : 0;
-    int32_t* sf = reinterpret_cast<int32_t*>(s);
-    if (x0) HIPCHK(h, hipMemcpyAsync(sx0, x0, c0 * sizeof(double), hipMemcpyHostToDevice, st));
-    if (w) HIPCHK(h, hipMemcpyAsync(sw, w, cw * sizeof(double), hipMemcpyHostToDevice, st));
-    const altro::SimIO io{sx0, sw, J ? sJ : nullptr, c_max ? sc : nullptr, dx_max ? sd : nullptr, fb ? sf : nullptr, sX, sU};
+    StageCursor sc(h);
+    altro::stage_simulate(sc, h->d.batch, h->d.N, h->d.n, h->d.m, nsamp, x0, w, J, c_max, dx_max, fb, Xout, Uout);
+    if (int rc = sc.open()) return rc;
+    const altro::SimIO io{sc.f64(altro::SIM_X0), sc.f64(altro::SIM_W), sc.f64(altro::SIM_J), sc.f64(altro::SIM_CMAX),
+                          sc.f64(altro::SIM_DXMAX), sc.i32(altro::SIM_FB), sc.f64(altro::SIM_XOUT), sc.f64(altro::SIM_UOUT)};
     if (int rc = simulate_launch(h, nsamp, clamp, io)) return rc;
-    if (J) HIPCHK(h, hipMemcpyAsync(J, sJ, R * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (c_max) HIPCHK(h, hipMemcpyAsync(c_max, sc, R * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (dx_max) HIPCHK(h, hipMemcpyAsync(dx_max, sd, R * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (fb) HIPCHK(h, hipMemcpyAsync(fb, sf, B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    if (Xout) HIPCHK(h, hipMemcpyAsync(Xout, sX, cx * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (Uout) HIPCHK(h, hipMemcpyAsync(Uout, sU, cu * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    return ALTRO_OK;
+    return sc.close();
   });
 }
 

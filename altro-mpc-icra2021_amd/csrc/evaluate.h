@@ -5,8 +5,12 @@
 // layout); the SCORING kernel reads states and controls from memory in every form, so a rollout followed by a scoring of what
 // it wrote gives the bytes a direct scoring of the same arrays gives.  The kernels read the tables the solve kernels read --
 // dynamics, cost rows, bounds rows, reference window, constraint rows -- and write nothing the library owns.  No
-// synchronisation between waves; LDS only as a wave-private copy of time-invariant dynamics on the one-wave-per-instance backend.  Contraction is off in every function of this file and each fused multiply-add is written out, so the
-// order of every sum is the one stated here:
+// synchronisation between waves; LDS only as a wave-private copy of time-invariant dynamics on the one-wave-per-instance backend.
+// THE SCORING CORE.  This file also holds, once per backend, what every kernel that scores a trajectory is made
+// of -- the kernels here and those of warm_start.h and simulate.h: the context of a row / wave (Ctx16, CtxW), the per-knot
+// score (score16_knot, scorew_knot: cost term, box test, constraint rows), its reduction (score_reduce) and the step of the
+// recurrence (eval16_step, evalw_advance).  Contraction is off in every function that holds a product followed by a sum and
+// each fused multiply-add is written out, so the order of every sum is the one stated here, and here only:
 //   dynamics / constraint row   acc = f_i (b_r); acc = fma(coefficient_j, z_j, acc) for j = 0, 1, ..., n + m - 1 in turn
 //   cost                        every lane adds its own w e^2 (product e * e rounded, then w * (e e), then the addition) knot
 //                               after knot, k = 0 .. N-1; the lanes are then added by an xor butterfly (strides 8, 4, 2, 1, and
@@ -24,6 +28,35 @@ namespace altro {
 
 // max that keeps a NaN once it has seen one (fmax would drop it: an overflowed rollout must not look feasible)
 __device__ __forceinline__ double eval_max(double acc, double v) { return (v > acc || v != v) ? v : acc; }
+
+// sum / eval_max over the W lanes of a row (W = 16) or wave (W = 64): xor butterfly, strides W/2 .. 1, every lane ends with it
+template <int W>
+__device__ __forceinline__ double lanes_sum(double v) {
+  for (int s = W / 2; s > 0; s >>= 1) v += __shfl_xor(v, s, W);
+  return v;
+}
+template <int W>
+__device__ __forceinline__ double lanes_max(double v) {
+  for (int s = W / 2; s > 0; s >>= 1) v = eval_max(v, __shfl_xor(v, s, W));
+  return v;
+}
+
+// one element's term of the tracking cost: w (z - zref)^2, each product rounded
+__device__ __forceinline__ double cost_term(double w, double z, double zref) {
+#pragma clang fp contract(off)
+  const double d = z - zref;
+  double q = d * d;
+  q = w * q;
+  return q;
+}
+
+// one element's box test (the solve kernels' test for a finite side); on = the lane holds the element
+__device__ __forceinline__ double box_max(double viol, bool on, double z, double lo, double hi) {
+  const bool has_hi = hi < 1e300, has_lo = lo > -1e300;
+  if (on && has_hi) viol = eval_max(viol, z - hi);
+  if (on && has_lo) viol = eval_max(viol, lo - z);
+  return viol;
+}
 
 // |Proj(v) - v| of element `pos` of a second-order cone of dimension p (2..4) whose values are v[0..p-1] (v[q] = 0 for
 // q >= p): the oracle's soc_project / con_violation.  Inside the cone 0, in the polar cone |v_pos|, otherwise the distance to
@@ -46,6 +79,22 @@ __device__ __forceinline__ double soc_row_violation(const double (&v)[4], int p,
   return fabs(proj - mine);   // (a NaN anywhere in the cone fails both tests above and comes out here)
 }
 
+// what a scoring kernel accumulates knot after knot, per lane, and what its row / wave has in the end
+struct Score {
+  double cost = 0.0, viol = 0.0;
+};
+template <int W>
+__device__ __forceinline__ void score_reduce(const Score& s, double& J, double& cmax) {
+  J = 0.5 * lanes_sum<W>(s.cost);
+  cmax = lanes_max<W>(s.viol);
+}
+
+__device__ __forceinline__ int eval_window(const int* window, int kref, size_t b, int N, int Nt) {
+  int w = window != nullptr ? window[b] : kref;
+  w = w + N > Nt ? Nt - N : w;   // (the host and the tick rule keep every window inside the track: this never moves one)
+  return w < 0 ? 0 : w;
+}
+
 // ------------------------------------------------------------------ 16-lane backend (SolveParams layout)
 // One 16-lane row per (instance, candidate), four per wave.  rows = batch * ncand padded to whole waves; rows >= R compute on
 // row 0 and store nothing, so EXEC is all ones wherever a DPP move reads another lane.  Lane j < n holds x_j, lane n + a holds
@@ -62,6 +111,22 @@ struct Eval16 {
   int ncrows, N, Nt, n, m, kref, box_k0, box_k1;
 };
 
+// The row a thread works on: r = the row it computes (0 for a padded row, which stores nothing: `live`), b = r / per its
+// instance, `in` = false beyond the padded rows (whole waves: such a thread leaves at once).
+struct Row16 {
+  size_t r, b;
+  int lane;
+  bool live, in, isx, isu;
+};
+__device__ __forceinline__ Row16 eval16_row(size_t R, size_t rows, size_t per, int n, int m) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t row = t / 16;
+  const int lane = (int)(t % 16);
+  const bool live = row < R;
+  const size_t r = live ? row : 0;
+  return {r, r / per, lane, live, row < rows, lane < n, lane >= n && lane < n + m};
+}
+
 // acc + sum_c g[c] * z_c over the 16 lanes of the row, c = 0 .. 15 in turn; g[c] is 0 for c >= n + m, where z_c is 0 too
 __device__ __forceinline__ double row_affine(const double (&g)[16], double acc, double z) {
   sfor<0, 16>([&](auto c) {
@@ -69,12 +134,6 @@ __device__ __forceinline__ double row_affine(const double (&g)[16], double acc, 
     acc = __builtin_fma(g[C], bcast<C>(z), acc);
   });
   return acc;
-}
-
-__device__ __forceinline__ int eval_window(const int* window, int kref, size_t b, int N, int Nt) {
-  int w = window != nullptr ? window[b] : kref;
-  w = w + N > Nt ? Nt - N : w;   // (the host and the tick rule keep every window inside the track: this never moves one)
-  return w < 0 ? 0 : w;
 }
 
 // lane i's column of [A B | f] of instance b: g[c] = [A B][i][c]
@@ -86,19 +145,79 @@ __device__ __forceinline__ void eval16_dyn(const Eval16& P, size_t b, int lane, 
   fv = lane < P.n ? P.fvec[b * 16 + lane] : 0.0;
 }
 
+// the step of the recurrence: the row's z = [x; u; 0] -> x_{k+1} on the state lanes, 0 elsewhere
+__device__ __forceinline__ double eval16_step(const double (&g)[16], double fv, double z, bool isx) {
+  const double nx = row_affine(g, fv, z);
+  return isx ? nx : 0.0;
+}
+
+// what a lane of a row of instance b keeps over the knots to score them
+struct Ctx16 {
+  int lane, pos;
+  bool isx, isu;
+  double wd, wf, zlo, zhi;
+  const double *Zr, *Ac, *bc;   // the lane's element of the reference row / constraint row / constraint offset of knot 0
+  __device__ __forceinline__ Ctx16(const Eval16& P, size_t b, int lane_) : lane(lane_), pos(lane_ & 3) {
+    isx = lane < P.n;
+    isu = lane >= P.n && lane < P.n + P.m;
+    const int kref = eval_window(P.window, P.kref, b, P.N, P.Nt);
+    const unsigned e = ((unsigned)b * 16u + (unsigned)lane) & P.imask;
+    wd = P.wd[e]; wf = P.wf[e]; zlo = P.zmin[e]; zhi = P.zmax[e];
+    Zr = P.Zref + (b * (size_t)P.Nt + (size_t)kref) * 16 + lane;
+    Ac = P.Acon + b * P.con_istride + (size_t)lane * 16;
+    bc = P.bcon + b * (P.con_istride / 16) + lane;
+  }
+};
+
+// the constraint rows of knot k: lane r owns row r of the knot's table (Ac, bc: the lane's row and offset of knot 0); viol comes
+// in and goes out by value
+__device__ __forceinline__ double con16_max(double viol, const Eval16& P, const double* Ac, const double* bc, int pos, int lane, int k,
+                                            double z) {
+  const int n = P.n, m = P.m;
+  if (P.ncrows > 0) {
+    const int* cm = P.cmeta + ((size_t)k * 16 + lane) * 4;
+    const int type = cm[0], p = cm[3];
+    const bool act = type != CT_NONE && k >= cm[1] && k <= cm[2];
+    double a[16], v = 0.0;
+#pragma unroll
+    for (int c = 0; c < 16; ++c) a[c] = 0.0;
+    if (act) {
+      const double* ar = Ac + (size_t)k * 256;
+#pragma unroll
+      for (int c = 0; c < 16; ++c) a[c] = c < n + m ? ar[c] : 0.0;
+      v = bc[(size_t)k * 16];
+    }
+    v = row_affine(a, v, z);
+    const bool is_soc = type == CT_SOC;
+    const bool row_on = act && (!is_soc || pos < p);   // (a linear row may sit in a spare lane of a cone's quad)
+    const double vv = (row_on && is_soc) ? v : 0.0;
+    double vq[4];
+    vq[0] = quad_bcast<0>(vv); vq[1] = quad_bcast<1>(vv); vq[2] = quad_bcast<2>(vv); vq[3] = quad_bcast<3>(vv);
+    const double cv = is_soc ? soc_row_violation(vq, p, pos) : (type == CT_EQ ? fabs(v) : v);
+    if (row_on) viol = eval_max(viol, cv);
+  }
+  return viol;
+}
+
+// knot k of the row: z = the lane's element (0 where the row holds none), zr = the lane's element of the knot's reference row
+// (an argument: k_sim16 loads it a knot ahead)
+__device__ __forceinline__ void score16_knot(Score& s, const Eval16& P, const Ctx16& c, int k, double z, double zr) {
+  const bool term = k == P.N - 1;
+  const bool on = c.isx || (c.isu && !term);
+  const double q = cost_term(term ? c.wf : c.wd, z, zr);
+  s.cost = on ? s.cost + q : s.cost;
+  if (on && k >= P.box_k0 && k <= P.box_k1) s.viol = box_max(s.viol, true, z, c.zlo, c.zhi);
+  s.viol = con16_max(s.viol, P, c.Ac, c.bc, c.pos, c.lane, k, z);
+}
+
 // Rollout: Xw [R][N][n] <- x_0 = x0[b] (x0s = its row stride: n for a caller's array, 16 for the handle's own), then the
 // recursion under U [R][N-1][m].
 __global__ void k_eval_rollout16(double* __restrict__ Xw, const double* __restrict__ U, const double* __restrict__ x0, int x0s, Eval16 P,
                                  int ncand, size_t R, size_t rows) {
 #pragma clang fp contract(off)
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t row = t / 16;
-  const int lane = (int)(t % 16);
-  if (row >= rows) return;   // (whole waves only)
-  const bool live = row < R;
-  const size_t r = live ? row : 0, b = r / (size_t)ncand;
   const int n = P.n, m = P.m, N = P.N;
-  const bool isx = lane < n, isu = lane >= n && lane < n + m;
+  const auto [r, b, lane, live, in, isx, isu] = eval16_row(R, rows, (size_t)ncand, n, m);
+  if (!in) return;
   double g[16], fv;
   eval16_dyn(P, b, lane, g, fv);
   double* Xr = Xw + r * (size_t)N * n;
@@ -108,8 +227,7 @@ __global__ void k_eval_rollout16(double* __restrict__ Xw, const double* __restri
     if (live && isx) Xr[(size_t)k * n + lane] = x;
     if (k == N - 1) break;
     const double z = isx ? x : (isu ? Ur[(size_t)k * m + (lane - n)] : 0.0);
-    const double nx = row_affine(g, fv, z);
-    x = isx ? nx : 0.0;
+    x = eval16_step(g, fv, z, isx);
   }
 }
 
@@ -117,79 +235,39 @@ __global__ void k_eval_rollout16(double* __restrict__ Xw, const double* __restri
 __global__ void k_eval_score16(double* __restrict__ J, double* __restrict__ cmax, double* __restrict__ defect, const double* __restrict__ X,
                                const double* __restrict__ U, Eval16 P, int ncand, size_t R, size_t rows, int given) {
 #pragma clang fp contract(off)
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t row = t / 16;
-  const int lane = (int)(t % 16);
-  if (row >= rows) return;
-  const bool live = row < R;
-  const size_t r = live ? row : 0, b = r / (size_t)ncand;
   const int n = P.n, m = P.m, N = P.N;
-  const bool isx = lane < n, isu = lane >= n && lane < n + m;
+  const auto [r, b, lane, live, in, isx, isu] = eval16_row(R, rows, (size_t)ncand, n, m);
+  if (!in) return;
   const bool want_defect = defect != nullptr && given != 0;
-  const int kref = eval_window(P.window, P.kref, b, N, P.Nt);
-  const unsigned e = ((unsigned)b * 16u + (unsigned)lane) & P.imask;
-  const double wd = P.wd[e], wf = P.wf[e], zlo = P.zmin[e], zhi = P.zmax[e];
-  const bool has_hi = zhi < 1e300, has_lo = zlo > -1e300;   // (the solve kernels' test for a finite side)
+  const Ctx16 c(P, b, lane);
   double g[16], fv = 0.0;
 #pragma unroll
-  for (int c = 0; c < 16; ++c) g[c] = 0.0;
+  for (int j = 0; j < 16; ++j) g[j] = 0.0;
   if (want_defect) eval16_dyn(P, b, lane, g, fv);
   const double* Xr = X + r * (size_t)N * n;
   const double* Ur = U + r * (size_t)(N - 1) * m;
-  const double* Zr = P.Zref + (b * (size_t)P.Nt + (size_t)kref) * 16 + lane;
-  const double* Ac = P.Acon + b * P.con_istride + (size_t)lane * 16;
-  const double* bc = P.bcon + b * (P.con_istride / 16) + lane;
-  const int pos = lane & 3;
-  double cost = 0.0, viol = 0.0, dfc = 0.0;
+  // score16_knot's terms with the defect between the box and the constraint rows, where it always stood
+  Score s;
+  double dfc = 0.0;
   for (int k = 0; k < N; ++k) {
     const bool term = k == N - 1;
     const bool on = isx || (isu && !term);
     const double z = isx ? Xr[(size_t)k * n + lane] : (on ? Ur[(size_t)k * m + (lane - n)] : 0.0);
-    {
-      const double d = z - Zr[(size_t)k * 16];
-      double q = d * d;
-      q = (term ? wf : wd) * q;
-      cost = on ? cost + q : cost;
-    }
-    if (on && k >= P.box_k0 && k <= P.box_k1) {
-      if (has_hi) viol = eval_max(viol, z - zhi);
-      if (has_lo) viol = eval_max(viol, zlo - z);
-    }
+    const double q = cost_term(term ? c.wf : c.wd, z, c.Zr[(size_t)k * 16]);
+    s.cost = on ? s.cost + q : s.cost;
+    if (on && k >= P.box_k0 && k <= P.box_k1) s.viol = box_max(s.viol, true, z, c.zlo, c.zhi);
     if (want_defect && !term) {
       const double pred = row_affine(g, fv, z);
       if (isx) dfc = eval_max(dfc, fabs(pred - Xr[(size_t)(k + 1) * n + lane]));
     }
-    if (P.ncrows > 0) {   // lane r owns constraint row r of the knot's table
-      const int* cm = P.cmeta + ((size_t)k * 16 + lane) * 4;
-      const int type = cm[0], p = cm[3];
-      const bool act = type != CT_NONE && k >= cm[1] && k <= cm[2];
-      double a[16], v = 0.0;
-#pragma unroll
-      for (int c = 0; c < 16; ++c) a[c] = 0.0;
-      if (act) {
-        const double* ar = Ac + (size_t)k * 256;
-#pragma unroll
-        for (int c = 0; c < 16; ++c) a[c] = c < n + m ? ar[c] : 0.0;
-        v = bc[(size_t)k * 16];
-      }
-      v = row_affine(a, v, z);
-      const bool is_soc = type == CT_SOC;
-      const bool row_on = act && (!is_soc || pos < p);   // (a linear row may sit in a spare lane of a cone's quad)
-      const double vv = (row_on && is_soc) ? v : 0.0;
-      double vq[4];
-      vq[0] = quad_bcast<0>(vv); vq[1] = quad_bcast<1>(vv); vq[2] = quad_bcast<2>(vv); vq[3] = quad_bcast<3>(vv);
-      const double cv = is_soc ? soc_row_violation(vq, p, pos) : (type == CT_EQ ? fabs(v) : v);
-      if (row_on) viol = eval_max(viol, cv);
-    }
+    s.viol = con16_max(s.viol, P, c.Ac, c.bc, c.pos, lane, k, z);
   }
-  for (int s = 8; s > 0; s >>= 1) {
-    cost += __shfl_xor(cost, s, 16);
-    viol = eval_max(viol, __shfl_xor(viol, s, 16));
-    dfc = eval_max(dfc, __shfl_xor(dfc, s, 16));
-  }
+  double Jr, cr;
+  score_reduce<16>(s, Jr, cr);
+  dfc = lanes_max<16>(dfc);
   if (!live || lane != 0) return;
-  if (J != nullptr) J[r] = 0.5 * cost;
-  if (cmax != nullptr) cmax[r] = viol;
+  if (J != nullptr) J[r] = Jr;
+  if (cmax != nullptr) cmax[r] = cr;
   if (defect != nullptr) defect[r] = dfc;   // (+0 in the rollout form)
 }
 
@@ -209,10 +287,12 @@ struct EvalW {
   int lds_dyn;   // 1: time-invariant dynamics whose [A | B] block fits: every wave keeps its instance's block in its slice of LDS
 };
 
-// LDS doubles a wave needs for lds_dyn, and the rule for it: four waves of a 256-thread block inside the 64 KB a kernel gets
-// without asking for more (n (n + m) <= 2048: up to (32, 32), (40, 11), ...).  Larger blocks are read from memory at every knot.
+// LDS doubles a wave needs for lds_dyn, the bytes a 256-thread block of four waves asks for, and the rule for it: inside the
+// 64 KB a kernel gets without asking for more (n (n + m) <= 2048: up to (32, 32), (40, 11), ...).  Larger blocks are read
+// from memory at every knot.
 __host__ __device__ inline size_t evalw_lds_doubles(int n, int m) { return (size_t)n * (n + m); }
-__host__ __device__ inline bool evalw_lds_fits(int n, int m, int ltv) { return !ltv && 4 * evalw_lds_doubles(n, m) * sizeof(double) <= 65536; }
+__host__ __device__ inline size_t evalw_lds_bytes(int n, int m) { return 4 * evalw_lds_doubles(n, m) * sizeof(double); }
+__host__ __device__ inline bool evalw_lds_fits(int n, int m, int ltv) { return !ltv && evalw_lds_bytes(n, m) <= 65536; }
 
 __device__ __forceinline__ double eval_readlane(double v, int j) {
   const int lo = __builtin_amdgcn_readlane(__double2loint(v), j), hi = __builtin_amdgcn_readlane(__double2hiint(v), j);
@@ -259,9 +339,12 @@ struct EvalWDyn {
   int kref, Tn;
   const double* lds;   // the wave's [A | B] in LDS, or null
   double f0;
-  __device__ __forceinline__ EvalWDyn(const EvalW& p, size_t b_, int kref_, int T, int Tn_, double* slice, bool wanted)
-      : P(p), b(b_), kref(kref_), Tn(Tn_), lds(nullptr), f0(0.0) {
+  // T: the lane; `wanted` = false: the kernel will not step (no copy)
+  __device__ __forceinline__ EvalWDyn(const EvalW& p, size_t b_, int kref_, int T, bool wanted)
+      : P(p), b(b_), kref(kref_), Tn(T < p.n ? T : p.n - 1), lds(nullptr), f0(0.0) {
     if (!wanted || !P.lds_dyn) return;
+    extern __shared__ double eval_lds[];
+    double* slice = eval_lds + (threadIdx.x >> 6) * evalw_lds_doubles(P.n, P.m);
     const size_t blk = evalw_block(P, b, kref, 0);
     const int na = P.n * P.n, nb = P.n * P.m;
     for (int e = T; e < na; e += 64) slice[e] = P.A[blk * na + e];
@@ -280,6 +363,72 @@ struct EvalWDyn {
   }
 };
 
+// the step of the recurrence: (x, u) of knot k -> x_{k+1} on the state lanes, 0 elsewhere
+__device__ __forceinline__ double evalw_advance(const EvalWDyn& dyn, int k, double x, double u, bool isx) {
+  const double nx = dyn.step(k, x, u);
+  return isx ? nx : 0.0;
+}
+
+// what lane T of a wave of instance b keeps over the knots to score and to step them (members in the order their loads go out)
+struct CtxW {
+  int T;
+  bool isx, isu, isr;
+  int Tn, Tm, kref;
+  double wx, wfx, wu, xlo, xhi, ulo, uhi;
+  const double *Xf, *Uf, *At, *bc;   // reference rows of knot 0; the lane's constraint row / offset of knot 0
+  int c0, cp;
+  EvalWDyn dyn;
+  __device__ __forceinline__ CtxW(const EvalW& P, size_t b, int T_, bool want_dyn)
+      : T(T_), isx(T_ < P.n), isu(T_ < P.m), isr(T_ < P.Pn), Tn(isx ? T_ : P.n - 1), Tm(isu ? T_ : P.m - 1),
+        kref(eval_window(P.window, P.kref, b, P.N, P.Nt)),
+        wx(P.wd[b * (size_t)P.w_pi * (P.n + P.m) + Tn]), wfx(P.wf[b * (size_t)P.w_pi * P.n + Tn]),
+        wu(P.wd[b * (size_t)P.w_pi * (P.n + P.m) + P.n + Tm]),
+        xlo(P.zmin[b * (size_t)P.b_pi * (P.n + P.m) + Tn]), xhi(P.zmax[b * (size_t)P.b_pi * (P.n + P.m) + Tn]),
+        ulo(P.zmin[b * (size_t)P.b_pi * (P.n + P.m) + P.n + Tm]), uhi(P.zmax[b * (size_t)P.b_pi * (P.n + P.m) + P.n + Tm]),
+        Xf(P.Xref + (b * (size_t)P.Nt + (size_t)kref) * P.n), Uf(P.Uref + (b * (size_t)(P.Nt - 1) + (size_t)kref) * P.m),
+        At(P.AconT + b * P.con_istride + (isr ? T_ : 0)), bc(P.bcon + b * P.bcon_istride + (isr ? T_ : 0)),
+        c0(isr ? P.rowc0[T_] : 0), cp(isr ? P.rowcp[T_] : 0), dyn(P, b, kref, T_, want_dyn) {}
+};
+
+// the constraint rows of knot k: lane T < Pn owns row T (At, bc: the lane's row and offset of knot 0; c0, cp: its cone); viol
+// comes in and goes out by value
+__device__ __forceinline__ double conw_max(double viol, const EvalW& P, const double* At, const double* bc, int c0, int cp, bool isr, int T,
+                                           int k, double x, double u) {
+  const int n = P.n, m = P.m, nz = P.n + P.m, Pn = P.Pn;
+  const bool term = k == P.N - 1;
+  if (Pn > 0) {
+    const int ct = isr ? P.ctype[(size_t)k * Pn + T] : 0;
+    const bool on = ct != 0;
+    const double* Ak = At + (size_t)k * nz * Pn;
+    double v = on ? bc[(size_t)k * Pn] : 0.0;
+    v = evalw_dot(Ak, (size_t)Pn, x, n, v, on);
+    if (!term) v = evalw_dot(Ak + (size_t)n * Pn, (size_t)Pn, u, m, v, on);
+    double vq[4];   // (every lane of the wave is here: the shuffles read live lanes)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const double s = __shfl(v, (c0 + q) & 63, 64);
+      vq[q] = q < cp ? s : 0.0;
+    }
+    const double cv = ct == 3 ? soc_row_violation(vq, cp, T - c0) : (ct == 1 ? fabs(v) : v);
+    if (on) viol = eval_max(viol, cv);
+  }
+  return viol;
+}
+
+// knot k of the wave: x, u = the lane's elements (0 where it owns none, u = 0 at the terminal knot)
+__device__ __forceinline__ void scorew_knot(Score& s, const EvalW& P, const CtxW& c, int k, double x, double u) {
+  const int T = c.T;
+  const bool term = k == P.N - 1;
+  const bool uon = c.isu && !term;
+  if (c.isx) s.cost += cost_term(term ? c.wfx : c.wx, x, c.Xf[(size_t)k * P.n + T]);
+  if (uon) s.cost += cost_term(c.wu, u, c.Uf[(size_t)k * P.m + T]);
+  if (k >= P.box_k0 && k <= P.box_k1) {
+    s.viol = box_max(s.viol, c.isx, x, c.xlo, c.xhi);
+    s.viol = box_max(s.viol, uon, u, c.ulo, c.uhi);
+  }
+  s.viol = conw_max(s.viol, P, c.At, c.bc, c.c0, c.cp, c.isr, T, k, x, u);
+}
+
 __global__ void k_eval_rollout_wide(double* __restrict__ Xw, const double* __restrict__ U, const double* __restrict__ x0, EvalW P, int ncand,
                                     size_t R) {
 #pragma clang fp contract(off)
@@ -289,19 +438,15 @@ __global__ void k_eval_rollout_wide(double* __restrict__ Xw, const double* __res
   const size_t b = r / (size_t)ncand;
   const int n = P.n, m = P.m, N = P.N;
   const bool isx = T < n, isu = T < m;
-  const int Tn = isx ? T : n - 1;
-  const int kref = eval_window(P.window, P.kref, b, N, P.Nt);
   double* Xr = Xw + r * (size_t)N * n;
   const double* Ur = U + r * (size_t)(N - 1) * m;
-  extern __shared__ double eval_lds[];
-  const EvalWDyn dyn(P, b, kref, T, Tn, eval_lds + (threadIdx.x >> 6) * evalw_lds_doubles(n, m), true);
+  const EvalWDyn dyn(P, b, eval_window(P.window, P.kref, b, N, P.Nt), T, true);
   double x = isx ? x0[b * (size_t)n + T] : 0.0;
   for (int k = 0;; ++k) {
     if (isx) Xr[(size_t)k * n + T] = x;
     if (k == N - 1) break;
     const double u = isu ? Ur[(size_t)k * m + T] : 0.0;
-    const double nx = dyn.step(k, x, u);
-    x = isx ? nx : 0.0;
+    x = evalw_advance(dyn, k, x, u, isx);
   }
 }
 
@@ -312,79 +457,38 @@ __global__ void k_eval_score_wide(double* __restrict__ J, double* __restrict__ c
   const int T = (int)(threadIdx.x & 63);
   if (r >= R) return;
   const size_t b = r / (size_t)ncand;
-  const int n = P.n, m = P.m, N = P.N, nz = P.n + P.m, Pn = P.Pn;
-  const bool isx = T < n, isu = T < m, isr = T < Pn;
-  const int Tn = isx ? T : n - 1, Tm = isu ? T : m - 1;
+  const int n = P.n, m = P.m, N = P.N;
   const bool want_defect = defect != nullptr && given != 0;
-  const int kref = eval_window(P.window, P.kref, b, N, P.Nt);
-  const double* wdi = P.wd + b * (size_t)P.w_pi * nz;
-  const double* wfi = P.wf + b * (size_t)P.w_pi * n;
-  const double* zlo = P.zmin + b * (size_t)P.b_pi * nz;
-  const double* zhi = P.zmax + b * (size_t)P.b_pi * nz;
-  const double wx = wdi[Tn], wfx = wfi[Tn], wu = wdi[n + Tm];
-  const double xlo = zlo[Tn], xhi = zhi[Tn], ulo = zlo[n + Tm], uhi = zhi[n + Tm];
+  const CtxW c(P, b, T, want_defect);
+  const bool isx = c.isx;
   const double* Xr = X + r * (size_t)N * n;
   const double* Ur = U + r * (size_t)(N - 1) * m;
-  const double* Xf = P.Xref + (b * (size_t)P.Nt + (size_t)kref) * n;
-  const double* Uf = P.Uref + (b * (size_t)(P.Nt - 1) + (size_t)kref) * m;
-  const double* At = P.AconT + b * P.con_istride + (isr ? T : 0);
-  const double* bc = P.bcon + b * P.bcon_istride + (isr ? T : 0);
-  const int c0 = isr ? P.rowc0[T] : 0, cp = isr ? P.rowcp[T] : 0;
-  extern __shared__ double eval_lds[];
-  const EvalWDyn dyn(P, b, kref, T, Tn, eval_lds + (threadIdx.x >> 6) * evalw_lds_doubles(n, m), want_defect);
-  double cost = 0.0, viol = 0.0, dfc = 0.0;
+  Score s;
+  double dfc = 0.0;
   for (int k = 0; k < N; ++k) {
     const bool term = k == N - 1;
-    const bool uon = isu && !term;
     const double x = isx ? Xr[(size_t)k * n + T] : 0.0;
+    const bool uon = c.isu && !term;
     const double u = uon ? Ur[(size_t)k * m + T] : 0.0;
-    if (isx) {
-      const double d = x - Xf[(size_t)k * n + T];
-      double q = d * d;
-      q = (term ? wfx : wx) * q;
-      cost += q;
-    }
-    if (uon) {
-      const double d = u - Uf[(size_t)k * m + T];
-      double q = d * d;
-      q = wu * q;
-      cost += q;
-    }
+    // scorew_knot's terms with the defect between the box and the constraint rows, where it always stood
+    if (isx) s.cost += cost_term(term ? c.wfx : c.wx, x, c.Xf[(size_t)k * n + T]);
+    if (uon) s.cost += cost_term(c.wu, u, c.Uf[(size_t)k * m + T]);
     if (k >= P.box_k0 && k <= P.box_k1) {
-      if (isx && xhi < 1e300) viol = eval_max(viol, x - xhi);
-      if (isx && xlo > -1e300) viol = eval_max(viol, xlo - x);
-      if (uon && uhi < 1e300) viol = eval_max(viol, u - uhi);
-      if (uon && ulo > -1e300) viol = eval_max(viol, ulo - u);
+      s.viol = box_max(s.viol, isx, x, c.xlo, c.xhi);
+      s.viol = box_max(s.viol, uon, u, c.ulo, c.uhi);
     }
     if (want_defect && !term) {
-      const double pred = dyn.step(k, x, u);
+      const double pred = c.dyn.step(k, x, u);
       if (isx) dfc = eval_max(dfc, fabs(pred - Xr[(size_t)(k + 1) * n + T]));
     }
-    if (Pn > 0) {
-      const int ct = isr ? P.ctype[(size_t)k * Pn + T] : 0;
-      const bool on = ct != 0;
-      const double* Ak = At + (size_t)k * nz * Pn;
-      double v = on ? bc[(size_t)k * Pn] : 0.0;
-      v = evalw_dot(Ak, (size_t)Pn, x, n, v, on);
-      if (!term) v = evalw_dot(Ak + (size_t)n * Pn, (size_t)Pn, u, m, v, on);
-      double vq[4];   // (every lane of the wave is here: the shuffles read live lanes)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const double s = __shfl(v, (c0 + q) & 63, 64);
-        vq[q] = q < cp ? s : 0.0;
-      }
-      const double cv = ct == 3 ? soc_row_violation(vq, cp, T - c0) : (ct == 1 ? fabs(v) : v);
-      if (on) viol = eval_max(viol, cv);
-    }
+    s.viol = conw_max(s.viol, P, c.At, c.bc, c.c0, c.cp, c.isr, T, k, x, u);
   }
-  for (int s = 32; s > 0; s >>= 1) {
-    cost += __shfl_xor(cost, s, 64);
-    viol = eval_max(viol, __shfl_xor(viol, s, 64));
-    dfc = eval_max(dfc, __shfl_xor(dfc, s, 64));
-  }
+  double Jr, cr;
+  score_reduce<64>(s, Jr, cr);
+  dfc = lanes_max<64>(dfc);
   if (T != 0) return;
-  if (J != nullptr) J[r] = 0.5 * cost;
-  if (cmax != nullptr) cmax[r] = viol;
+  if (J != nullptr) J[r] = Jr;
+  if (cmax != nullptr) cmax[r] = cr;
   if (defect != nullptr) defect[r] = dfc;
 }
 

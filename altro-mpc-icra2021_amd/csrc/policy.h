@@ -19,14 +19,23 @@ __device__ __forceinline__ double policy_clamp(double u, double lo, double hi) {
   return u > hi ? hi : u;
 }
 
+// Control a of a 16-lane row: kd = the lane's element of gain row a, `on` = the gains are valid and the lane is a state lane.
+// Lane j holds K[a][j] * dx_j (the others +0), the xor butterfly over the row adds them (strides 8, 4, 2, 1: after stride s
+// every lane holds the sum of its aligned group of 16 / s lanes, built pairwise), and lane n + a (`mine`) takes
+// policy_add(zl, sum) for `out`.  The product is rounded before the first addition and IEEE addition commutes, so every lane of
+// the row ends with the same bits.  Every lane of the wave must be here (EXEC all ones at the shuffles).
+__device__ __forceinline__ double policy16_control(double out, double kd, double dx, bool on, bool mine, double zl) {
+#pragma clang fp contract(off)
+  double p = on ? kd * dx : 0.0;
+  for (int s = 8; s > 0; s >>= 1) p += __shfl_xor(p, s, 16);
+  return mine ? policy_add(zl, p) : out;
+}
+
 // 16-lane backend.  One 16-lane row per instance, four instances per wave (256 threads: 16 rows); `rows` = the batch padded to
 // whole waves, rows >= B compute on instance 0 and write nothing.  Zp: [Bp] blocks of (2N + 1) knots x 16 lanes, plane cur[b];
 // lane j < n of knot k holds x_k[j], lane n + a holds u_k[a].  KD [b][k (N)][a][16]: state lane j of gain row a holds K[a][j];
 // the control lanes hold factors of Quu and d and are masked out of the product.  kmu[b] < 0: no valid gains (fb 0).
-// Summation order: lane j holds K[a][j] * dx_j (lanes >= n hold +0), then the xor butterfly over the row with the strides
-// 8, 4, 2, 1 -- after stride s every lane holds the sum of its aligned group of 16 / s lanes, built pairwise.  The product is
-// rounded before the first addition (contraction is off in this kernel) and IEEE addition commutes, so every lane of the row
-// ends with the same bits.
+// Summation order: policy16_control.
 // Bounds: zmin / zmax element (b * 16 + lane) & imask, as the solve kernels address them (imask 15: one shared row).
 __global__ void k_eval_policy(double* __restrict__ u, int* __restrict__ fb, const double* __restrict__ x, const int* __restrict__ knot,
                               const double* __restrict__ Zp, const int* __restrict__ cur, const double* __restrict__ KD,
@@ -48,11 +57,8 @@ __global__ void k_eval_policy(double* __restrict__ u, int* __restrict__ fb, cons
   const double dx = lane < n ? x[b * n + lane] - zl : 0.0;
   const double* kd = KD + ((b * N + k) * m) * LW_ + lane;
   double out = zl;
-  for (int a = 0; a < m; ++a) {
-    double p = (valid && lane < n) ? kd[(size_t)a * LW_] * dx : 0.0;
-    for (int s = 8; s > 0; s >>= 1) p += __shfl_xor(p, s, LW_);
-    if (lane == n + a) out = policy_add(zl, p);
-  }
+  const bool on = valid && lane < n;
+  for (int a = 0; a < m; ++a) out = policy16_control(out, on ? kd[(size_t)a * LW_] : 0.0, dx, on, lane == n + a, zl);
   if (!live) return;
   if (lane == 0 && fb != nullptr) fb[b] = inside ? (valid ? 1 : 0) : -1;
   if (!inside || lane < n || lane >= n + m) return;

@@ -5,12 +5,11 @@
 // and constraint rows in cache.  The state stays in registers: per knot the policy forms u_k from x_k, the pair is consumed for
 // the cost, the box and the constraint rows, and advanced to x_{k+1} (+ w_k) -- no state reaches memory unless the caller asks
 // for Xout / Uout, and no workspace grows with nsamp * N * n.
-// The arithmetic is that of the calls a caller would compose, through their device functions, contraction off and every fused
-// multiply-add written out:
-//   u_k      the bytes k_eval_policy / k_eval_policy_wide write for x = x_k, knot = k (policy.h: the products on their state
-//            lanes and the xor butterfly 8, 4, 2, 1, resp. the fma chain over j; policy_add last; policy_clamp in the box range)
-//   x_{k+1}  row_affine / EvalWDyn::step of evaluate.h; with w one more rounded addition, performed last
-//   J, c_max the per-knot terms, their order, the butterfly and the final * 0.5 of k_eval_score16 / k_eval_score_wide
+// The arithmetic is that of the calls a caller would compose, because the same device functions compute it:
+//   u_k      the bytes k_eval_policy / k_eval_policy_wide write for x = x_k, knot = k (policy.h: policy16_control, resp. the
+//            fma chain over j; policy_add last; policy_clamp in the box range)
+//   x_{k+1}  eval16_step / evalw_advance of evaluate.h; with w one more rounded addition, performed last
+//   J, c_max the scoring core of evaluate.h (score16_knot / scorew_knot, score_reduce)
 //   dx_max   max over k = 0 .. N-1 and i of |x_k[i] - xbar_k[i]| (eval_max: a NaN stays)
 // fb[b]: 1 the stored gains are valid (kmu[b] >= 0, resp. reuse_ok and word 128 of the instance's reuse state), 0 they are not
 // and the loop is open: u_k = ubar_k, clamped if asked.  Nothing the library owns is written.
@@ -50,34 +49,23 @@ __global__ void __launch_bounds__(256)
 k_sim16(SimIO io, const double* __restrict__ Zp, const int* __restrict__ cur, size_t plane, const double* __restrict__ KD,
         const double* __restrict__ kmu, const double* __restrict__ hx0, Eval16 P, int nsamp, int clamp, size_t R, size_t rows) {
 #pragma clang fp contract(off)
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t row = t / 16;
-  const int lane = (int)(t % 16);
-  if (row >= rows) return;   // (whole waves only)
-  const bool live = row < R;
-  const size_t r = live ? row : 0, b = r / (size_t)nsamp;
   const int n = P.n, m = P.m, N = P.N;
-  const bool isx = lane < n, isu = lane >= n && lane < n + m;
+  const auto [r, b, lane, live, in, isx, isu] = eval16_row(R, rows, (size_t)nsamp, n, m);
+  if (!in) return;   // (whole waves only)
   const bool valid = !(kmu[b] < 0.0);
-  const int kref = eval_window(P.window, P.kref, b, N, P.Nt);
-  const unsigned e = ((unsigned)b * 16u + (unsigned)lane) & P.imask;
-  const double wd = P.wd[e], wf = P.wf[e], zlo = P.zmin[e], zhi = P.zmax[e];
-  const bool has_hi = zhi < 1e300, has_lo = zlo > -1e300;   // (the solve kernels' test for a finite side)
+  const Ctx16 c(P, b, lane);
   double g[16], fv;
   eval16_dyn(P, b, lane, g, fv);
   const double* Zn = Zp + b * (2 * (size_t)N + 1) * 16 + (size_t)cur[b] * plane + lane;
   const double* kdp = KD + b * (size_t)N * m * 16 + lane;
-  const double* Zr = P.Zref + (b * (size_t)P.Nt + (size_t)kref) * 16 + lane;
-  const double* Ac = P.Acon + b * P.con_istride + (size_t)lane * 16;
-  const double* bc = P.bcon + b * (P.con_istride / 16) + lane;
   const double* wr = io.w != nullptr ? io.w + r * (size_t)(N - 1) * n + (isx ? lane : 0) : nullptr;
   double* Xr = io.Xout != nullptr ? io.Xout + r * (size_t)N * n + (isx ? lane : 0) : nullptr;
   double* Ur = io.Uout != nullptr ? io.Uout + r * (size_t)(N - 1) * m + (isu ? lane - n : 0) : nullptr;
-  const int pos = lane & 3;
-  double cost = 0.0, viol = 0.0, dxm = 0.0;
+  Score s;
+  double dxm = 0.0;
   double x = isx ? (io.x0 != nullptr ? io.x0[r * (size_t)n + lane] : hx0[b * 16 + lane]) : 0.0;
   // knot 0's loads
-  double kd_n[16], zl_n = Zn[0], zr_n = Zr[0], w_n = (wr != nullptr && isx) ? wr[0] : 0.0;
+  double kd_n[16], zl_n = Zn[0], zr_n = c.Zr[0], w_n = (wr != nullptr && isx) ? wr[0] : 0.0;
 #pragma unroll
   for (int a = 0; a < 16; ++a) kd_n[a] = (a < m && valid && isx) ? kdp[(size_t)a * 16] : 0.0;
   for (int k = 0; k < N; ++k) {
@@ -90,7 +78,7 @@ k_sim16(SimIO io, const double* __restrict__ Zp, const int* __restrict__ cur, si
     if (!term) {   // the next knot's loads go out ahead of this knot's chain (knot N - 1 has a gain block too: KD holds N)
       const size_t k1 = (size_t)k + 1;
       zl_n = Zn[k1 * 16];
-      zr_n = Zr[k1 * 16];
+      zr_n = c.Zr[k1 * 16];
       w_n = (wr != nullptr && isx && k1 < (size_t)(N - 1)) ? wr[k1 * n] : 0.0;
 #pragma unroll
       for (int a = 0; a < 16; ++a) kd_n[a] = (a < m && valid && isx) ? kdp[(k1 * m + a) * 16] : 0.0;
@@ -101,65 +89,25 @@ k_sim16(SimIO io, const double* __restrict__ Zp, const int* __restrict__ cur, si
     double out = zl;
     if (!term) {
 #pragma unroll
-      for (int a = 0; a < 16; ++a) {
-        if (a < m) {   // (uniform: EXEC stays all ones at the shuffles)
-          double p = (valid && isx) ? kd[a] * dx : 0.0;
-          for (int s = 8; s > 0; s >>= 1) p += __shfl_xor(p, s, 16);
-          if (lane == n + a) out = policy_add(zl, p);
-        }
-      }
-      if (clamp && isu && k >= P.box_k0 && k <= P.box_k1) out = policy_clamp(out, zlo, zhi);
+      for (int a = 0; a < 16; ++a)
+        if (a < m) out = policy16_control(out, kd[a], dx, valid && isx, lane == n + a, zl);   // (uniform: EXEC stays all ones at the shuffles)
+      if (clamp && isu && k >= P.box_k0 && k <= P.box_k1) out = policy_clamp(out, c.zlo, c.zhi);
     }
     const double z = isx ? x : (on ? out : 0.0);
     if (live && isx && Xr != nullptr) Xr[(size_t)k * n] = x;
     if (live && on && !isx && Ur != nullptr) Ur[(size_t)k * m] = z;
-    // the score (k_eval_score16)
-    {
-      const double d = z - zr;
-      double q = d * d;
-      q = (term ? wf : wd) * q;
-      cost = on ? cost + q : cost;
-    }
-    if (on && k >= P.box_k0 && k <= P.box_k1) {
-      if (has_hi) viol = eval_max(viol, z - zhi);
-      if (has_lo) viol = eval_max(viol, zlo - z);
-    }
-    if (P.ncrows > 0) {   // lane r owns constraint row r of the knot's table
-      const int* cm = P.cmeta + ((size_t)k * 16 + lane) * 4;
-      const int type = cm[0], p = cm[3];
-      const bool act = type != CT_NONE && k >= cm[1] && k <= cm[2];
-      double a[16], v = 0.0;
-#pragma unroll
-      for (int q = 0; q < 16; ++q) a[q] = 0.0;
-      if (act) {
-        const double* ar = Ac + (size_t)k * 256;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) a[q] = q < n + m ? ar[q] : 0.0;
-        v = bc[(size_t)k * 16];
-      }
-      v = row_affine(a, v, z);
-      const bool is_soc = type == CT_SOC;
-      const bool row_on = act && (!is_soc || pos < p);
-      const double vv = (row_on && is_soc) ? v : 0.0;
-      double vq[4];
-      vq[0] = quad_bcast<0>(vv); vq[1] = quad_bcast<1>(vv); vq[2] = quad_bcast<2>(vv); vq[3] = quad_bcast<3>(vv);
-      const double cv = is_soc ? soc_row_violation(vq, p, pos) : (type == CT_EQ ? fabs(v) : v);
-      if (row_on) viol = eval_max(viol, cv);
-    }
+    score16_knot(s, P, c, k, z, zr);
     if (!term) {   // z is consumed: advance it in registers
-      double nx = row_affine(g, fv, z);
-      if (wr != nullptr) nx = nx + wk;
-      x = isx ? nx : 0.0;
+      x = eval16_step(g, fv, z, isx);
+      if (wr != nullptr) x = x + wk;   // (wk is 0 off the state lanes)
     }
   }
-  for (int s = 8; s > 0; s >>= 1) {
-    cost += __shfl_xor(cost, s, 16);
-    viol = eval_max(viol, __shfl_xor(viol, s, 16));
-    dxm = eval_max(dxm, __shfl_xor(dxm, s, 16));
-  }
+  double Jr, cr;
+  score_reduce<16>(s, Jr, cr);
+  dxm = lanes_max<16>(dxm);
   if (!live || lane != 0) return;
-  if (io.J != nullptr) io.J[r] = 0.5 * cost;
-  if (io.cmax != nullptr) io.cmax[r] = viol;
+  if (io.J != nullptr) io.J[r] = Jr;
+  if (io.cmax != nullptr) io.cmax[r] = cr;
   if (io.dxmax != nullptr) io.dxmax[r] = dxm;
   if (io.fb != nullptr && r == b * (size_t)nsamp) io.fb[b] = valid ? 1 : 0;
 }
@@ -177,32 +125,19 @@ k_sim_wide(SimIO io, const double* __restrict__ Xp, const double* __restrict__ U
   const int T = (int)(threadIdx.x & 63);
   if (r >= R) return;   // (whole waves)
   const size_t b = r / (size_t)nsamp;
-  const int n = P.n, m = P.m, N = P.N, nz = P.n + P.m, Pn = P.Pn;
-  const bool isx = T < n, isu = T < m, isr = T < Pn;
-  const int Tn = isx ? T : n - 1, Tm = isu ? T : m - 1;
+  const int n = P.n, m = P.m, N = P.N;
   const bool valid = reuse_ok != 0 && bwst[b * 136 + 128] != 0u;
-  const int kref = eval_window(P.window, P.kref, b, N, P.Nt);
-  const double* wdi = P.wd + b * (size_t)P.w_pi * nz;
-  const double* wfi = P.wf + b * (size_t)P.w_pi * n;
-  const double* zlo = P.zmin + b * (size_t)P.b_pi * nz;
-  const double* zhi = P.zmax + b * (size_t)P.b_pi * nz;
-  const double wx = wdi[Tn], wfx = wfi[Tn], wu = wdi[n + Tm];
-  const double xlo = zlo[Tn], xhi = zhi[Tn], ulo = zlo[n + Tm], uhi = zhi[n + Tm];
+  const CtxW c(P, b, T, true);
+  const bool isx = c.isx, isu = c.isu;
   const size_t pl = b * 2 + (size_t)cur[b];
-  const double* Xn = Xp + pl * (size_t)N * n + Tn;
-  const double* Un = Up + pl * (size_t)(N - 1) * m + Tm;
-  const double* kg = Kg + b * (size_t)(N - 1) * n * m + Tm;
-  const double* Xf = P.Xref + (b * (size_t)P.Nt + (size_t)kref) * n;
-  const double* Uf = P.Uref + (b * (size_t)(P.Nt - 1) + (size_t)kref) * m;
-  const double* At = P.AconT + b * P.con_istride + (isr ? T : 0);
-  const double* bc = P.bcon + b * P.bcon_istride + (isr ? T : 0);
-  const int c0 = isr ? P.rowc0[T] : 0, cp = isr ? P.rowcp[T] : 0;
-  const double* wr = io.w != nullptr ? io.w + r * (size_t)(N - 1) * n + Tn : nullptr;
-  double* Xr = io.Xout != nullptr ? io.Xout + r * (size_t)N * n + Tn : nullptr;
-  double* Ur = io.Uout != nullptr ? io.Uout + r * (size_t)(N - 1) * m + Tm : nullptr;
-  extern __shared__ double eval_lds[];
-  const EvalWDyn dyn(P, b, kref, T, Tn, eval_lds + (threadIdx.x >> 6) * evalw_lds_doubles(n, m), true);
-  double cost = 0.0, viol = 0.0, dxm = 0.0;
+  const double* Xn = Xp + pl * (size_t)N * n + c.Tn;
+  const double* Un = Up + pl * (size_t)(N - 1) * m + c.Tm;
+  const double* kg = Kg + b * (size_t)(N - 1) * n * m + c.Tm;
+  const double* wr = io.w != nullptr ? io.w + r * (size_t)(N - 1) * n + c.Tn : nullptr;
+  double* Xr = io.Xout != nullptr ? io.Xout + r * (size_t)N * n + c.Tn : nullptr;
+  double* Ur = io.Uout != nullptr ? io.Uout + r * (size_t)(N - 1) * m + c.Tm : nullptr;
+  Score s;
+  double dxm = 0.0;
   double x = isx ? (io.x0 != nullptr ? io.x0[r * (size_t)n + T] : hx0[b * (size_t)n + T]) : 0.0;
   for (int k = 0; k < N; ++k) {
     const bool term = k == N - 1;
@@ -212,63 +147,26 @@ k_sim_wide(SimIO io, const double* __restrict__ Xp, const double* __restrict__ U
     if (isx) dxm = eval_max(dxm, fabs(dx));
     double u = 0.0;
     if (!term) {   // the policy (k_eval_policy_wide); every lane of the wave walks the chain, lanes >= m on row m - 1
-      double s = 0.0;
-      if (valid) s = evalw_dot(kg + (size_t)k * n * m, (size_t)m, dx, n, 0.0, true);
-      double out = policy_add(Un[(size_t)k * m], s);
-      if (clamp && k >= P.box_k0 && k <= P.box_k1) out = policy_clamp(out, ulo, uhi);
+      double sum = 0.0;
+      if (valid) sum = evalw_dot(kg + (size_t)k * n * m, (size_t)m, dx, n, 0.0, true);
+      double out = policy_add(Un[(size_t)k * m], sum);
+      if (clamp && k >= P.box_k0 && k <= P.box_k1) out = policy_clamp(out, c.ulo, c.uhi);
       u = isu ? out : 0.0;
     }
     if (isx && Xr != nullptr) Xr[(size_t)k * n] = x;
     if (uon && Ur != nullptr) Ur[(size_t)k * m] = u;
-    // the score (k_eval_score_wide)
-    if (isx) {
-      const double d = x - Xf[(size_t)k * n + T];
-      double q = d * d;
-      q = (term ? wfx : wx) * q;
-      cost += q;
-    }
-    if (uon) {
-      const double d = u - Uf[(size_t)k * m + T];
-      double q = d * d;
-      q = wu * q;
-      cost += q;
-    }
-    if (k >= P.box_k0 && k <= P.box_k1) {
-      if (isx && xhi < 1e300) viol = eval_max(viol, x - xhi);
-      if (isx && xlo > -1e300) viol = eval_max(viol, xlo - x);
-      if (uon && uhi < 1e300) viol = eval_max(viol, u - uhi);
-      if (uon && ulo > -1e300) viol = eval_max(viol, ulo - u);
-    }
-    if (Pn > 0) {
-      const int ct = isr ? P.ctype[(size_t)k * Pn + T] : 0;
-      const bool on = ct != 0;
-      const double* Ak = At + (size_t)k * nz * Pn;
-      double v = on ? bc[(size_t)k * Pn] : 0.0;
-      v = evalw_dot(Ak, (size_t)Pn, x, n, v, on);
-      if (!term) v = evalw_dot(Ak + (size_t)n * Pn, (size_t)Pn, u, m, v, on);
-      double vq[4];   // (every lane of the wave is here: the shuffles read live lanes)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const double s = __shfl(v, (c0 + q) & 63, 64);
-        vq[q] = q < cp ? s : 0.0;
-      }
-      const double cv = ct == 3 ? soc_row_violation(vq, cp, T - c0) : (ct == 1 ? fabs(v) : v);
-      if (on) viol = eval_max(viol, cv);
-    }
+    scorew_knot(s, P, c, k, x, u);
     if (!term) {   // x, u are consumed: advance in registers
-      double nx = dyn.step(k, x, u);
-      if (wr != nullptr) nx = nx + wk;
-      x = isx ? nx : 0.0;
+      x = evalw_advance(c.dyn, k, x, u, isx);
+      if (wr != nullptr && isx) x = x + wk;
     }
   }
-  for (int s = 32; s > 0; s >>= 1) {
-    cost += __shfl_xor(cost, s, 64);
-    viol = eval_max(viol, __shfl_xor(viol, s, 64));
-    dxm = eval_max(dxm, __shfl_xor(dxm, s, 64));
-  }
+  double Jr, cr;
+  score_reduce<64>(s, Jr, cr);
+  dxm = lanes_max<64>(dxm);
   if (T != 0) return;
-  if (io.J != nullptr) io.J[r] = 0.5 * cost;
-  if (io.cmax != nullptr) io.cmax[r] = viol;
+  if (io.J != nullptr) io.J[r] = Jr;
+  if (io.cmax != nullptr) io.cmax[r] = cr;
   if (io.dxmax != nullptr) io.dxmax[r] = dxm;
   if (io.fb != nullptr && r == b * (size_t)nsamp) io.fb[b] = valid ? 1 : 0;
 }

@@ -1,0 +1,81 @@
+// stage_layout.h -- where the arrays of a host twin (altro_batch_evaluate, altro_batch_warm_start, altro_batch_simulate_policy)
+// sit in the handle's staging buffer.  Plain host arithmetic, no HIP: altro_batch.hip's StageCursor adds the copies, and
+// tools/stage_layout_check.cpp runs this file alone on the CPU against the sizes and offsets written out by hand.
+#pragma once
+#include <cassert>
+#include <cstddef>
+#include <cstdint>
+
+namespace altro {
+
+// Consecutive sub-arrays of the staging buffer, in the order they are added.
+struct StageLayout {
+  enum Mode {
+    OPTIONAL,   // room only when the caller passes the array; the kernels get null otherwise
+    RESERVED,   // room either way; the kernels get null when the caller passes no array
+    KEPT        // room either way, and the kernels get the sub-array either way (they read it themselves)
+  };
+  struct Slot {
+    size_t off, bytes;   // bytes = 0: no room
+    const void* in;      // copied to the device before the launch, or null
+    void* out;           // copied back after it, or null
+    bool dev;            // the kernels get the sub-array
+  };
+  static constexpr int MAX_SLOTS = 8;
+  Slot slot[MAX_SLOTS] = {};
+  int nslots = 0;
+  size_t bytes = 0;
+
+  template <class T>
+  void add(size_t count, const T* in, T* out, Mode mode) {
+    const bool present = in != nullptr || out != nullptr;
+    assert(nslots < MAX_SLOTS);   // (a twin with more sub-arrays raises MAX_SLOTS)
+    Slot& s = slot[nslots++];
+    s.off = bytes;
+    s.bytes = (present || mode != OPTIONAL) ? count * sizeof(T) : 0;
+    s.in = in;
+    s.out = out;
+    s.dev = present || mode == KEPT;
+    bytes += s.bytes;
+  }
+};
+
+// the slots of each twin, in the order of its layout
+enum { EV_J, EV_CMAX, EV_DEFECT, EV_U, EV_X, EV_X0, EV_XOUT };
+inline void stage_evaluate(StageLayout& L, size_t B, size_t N, size_t n, size_t m, size_t ncand, const double* U, const double* X,
+                           const double* x0, double* J, double* c_max, double* defect, double* Xout) {
+  const size_t R = B * ncand, cu = R * (N - 1) * m, cx = R * N * n;
+  L.add<double>(R, nullptr, J, StageLayout::RESERVED);
+  L.add<double>(R, nullptr, c_max, StageLayout::RESERVED);
+  L.add<double>(R, nullptr, defect, StageLayout::RESERVED);
+  L.add<double>(cu, U, nullptr, StageLayout::OPTIONAL);
+  L.add<double>(cx, X, nullptr, StageLayout::OPTIONAL);
+  L.add<double>(B * n, x0, nullptr, StageLayout::OPTIONAL);
+  L.add<double>(cx, nullptr, Xout, StageLayout::OPTIONAL);
+}
+
+enum { WS_J, WS_CMAX, WS_U, WS_CHOSEN };
+inline void stage_warm_start(StageLayout& L, size_t B, size_t N, size_t m, size_t ncand, size_t inc, const double* U, int32_t* chosen,
+                             double* J, double* c_max) {
+  const size_t R1 = B * (ncand + inc);
+  L.add<double>(R1, nullptr, J, StageLayout::KEPT);   // (the install kernel reads the merits)
+  L.add<double>(R1, nullptr, c_max, StageLayout::KEPT);
+  L.add<double>(B * ncand * (N - 1) * m, U, nullptr, StageLayout::KEPT);
+  L.add<int32_t>(B, nullptr, chosen, StageLayout::KEPT);
+}
+
+enum { SIM_J, SIM_CMAX, SIM_DXMAX, SIM_X0, SIM_W, SIM_XOUT, SIM_UOUT, SIM_FB };
+inline void stage_simulate(StageLayout& L, size_t B, size_t N, size_t n, size_t m, size_t nsamp, const double* x0, const double* w, double* J,
+                           double* c_max, double* dx_max, int32_t* fb, double* Xout, double* Uout) {
+  const size_t R = B * nsamp;
+  L.add<double>(R, nullptr, J, StageLayout::RESERVED);
+  L.add<double>(R, nullptr, c_max, StageLayout::RESERVED);
+  L.add<double>(R, nullptr, dx_max, StageLayout::RESERVED);
+  L.add<double>(R * n, x0, nullptr, StageLayout::OPTIONAL);
+  L.add<double>(R * (N - 1) * n, w, nullptr, StageLayout::OPTIONAL);
+  L.add<double>(R * N * n, nullptr, Xout, StageLayout::OPTIONAL);
+  L.add<double>(R * (N - 1) * m, nullptr, Uout, StageLayout::OPTIONAL);
+  L.add<int32_t>(B, nullptr, fb, StageLayout::RESERVED);
+}
+
+}  // namespace altro

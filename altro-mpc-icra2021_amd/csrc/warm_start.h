@@ -7,10 +7,9 @@
 // ncand), its controls read from plane cur[b].  The SELECT-AND-INSTALL kernel takes one row / wave per instance: it walks the
 // instance's merits in the stated order, writes `chosen`, tests the active mask and rolls the winner out once more, straight
 // into plane cur[b] -- one extra rollout per instance instead of ncand state planes.
-// The arithmetic is evaluate.h's, through its device functions (row_affine, evalw_step, eval_max, soc_row_violation, the
-// window rule), contraction off and every fused multiply-add written out: the states are those k_eval_rollout16 /
-// k_eval_rollout_wide write, and J, c_max are the bytes k_eval_score16 / k_eval_score_wide give for them (the per-knot terms,
-// their order, the xor butterfly and the final * 0.5 are restated here term by term).
+// The arithmetic is the scoring core's (evaluate.h: Ctx16 / CtxW, score16_knot / scorew_knot, score_reduce, eval16_step /
+// evalw_advance): the states are those k_eval_rollout16 / k_eval_rollout_wide write, and J, c_max are the bytes
+// k_eval_score16 / k_eval_score_wide give for them, because the same functions compute them.
 //   merit = fma(rho, c_max, J) (one rounding); best = +Inf, chosen = -1; the incumbent first, then c = 0 .. ncand-1; a
 //   candidate takes over only if merit < best -- ties stay with the earlier visit, a NaN or +Inf merit never wins.
 #pragma once
@@ -66,77 +65,30 @@ __global__ void k_ws_score16(double* __restrict__ J, double* __restrict__ cmax, 
                              const int* __restrict__ cur, size_t plane, const double* __restrict__ x0, Eval16 P, int ncand, int inc, size_t R,
                              size_t rows) {
 #pragma clang fp contract(off)
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t row = t / 16;
-  const int lane = (int)(t % 16);
-  if (row >= rows) return;   // (whole waves only)
-  const bool live = row < R;
-  const size_t r = live ? row : 0, nc1 = (size_t)(ncand + inc), b = r / nc1;
-  const int c = (int)(r - b * nc1);
   const int n = P.n, m = P.m, N = P.N;
-  const bool isx = lane < n, isu = lane >= n && lane < n + m;
-  const int kref = eval_window(P.window, P.kref, b, N, P.Nt);
-  const unsigned e = ((unsigned)b * 16u + (unsigned)lane) & P.imask;
-  const double wd = P.wd[e], wf = P.wf[e], zlo = P.zmin[e], zhi = P.zmax[e];
-  const bool has_hi = zhi < 1e300, has_lo = zlo > -1e300;   // (the solve kernels' test for a finite side)
+  const size_t nc1 = (size_t)(ncand + inc);
+  const auto [r, b, lane, live, in, isx, isu] = eval16_row(R, rows, nc1, n, m);
+  if (!in) return;   // (whole waves only)
+  const int c = (int)(r - b * nc1);
+  const Ctx16 cx(P, b, lane);
   double g[16], fv;
   eval16_dyn(P, b, lane, g, fv);
   size_t us;
   const double* up = ws16_controls(U, Zp, cur, plane, b, c, ncand, N, n, m, lane, isu, us);
-  const double* Zr = P.Zref + (b * (size_t)P.Nt + (size_t)kref) * 16 + lane;
-  const double* Ac = P.Acon + b * P.con_istride + (size_t)lane * 16;
-  const double* bc = P.bcon + b * (P.con_istride / 16) + lane;
-  const int pos = lane & 3;
-  double cost = 0.0, viol = 0.0;
+  Score s;
   double x = isx ? x0[b * 16 + lane] : 0.0;
   for (int k = 0; k < N; ++k) {
     const bool term = k == N - 1;
     const bool on = isx || (isu && !term);
     const double z = isx ? x : (on ? up[(size_t)k * us] : 0.0);
-    {
-      const double d = z - Zr[(size_t)k * 16];
-      double q = d * d;
-      q = (term ? wf : wd) * q;
-      cost = on ? cost + q : cost;
-    }
-    if (on && k >= P.box_k0 && k <= P.box_k1) {
-      if (has_hi) viol = eval_max(viol, z - zhi);
-      if (has_lo) viol = eval_max(viol, zlo - z);
-    }
-    if (P.ncrows > 0) {   // lane r owns constraint row r of the knot's table
-      const int* cm = P.cmeta + ((size_t)k * 16 + lane) * 4;
-      const int type = cm[0], p = cm[3];
-      const bool act = type != CT_NONE && k >= cm[1] && k <= cm[2];
-      double a[16], v = 0.0;
-#pragma unroll
-      for (int q = 0; q < 16; ++q) a[q] = 0.0;
-      if (act) {
-        const double* ar = Ac + (size_t)k * 256;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) a[q] = q < n + m ? ar[q] : 0.0;
-        v = bc[(size_t)k * 16];
-      }
-      v = row_affine(a, v, z);
-      const bool is_soc = type == CT_SOC;
-      const bool row_on = act && (!is_soc || pos < p);
-      const double vv = (row_on && is_soc) ? v : 0.0;
-      double vq[4];
-      vq[0] = quad_bcast<0>(vv); vq[1] = quad_bcast<1>(vv); vq[2] = quad_bcast<2>(vv); vq[3] = quad_bcast<3>(vv);
-      const double cv = is_soc ? soc_row_violation(vq, p, pos) : (type == CT_EQ ? fabs(v) : v);
-      if (row_on) viol = eval_max(viol, cv);
-    }
-    if (!term) {   // z is consumed: advance it in registers
-      const double nx = row_affine(g, fv, z);
-      x = isx ? nx : 0.0;
-    }
+    score16_knot(s, P, cx, k, z, cx.Zr[(size_t)k * 16]);
+    if (!term) x = eval16_step(g, fv, z, isx);   // z is consumed: advance it in registers
   }
-  for (int s = 8; s > 0; s >>= 1) {
-    cost += __shfl_xor(cost, s, 16);
-    viol = eval_max(viol, __shfl_xor(viol, s, 16));
-  }
+  double Jr, cr;
+  score_reduce<16>(s, Jr, cr);
   if (!live || lane != 0) return;
-  J[r] = 0.5 * cost;
-  cmax[r] = viol;
+  J[r] = Jr;
+  cmax[r] = cr;
 }
 
 // One row per instance slot (Bp of them, padded to whole waves; a padded slot mirrors instance B - 1, as k_pack_traj has it).
@@ -147,21 +99,16 @@ __global__ void k_ws_install16(int* __restrict__ chosen, const double* __restric
                                const double* __restrict__ x0, const int* __restrict__ active, Eval16 P, int ncand, int inc, double rho, int B,
                                int Bp, size_t rows) {
 #pragma clang fp contract(off)
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t row = t / 16;
-  const int lane = (int)(t % 16);
-  if (row >= rows) return;   // (whole waves only)
-  const bool slot = row < (size_t)Bp;
-  const size_t inst = slot ? row : 0;
-  const size_t b = inst < (size_t)B ? inst : (size_t)B - 1;
+  const int n = P.n, m = P.m, N = P.N;
+  const auto [inst, b0, lane, slot, in, isx, isu] = eval16_row((size_t)Bp, rows, 1, n, m);
+  if (!in) return;   // (whole waves only)
+  const size_t b = b0 < (size_t)B ? b0 : (size_t)B - 1;
   const size_t nc1 = (size_t)(ncand + inc);
   const bool masked = active != nullptr && active[inst] == 0;
   int w = ws_select(J + b * nc1, cmax + b * nc1, ncand, inc, rho);
   if (slot && inst < (size_t)B && lane == 0 && chosen != nullptr) chosen[inst] = masked ? WS_INACTIVE : w;
   const bool store = slot && !masked && w >= 0 && w <= ncand && (w < ncand || inc != 0);   // (the winner is range-checked before it addresses anything)
   if (!store) w = 0;
-  const int n = P.n, m = P.m, N = P.N;
-  const bool isx = lane < n, isu = lane >= n && lane < n + m;
   double g[16], fv;
   eval16_dyn(P, b, lane, g, fv);
   size_t us;
@@ -175,10 +122,7 @@ __global__ void k_ws_install16(int* __restrict__ chosen, const double* __restric
     const bool on = isx || (isu && !term);
     const double z = isx ? x : (on ? up[(size_t)k * us] : 0.0);
     if (store) dst[(size_t)k * 16] = z;
-    if (!term) {
-      const double nx = row_affine(g, fv, z);
-      x = isx ? nx : 0.0;
-    }
+    if (!term) x = eval16_step(g, fv, z, isx);
   }
 }
 
@@ -199,76 +143,23 @@ __global__ void k_ws_score_wide(double* __restrict__ J, double* __restrict__ cma
   if (r >= R) return;   // (whole waves)
   const size_t nc1 = (size_t)(ncand + inc), b = r / nc1;
   const int c = (int)(r - b * nc1);
-  const int n = P.n, m = P.m, N = P.N, nz = P.n + P.m, Pn = P.Pn;
-  const bool isx = T < n, isu = T < m, isr = T < Pn;
-  const int Tn = isx ? T : n - 1, Tm = isu ? T : m - 1;
-  const int kref = eval_window(P.window, P.kref, b, N, P.Nt);
-  const double* wdi = P.wd + b * (size_t)P.w_pi * nz;
-  const double* wfi = P.wf + b * (size_t)P.w_pi * n;
-  const double* zlo = P.zmin + b * (size_t)P.b_pi * nz;
-  const double* zhi = P.zmax + b * (size_t)P.b_pi * nz;
-  const double wx = wdi[Tn], wfx = wfi[Tn], wu = wdi[n + Tm];
-  const double xlo = zlo[Tn], xhi = zhi[Tn], ulo = zlo[n + Tm], uhi = zhi[n + Tm];
+  const int n = P.n, m = P.m, N = P.N;
+  const CtxW cx(P, b, T, true);
+  const bool isx = cx.isx;
   const double* Ur = wsw_controls(U, Up, cur, b, c, ncand, N, m);
-  const double* Xf = P.Xref + (b * (size_t)P.Nt + (size_t)kref) * n;
-  const double* Uf = P.Uref + (b * (size_t)(P.Nt - 1) + (size_t)kref) * m;
-  const double* At = P.AconT + b * P.con_istride + (isr ? T : 0);
-  const double* bc = P.bcon + b * P.bcon_istride + (isr ? T : 0);
-  const int c0 = isr ? P.rowc0[T] : 0, cp = isr ? P.rowcp[T] : 0;
-  extern __shared__ double eval_lds[];
-  const EvalWDyn dyn(P, b, kref, T, Tn, eval_lds + (threadIdx.x >> 6) * evalw_lds_doubles(n, m), true);
-  double cost = 0.0, viol = 0.0;
+  Score s;
   double x = isx ? x0[b * (size_t)n + T] : 0.0;
   for (int k = 0; k < N; ++k) {
     const bool term = k == N - 1;
-    const bool uon = isu && !term;
-    const double u = uon ? Ur[(size_t)k * m + T] : 0.0;
-    if (isx) {
-      const double d = x - Xf[(size_t)k * n + T];
-      double q = d * d;
-      q = (term ? wfx : wx) * q;
-      cost += q;
-    }
-    if (uon) {
-      const double d = u - Uf[(size_t)k * m + T];
-      double q = d * d;
-      q = wu * q;
-      cost += q;
-    }
-    if (k >= P.box_k0 && k <= P.box_k1) {
-      if (isx && xhi < 1e300) viol = eval_max(viol, x - xhi);
-      if (isx && xlo > -1e300) viol = eval_max(viol, xlo - x);
-      if (uon && uhi < 1e300) viol = eval_max(viol, u - uhi);
-      if (uon && ulo > -1e300) viol = eval_max(viol, ulo - u);
-    }
-    if (Pn > 0) {
-      const int ct = isr ? P.ctype[(size_t)k * Pn + T] : 0;
-      const bool on = ct != 0;
-      const double* Ak = At + (size_t)k * nz * Pn;
-      double v = on ? bc[(size_t)k * Pn] : 0.0;
-      v = evalw_dot(Ak, (size_t)Pn, x, n, v, on);
-      if (!term) v = evalw_dot(Ak + (size_t)n * Pn, (size_t)Pn, u, m, v, on);
-      double vq[4];   // (every lane of the wave is here: the shuffles read live lanes)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const double s = __shfl(v, (c0 + q) & 63, 64);
-        vq[q] = q < cp ? s : 0.0;
-      }
-      const double cv = ct == 3 ? soc_row_violation(vq, cp, T - c0) : (ct == 1 ? fabs(v) : v);
-      if (on) viol = eval_max(viol, cv);
-    }
-    if (!term) {   // x, u are consumed: advance in registers
-      const double nx = dyn.step(k, x, u);
-      x = isx ? nx : 0.0;
-    }
+    const double u = (cx.isu && !term) ? Ur[(size_t)k * m + T] : 0.0;
+    scorew_knot(s, P, cx, k, x, u);
+    if (!term) x = evalw_advance(cx.dyn, k, x, u, isx);   // x, u are consumed: advance in registers
   }
-  for (int s = 32; s > 0; s >>= 1) {
-    cost += __shfl_xor(cost, s, 64);
-    viol = eval_max(viol, __shfl_xor(viol, s, 64));
-  }
+  double Jr, cr;
+  score_reduce<64>(s, Jr, cr);
   if (T != 0) return;
-  J[r] = 0.5 * cost;
-  cmax[r] = viol;
+  J[r] = Jr;
+  cmax[r] = cr;
 }
 
 // One wave per instance; a wave that installs nothing leaves as a whole.
@@ -286,22 +177,18 @@ __global__ void k_ws_install_wide(int* __restrict__ chosen, const double* __rest
   if (masked || w < 0 || w > ncand || (w == ncand && inc == 0)) return;   // (the winner is range-checked before it addresses anything)
   const int n = P.n, m = P.m, N = P.N;
   const bool isx = T < n, isu = T < m;
-  const int Tn = isx ? T : n - 1;
-  const int kref = eval_window(P.window, P.kref, b, N, P.Nt);
   const double* Ur = wsw_controls(U, Up, cur, b, w, ncand, N, m);
   const size_t pl = b * 2 + (size_t)cur[b];
   double* Xd = Xp + pl * (size_t)N * n;
   double* Ud = Up + pl * (size_t)(N - 1) * m;
-  extern __shared__ double eval_lds[];
-  const EvalWDyn dyn(P, b, kref, T, Tn, eval_lds + (threadIdx.x >> 6) * evalw_lds_doubles(n, m), true);
+  const EvalWDyn dyn(P, b, eval_window(P.window, P.kref, b, N, P.Nt), T, true);
   double x = isx ? x0[b * (size_t)n + T] : 0.0;
   for (int k = 0;; ++k) {
     if (isx) Xd[(size_t)k * n + T] = x;
     if (k == N - 1) break;
     const double u = isu ? Ur[(size_t)k * m + T] : 0.0;
     if (isu) Ud[(size_t)k * m + T] = u;
-    const double nx = dyn.step(k, x, u);
-    x = isx ? nx : 0.0;
+    x = evalw_advance(dyn, k, x, u, isx);
   }
 }
 

@@ -763,6 +763,8 @@ struct WideBackend {
     p.lds_dyn = altro::evalw_lds_fits(d.n, d.m, ltv) ? 1 : 0;
     return p;
   }
+  // the LDS a block of their kernels asks for
+  static size_t eval_lds(const altro::EvalW& p) { return p.lds_dyn ? altro::evalw_lds_bytes(p.n, p.m) : 0; }
   // altro_batch_evaluate_dev (evaluate.h; pointers and argument rules checked by the caller, the host twin passes staged
   // copies): the rollout kernel when there is no X, then the scoring kernel on states and controls in memory.  Reads what the
   // next solve would read; writes the caller's outputs and eval_ws only.
@@ -773,7 +775,7 @@ struct WideBackend {
     const size_t need = !Ud ? R * (lx + lu) : (!Xd && !Xout) ? R * lx : 0;
     if (need) WCHK(pool.reserve(&eval_ws, &eval_ws_elems, need));
     const altro::EvalW p = eval_params();
-    const size_t lds = p.lds_dyn ? 4 * altro::evalw_lds_doubles(d.n, d.m) * sizeof(double) : 0;
+    const size_t lds = eval_lds(p);
     const dim3 grid((unsigned)((R * 64 + 255) / 256)), block(256);
     int given = 1;
     if (!Ud) {   // own trajectory: the current planes, gathered into the workspace in the caller's layout
@@ -804,7 +806,7 @@ struct WideBackend {
       if (!cd) cd = ws_merit + R;
     }
     const altro::EvalW p = eval_params();
-    const size_t lds = p.lds_dyn ? 4 * altro::evalw_lds_doubles(d.n, d.m) * sizeof(double) : 0;
+    const size_t lds = eval_lds(p);
     hipLaunchKernelGGL(altro::k_ws_score_wide, dim3((unsigned)((R * 64 + 255) / 256)), dim3(256), lds, stream, Jd, cd, Ud, U, cur, x0, p, ncand, inc, R);
     WCHK(hipGetLastError());
     hipLaunchKernelGGL(altro::k_ws_install_wide, dim3((unsigned)(((size_t)d.batch * 64 + 255) / 256)), dim3(256), lds, stream, chosen, Jd, cd, Ud, X, U,
@@ -820,7 +822,7 @@ struct WideBackend {
     if (int rc = eval_ready()) return rc;
     const size_t R = (size_t)d.batch * (size_t)nsamp;
     const altro::EvalW p = eval_params();
-    const size_t lds = p.lds_dyn ? 4 * altro::evalw_lds_doubles(d.n, d.m) * sizeof(double) : 0;
+    const size_t lds = eval_lds(p);
     hipLaunchKernelGGL(altro::k_sim_wide, dim3((unsigned)((R * 64 + 255) / 256)), dim3(256), lds, stream, io, X, U, cur, Kg, bwst,
                        (gains_valid || debug_keep_gains) ? 1 : 0, x0, p, nsamp, clamp ? 1 : 0, R);
     WCHK(hipGetLastError());

@@ -1,8 +1,63 @@
 #!/usr/bin/env python3
 """Summarise the innermost loops of a kernel's ISA listing (tools/kernel_meta.sh leaves /tmp/last_kernel.s):
-per loop (backward branch to a label) the instruction mix of its body.  python tools/isa_loops.py [file.s] [min_len]"""
+per loop (backward branch to a label) the instruction mix of its body.  python tools/isa_loops.py [file.s] [min_len] [waits]
+python tools/isa_loops.py file.s blocks: per kernel, the instructions of the blocks the compiler's own comments assign to each
+depth-1 loop (robust against block layout: a loop body need not be one span of the listing), its loads, stores and vmcnt waits."""
 import re, sys
 path = sys.argv[1] if len(sys.argv) > 1 else "/tmp/last_kernel.s"
+def is_instruction(line):
+    return bool(re.match(r"\s+[a-z_0-9]+", line)) and not line.strip().startswith((";", "."))
+
+
+def blocks_mode(path):
+    """per kernel: instructions of the blocks that the compiler's comments put into each depth-1 loop"""
+    kernel = None        # name of the kernel the current line belongs to
+    header = None        # depth-1 loop the current block belongs to, or None
+    loops = {}           # (kernel, loop header) -> instructions
+    total = {}           # kernel -> instructions
+    for line in open(path).read().split("\n"):
+        m = re.match(r"^(_Z\w+):", line)
+        if m:
+            short = re.search(r"k_\w+?(?=E[PNi])", m.group(1))
+            kernel = short.group(0) if short else m.group(1)
+            header = None
+            total[kernel] = 0
+            continue
+        if line.startswith(".Lfunc_end"):
+            kernel = None
+        if kernel is None:
+            continue
+        m = re.match(r"^\.(LBB\d+_\d+):(.*)", line)
+        if m:   # a new block: its comment says which loop it is in
+            inside = re.search(r"in Loop: Header=(BB\d+_\d+) Depth=1", m.group(2))
+            if inside:
+                header = inside.group(1)
+            elif "Loop Header: Depth=1" in m.group(2):
+                header = m.group(1)[1:]
+            else:
+                header = None
+            continue
+        parent = re.search(r"Parent Loop (BB\d+_\d+) Depth=1", line)   # (blocks of nested loops name their parent on a comment line)
+        if parent and header is None:
+            header = parent.group(1)
+        if is_instruction(line):
+            total[kernel] += 1
+            if header:
+                loops.setdefault((kernel, header), []).append(line.strip())
+    for kernel, count in total.items():
+        mine = [(h, body) for (k, h), body in loops.items() if k == kernel and len(body) >= 40]
+        if not mine:
+            print("%-22s kernel %5d  no natural depth-1 loop of 40 instructions" % (kernel, count))
+        for h, body in mine:
+            waits = [re.search(r"vmcnt\((\d+)\)", i).group(1) for i in body if i.startswith("s_waitcnt") and "vmcnt" in i]
+            loads = sum(i.startswith("global_load") for i in body)
+            stores = sum(i.startswith("global_store") for i in body)
+            print("%-22s kernel %5d  loop %-9s %5d instr  %3d loads %2d stores  vmcnt waits: %s" % (kernel, count, h, len(body), loads, stores, " ".join(waits)))
+
+
+if len(sys.argv) > 2 and sys.argv[2] == "blocks":
+    blocks_mode(path)
+    sys.exit(0)
 minlen = int(sys.argv[2]) if len(sys.argv) > 2 else 40
 L = open(path).read().split("\n")
 labels = {}

@@ -1,0 +1,96 @@
+// Stand-alone CPU check of csrc/stage_layout.h: for every null / non-null combination of the arguments of the
+// three host twins, the total size and the offset of every sub-array against the sums altro_batch.hip wrote out by hand
+// before the layout was shared.  No GPU, no library:
+//   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -o /tmp/stage_layout_check \
+//       tools/stage_layout_check.cpp && /tmp/stage_layout_check
+#include <cstdio>
+#include <cstdlib>
+
+#include "../altro-mpc-icra2021_amd/csrc/stage_layout.h"
+
+using altro::StageLayout;
+static long checks = 0;
+
+static void expect(bool ok, const char* what, int combo) {
+  ++checks;
+  if (ok) return;
+  std::fprintf(stderr, "FAILED: %s (combination %d)\n", what, combo);
+  std::exit(1);
+}
+
+// slot i: offset, room, whether the kernels get it, and that a sub-array handed to them is aligned for its type
+static void slot_is(const StageLayout& L, int i, size_t off, size_t bytes, bool dev, size_t align, const char* what, int combo) {
+  const StageLayout::Slot& s = L.slot[i];
+  expect(s.bytes == bytes, what, combo);
+  expect(bytes == 0 || s.off == off, what, combo);
+  expect(s.dev == dev, what, combo);
+  expect(!dev || s.off % align == 0, what, combo);
+}
+
+int main() {
+  static double d[1];    // stands for a caller's array: only null / non-null matters here
+  static int32_t i32[1];
+  const size_t D = sizeof(double), I = sizeof(int32_t);
+  const size_t dims[][5] = {{5, 9, 12, 4, 1}, {5, 9, 12, 4, 17}, {2, 4, 64, 32, 3}, {1, 2, 1, 1, 1}, {8192, 50, 12, 4, 8}};
+  for (const auto& q : dims) {
+    const size_t B = q[0], N = q[1], n = q[2], m = q[3], nc = q[4];
+    // altro_batch_evaluate: elems = 3 R + (U ? cu : 0) + (X ? cx : 0) + (x0 ? B n : 0) + (Xout ? cx : 0); J, c_max, defect first
+    for (int c = 0; c < 128; ++c) {
+      const double *U = c & 1 ? d : nullptr, *X = c & 2 ? d : nullptr, *x0 = c & 4 ? d : nullptr;
+      double *J = c & 8 ? d : nullptr, *cm = c & 16 ? d : nullptr, *df = c & 32 ? d : nullptr, *Xo = c & 64 ? d : nullptr;
+      const size_t R = B * nc, cu = R * (N - 1) * m, cx = R * N * n;
+      StageLayout L;
+      altro::stage_evaluate(L, B, N, n, m, nc, U, X, x0, J, cm, df, Xo);
+      expect(L.nslots == 7, "evaluate: slots", c);
+      expect(L.bytes == (3 * R + (U ? cu : 0) + (X ? cx : 0) + (x0 ? B * n : 0) + (Xo ? cx : 0)) * D, "evaluate: size", c);
+      size_t s = 0;
+      slot_is(L, altro::EV_J, s, R * D, J, D, "evaluate: J", c); s += R * D;
+      slot_is(L, altro::EV_CMAX, s, R * D, cm, D, "evaluate: c_max", c); s += R * D;
+      slot_is(L, altro::EV_DEFECT, s, R * D, df, D, "evaluate: defect", c); s += R * D;
+      slot_is(L, altro::EV_U, s, U ? cu * D : 0, U, D, "evaluate: U", c); s += U ? cu * D : 0;
+      slot_is(L, altro::EV_X, s, X ? cx * D : 0, X, D, "evaluate: X", c); s += X ? cx * D : 0;
+      slot_is(L, altro::EV_X0, s, x0 ? B * n * D : 0, x0, D, "evaluate: x0", c); s += x0 ? B * n * D : 0;
+      slot_is(L, altro::EV_XOUT, s, Xo ? cx * D : 0, Xo, D, "evaluate: Xout", c);
+      expect((L.slot[altro::EV_U].in == U) && (L.slot[altro::EV_J].out == J) && (L.slot[altro::EV_XOUT].out == Xo), "evaluate: copies", c);
+    }
+    // altro_batch_warm_start: bytes = (2 R1 + cu) doubles + B ints; J, c_max, U, chosen, all handed to the kernels
+    for (int c = 0; c < 16; ++c) {
+      const size_t inc = c & 1;
+      int32_t* ch = c & 2 ? i32 : nullptr;
+      double *J = c & 4 ? d : nullptr, *cm = c & 8 ? d : nullptr;
+      const size_t R1 = B * (nc + inc), cu = B * nc * (N - 1) * m;
+      StageLayout L;
+      altro::stage_warm_start(L, B, N, m, nc, inc, d, ch, J, cm);
+      expect(L.nslots == 4, "warm_start: slots", c);
+      expect(L.bytes == (2 * R1 + cu) * D + B * I, "warm_start: size", c);
+      slot_is(L, altro::WS_J, 0, R1 * D, true, D, "warm_start: J", c);
+      slot_is(L, altro::WS_CMAX, R1 * D, R1 * D, true, D, "warm_start: c_max", c);
+      slot_is(L, altro::WS_U, 2 * R1 * D, cu * D, true, D, "warm_start: U", c);
+      slot_is(L, altro::WS_CHOSEN, (2 * R1 + cu) * D, B * I, true, I, "warm_start: chosen", c);
+      expect(L.slot[altro::WS_U].in == d && L.slot[altro::WS_CHOSEN].out == ch && L.slot[altro::WS_J].out == J, "warm_start: copies", c);
+    }
+    // altro_batch_simulate_policy: elems = 3 R + (x0 ? c0 : 0) + (w ? cw : 0) + (Xout ? cx : 0) + (Uout ? cu : 0) doubles + B ints
+    for (int c = 0; c < 256; ++c) {
+      const double *x0 = c & 1 ? d : nullptr, *w = c & 2 ? d : nullptr;
+      double *J = c & 4 ? d : nullptr, *cm = c & 8 ? d : nullptr, *dx = c & 16 ? d : nullptr, *Xo = c & 64 ? d : nullptr, *Uo = c & 128 ? d : nullptr;
+      int32_t* fb = c & 32 ? i32 : nullptr;
+      const size_t R = B * nc, c0 = R * n, cw = R * (N - 1) * n, cx = R * N * n, cu = R * (N - 1) * m;
+      StageLayout L;
+      altro::stage_simulate(L, B, N, n, m, nc, x0, w, J, cm, dx, fb, Xo, Uo);
+      expect(L.nslots == 8, "simulate: slots", c);
+      expect(L.bytes == (3 * R + (x0 ? c0 : 0) + (w ? cw : 0) + (Xo ? cx : 0) + (Uo ? cu : 0)) * D + B * I, "simulate: size", c);
+      size_t s = 0;
+      slot_is(L, altro::SIM_J, s, R * D, J, D, "simulate: J", c); s += R * D;
+      slot_is(L, altro::SIM_CMAX, s, R * D, cm, D, "simulate: c_max", c); s += R * D;
+      slot_is(L, altro::SIM_DXMAX, s, R * D, dx, D, "simulate: dx_max", c); s += R * D;
+      slot_is(L, altro::SIM_X0, s, x0 ? c0 * D : 0, x0, D, "simulate: x0", c); s += x0 ? c0 * D : 0;
+      slot_is(L, altro::SIM_W, s, w ? cw * D : 0, w, D, "simulate: w", c); s += w ? cw * D : 0;
+      slot_is(L, altro::SIM_XOUT, s, Xo ? cx * D : 0, Xo, D, "simulate: Xout", c); s += Xo ? cx * D : 0;
+      slot_is(L, altro::SIM_UOUT, s, Uo ? cu * D : 0, Uo, D, "simulate: Uout", c); s += Uo ? cu * D : 0;
+      slot_is(L, altro::SIM_FB, s, B * I, fb, I, "simulate: fb", c);
+      expect(L.slot[altro::SIM_X0].in == x0 && L.slot[altro::SIM_W].in == w && L.slot[altro::SIM_FB].out == fb, "simulate: copies", c);
+    }
+  }
+  std::printf("stage_layout_check: %ld checks passed\n", checks);
+  return 0;
+}
