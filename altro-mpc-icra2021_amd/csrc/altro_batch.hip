@@ -106,12 +106,9 @@ struct altro_handle {
          *KD = nullptr, *Qz = nullptr, *Dff = nullptr, *kmu = nullptr;
   altro::ASet* ahash = nullptr;  // [Bp][16] active set of the backward pass behind the gains in KD (gain reuse, solve_dpp16.h)
   long long* n_fo = nullptr;
-  // projected-Newton polish (pn_polish.h): per-instance results and the workspace, allocated by the first solve that asks for it
-  int *pn_ran = nullptr, *pn_failed = nullptr, *pn_dfail = nullptr;
-  double *pn_res = nullptr, *pn_dres0 = nullptr, *pn_dres = nullptr;
-  double *pnE = nullptr, *pndv = nullptr, *pnLd = nullptr, *pnLo = nullptr, *pnvec = nullptr, *pntz = nullptr;
-  int *pnnb = nullptr, *pnnst = nullptr, *pnrinfo = nullptr;
-  int pn_bm = 0;
+  // projected-Newton polish (pn_core.h): per-instance results and the workspace, allocated by the first solve that asks for it
+  altro_pn::PnOut pn_out;
+  altro_pn::PnWork pn_ws;
   double *noise = nullptr, *noise_w = nullptr;
   int* noise_grp = nullptr;
   int noise_mode = 0;
@@ -908,7 +905,7 @@ int32_t altro_batch_create(const altro_dims* dims, const altro_opts* opts, int32
     DA(mu, Bp); DA(kmu, Bp); DA(ahash, row); DA(dzero, Bp);
     DA(KD, N * Bp * m * LW);     // N-1 gain blocks + a trash slot
     DA(Qz, (N + 1) * row); DA(Dff, (N + 1) * row);
-    DA(pn_ran, Bp); DA(pn_failed, Bp); DA(pn_dfail, Bp); DA(pn_res, Bp); DA(pn_dres0, Bp); DA(pn_dres, Bp);
+    DA(pn_out.ran, Bp); DA(pn_out.failed, Bp); DA(pn_out.dfail, Bp); DA(pn_out.res, Bp); DA(pn_out.dres0, Bp); DA(pn_out.dres, Bp);
     DA(cur, Bp); DA(perm, Bp); DA(gscore, Bp); DA(refusals, 1);
     DA(iters, Bp); DA(iters_outer, Bp); DA(status, Bp); DA(cost, Bp); DA(cmax, Bp);
     DA(Jtrace, Bp * ALTRO_TRACE_LEN); DA(ctrace, Bp * ALTRO_TRACE_LEN); DA(atrace, Bp * ALTRO_TRACE_LEN);
@@ -947,7 +944,7 @@ static void free_dpp_backend(altro_handle* h) {
   h->stage_bytes = 0;
   h->eval_ws_elems = 0;
   h->mlog_cap = 0;
-  h->pn_bm = 0;
+  h->pn_ws.bm = h->pn_ws.slots = 0;
   h->ring.destroy();
   if (h->bev0) { hipEventDestroy(h->bev0); h->bev0 = nullptr; }
   if (h->bev1) { hipEventDestroy(h->bev1); h->bev1 = nullptr; }
@@ -1517,45 +1514,26 @@ int32_t altro_batch_set_options(altro_handle* h, const altro_opts* o) {
 // prepare_polish: every check and allocation the polish needs -- run BEFORE a launch takes its slot of the timing ring, so
 // that a failure leaves no slot with a start event and no end event.
 static int prepare_polish(altro_handle* h) {
-  const size_t Bp = h->Bp, N = h->d.N;
   int nbounded = 0;
   for (int j = 0; j < LW; ++j) nbounded += h->bslot_h[j] >= 0 ? 1 : 0;
   const int bm = 2 * h->d.n + (h->box_k1 >= h->box_k0 ? 2 * nbounded : 0) + (h->ncrows > 0 ? LW : 0);
   if (bm > altro_pn::BMAX) FAIL(h, ALTRO_ERR_UNSUPPORTED, "projected_newton: more rows per knot than pn_polish.h holds");
-  if (h->pn_bm != bm || !h->pnE) {
-    h->pn_bm = 0;   // (until every array of the workspace exists)
-    altro::DevicePool& pl = h->pool;
-    const hipStream_t st = h->stream;
-    HIPCHK(h, pl.alloc(&h->pnE, Bp * N * bm * LW, st, false));
-    HIPCHK(h, pl.alloc(&h->pndv, Bp * N * bm, st, false));
-    HIPCHK(h, pl.alloc(&h->pnLd, Bp * N * bm * bm, st, false));
-    HIPCHK(h, pl.alloc(&h->pnLo, Bp * N * bm * bm, st, false));
-    HIPCHK(h, pl.alloc(&h->pnvec, Bp * 6 * N * bm, st, false));
-    HIPCHK(h, pl.alloc(&h->pntz, Bp * 3 * N * LW, st, false));
-    HIPCHK(h, pl.alloc(&h->pnnb, Bp * N, st, false));
-    HIPCHK(h, pl.alloc(&h->pnnst, Bp * N, st, false));
-    HIPCHK(h, pl.alloc(&h->pnrinfo, Bp * N * bm, st, false));
-    h->pn_bm = bm;
-  }
+  HIPCHK(h, h->pn_ws.alloc(h->pool, h->stream, (int)h->Bp, h->d.N, bm, LW, false));
   return ALTRO_OK;
 }
 
 // mask: the instances to polish (null: all) -- the active mask, or under an episode clock the mask of the step just solved
 static int launch_polish(altro_handle* h, const int* mask) {
-  const int bm = h->pn_bm;
   altro_pn::PnParams q{};
-  q.B = h->d.batch; q.Bp = h->Bp; q.N = h->d.N; q.Nt = h->Nt; q.n = h->d.n; q.m = h->d.m; q.bm = bm;
+  q.B = h->d.batch; q.Bp = h->Bp; q.N = h->d.N; q.Nt = h->Nt; q.n = h->d.n; q.m = h->d.m;
   q.box_k0 = h->box_k0; q.box_k1 = h->box_k1; q.ncrows = h->ncrows;
   q.con_istride = h->con_per_instance ? (unsigned)(h->d.N * LW * LW) : 0u;
   q.Grow = h->Grow; q.fvec = h->fvec; q.wd = h->wd; q.wf = h->wf; q.zmin = h->zmin; q.zmax = h->zmax; q.x0 = h->x0;
   q.wstride = q.bstride = tab_imask(h) == 15u ? 0u : (unsigned)LW;
   q.Acon = h->Acon; q.bcon = h->bcon; q.cmeta = h->cmeta; q.active = mask;
   q.Z = h->Z; q.Zref = h->Zref; q.kref = h->kref; q.win = h->clock.on ? h->clock.window : nullptr; q.cur = h->cur; q.status = h->status; q.cost = h->cost; q.cmax = h->cmax;
-  q.pn_ran = h->pn_ran; q.pn_failed = h->pn_failed; q.pn_res = h->pn_res;
   q.Lb = h->Lb; q.Lc = h->Lc; q.bslot = h->bslot; q.nbp = h->nbp;
-  q.pn_dfail = h->pn_dfail; q.pn_dres0 = h->pn_dres0; q.pn_dres = h->pn_dres;
-  q.E = h->pnE; q.dv = h->pndv; q.Ld = h->pnLd; q.Lo = h->pnLo; q.vec = h->pnvec; q.tz = h->pntz;
-  q.nb = h->pnnb; q.nst = h->pnnst; q.rinfo = h->pnrinfo;
+  q.out = h->pn_out; q.ws = h->pn_ws;
   q.o = h->o;
   hipLaunchKernelGGL(altro_pn::pn_kernel, dim3(h->d.batch), dim3(64), 0, h->stream, q);
   HIPCHK(h, hipGetLastError());
@@ -1906,44 +1884,31 @@ int32_t altro_batch_get_reuse_counter(altro_handle* h, int64_t* reused) {
   });
 }
 
+// Both polish getters on both backends (pn_core.h PnOut::read): zeros while projected_newton is off, or before a handle on
+// the one-wave-per-instance backend has polished.
+static int32_t read_polish(altro_handle* h, bool stats, int32_t* ran, int32_t* failed, double* res, double* dres0, double* dres, int32_t* dfail) {
+  if (!h) return ALTRO_ERR_INVALID_ARG;
+  HIPCHK(h, hipSetDevice(h->device));
+  const altro_pn::PnOut& out = h->wide ? h->wide->pn_out : h->pn_out;
+  const hipStream_t st = h->wide ? h->wide->stream : h->stream;
+  const bool on = (h->wide ? h->wide->o : h->o).projected_newton;
+  if (stats && !on && !h->wide) {
+    // the statistics themselves go back to zero: an instance that a mask keeps out of the first polish after the option is
+    // switched on reports them
+    HIPCHK(h, hipMemsetAsync(out.ran, 0, h->Bp * sizeof(int), st));
+    HIPCHK(h, hipMemsetAsync(out.failed, 0, h->Bp * sizeof(int), st));
+    HIPCHK(h, hipMemsetAsync(out.res, 0, h->Bp * sizeof(double), st));
+  }
+  HIPCHK(h, out.read(st, on && out.ran, (size_t)h->d.batch, ran, failed, res, dres0, dres, dfail));
+  return ALTRO_OK;
+}
+
 int32_t altro_batch_get_polish_stats(altro_handle* h, int32_t* ran, int32_t* failed, double* residual) {
-  return guard(h, [&]() -> int32_t {
-    if (!h) return ALTRO_ERR_INVALID_ARG;
-    const size_t B = h->d.batch;
-    if (h->wide) { const int rc_ = h->wide->polish_stats(ran, failed, residual); if (rc_) h->err = h->wide->err; return rc_; }
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (!h->o.projected_newton) {
-      HIPCHK(h, hipMemsetAsync(h->pn_ran, 0, h->Bp * sizeof(int), h->stream));
-      HIPCHK(h, hipMemsetAsync(h->pn_failed, 0, h->Bp * sizeof(int), h->stream));
-      HIPCHK(h, hipMemsetAsync(h->pn_res, 0, h->Bp * sizeof(double), h->stream));
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    if (ran) HIPCHK(h, hipMemcpy(ran, h->pn_ran, B * sizeof(int), hipMemcpyDeviceToHost));
-    if (failed) HIPCHK(h, hipMemcpy(failed, h->pn_failed, B * sizeof(int), hipMemcpyDeviceToHost));
-    if (residual) HIPCHK(h, hipMemcpy(residual, h->pn_res, B * sizeof(double), hipMemcpyDeviceToHost));
-    return ALTRO_OK;
-  });
+  return guard(h, [&]() -> int32_t { return read_polish(h, true, ran, failed, residual, nullptr, nullptr, nullptr); });
 }
 
 int32_t altro_batch_get_polish_dual_residuals(altro_handle* h, double* before, double* after, int32_t* failed) {
-  return guard(h, [&]() -> int32_t {
-    if (!h) return ALTRO_ERR_INVALID_ARG;
-    const size_t B = h->d.batch;
-    if (h->wide) { const int rc_ = h->wide->polish_dual(before, after, failed); if (rc_) h->err = h->wide->err; return rc_; }
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (!h->o.projected_newton) {
-      if (before) std::memset(before, 0, B * sizeof(double));
-      if (after) std::memset(after, 0, B * sizeof(double));
-      if (failed) std::memset(failed, 0, B * sizeof(int32_t));
-      return ALTRO_OK;
-    }
-    if (before) HIPCHK(h, hipMemcpy(before, h->pn_dres0, B * sizeof(double), hipMemcpyDeviceToHost));
-    if (after) HIPCHK(h, hipMemcpy(after, h->pn_dres, B * sizeof(double), hipMemcpyDeviceToHost));
-    if (failed) HIPCHK(h, hipMemcpy(failed, h->pn_dfail, B * sizeof(int), hipMemcpyDeviceToHost));
-    return ALTRO_OK;
-  });
+  return guard(h, [&]() -> int32_t { return read_polish(h, false, nullptr, nullptr, nullptr, before, after, failed); });
 }
 
 int32_t altro_batch_get_confirm_counter(altro_handle* h, int64_t* confirmed) {

@@ -145,12 +145,9 @@ struct WideBackend {
   int coop_mode = -1, static_mask = 7;  // altro_debug_set "wide_coop", "wide_static_mask" (before create)
   int compact_np_max = 48;  // wide_compact: the LDS carve-up with Qux and K inside W, for padded state dimensions up to this
   bool debug_keep_gains = false;  // altro_debug_set "keep_gains" (-DALTRO_DEBUG builds only): stale gains are kept (exists to show that the tests notice them)
-  // projected-Newton polish (pn_wide.h): per-instance results, and the workspace slots allocated by the first solve that asks
-  int *pn_ran = nullptr, *pn_failed = nullptr, *pn_dfail = nullptr;
-  double *pn_res = nullptr, *pn_dres0 = nullptr, *pn_dres = nullptr;
-  double *pnE = nullptr, *pndv = nullptr, *pnLd = nullptr, *pnLo = nullptr, *pnvec = nullptr, *pntz = nullptr, *pnblk = nullptr;
-  int *pnnb = nullptr, *pnnst = nullptr, *pnrinfo = nullptr;
-  int pn_bm = 0, pn_slots = 0;
+  // projected-Newton polish (pn_core.h): per-instance results, and the workspace slots allocated by the first solve that asks
+  altro_pn::PnOut pn_out;
+  altro_pn::PnWork pn_ws;
   bool gains_valid = false;   // nothing the stored gains depend on (model, cost, constraints, options) has changed since the last launch
   double *Xsave = nullptr, *Usave = nullptr;  // Z0 of benchmark_solve
   std::vector<hipEvent_t> bench_ev;
@@ -887,32 +884,15 @@ struct WideBackend {
   // solve!(::ProjectedNewtonSolver) after the AL kernel of a plain solve: every check and allocation BEFORE the launch takes
   // its slot of the timing ring
   int polish_prepare() {
-    const size_t B = d.batch, N = d.N, z = nz();
-    if (!pn_ran) {   // (pn_ran last: it exists only once the other five do)
-      for (int** p : {&pn_failed, &pn_dfail, &pn_ran}) WCHK(pool.alloc(p, B, stream));
-      for (double** p : {&pn_res, &pn_dres0, &pn_dres}) WCHK(pool.alloc(p, B, stream));
+    const size_t B = d.batch;
+    if (!pn_out.ran) {   // (ran last: it exists only once the other five do)
+      for (double** p : {&pn_out.res, &pn_out.dres0, &pn_out.dres}) WCHK(pool.alloc(p, B, stream));
+      for (int** p : {&pn_out.failed, &pn_out.dfail, &pn_out.ran}) WCHK(pool.alloc(p, B, stream));
     }
     int sides = 0;   // from the host copy of the BOX's finite sides (common to every instance)
     if (box_k1 >= box_k0)
-      for (size_t j = 0; j < z; ++j) sides += (box_lo_fin[j] ? 1 : 0) + (box_hi_fin[j] ? 1 : 0);
-    const int bm = 2 * d.n + sides + Pn;
-    const int slots = (int)(B < 64 ? B : 64);
-    if (bm != pn_bm || slots != pn_slots || !pnE) {
-      const size_t S = slots, b = bm;
-      pn_bm = pn_slots = 0;   // (until every array of the workspace exists)
-      WCHK(pool.alloc(&pnE, S * N * b * z, stream, false));
-      WCHK(pool.alloc(&pndv, S * N * b, stream, false));
-      WCHK(pool.alloc(&pnLd, S * N * b * b, stream, false));
-      WCHK(pool.alloc(&pnLo, S * N * b * b, stream, false));
-      WCHK(pool.alloc(&pnvec, S * 6 * N * b, stream, false));
-      WCHK(pool.alloc(&pntz, S * 3 * N * z, stream, false));
-      WCHK(pool.alloc(&pnblk, S * (2 * b * (b + 1) + 4 * b), stream, false));
-      WCHK(pool.alloc(&pnnb, S * N, stream, false));
-      WCHK(pool.alloc(&pnnst, S * N, stream, false));
-      WCHK(pool.alloc(&pnrinfo, S * N * b, stream, false));
-      pn_bm = bm;
-      pn_slots = slots;
-    }
+      for (size_t j = 0; j < nz(); ++j) sides += (box_lo_fin[j] ? 1 : 0) + (box_hi_fin[j] ? 1 : 0);
+    WCHK(pn_ws.alloc(pool, stream, (int)(B < 64 ? B : 64), d.N, 2 * d.n + sides + Pn, nz(), true));
     return ALTRO_OK;
   }
   // mask: the instances to polish (null: all) -- the active mask, or under an episode clock the mask of the step just solved
@@ -921,32 +901,9 @@ struct WideBackend {
     w.P = params();
     w.P.active = mask;
     w.P.o = o;   // the caller's tolerances (params() carries the AL stage's)
-    w.bm = pn_bm; w.nslots = pn_slots;
-    w.pn_ran = pn_ran; w.pn_failed = pn_failed; w.pn_dfail = pn_dfail; w.pn_res = pn_res; w.pn_dres0 = pn_dres0; w.pn_dres = pn_dres;
-    w.E = pnE; w.dv = pndv; w.Ld = pnLd; w.Lo = pnLo; w.vec = pnvec; w.tz = pntz; w.blk = pnblk;
-    w.nb = pnnb; w.nst = pnnst; w.rinfo = pnrinfo;
-    hipLaunchKernelGGL(altro_pnw::pnw_kernel, dim3(pn_slots), dim3(64), 0, stream, w, o.constraint_tolerance);
+    w.out = pn_out; w.ws = pn_ws;
+    hipLaunchKernelGGL(altro_pnw::pnw_kernel, dim3(pn_ws.slots), dim3(64), 0, stream, w);
     WCHK(hipGetLastError());
-    return ALTRO_OK;
-  }
-  int polish_stats(int32_t* ran, int32_t* failed, double* residual) {
-    WCHK(hipSetDevice(device));
-    WCHK(hipStreamSynchronize(stream));
-    const size_t B = d.batch;
-    const bool have = o.projected_newton && pn_ran;
-    if (ran) { if (have) WCHK(hipMemcpy(ran, pn_ran, B * sizeof(int), hipMemcpyDeviceToHost)); else std::memset(ran, 0, B * sizeof(int32_t)); }
-    if (failed) { if (have) WCHK(hipMemcpy(failed, pn_failed, B * sizeof(int), hipMemcpyDeviceToHost)); else std::memset(failed, 0, B * sizeof(int32_t)); }
-    if (residual) { if (have) WCHK(hipMemcpy(residual, pn_res, B * sizeof(double), hipMemcpyDeviceToHost)); else std::memset(residual, 0, B * sizeof(double)); }
-    return ALTRO_OK;
-  }
-  int polish_dual(double* before, double* after, int32_t* failed) {
-    WCHK(hipSetDevice(device));
-    WCHK(hipStreamSynchronize(stream));
-    const size_t B = d.batch;
-    const bool have = o.projected_newton && pn_ran;
-    if (before) { if (have) WCHK(hipMemcpy(before, pn_dres0, B * sizeof(double), hipMemcpyDeviceToHost)); else std::memset(before, 0, B * sizeof(double)); }
-    if (after) { if (have) WCHK(hipMemcpy(after, pn_dres, B * sizeof(double), hipMemcpyDeviceToHost)); else std::memset(after, 0, B * sizeof(double)); }
-    if (failed) { if (have) WCHK(hipMemcpy(failed, pn_dfail, B * sizeof(int), hipMemcpyDeviceToHost)); else std::memset(failed, 0, B * sizeof(int32_t)); }
     return ALTRO_OK;
   }
 

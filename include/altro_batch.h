@@ -133,8 +133,9 @@ typedef struct altro_opts {
    * solve!(::ProjectedNewtonSolver) if the violation is still above constraint_tolerance; ALTRO, IROS 2019, Algorithm 4).
    * altro_default_opts() gives 0: Altro.jl's own default is true, but every script of the reference on this path sets
    * projected_newton = false (eleven occurrences), and the ccall shim passes the Julia-side value explicitly.  1: plain
-   * solves (altro_batch_solve) run the polish after the AL kernel -- csrc/pn_polish.h on the 16-lane backend, csrc/pn_wide.h
-   * on the one-wave-per-instance backend (any n <= 64, m <= 32, per-knot dynamics) -- primal projection first, then
+   * solves (altro_batch_solve) run the polish after the AL kernel -- the algorithm is csrc/pn_core.h, seen through
+   * csrc/pn_polish.h on the 16-lane backend and through csrc/pn_wide.h on the one-wave-per-instance backend (any n <= 64,
+   * m <= 32, per-knot dynamics) -- primal projection first, then
    * Altro's multiplier projection (altro_batch_get_polish_dual_residuals).  Inside the device-resident MPC loop
    * (altro_mpc_step_async / altro_mpc_run_async) every step is then a one-step solve kernel followed by the polish kernel:
    * the next step shifts the polished trajectory and the projected multipliers.

@@ -1670,7 +1670,7 @@ def test_error_paths():
 
 def test_projected_newton_polish_matches_oracle(oracle):
     """SURVEY 8 f4 (parity with Altro.jl unpinned; see tests/test_oracle_cones.py): altro_opts.projected_newton = 1 --
-    the AL kernel stops at projected_newton_tolerance, then csrc/pn_polish.h projects the trajectory onto the active
+    the AL kernel stops at projected_newton_tolerance, then csrc/pn_core.h (view: csrc/pn_polish.h) projects the trajectory onto the active
     constraints and the dynamics.  Against the oracle's polish on (a) a box-constrained LQ batch with saturating
     controls and (b) the grasp problem (cones, per-knot equalities and inequalities, goal): same AL stage, same
     decision to polish, the polished trajectories within 1e-6, constraints and dynamics to the polish tolerance."""
@@ -1765,7 +1765,7 @@ def test_projected_newton_polish_inside_the_mpc_loop(oracle, n, m, N):
 
 
 def test_projected_newton_polish_on_the_one_wave_per_instance_backend(oracle, monkeypatch):
-    """SURVEY 8 f4 on the second backend (csrc/pn_wide.h; parity with Altro.jl unpinned as above): projected_newton = 1 on
+    """SURVEY 8 f4 on the second backend (csrc/pn_core.h through the view csrc/pn_wide.h; parity with Altro.jl unpinned as above): projected_newton = 1 on
     sizes outside the 16-lane set -- (a) box-constrained LQ at (20, 4) with saturating controls, (b) the quadruped tick
     (n = m = 12, per-knot dynamics, friction rows + f_z box), (c) the grasp problem forced onto this backend (cones,
     per-knot equalities and inequalities, goal) -- against the oracle's polish: same AL stage, same decision to polish,
@@ -1832,6 +1832,37 @@ def test_projected_newton_polish_on_the_one_wave_per_instance_backend(oracle, mo
         assert so.pn_ran == 1 and int(st.status[b]) == so.status == 1 and int(st.iterations[b]) == so.iterations
         assert st.c_max[b] < 1e-6 and abs(st.cost[b] - so.cost) <= 1e-5 * max(1.0, abs(so.cost))
         assert rel_err(X[b], o.states()) <= 1e-5 and rel_err(U[b], o.controls()) <= 1e-5
+
+
+def test_projected_newton_polish_walks_its_workspace_slots():
+    """The one-wave-per-instance polish (csrc/pn_core.h through csrc/pn_wide.h) runs min(B, 64) blocks; block s polishes the instances s, s + 64, ...
+    in the workspace of slot s.  Batch 66 at (20, 4, 21), recipe of case (a) above, with instances 64 and 65 exact copies
+    of 0 and 1 (dynamics, reference, x0; the bounds are common): what the second visit of slots 0 and 1 leaves must equal
+    the first visit's byte for byte -- it would not if a slot's workspace were read where the instance's is meant, or the
+    other way round.  Instance 2 differs from instance 0, so the comparison cannot pass on a constant."""
+    B = 66
+    pb = altro.problems.gen_random_linear_batch(B, n=20, m=4, N=21, steps=1, seed=85)
+    for a in (pb.A, pb.Bm, pb.Xtrack, pb.Utrack):
+        a[64:66] = a[0:2]
+    prob = altro.mpc.gen_tracking_problem(pb)
+    prob.x0 = prob.x0 + np.resize(np.array([20.0, 15.0, 0.1, 25.0]), B)[:, None]
+    prob.x0[64:66] = prob.x0[0:2]
+    opts = dict(REF_OPTS, constraint_tolerance=1e-8, projected_newton=1)
+    sv = altro.ALTROSolver(prob, altro.SolverOptions(**opts))
+    assert altro.wave_cycles(sv).size == 0        # wide path
+    altro.solve(sv)
+    st, X, U = altro.stats(sv), altro.states(sv), altro.controls(sv)
+    ran, failed, res = altro.polish_stats(sv)
+    d0, d1, dfail = altro.polish_dual_residuals(sv)
+    sv.close()
+    assert ran[0] + ran[1] >= 1
+    outs = dict(states=X, controls=U, cost=st.cost, c_max=st.c_max, status=st.status, iterations=st.iterations,
+                ran=ran, failed=failed, residual=res, dual_before=d0, dual_after=d1, dual_failed=dfail)
+    for name, a in outs.items():
+        a = np.asarray(a)
+        for i in (0, 1):
+            assert a[i].tobytes() == a[64 + i].tobytes(), (name, i)
+    assert not np.array_equal(X[2], X[0]) and not np.array_equal(U[2], U[0]) and st.cost[2] != st.cost[0]
 
 
 def test_initial_state_uploaded_before_per_knot_dynamics_survives_the_move_to_the_wide_kernel():

@@ -1,4 +1,4 @@
-"""Timing line of the projected-Newton polish (csrc/pn_polish.h, csrc/pn_wide.h): the grasp cold solve at the reference's
+"""Timing line of the projected-Newton polish (csrc/pn_core.h through its views csrc/pn_polish.h, csrc/pn_wide.h): the grasp cold solve at the reference's
 N = 251 (grasp_benchmark.jl:19-25), AL stage to a loose 1e-2, polish to 1e-6 -- device time of the solve with and without
 the polish, on the 16-lane backend and forced onto the one-wave-per-instance backend.  python tools/gpu_pn_timing.py [batch]"""
 import sys, os, json
