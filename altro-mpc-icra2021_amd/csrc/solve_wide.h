@@ -3189,7 +3189,7 @@ inline int wide_class(int m) { return m <= 4 ? 4 : m <= 8 ? 8 : m <= 12 ? 12 : m
 // units compiled side by side (_lib.build): altro_batch.hip declares all of these `extern`, wide_inst.hip defines the ones of
 // the unit it is compiled for (-DALTRO_WIDE_TU=k).
 #define ALTRO_WIDE_KERNELS(X)                                                                                   \
-  X(0, 4, true, 0, -1) X(0, 4, true, 0, 0) X(0, 8, true, 0, -1) X(0, 4, false, 0, -1) X(0, 0, false, 0, -1)         \
+  X(0, 4, true, 0, -1) X(0, 4, true, 0, 0) X(0, 8, true, 0, -1) X(0, 0, false, 0, -1)                              \
   X(1, 12, true, 0, -1) X(1, 16, true, 0, -1) X(1, 8, false, 0, -1) X(1, 8, false, 32, -1) X(1, 12, true, 0, 16)    \
   X(2, 12, false, 0, -1) X(2, 16, false, 0, -1) X(2, 12, false, 32, -1) X(2, 16, false, 32, -1)                    \
   X(3, 4, false, 32, -1) X(3, 4, false, 48, -1) X(3, 4, false, 64, -1)                                            \
@@ -3249,8 +3249,7 @@ inline wide_kernel_t wide_kernel_for(int n, int m, int nrows) {
       if (sm) return plain ? wide_kernel<4, true, 0, 0> : wide_kernel<4, true>;
       if (np == 32) return plain ? wide_kernel<4, false, 32, 0> : wide_kernel<4, false, 32>;
       if (np == 48) return plain ? wide_kernel<4, false, 48, 0> : wide_kernel<4, false, 48>;
-      if (np == 64) return plain ? wide_kernel<4, false, 64, 0> : wide_kernel<4, false, 64>;
-      return wide_kernel<4, false>;
+      return plain ? wide_kernel<4, false, 64, 0> : wide_kernel<4, false, 64>;   // (n <= kMaxN: the padded n is 32, 48 or 64)
     // (m = 5 .. 16: the reference's control-dimension sweep runs at n = 30 -- padded 32; the quadruped has sixteen rows)
     case 8: return sm ? wide_kernel<8, true> : np == 32 ? wide_kernel<8, false, 32> : wide_kernel<8, false>;
     case 12: return sm ? (nrows == 16 ? wide_kernel<12, true, 0, 16> : wide_kernel<12, true>) : np == 32 ? wide_kernel<12, false, 32> : wide_kernel<12, false>;

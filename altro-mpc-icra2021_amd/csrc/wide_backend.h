@@ -970,6 +970,7 @@ struct WideBackend {
         hipLaunchKernelGGL(wide_kernel_for(d.n, d.m, Pn), dim3(d.batch), dim3(wide_block_threads(d.n, d.m, lds_bytes(), coop_mode)), lds_bytes(), stream, params(), mpc, first_step + s, 1);
         rc = hipGetLastError() == hipSuccess ? ALTRO_OK : ALTRO_ERR_HIP;
         if (rc) err = "launch of the solve kernel failed";
+        gains_valid = true;   // params() of the next step: its launch may reuse the pass this one stores, as a single step would
         kref = first_step + s + 1;
         if (!rc) rc = polish_launch(mask);
         if (!rc && mlog) {
