@@ -201,6 +201,7 @@ class RowsProblem:
     x0_warm: np.ndarray        # x0 moved by 2 % (time-invariant variant: the warm solve)
     opts: dict
     kinds: list = field(default_factory=list)    # name of every constraint block, in order
+    cons_b: list = None        # [instance][block]: constraint data of each instance's own (tests/lane16_matrix.py); None: rp.constraints
 
 
 def _flip_to_positive_peak(A, vals):
@@ -222,7 +223,7 @@ def _free_solution(oracle, rp, x0, opts):
 
 
 @functools.lru_cache(maxsize=None)
-def _rows_problem(case, ltv):
+def _rows_problem(case, ltv, nb):
     import oracle_py as oracle
     oracle.build()
     t = case.tune(ltv)
@@ -235,8 +236,8 @@ def _rows_problem(case, ltv):
         A = A[None] * (1.0 + 0.1 * rng.standard_normal((N - 1, 1, 1)))
         Bm = Bm[None] * (1.0 + 0.1 * rng.standard_normal((N - 1, 1, 1)))
         f = 0.05 * rng.standard_normal((N - 1, n))
-    x0 = rng.standard_normal((B, n))
-    x0_warm = x0 + 0.02 * np.abs(x0).max() * rng.standard_normal((B, n))
+    x0 = rng.standard_normal((nb, n))
+    x0_warm = x0 + 0.02 * np.abs(x0).max() * rng.standard_normal((nb, n))
     rp = P.RocketProblemData(n=n, m=m, N=N, dt=DT, A=A, Bm=Bm, f=f, Q=np.full(n, 10.0), R=np.full(m, 0.1), Qf=np.full(n, 10.0),
                              xf=np.zeros(n), x0=np.zeros(n), U0=np.zeros((N - 1, m)), constraints=[])
     Xf, Uf = _free_solution(oracle, rp, x0, ROWS_OPTS)
@@ -272,12 +273,13 @@ def _rows_problem(case, ltv):
     return RowsProblem(case, ltv, rp, x0, x0_warm, dict(ROWS_OPTS), kinds)
 
 
-def rows_problem(case, ltv=False):
-    return _rows_problem(case, bool(ltv))
+def rows_problem(case, ltv=False, nb=B):
+    """nb: instances (the table of this file: B)."""
+    return _rows_problem(case, bool(ltv), nb)
 
 
 def rows_oracles(oracle, pr):
-    return [rocket_oracle(oracle, pr.rp, pr.x0[b], pr.opts) for b in range(B)]
+    return [rocket_oracle(oracle, pr.rp, pr.x0[b], pr.opts, constraints=pr.cons_b[b] if pr.cons_b else None) for b in range(len(pr.x0))]
 
 
 def rows_gpu_problem(altro, pr):
@@ -307,9 +309,10 @@ def at_penalty_cap(so):
 
 def rows_guard(oracle, pr):
     """Solve on the oracle (cold; warm too for the time-invariant variant) and return what the guards look at:
-    dict(status (nsolves, B), outer (nsolves, B), capped, nonzero {kind: instances with a nonzero dual after the cold solve})."""
+    dict(status (nsolves, B), outer (nsolves, B), capped, nonzero {kind: instances with a nonzero dual after the cold solve},
+    nonzero_rows {kind: the same count for every row of an affine block})."""
     orcs = rows_oracles(oracle, pr)
-    status, outer, capped, nonzero = [], [], False, {}
+    status, outer, capped, nonzero, nonzero_rows = [], [], False, {}, {}
     for rep in range(1 if pr.ltv else 2):
         if rep:
             for b, o in enumerate(orcs):
@@ -320,7 +323,11 @@ def rows_guard(oracle, pr):
         if rep == 0:
             for ci, kind in enumerate(pr.kinds):
                 nonzero[kind] = sum(bool(np.any(o.duals(o.con_ids[ci]) != 0.0)) for o in orcs)
-    return dict(status=np.array(status), outer=np.array(outer), capped=capped, nonzero=nonzero)
+                c = (pr.cons_b[0] if pr.cons_b else pr.rp.constraints)[ci]
+                if c.A is not None:
+                    p = c.A.shape[-2]
+                    nonzero_rows[kind] = sum(np.any(o.duals(o.con_ids[ci]).reshape(-1, p) != 0.0, axis=0).astype(int) for o in orcs).tolist()
+    return dict(status=np.array(status), outer=np.array(outer), capped=capped, nonzero=nonzero, nonzero_rows=nonzero_rows)
 
 
 def box_guard(oracle, bc):
