@@ -50,6 +50,7 @@ EXPORTS = [
     "altro_batch_evaluate_dev", "altro_batch_evaluate",
     "altro_batch_warm_start_dev", "altro_batch_warm_start",
     "altro_batch_simulate_policy_dev", "altro_batch_simulate_policy",
+    "altro_batch_propagate_covariance_dev", "altro_batch_propagate_covariance",
 ]
 """every symbol include/altro_batch.h declares"""
 
@@ -82,7 +83,7 @@ def build(force=False, verbose=False):
     """Generate the DPP block include and compile the HIP library for gfx950, in tree.  The library is several translation
     units (altro_batch.hip: the C-ABI, the 16-lane kernels, the polish; wide_inst.hip once per group of one-wave-per-instance
     kernels, solve_wide.h ALTRO_WIDE_KERNELS) compiled side by side -- one after the other they take ~6 minutes."""
-    srcs = [os.path.join(CSRC, f) for f in ("altro_batch.hip", "wide_inst.hip", "solve_dpp16.h", "solve_wide.h", "wide_backend.h", "launch_ring.h", "pn_core.h", "pn_polish.h", "pn_wide.h", "mpc_log.h", "device_io.h", "device_pool.h", "episode_clock.h", "policy.h", "evaluate.h", "warm_start.h", "simulate.h", "stage_layout.h", "gen_dpp_blocks.py")]
+    srcs = [os.path.join(CSRC, f) for f in ("altro_batch.hip", "wide_inst.hip", "solve_dpp16.h", "solve_wide.h", "wide_backend.h", "launch_ring.h", "pn_core.h", "pn_polish.h", "pn_wide.h", "mpc_log.h", "device_io.h", "device_pool.h", "episode_clock.h", "policy.h", "evaluate.h", "warm_start.h", "simulate.h", "covariance.h", "stage_layout.h", "gen_dpp_blocks.py")]
     srcs.append(os.path.join(os.path.dirname(_HERE), "include", "altro_batch.h"))
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):
         return LIB_PATH
@@ -182,6 +183,9 @@ def lib():
     if hasattr(L, "altro_batch_simulate_policy_dev"):   # closed-loop simulation of the stored policy
         L.altro_batch_simulate_policy_dev.argtypes = [H, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 6
         L.altro_batch_simulate_policy.argtypes = [H, C.c_int32, dp, dp, C.c_int32, dp, dp, dp, ip, dp, dp]
+    if hasattr(L, "altro_batch_propagate_covariance_dev"):   # closed-loop covariance of the stored policy
+        L.altro_batch_propagate_covariance_dev.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double] + [C.c_void_p] * 8
+        L.altro_batch_propagate_covariance.argtypes = [H, dp, dp, C.c_int32, C.c_int32, C.c_double, dp, dp, dp, dp, ip, dp, dp, dp]
     L.altro_batch_add_constraint.argtypes = [H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                              dp, dp, dp, dp, C.c_int32, ip]
     L.altro_batch_update_constraint_data.argtypes = [H, C.c_int32, dp, dp]

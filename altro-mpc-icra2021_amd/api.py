@@ -25,7 +25,8 @@ live on the solver's GPU (the altro_*_dev entry points: nothing crosses PCIe, no
 and first_knot write into such tensors; eval_policy (the feedback policy between two ticks), get_gains_dev, evaluate and
 rollout (candidate trajectories scored against the next solve's problem) read and write them.  warm_start scores candidate
 controls the same way and installs the best as the next solve's initial trajectory; simulate_policy runs the policy the last
-solve holds in closed loop on the model, many disturbed samples per instance.  A GPU tensor is never copied, cast or moved behind the caller's back: float64,
+solve holds in closed loop on the model, many disturbed samples per instance, and propagate_covariance gives the first two
+moments of that loop without samples.  A GPU tensor is never copied, cast or moved behind the caller's back: float64,
 contiguous, on the solver's device and of the exact shape, or ValueError.  Matrices keep their natural (row, col) indexing;
 since the C-ABI reads column-major blocks, a dynamics tensor must be STORED column-major, i.e. `At.transpose(-1, -2)` of a
 contiguous tensor At that holds the transposed blocks.  Every tensor call is ordered against torch's current stream
@@ -1168,6 +1169,100 @@ def simulate_policy(solver, x0=None, w=None, nsamp=None, clamp=True, out=None, f
             raise ValueError(f"simulate_policy: {nm} must be a C-contiguous {np.dtype(dt).name} array of shape {shp}")
     solver._chk(solver._L.altro_batch_simulate_policy(solver.h, ns, _p(x0), _p(w), int(bool(clamp)), _p(out[0]), _p(out[1]), _p(out[2]),
                                                       None if fb is None else fb.ctypes.data_as(_IP), _p(Xout), _p(Uout)))
+    return out
+
+
+COV_OUTPUTS = ("sx", "su", "sc", "dJ", "fb", "zmin_t", "zmax_t", "Sout")
+
+
+def _covariance_args(solver, Sigma0, W, con_id, kappa, out):
+    """(per_instance, library constraint id or -1, kappa, {name: shape} of every output the call may write, the names a default
+    `out` gets); refuses here what the library would refuse, so that it is not called with it"""
+    B, N, n, m = solver.B, solver.N, solver.n, solver.m
+    if Sigma0 is None and W is None:
+        raise ValueError("propagate_covariance: Sigma0 and W are both None")
+    shp = {tuple(int(k) for k in a.shape) for a in (Sigma0, W) if a is not None}
+    if len(shp) != 1 or next(iter(shp)) not in ((n, n), (B, n, n)):
+        raise ValueError(f"propagate_covariance: Sigma0 / W: shapes {sorted(shp)}, expected ({n}, {n}) or ({B}, {n}, {n}), the same for both")
+    pi = int(len(next(iter(shp))) == 3)
+    shapes = {"sx": (B, N, n), "su": (B, N - 1, m), "dJ": (B,), "fb": (B,), "Sout": (B, N, n, n)}
+    default = ["sx", "su", "dJ", "fb"]
+    cid = -1
+    if con_id is not None:
+        items = solver.prob.constraints.items
+        if int(con_id) != con_id or not 0 <= int(con_id) < len(items) or isinstance(items[int(con_id)][0], BoundConstraint):
+            raise ValueError(f"propagate_covariance: con_id = {con_id}: it must index a LINEAR or SOC constraint of the problem "
+                             "(the deviations of a BOX are sx and su)")
+        c, first, last = items[int(con_id)]
+        shapes["sc"] = (B, last - first + 1, int(np.asarray(c.b).shape[-1]))
+        default.append("sc")
+        cid = solver.con_ids[int(con_id)]
+    if kappa is not None:
+        if not (float(kappa) >= 0.0) or float(kappa) == float("inf"):
+            raise ValueError(f"propagate_covariance: kappa = {kappa}: it must be finite and not negative")
+        shapes["zmin_t"] = shapes["zmax_t"] = (B, n + m)
+        default += ["zmin_t", "zmax_t"]
+    if out is not None:
+        if not isinstance(out, dict) or not out or any(o is None for o in out.values()):
+            raise ValueError("propagate_covariance: out is a dict {name: array} with at least one of " + ", ".join(COV_OUTPUTS))
+        for k in out:
+            if k not in shapes:
+                why = "unknown" if k not in COV_OUTPUTS else "needs con_id" if k == "sc" else "needs kappa"
+                raise ValueError(f"propagate_covariance: out[{k!r}]: {why}")
+        if ("zmin_t" in out) != ("zmax_t" in out):
+            raise ValueError("propagate_covariance: zmin_t and zmax_t go together")
+        if con_id is not None and "sc" not in out:
+            raise ValueError("propagate_covariance: con_id is given: out needs 'sc'")
+    return pi, cid, 0.0 if kappa is None else float(kappa), shapes, default
+
+
+def _propagate_covariance_dev(solver, Sigma0=None, W=None, con_id=None, kappa=None, out=None):
+    """device form of propagate_covariance: every tensor is validated (shape, dtype, strides, device) before the library is called"""
+    pi, cid, kap, shapes, default = _covariance_args(solver, Sigma0, W, con_id, kappa, out)
+    mat = (solver.B, solver.n, solver.n) if pi else (solver.n, solver.n)
+    for t, nm in ((Sigma0, "Sigma0"), (W, "W")):
+        if t is not None:
+            check_device_tensor(t, mat, solver.device, nm)
+    if out is None:
+        import torch
+        dev = torch.device("cuda", solver.device)
+        out = {k: torch.empty(shapes[k], dtype=torch.int32 if k == "fb" else torch.float64, device=dev) for k in default}
+    for k, t in out.items():
+        check_device_tensor(t, shapes[k], solver.device, k, dtype="torch.int32" if k == "fb" else "torch.float64")
+    solver._chk(solver._L.altro_batch_propagate_covariance_dev(solver.h, _addr(Sigma0), _addr(W), pi, cid, kap, *(_addr(out.get(k)) for k in COV_OUTPUTS)))
+    return out
+
+
+def propagate_covariance(solver, Sigma0=None, W=None, con_id=None, kappa=None, out=None):
+    """The covariance of the closed loop under the stored policy, propagated over the horizon on the device
+    (altro_batch_propagate_covariance / _dev):  S_0 = Sigma0, S_{k+1} = (A_k + B_k K_k) S_k (A_k + B_k K_k)' + W -- the analytic
+    twin of simulate_policy for the unsaturated loop (no clamp is modelled).  Sigma0 and W are (n, n) for the batch or (B, n, n)
+    per instance, the same shape for both; either may be None (zero), not both; symmetry is the caller's business.
+    Returns a dict: sx (B, N, n) and su (B, N-1, m) the standard deviations of states and controls, dJ (B,) the expected cost
+    over the nominal, fb (B,) int32 1 where the stored gains are valid (0: the loop is open, K = 0); with con_id (the index of a
+    LINEAR or SOC constraint of the problem) sc (B, nk, p), the deviations of its row values; with kappa (>= 0) zmin_t and
+    zmax_t (B, n+m), the BOX pulled in by kappa deviations, which set_bounds accepts as they are.  out: a dict of arrays to
+    write into instead, any subset of those names plus Sout (B, N, n, n), the matrices themselves.  Nothing the solver owns
+    changes.  With GPU tensors (float64, contiguous; fb int32) the call is stream-ordered and nothing synchronises; with numpy
+    the host twin runs: the same bytes.  Nothing is converted: a mix of the two is refused."""
+    args = (Sigma0, W) + (tuple(out.values()) if isinstance(out, dict) else ())
+    if any(_on_gpu(a) for a in args):
+        if not all(a is None or _on_gpu(a) for a in args):
+            raise ValueError("propagate_covariance: Sigma0, W and the arrays of out must all be GPU tensors (or None), or none of them")
+        with _bracket(solver):
+            return _propagate_covariance_dev(solver, Sigma0, W, con_id, kappa, out)
+    for a, nm in ((Sigma0, "Sigma0"), (W, "W")):
+        if a is not None and not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous):
+            raise ValueError(f"propagate_covariance: {nm} must be a C-contiguous float64 array (or a GPU tensor)")
+    pi, cid, kap, shapes, default = _covariance_args(solver, Sigma0, W, con_id, kappa, out)
+    if out is None:
+        out = {k: np.empty(shapes[k], dtype=np.int32 if k == "fb" else np.float64) for k in default}
+    for k, o in out.items():
+        dt = np.int32 if k == "fb" else np.float64
+        if not (isinstance(o, np.ndarray) and o.dtype == dt and o.flags.c_contiguous and o.shape == shapes[k]):
+            raise ValueError(f"propagate_covariance: {k} must be a C-contiguous {np.dtype(dt).name} array of shape {shapes[k]}")
+    ptr = lambda k: None if k not in out else out[k].ctypes.data_as(_IP) if k == "fb" else _p(out[k])
+    solver._chk(solver._L.altro_batch_propagate_covariance(solver.h, _p(Sigma0), _p(W), pi, cid, kap, *(ptr(k) for k in COV_OUTPUTS)))
     return out
 
 

@@ -2704,6 +2704,103 @@ int32_t altro_batch_simulate_policy(altro_handle* h, int32_t nsamp, const double
   });
 }
 
+// ---- closed-loop covariance of the stored policy (kernels in covariance.h)
+// The argument rules both forms share, checked before anything else; nsc <- the doubles of sc per instance (nk * p of con_id).
+static int covariance_rules(altro_handle* h, const char* fn, const altro::CovIO& io, int32_t per_instance, int32_t con_id, size_t* nsc) {
+  const std::string f(fn);
+  *nsc = 0;
+  if (!io.S0 && !io.W) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": Sigma0 and W are both null");
+  if (!io.sx && !io.su && !io.sc && !io.dJ && !io.fb && !io.zlo_t && !io.zhi_t && !io.Sout)
+    FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": sx, su, sc, dJ, fb, zmin_t, zmax_t and Sout are all null");
+  if (per_instance != 0 && per_instance != 1) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": per_instance must be 0 or 1");
+  if (!(io.kappa >= 0.0) || std::isinf(io.kappa)) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": kappa must be finite and not negative");
+  if ((io.zlo_t != nullptr) != (io.zhi_t != nullptr)) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": zmin_t and zmax_t go together: both or neither");
+  const int box_id = h->wide ? h->wide->box_id : h->box_id;
+  if (io.zlo_t && box_id < 0) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": zmin_t / zmax_t need a BOX constraint on the handle");
+  if (con_id < 0) {
+    if (con_id != -1) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": unknown constraint id");
+    if (io.sc) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": sc needs the id of a LINEAR or SOC constraint (con_id = -1)");
+    return ALTRO_OK;
+  }
+  if (con_id == box_id) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": con_id is a BOX constraint: its deviations are sx and su");
+  if (h->wide) {
+    if (const auto* bl = h->wide->find(con_id)) *nsc = (size_t)(bl->k1 - bl->k0 + 1) * bl->p;
+  } else {
+    for (const auto& cb : h->cons)
+      if (cb.id == con_id) *nsc = (size_t)(cb.k1 - cb.k0 + 1) * cb.p;
+  }
+  if (!*nsc) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": unknown constraint id");
+  if (!io.sc) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": con_id is given without sc");
+  return ALTRO_OK;
+}
+
+// io: device arrays (the caller's, validated; or the staged copies of the host twin).  Enqueues one kernel, allocates nothing:
+// the covariance lives in registers (16-lane backend) or LDS (one-wave-per-instance backend).
+static int covariance_launch(altro_handle* h, const altro::CovIO& io, int32_t con_id) {
+  if (h->wide) {
+    const int rc = h->wide->propagate_covariance_dev(io, con_id);
+    if (rc) h->err = h->wide->err;
+    return rc;
+  }
+  if (int rc = score_ready(h)) return rc;
+  altro::CovRows cr{};
+  for (const auto& cb : h->cons) {
+    if (cb.id != con_id) continue;
+    cr.p = cb.p; cr.k0 = cb.k0; cr.k1 = cb.k1;
+    for (int r = 0; r < cb.p; ++r) cr.lanes |= (unsigned long long)(cb.lanes[r] & 15) << (4 * r);
+  }
+  const size_t B = h->d.batch;
+  const size_t rows = (B + 3) & ~(size_t)3;   // whole waves of four rows
+  hipLaunchKernelGGL(altro::k_cov16, grid_for(rows * LW), dim3(256), 0, h->stream, io, cr, h->KD, h->kmu, eval16_params(h), B, rows);
+  HIPCHK(h, hipGetLastError());
+  return ALTRO_OK;
+}
+
+int32_t altro_batch_propagate_covariance_dev(altro_handle* h, const double* Sigma0, const double* W, int32_t per_instance, int32_t con_id,
+                                             double kappa, double* sx, double* su, double* sc, double* dJ, int32_t* fb, double* zmin_t,
+                                             double* zmax_t, double* Sout) {
+  return guard(h, [&]() -> int32_t {
+    DEV_ENTER(h, "altro_batch_propagate_covariance_dev");
+    const altro::CovIO io{Sigma0, W, per_instance, kappa, sx, su, sc, dJ, fb, zmin_t, zmax_t, Sout};
+    size_t nsc = 0;
+    if (int rc = covariance_rules(h, fn_, io, per_instance, con_id, &nsc)) return rc;
+    const size_t mat = (per_instance ? B_ : 1) * n_ * n_;
+    DEV_ARG(h, "Sigma0", Sigma0, mat, double, true);
+    DEV_ARG(h, "W", W, mat, double, true);
+    DEV_ARG(h, "sx", sx, B_ * N_ * n_, double, true);
+    DEV_ARG(h, "su", su, B_ * (N_ - 1) * m_, double, true);
+    DEV_ARG(h, "sc", sc, B_ * nsc, double, true);
+    DEV_ARG(h, "dJ", dJ, B_, double, true);
+    DEV_ARG(h, "fb", fb, B_, int32_t, true);
+    DEV_ARG(h, "zmin_t", zmin_t, B_ * (n_ + m_), double, true);
+    DEV_ARG(h, "zmax_t", zmax_t, B_ * (n_ + m_), double, true);
+    DEV_ARG(h, "Sout", Sout, B_ * N_ * n_ * n_, double, true);
+    return covariance_launch(h, io, con_id);
+  });
+}
+
+// The host twin (StageCursor)
+int32_t altro_batch_propagate_covariance(altro_handle* h, const double* Sigma0, const double* W, int32_t per_instance, int32_t con_id,
+                                         double kappa, double* sx, double* su, double* sc, double* dJ, int32_t* fb, double* zmin_t,
+                                         double* zmax_t, double* Sout) {
+  return guard(h, [&]() -> int32_t {
+    if (!h) return dev_null_handle("altro_batch_propagate_covariance");
+    size_t nsc = 0;
+    if (int rc = covariance_rules(h, "altro_batch_propagate_covariance",
+                                  altro::CovIO{Sigma0, W, per_instance, kappa, sx, su, sc, dJ, fb, zmin_t, zmax_t, Sout}, per_instance, con_id, &nsc))
+      return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    StageCursor sc_(h);
+    altro::stage_covariance(sc_, h->d.batch, h->d.N, h->d.n, h->d.m, per_instance, nsc, Sigma0, W, sx, su, sc, dJ, fb, zmin_t, zmax_t, Sout);
+    if (int rc = sc_.open()) return rc;
+    const altro::CovIO io{sc_.f64(altro::COV_S0), sc_.f64(altro::COV_W), per_instance, kappa, sc_.f64(altro::COV_SX), sc_.f64(altro::COV_SU),
+                          sc_.f64(altro::COV_SC), sc_.f64(altro::COV_DJ), sc_.i32(altro::COV_FB), sc_.f64(altro::COV_ZLO),
+                          sc_.f64(altro::COV_ZHI), sc_.f64(altro::COV_SOUT)};
+    if (int rc = covariance_launch(h, io, con_id)) return rc;
+    return sc_.close();
+  });
+}
+
 // ---- per-instance active mask and cold restart
 static int set_active_common(altro_handle* h, const int32_t* active, bool dev) {
   altro::InstanceFlags& fl = h->wide ? h->wide->flags : h->flags;

@@ -1,5 +1,5 @@
-// stage_layout.h -- where the arrays of a host twin (altro_batch_evaluate, altro_batch_warm_start, altro_batch_simulate_policy)
-// sit in the handle's staging buffer.  Plain host arithmetic, no HIP: altro_batch.hip's StageCursor adds the copies, and
+// stage_layout.h -- where the arrays of a host twin (altro_batch_evaluate, altro_batch_warm_start, altro_batch_simulate_policy,
+// altro_batch_propagate_covariance) sit in the handle's staging buffer.  Plain host arithmetic, no HIP: altro_batch.hip's StageCursor adds the copies, and
 // tools/stage_layout_check.cpp runs this file alone on the CPU against the sizes and offsets written out by hand.
 #pragma once
 #include <cassert>
@@ -21,7 +21,7 @@ struct StageLayout {
     void* out;           // copied back after it, or null
     bool dev;            // the kernels get the sub-array
   };
-  static constexpr int MAX_SLOTS = 8;
+  static constexpr int MAX_SLOTS = 10;
   Slot slot[MAX_SLOTS] = {};
   int nslots = 0;
   size_t bytes = 0;
@@ -75,6 +75,23 @@ inline void stage_simulate(StageLayout& L, size_t B, size_t N, size_t n, size_t 
   L.add<double>(R * (N - 1) * n, w, nullptr, StageLayout::OPTIONAL);
   L.add<double>(R * N * n, nullptr, Xout, StageLayout::OPTIONAL);
   L.add<double>(R * (N - 1) * m, nullptr, Uout, StageLayout::OPTIONAL);
+  L.add<int32_t>(B, nullptr, fb, StageLayout::RESERVED);
+}
+
+enum { COV_DJ, COV_S0, COV_W, COV_SX, COV_SU, COV_SC, COV_ZLO, COV_ZHI, COV_SOUT, COV_FB };
+inline void stage_covariance(StageLayout& L, size_t B, size_t N, size_t n, size_t m, size_t per_instance, size_t nsc, const double* Sigma0,
+                             const double* W, double* sx, double* su, double* sc, double* dJ, int32_t* fb, double* zmin_t, double* zmax_t,
+                             double* Sout) {
+  const size_t mat = (per_instance ? B : 1) * n * n;
+  L.add<double>(B, nullptr, dJ, StageLayout::RESERVED);
+  L.add<double>(mat, Sigma0, nullptr, StageLayout::OPTIONAL);
+  L.add<double>(mat, W, nullptr, StageLayout::OPTIONAL);
+  L.add<double>(B * N * n, nullptr, sx, StageLayout::OPTIONAL);
+  L.add<double>(B * (N - 1) * m, nullptr, su, StageLayout::OPTIONAL);
+  L.add<double>(B * nsc, nullptr, sc, StageLayout::OPTIONAL);
+  L.add<double>(B * (n + m), nullptr, zmin_t, StageLayout::OPTIONAL);
+  L.add<double>(B * (n + m), nullptr, zmax_t, StageLayout::OPTIONAL);
+  L.add<double>(B * N * n * n, nullptr, Sout, StageLayout::OPTIONAL);
   L.add<int32_t>(B, nullptr, fb, StageLayout::RESERVED);
 }
 

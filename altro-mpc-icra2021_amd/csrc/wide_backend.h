@@ -18,6 +18,7 @@
 #include "launch_ring.h"
 #include "policy.h"
 #include "solve_wide.h"
+#include "covariance.h"
 #include "pn_wide.h"
 
 namespace altro_wide {
@@ -162,6 +163,7 @@ struct WideBackend {
   size_t eval_ws_elems = 0;
   double* ws_merit = nullptr;  // altro_batch_warm_start(_dev): J, c_max [batch * (ncand + 1)] each when the caller passes none (grow-only)
   size_t ws_merit_elems = 0;
+  size_t cov_lds_set = 0;      // altro_batch_propagate_covariance(_dev): the LDS bytes its kernel has been allowed (above the 64 KB a kernel gets unasked)
   int Nt = 0, kref = 0, noise_steps = 0, noise_mode = 0, mpc_shift = 1;
   double* mlog = nullptr;  // per-step log of the MPC loop (mpc_log.h): [mlog_cap][B][n + m + MLOG_TAIL]; null: off
   int mlog_cap = 0;
@@ -822,6 +824,28 @@ struct WideBackend {
     const size_t lds = eval_lds(p);
     hipLaunchKernelGGL(altro::k_sim_wide, dim3((unsigned)((R * 64 + 255) / 256)), dim3(256), lds, stream, io, X, U, cur, Kg, bwst,
                        (gains_valid || debug_keep_gains) ? 1 : 0, x0, p, nsamp, clamp ? 1 : 0, R);
+    WCHK(hipGetLastError());
+    return ALTRO_OK;
+  }
+  // altro_batch_propagate_covariance_dev (covariance.h; pointers and argument rules checked by the caller, the host twin passes
+  // staged copies): one kernel, one wave per instance.  Reads what the next solve and eval_policy_dev would read; writes the
+  // caller's outputs only and allocates nothing.  con_id: the LINEAR / SOC constraint behind io.sc (the caller has found it), or -1.
+  int propagate_covariance_dev(const altro::CovIO& io, int con_id) {
+    WCHK(hipSetDevice(device));
+    if (int rc = eval_ready()) return rc;
+    altro::CovRows cr{};
+    if (con_id >= 0) {
+      const Block* bl = find(con_id);
+      if (!bl) WFAIL(ALTRO_ERR_INVALID_ARG, "no such constraint");
+      cr.p = bl->p; cr.k0 = bl->k0; cr.k1 = bl->k1; cr.r0 = bl->r0;
+    }
+    const size_t lds = altro::covw_lds_doubles(d.n, d.m) * sizeof(double);
+    if (lds > 65536 && lds > cov_lds_set) {
+      WCHK(hipFuncSetAttribute((const void*)altro::k_cov_wide, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      cov_lds_set = lds;
+    }
+    hipLaunchKernelGGL(altro::k_cov_wide, dim3((unsigned)d.batch), dim3(64), lds, stream, io, cr, Kg, bwst,
+                       (gains_valid || debug_keep_gains) ? 1 : 0, eval_params());
     WCHK(hipGetLastError());
     return ALTRO_OK;
   }

@@ -358,6 +358,13 @@ class ExternalMPC:
         last solve is worth if the state estimate is off or the plant is pushed: a pass-through, GPU tensors or numpy."""
         return api.simulate_policy(self.solver, x0=x0, w=w, nsamp=nsamp, clamp=clamp, out=out, fb=fb, Xout=Xout, Uout=Uout)
 
+    def covariance(self, Sigma0=None, W=None, con_id=None, kappa=None, out=None):
+        """The dict of api.propagate_covariance: the covariance of the closed loop under the policy the solver holds once its
+        stream reaches this point, from the covariance Sigma0 of the state estimate and W of the disturbance per step -- the
+        standard deviations of states, controls and constraint rows, the expected cost increase and, with kappa, a box pulled
+        in by kappa deviations that set_bounds takes as it is: a pass-through, GPU tensors or numpy."""
+        return api.propagate_covariance(self.solver, Sigma0=Sigma0, W=W, con_id=con_id, kappa=kappa, out=out)
+
     def _constraints_dev(self, constraint_data, bounds):
         s = self.solver
         for con, (A, b) in (constraint_data or {}).items():

@@ -660,6 +660,57 @@ int32_t altro_batch_simulate_policy_dev(altro_handle* h, int32_t nsamp, const do
 int32_t altro_batch_simulate_policy(altro_handle* h, int32_t nsamp, const double* x0, const double* w, int32_t clamp, double* J,
                                     double* c_max, double* dx_max, int32_t* fb, double* Xout, double* Uout);
 
+/* ---- closed-loop covariance of the stored policy: the analytic twin of the simulation above.  The perturbations of the
+ * reference's closed loops (random_linear_problem.jl:129, simple_rocket.jl:65-71, flexible_sat_mpc.jl:266) are additive and
+ * zero-mean; the model is affine and the policy u = ubar_k + K_k (x - xbar_k) is too, so while no control saturates the first
+ * two moments of the loop obey an exact recursion and one pass over the horizon gives, without samples, what sizes a constraint
+ * back-off: the standard deviation of every state, control and constraint row, the expected cost increase and a tightened box.
+ * altro_batch_propagate_covariance_dev: every pointer is a device pointer under the rules of the device-pointer block (validated
+ * before anything is enqueued, stream-ordered on the handle's stream, no host synchronisation, no caller pointer kept).
+ *   Sigma0, W  n x n row-major: the covariance of x_0 - xbar_0 and of the disturbance added at every step.  per_instance = 0:
+ *            one matrix for the batch; 1: [batch][n][n].  Either may be NULL -- zero, and for W no addition is performed --
+ *            not both.  The matrices are used as given: symmetry is the caller's responsibility and is not checked.
+ *   con_id   a LINEAR or SOC constraint whose rows' deviations go to sc, or -1 (then sc must be NULL)
+ *   kappa    >= 0, finite: the back-off of the tightened box in standard deviations
+ * With K_k the matrix altro_batch_get_gains returns and M_k = A_k + B_k K_k:
+ *   S_0 = Sigma0,   S_{k+1} = M_k S_k M_k' + W,   k = 0 .. N-2
+ * fb[b] (int32 [batch]) has the validity meaning of altro_batch_eval_policy_dev: 1 the stored gains are valid, 0 they are not
+ * and the loop is open, K = 0, as in altro_batch_simulate_policy_dev.  No clamp is modelled: the augmented-Lagrangian gains
+ * already shrink the rows of controls held at a bound, and the saturated loop is what altro_batch_simulate_policy_dev is for.
+ * Outputs, each may be NULL, not all:
+ *   sx    [batch][N][n]      sqrt(max(S_k[i][i], 0))
+ *   su    [batch][N-1][m]    sqrt(max((K_k S_k K_k')[a][a], 0))
+ *   sc    [batch][nk][p]     in the layout of altro_batch_get_duals for con_id: the standard deviation of the row value
+ *                            (A z + b)_r, sqrt(max(g' S_k g, 0)) with g = a_x + K_k' a_u (at knot N-1: g = a_x)
+ *   dJ    [batch]            E[J] - J(xbar, ubar) with the instance's own weights as altro_batch_evaluate_dev applies them:
+ *                            1/2 sum_{k<N-1} dt (sum_i Q_i S_k[i][i] + sum_a R_a (K S_k K')[a][a]) + 1/2 sum_i Qf_i S_{N-1}[i][i]
+ *   zmin_t, zmax_t [batch][n+m]   both or neither; they need a BOX on the handle.  s_e = the maximum of element e's deviation
+ *                            over the knots of the BOX's range (control columns: up to knot N-2).  Two finite sides, mid =
+ *                            0.5 (lo + hi): lo' = min(lo + kappa s_e, mid), hi' = max(hi - kappa s_e, mid); a lone finite
+ *                            side lo + kappa s_e or hi - kappa s_e; infinite sides stay.  The row has lo' <= hi' and the
+ *                            BOX's pattern of finite sides: altro_batch_set_bounds_dev(.., per_instance = 1) accepts it as
+ *                            it is, which closes solve -> propagate -> tighten -> solve on the device.
+ *   Sout  [batch][N][n][n]   the matrices S_k as computed, not re-symmetrised
+ * The window, the dynamics blocks (altro_mpc_set_dynamics_track: kref * step_stride + k), the weights, the bounds and the
+ * constraint tables are those altro_batch_evaluate_dev sees at that point of the stream (under an episode clock the instance's
+ * own window).  A NaN stays a NaN.  Nothing the library owns changes and the stored gains stay.  There is no masking: an
+ * instance the active mask or the clock leaves out answers from its last solve.  Instance b gets the bytes it would get on a
+ * batch-1 handle holding its data.  One kernel (csrc/covariance.h, with the summation orders); the covariance stays in
+ * registers or LDS, so the call allocates nothing, with or without Sout.  Like altro_batch_evaluate_dev the call first packs
+ * constraint tables a HOST edit has left unpacked.
+ * altro_batch_propagate_covariance: the same with host arrays, through the handle's staging buffer (grown if needed);
+ * synchronises; writes the bytes the `_dev` call writes.
+ * ALTRO_ERR_INVALID_ARG (nothing enqueued, the handle unchanged and usable): NULL handle; Sigma0 and W both NULL; every output
+ * NULL; per_instance not 0 or 1; kappa negative, NaN or infinite; exactly one of zmin_t / zmax_t; the pair on a handle with no
+ * BOX; sc with con_id = -1, or con_id >= 0 without sc; an unknown or BOX con_id; _dev: what the device-pointer block refuses.
+ * ALTRO_ERR_STATE: dynamics, cost or reference not set, or the window runs past the stored reference or dynamics track. */
+int32_t altro_batch_propagate_covariance_dev(altro_handle* h, const double* Sigma0, const double* W, int32_t per_instance,
+                                             int32_t con_id, double kappa, double* sx, double* su, double* sc, double* dJ,
+                                             int32_t* fb, double* zmin_t, double* zmax_t, double* Sout);
+int32_t altro_batch_propagate_covariance(altro_handle* h, const double* Sigma0, const double* W, int32_t per_instance,
+                                         int32_t con_id, double kappa, double* sx, double* su, double* sc, double* dJ, int32_t* fb,
+                                         double* zmin_t, double* zmax_t, double* Sout);
+
 /* ---- per-instance active mask and cold restart: ragged batches of closed loops.
  * The reference runs one problem per loop, and a loop that ends simply stops calling solve! (simple_rocket.jl:137-205); in a
  * batch the instance whose rocket has landed, or whose episode has ended and is re-spawned, sits among others that go on.

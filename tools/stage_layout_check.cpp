@@ -1,5 +1,5 @@
 // Stand-alone CPU check of csrc/stage_layout.h: for every null / non-null combination of the arguments of the
-// three host twins, the total size and the offset of every sub-array against the sums altro_batch.hip wrote out by hand
+// host twins, the total size and the offset of every sub-array against the sums altro_batch.hip wrote out by hand
 // before the layout was shared.  No GPU, no library:
 //   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -o /tmp/stage_layout_check \
 //       tools/stage_layout_check.cpp && /tmp/stage_layout_check
@@ -89,6 +89,32 @@ int main() {
       slot_is(L, altro::SIM_UOUT, s, Uo ? cu * D : 0, Uo, D, "simulate: Uout", c); s += Uo ? cu * D : 0;
       slot_is(L, altro::SIM_FB, s, B * I, fb, I, "simulate: fb", c);
       expect(L.slot[altro::SIM_X0].in == x0 && L.slot[altro::SIM_W].in == w && L.slot[altro::SIM_FB].out == fb, "simulate: copies", c);
+    }
+    // altro_batch_propagate_covariance: dJ and fb have room either way, the eight others only when given; fb last (ints)
+    for (int c = 0; c < 2048; ++c) {
+      const double *S0 = c & 1 ? d : nullptr, *W = c & 2 ? d : nullptr;
+      double *sx = c & 4 ? d : nullptr, *su = c & 8 ? d : nullptr, *sc = c & 16 ? d : nullptr, *dJ = c & 32 ? d : nullptr;
+      double *zl = c & 128 ? d : nullptr, *zh = c & 256 ? d : nullptr, *So = c & 512 ? d : nullptr;
+      int32_t* fb = c & 64 ? i32 : nullptr;
+      const size_t pi = (c >> 10) & 1, nsc = 3 * nc;
+      const size_t mat = (pi ? B : 1) * n * n, cx = B * N * n, cu = B * (N - 1) * m, cz = B * (n + m), cs = B * N * n * n;
+      StageLayout L;
+      altro::stage_covariance(L, B, N, n, m, pi, nsc, S0, W, sx, su, sc, dJ, fb, zl, zh, So);
+      expect(L.nslots == 10 && L.nslots <= StageLayout::MAX_SLOTS, "covariance: slots", c);
+      size_t s = 0;
+      slot_is(L, altro::COV_DJ, s, B * D, dJ, D, "covariance: dJ", c); s += B * D;
+      slot_is(L, altro::COV_S0, s, S0 ? mat * D : 0, S0, D, "covariance: Sigma0", c); s += S0 ? mat * D : 0;
+      slot_is(L, altro::COV_W, s, W ? mat * D : 0, W, D, "covariance: W", c); s += W ? mat * D : 0;
+      slot_is(L, altro::COV_SX, s, sx ? cx * D : 0, sx, D, "covariance: sx", c); s += sx ? cx * D : 0;
+      slot_is(L, altro::COV_SU, s, su ? cu * D : 0, su, D, "covariance: su", c); s += su ? cu * D : 0;
+      slot_is(L, altro::COV_SC, s, sc ? B * nsc * D : 0, sc, D, "covariance: sc", c); s += sc ? B * nsc * D : 0;
+      slot_is(L, altro::COV_ZLO, s, zl ? cz * D : 0, zl, D, "covariance: zmin_t", c); s += zl ? cz * D : 0;
+      slot_is(L, altro::COV_ZHI, s, zh ? cz * D : 0, zh, D, "covariance: zmax_t", c); s += zh ? cz * D : 0;
+      slot_is(L, altro::COV_SOUT, s, So ? cs * D : 0, So, D, "covariance: Sout", c); s += So ? cs * D : 0;
+      slot_is(L, altro::COV_FB, s, B * I, fb, I, "covariance: fb", c); s += B * I;
+      expect(L.bytes == s, "covariance: size", c);
+      expect(L.slot[altro::COV_S0].in == S0 && L.slot[altro::COV_W].in == W && L.slot[altro::COV_FB].out == fb && L.slot[altro::COV_SOUT].out == So,
+             "covariance: copies", c);
     }
   }
   std::printf("stage_layout_check: %ld checks passed\n", checks);
