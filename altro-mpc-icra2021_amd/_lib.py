@@ -83,7 +83,7 @@ def build(force=False, verbose=False):
     """Generate the DPP block include and compile the HIP library for gfx950, in tree.  The library is several translation
     units (altro_batch.hip: the C-ABI, the 16-lane kernels, the polish; wide_inst.hip once per group of one-wave-per-instance
     kernels, solve_wide.h ALTRO_WIDE_KERNELS) compiled side by side -- one after the other they take ~6 minutes."""
-    srcs = [os.path.join(CSRC, f) for f in ("altro_batch.hip", "wide_inst.hip", "solve_dpp16.h", "solve_wide.h", "wide_backend.h", "launch_ring.h", "pn_core.h", "pn_polish.h", "pn_wide.h", "mpc_log.h", "device_io.h", "device_pool.h", "episode_clock.h", "policy.h", "evaluate.h", "warm_start.h", "simulate.h", "covariance.h", "stage_layout.h", "gen_dpp_blocks.py")]
+    srcs = [os.path.join(CSRC, f) for f in ("altro_batch.hip", "wide_inst.hip", "solve_dpp16.h", "solve_wide.h", "wide_backend.h", "backend_common.h", "launch_ring.h", "pn_core.h", "pn_polish.h", "pn_wide.h", "mpc_log.h", "device_io.h", "device_pool.h", "episode_clock.h", "policy.h", "evaluate.h", "warm_start.h", "simulate.h", "covariance.h", "stage_layout.h", "gen_dpp_blocks.py")]
     srcs.append(os.path.join(os.path.dirname(_HERE), "include", "altro_batch.h"))
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):
         return LIB_PATH

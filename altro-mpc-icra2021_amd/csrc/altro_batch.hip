@@ -75,22 +75,14 @@ static const SwitchKey kSwitchKeys[] = {
     {"wide_static_mask", &DebugSwitches::wide_static_mask, false, true},
 };
 
-struct altro_handle {
+struct altro_handle : altro::BackendCommon {   // what both backends hold and do alike: backend_common.h (on a wide handle
+                                                // the copy here keeps d, o, device and err, its arrays are never allocated)
   altro_wide::WideBackend* wide = nullptr;  // set: this handle runs on the one-wave-per-instance kernel
-  altro::DevicePool pool;                   // owns every device array below (device_pool.h); the members stay plain pointers
   DebugSwitches sw;                         // the switches as they were when the handle was created, then altro_debug_set(h, ..)
-  altro_dims d{};
-  altro_opts o{};
-  int device = 0;
-  int Bp = 0;  // batch padded to a multiple of IPW
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  bool timed = false;
-  altro::LaunchRing ring;        // start/end event pairs of the most recent solve launches
+  int Bp = 0;  // batch padded to a multiple of IPW (= slots)
   double* Zsave = nullptr;       // [Bp][N][16]: Z0 of altro_batch_benchmark_solve
   hipEvent_t bev0 = nullptr, bev1 = nullptr;
-  long long *n_backward = nullptr, *n_rollout = nullptr, *wave_cycles = nullptr;
-  long long *n_solves = nullptr, *n_iters = nullptr, *n_ok = nullptr, *n_trials = nullptr, *n_gconf = nullptr;
+  long long* wave_cycles = nullptr;
   int* dzero = nullptr;  // [Bp] the last iteration of the last solve was costate-confirmed: its d is zero
   // problem data (device)
   double *Gcol = nullptr, *Grow = nullptr, *fvec = nullptr;
@@ -98,43 +90,18 @@ struct altro_handle {
   // host copies of the cost weights and bounds: [rows][16] each, rows = 1 (shared by the batch) or batch (per instance)
   std::vector<double> wd_h, wf_h, zmin_h, zmax_h;
   bool bnd_stale = false;                // altro_batch_set_bounds_dev wrote the device rows: zmin_h / zmax_h are refreshed before use
-  unsigned long long* refusals = nullptr;  // device counter: rows altro_batch_set_bounds_dev refused since create
   bool cost_pi = false, bnd_pi = false;  // per-instance cost weights / bounds: the device tables then hold Bp rows (imask)
   int tab_cap = 1;                       // rows the device tables have room for
   bool box_lo_fin[LW] = {}, box_hi_fin[LW] = {};  // finite sides of the BOX as it was added (altro_batch_set_bounds)
   double *x0 = nullptr, *Zref = nullptr, *Z = nullptr, *Lb = nullptr, *mu = nullptr,
          *KD = nullptr, *Qz = nullptr, *Dff = nullptr, *kmu = nullptr;
   altro::ASet* ahash = nullptr;  // [Bp][16] active set of the backward pass behind the gains in KD (gain reuse, solve_dpp16.h)
-  long long* n_fo = nullptr;
-  // projected-Newton polish (pn_core.h): per-instance results and the workspace, allocated by the first solve that asks for it
-  altro_pn::PnOut pn_out;
-  altro_pn::PnWork pn_ws;
-  double *noise = nullptr, *noise_w = nullptr;
-  int* noise_grp = nullptr;
-  int noise_mode = 0;
-  int mpc_shift = 1;
-  double* mlog = nullptr;  // per-step log of the MPC loop (mpc_log.h): [mlog_cap][batch][16 + MLOG_TAIL]; null: off
-  int mlog_cap = 0;        // steps it holds
   bool d_in_kd = false;  // the last solve launch's kernel keeps d in the gain rows (altro::kd_holds_d), not in Dff
   int* cur = nullptr;
   int *perm = nullptr, *gscore = nullptr;  // [Bp] wave slot -> instance of a grouped MPC launch, and its sort key
   unsigned* simd_tab = nullptr;            // [65536][16], zero between launches
-  int *iters = nullptr, *iters_outer = nullptr, *status = nullptr;
-  double *cost = nullptr, *cmax = nullptr, *Jtrace = nullptr, *ctrace = nullptr, *atrace = nullptr;
-  double* stage = nullptr;  // device staging buffer for host<->device layout conversion
-  double* eval_ws = nullptr;   // altro_batch_evaluate(_dev): states of a rollout without Xout, or the gathered own trajectory (grow-only)
-  size_t eval_ws_elems = 0;
-  double* ws_merit = nullptr;  // altro_batch_warm_start(_dev): J, c_max [batch * (ncand + 1)] each when the caller passes none (grow-only)
-  size_t ws_merit_elems = 0;
   altro::StreamLink link;   // events of altro_batch_wait_stream / altro_batch_signal_stream (device_io.h)
-  altro::InstanceFlags flags;  // active mask and restart selection of a 16-lane handle, [Bp] (device_io.h; a wide handle's live in its backend)
-  altro::EpisodeClock clock;   // per-instance episode clock of a 16-lane handle, [Bp] (device_io.h; a wide handle's lives in its backend)
   int dev_via_stage = 0;    // "dev_via_stage": the _dev setters of x0 and the reference copy into `stage` first (measurement only)
-  size_t stage_bytes = 0;
-  int Nt = 0;    // knots held by Zref
-  int kref = 0;  // current reference window start
-  int noise_steps = 0;
-  int box_k0 = 0, box_k1 = -1, box_id = -1;
   // generic affine constraints packed into 4 quads of 4 constraint rows (see solve_dpp16.h)
   double *Acon = nullptr, *bcon = nullptr, *Lc = nullptr;
   int* cmeta = nullptr;
@@ -159,11 +126,20 @@ struct altro_handle {
   int bslot_h[LW];       // host copy: slot of z element j among the bounded ones, -1 if none
   int nbp = 1;           // slots per side of the compact dual rows
   int ncon = 0;
-  bool have_dyn = false, have_cost = false, have_ref = false, have_x0 = false;
-  bool dyn_per_instance = false;
+  bool have_x0 = false;
   double dt = 0.0;
-  std::string err;
 };
+
+// What the shared entry points act on: the backend the handle runs on.  They check their arguments, then
+// `return fwd(h, common(h).get_stats(..))`; fwd is the one place where a wide backend's message reaches altro_last_error.
+static altro::BackendCommon& common(altro_handle* h) {
+  if (h->wide) return *h->wide;
+  return *h;
+}
+static int fwd(altro_handle* h, int rc) {
+  if (rc && h->wide) h->err = h->wide->err;
+  return rc;
+}
 
 #define HIPCHK(h, call)                                                                   \
   do {                                                                                    \
@@ -180,20 +156,11 @@ struct altro_handle {
     return (code);         \
   } while (0)
 
-// forward an entry point to the wide backend when the handle runs on it (the device-pointer entry points: after the validation)
-#define WIDE_FWD(h, call)                           \
-  do {                                              \
-    if ((h) && (h)->wide) {                         \
-      const int rc_ = (h)->wide->call;              \
-      if (rc_) (h)->err = (h)->wide->err;           \
-      return rc_;                                   \
-    }                                               \
+// forward an entry point to the wide backend when the handle runs on it: always AFTER the handle and the arguments are checked
+#define WIDE_FWD(h, call)                                  \
+  do {                                                     \
+    if ((h)->wide) return fwd(h, (h)->wide->call);         \
   } while (0)
-
-static int ensure_stage(altro_handle* h, size_t bytes) {
-  HIPCHK(h, h->pool.reserve(reinterpret_cast<char**>(&h->stage), &h->stage_bytes, bytes));
-  return ALTRO_OK;
-}
 
 // ------------------------------------------------------------------ layout kernels
 // All take one thread per (instance slot, lane); padded slots mirror instance B-1.
@@ -628,7 +595,7 @@ static int launch_solve(altro_handle* h, int first_step, int nsteps, int prepare
   p.wd = h->wd; p.wf = h->wf; p.zmin = h->zmin; p.zmax = h->zmax; p.imask = tab_imask(h);
   p.x0 = h->x0; p.Zref = h->Zref; p.Z = h->Z; p.cur = h->cur;
   p.Lb = h->Lb; p.bslot = h->bslot; p.nbp = h->nbp; p.mu = h->mu; p.lone = h->sw.lone; p.pair = h->sw.pair; p.useqz = h->sw.useqz; p.shadow = h->sw.shadow; p.reuse = h->sw.reuse; p.resync = h->sw.resync; p.dbg_wave = h->sw.dbg_wave;
-  p.Dff = h->Dff; p.ahash = h->ahash; p.kmu = h->kmu; p.n_fo = h->n_fo;
+  p.Dff = h->Dff; p.ahash = h->ahash; p.kmu = h->kmu; p.n_fo = h->n_reuse;
   p.Qz = h->Qz;
   p.Acon = h->Acon; p.bcon = h->bcon; p.cmeta = h->cmeta; p.ckn = h->ckn; p.con_inv = h->con_inv;
   p.con_istride = h->con_per_instance ? (unsigned)(h->d.N * LW * LW) : 0u; p.Lc = h->Lc; p.ncrows = h->ncrows; p.KD = h->KD;
@@ -691,13 +658,6 @@ static int drop_gains(altro_handle* h) {
     hipLaunchKernelGGL(k_fill, grid_for((size_t)h->Bp), dim3(256), 0, h->stream, h->kmu, -1.0, (size_t)h->Bp);
     HIPCHK(h, hipGetLastError());
   }
-  return ALTRO_OK;
-}
-
-static int check_ready(altro_handle* h) {
-  if (!h->have_dyn) FAIL(h, ALTRO_ERR_STATE, "altro_batch_set_dynamics has not been called");
-  if (!h->have_cost) FAIL(h, ALTRO_ERR_STATE, "altro_batch_set_tracking_cost has not been called");
-  if (!h->have_ref) FAIL(h, ALTRO_ERR_STATE, "no reference trajectory (altro_batch_set_reference / altro_mpc_set_track)");
   return ALTRO_OK;
 }
 
@@ -873,6 +833,9 @@ int32_t altro_batch_create(const altro_dims* dims, const altro_opts* opts, int32
     h->device = device;
     h->sw = g_dbg;
     h->Bp = (dims->batch + IPW - 1) / IPW * IPW;
+    h->slots = h->Bp;
+    h->mlog_rec = LW + altro::MLOG_TAIL;
+    h->noise_len = LW;
     auto fail = [&](const char* what, hipError_t er) {
       g_create_err = std::string(what) + ": " + hipGetErrorString(er);
       return ALTRO_ERR_HIP;      // (the Owner releases the handle)
@@ -909,7 +872,7 @@ int32_t altro_batch_create(const altro_dims* dims, const altro_opts* opts, int32
     DA(cur, Bp); DA(perm, Bp); DA(gscore, Bp); DA(refusals, 1);
     DA(iters, Bp); DA(iters_outer, Bp); DA(status, Bp); DA(cost, Bp); DA(cmax, Bp);
     DA(Jtrace, Bp * ALTRO_TRACE_LEN); DA(ctrace, Bp * ALTRO_TRACE_LEN); DA(atrace, Bp * ALTRO_TRACE_LEN);
-    DA(n_backward, Bp); DA(n_rollout, Bp); DA(n_solves, Bp); DA(n_iters, Bp); DA(n_ok, Bp); DA(n_trials, Bp); DA(n_gconf, Bp); DA(n_fo, Bp);
+    DA(n_backward, Bp); DA(n_rollout, Bp); DA(n_solves, Bp); DA(n_iters, Bp); DA(n_ok, Bp); DA(n_trials, Bp); DA(n_gconf, Bp); DA(n_reuse, Bp);
     DA(wave_cycles, Bp * 6 + 4096); DA(simd_tab, (size_t)65536 * 16);
   #undef DA
     // what does not start at zero: no bounds until a BOX constraint is added, no bounded element, no constraint row on any
@@ -957,14 +920,10 @@ int32_t altro_batch_destroy(altro_handle* h) {
   if (!h) return ALTRO_OK;
   if (h->wide) {
     h->wide->destroy();
-    h->flags.destroy();
-    h->clock.destroy();
-    h->link.destroy();
     delete h->wide;
-    delete h;
-    return ALTRO_OK;
+  } else {
+    free_dpp_backend(h);
   }
-  free_dpp_backend(h);
   h->flags.destroy();
   h->clock.destroy();
   h->link.destroy();
@@ -993,7 +952,7 @@ static int migrate_to_wide(altro_handle* h) {
   }
   if (h->have_x0) {  // an initial state uploaded before the model: carried over, not dropped
     std::vector<double> x((size_t)h->d.batch * h->d.n);
-    int rcx = ensure_stage(h, x.size() * sizeof(double));
+    int rcx = h->ensure_stage(x.size() * sizeof(double));
     if (!rcx) {
       hipLaunchKernelGGL(k_unpack_x0, grid_for((size_t)h->d.batch * LW), dim3(256), 0, h->stream, h->stage, h->x0, h->d.batch, h->d.n);
       if (hipMemcpyAsync(x.data(), h->stage, x.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
@@ -1008,7 +967,7 @@ static int migrate_to_wide(altro_handle* h) {
     }
   }
   if (h->mlog_cap > 0) {  // altro_mpc_set_log before the model: the setting moves with the handle (the records start empty)
-    const int rcl = wb->mpc_set_log(h->mlog_cap);
+    const int rcl = wb->set_log(h->mlog_cap);
     if (rcl) {
       h->err = wb->err;
       wb->destroy();
@@ -1033,7 +992,7 @@ static int set_dynamics_16(altro_handle* h, const double* A, const double* B, co
   const size_t nb = per_instance ? h->d.batch : 1;
   if (!dev) {
     const size_t tot = nb * (n * n + n * m + n);
-    int rc = ensure_stage(h, tot * sizeof(double));
+    int rc = h->ensure_stage(tot * sizeof(double));
     if (rc) return rc;
     if ((rc = upload(h, A, nb * n * n, 0))) return rc;
     if ((rc = upload(h, B, nb * n * m, nb * n * n))) return rc;
@@ -1055,15 +1014,11 @@ static int set_dynamics_16(altro_handle* h, const double* A, const double* B, co
 int32_t altro_batch_set_dynamics(altro_handle* h, const double* A, const double* B, const double* f,
                                  int32_t per_knot, int32_t per_instance) {
   return guard(h, [&]() -> int32_t {
-    WIDE_FWD(h, set_dynamics(A, B, f, per_knot, per_instance));
     if (!h || !A || !B) return ALTRO_ERR_INVALID_ARG;
-    if (per_knot) {
-      const int rc = migrate_to_wide(h);
-      if (rc) return rc;
-      const int rc2 = h->wide->set_dynamics(A, B, f, per_knot, per_instance);
-      if (rc2) h->err = h->wide->err;
-      return rc2;
+    if (per_knot && !h->wide) {
+      if (int rc = migrate_to_wide(h)) return rc;
     }
+    WIDE_FWD(h, set_dynamics(A, B, f, per_knot, per_instance));
     return set_dynamics_16(h, A, B, f, per_instance, false);
   });
 }
@@ -1091,8 +1046,8 @@ static int set_cost_rows(altro_handle* h, const double* Qd, const double* Rd, co
 
 int32_t altro_batch_set_tracking_cost(altro_handle* h, const double* Qd, const double* Rd, const double* Qfd, double dt) {
   return guard(h, [&]() -> int32_t {
-    WIDE_FWD(h, set_tracking_cost(Qd, Rd, Qfd, dt));
     if (!h || !Qd || !Rd || !Qfd || !(dt > 0)) return ALTRO_ERR_INVALID_ARG;
+    WIDE_FWD(h, set_tracking_cost(Qd, Rd, Qfd, dt));
     return set_cost_rows(h, Qd, Rd, Qfd, dt, false);
   });
 }
@@ -1100,8 +1055,8 @@ int32_t altro_batch_set_tracking_cost(altro_handle* h, const double* Qd, const d
 int32_t altro_batch_set_tracking_cost_per_instance(altro_handle* h, const double* Qd, const double* Rd, const double* Qfd,
                                                    double dt) {
   return guard(h, [&]() -> int32_t {
-    WIDE_FWD(h, set_tracking_cost_per_instance(Qd, Rd, Qfd, dt));
     if (!h || !Qd || !Rd || !Qfd || !(dt > 0)) return ALTRO_ERR_INVALID_ARG;
+    WIDE_FWD(h, set_tracking_cost_per_instance(Qd, Rd, Qfd, dt));
     return set_cost_rows(h, Qd, Rd, Qfd, dt, true);
   });
 }
@@ -1253,15 +1208,16 @@ int32_t altro_batch_add_constraint(altro_handle* h, int32_t kind, int32_t sense,
                                    int32_t p, const double* A, const double* b, const double* zmin, const double* zmax,
                                    int32_t per_knot, int32_t* con_id) {
   return guard(h, [&]() -> int32_t {
-    WIDE_FWD(h, add_constraint(kind, sense, k_first, k_last, p, A, b, zmin, zmax, per_knot, con_id));
     if (!h) return ALTRO_ERR_INVALID_ARG;
     if (k_first < 0 || k_last >= h->d.N || k_last < k_first) FAIL(h, ALTRO_ERR_INVALID_ARG, "bad knot range");
+    if (kind == ALTRO_CON_BOX ? (!zmin || !zmax) : (kind != ALTRO_CON_LINEAR && kind != ALTRO_CON_SOC) || !A || !b || p < 1) return ALTRO_ERR_INVALID_ARG;
+    if (kind == ALTRO_CON_LINEAR && sense != ALTRO_SENSE_EQ && sense != ALTRO_SENSE_INEQ) return ALTRO_ERR_INVALID_ARG;
+    // (what a backend cannot hold, and what the state of the handle forbids, is each backend's own answer from here on)
+    WIDE_FWD(h, add_constraint(kind, sense, k_first, k_last, p, A, b, zmin, zmax, per_knot, con_id));
     HIPCHK(h, hipSetDevice(h->device));
     const int nz = h->d.n + h->d.m;
     if (kind == ALTRO_CON_LINEAR || kind == ALTRO_CON_SOC) {
-      if (!A || !b || p < 1) return ALTRO_ERR_INVALID_ARG;
       if (kind == ALTRO_CON_SOC && (p < 2 || p > 4)) FAIL(h, ALTRO_ERR_UNSUPPORTED, "second-order cones of dimension 2..4 are built");
-      if (kind == ALTRO_CON_LINEAR && sense != ALTRO_SENSE_EQ && sense != ALTRO_SENSE_INEQ) return ALTRO_ERR_INVALID_ARG;
       if (h->con_locked) FAIL(h, ALTRO_ERR_STATE, "constraints must be added before the first solve");
       altro_handle::ConBlock cb;
       cb.id = h->ncon; cb.kind = kind; cb.sense = sense; cb.k0 = k_first; cb.k1 = k_last; cb.p = p;
@@ -1279,9 +1235,7 @@ int32_t altro_batch_add_constraint(altro_handle* h, int32_t kind, int32_t sense,
       h->ncon++;
       return ALTRO_OK;
     }
-    if (kind != ALTRO_CON_BOX) return ALTRO_ERR_INVALID_ARG;
     if (h->box_id >= 0) FAIL(h, ALTRO_ERR_UNSUPPORTED, "one BOX constraint per problem");
-    if (!zmin || !zmax) return ALTRO_ERR_INVALID_ARG;
     std::vector<double> lo(LW, -INFINITY), hi(LW, INFINITY);
     for (int j = 0; j < nz; ++j) { lo[j] = zmin[j]; hi[j] = zmax[j]; }
     for (int j = 0; j < LW; ++j) { h->box_lo_fin[j] = j < nz && lo[j] > -1e300; h->box_hi_fin[j] = j < nz && hi[j] < 1e300; }
@@ -1313,8 +1267,8 @@ int32_t altro_batch_add_constraint(altro_handle* h, int32_t kind, int32_t sense,
 
 int32_t altro_batch_update_constraint_data(altro_handle* h, int32_t con_id, const double* A, const double* b) {
   return guard(h, [&]() -> int32_t {
-    WIDE_FWD(h, update_constraint_data(con_id, A, b));
     if (!h) return ALTRO_ERR_INVALID_ARG;
+    WIDE_FWD(h, update_constraint_data(con_id, A, b));
     HIPCHK(h, hipSetDevice(h->device));
     const int nz = h->d.n + h->d.m;
     for (auto& cb : h->cons) {
@@ -1335,10 +1289,10 @@ int32_t altro_batch_update_constraint_data(altro_handle* h, int32_t con_id, cons
 
 int32_t altro_batch_set_bounds(altro_handle* h, int32_t con_id, const double* zmin, const double* zmax, int32_t per_instance) {
   return guard(h, [&]() -> int32_t {
-    WIDE_FWD(h, set_bounds(con_id, zmin, zmax, per_instance));
     if (!h) return ALTRO_ERR_INVALID_ARG;
-    if (h->box_id < 0 || con_id != h->box_id) FAIL(h, ALTRO_ERR_INVALID_ARG, "altro_batch_set_bounds: con_id is not a BOX constraint");
+    if (common(h).box_id < 0 || con_id != common(h).box_id) FAIL(h, ALTRO_ERR_INVALID_ARG, "altro_batch_set_bounds: con_id is not a BOX constraint");
     if (!zmin || !zmax) return ALTRO_ERR_INVALID_ARG;
+    WIDE_FWD(h, set_bounds(zmin, zmax, per_instance));
     const int nz = h->d.n + h->d.m;
     const size_t rows = per_instance ? (size_t)h->d.batch : 1;
     if (const char* e = altro_wide::check_bound_rows(zmin, zmax, rows, nz, h->box_lo_fin, h->box_hi_fin)) FAIL(h, ALTRO_ERR_INVALID_ARG, e);
@@ -1369,7 +1323,7 @@ static int set_x0_16(altro_handle* h, const double* x0, bool dev) {
   HIPCHK(h, hipSetDevice(h->device));
   const size_t cnt = (size_t)h->d.batch * h->d.n;
   if (!dev || h->dev_via_stage) {
-    int rc = ensure_stage(h, cnt * sizeof(double));
+    int rc = h->ensure_stage(cnt * sizeof(double));
     if (rc) return rc;
     if ((rc = dev ? stage_d2d(h, x0, cnt) : upload(h, x0, cnt))) return rc;
     x0 = h->stage;
@@ -1384,8 +1338,8 @@ static int set_x0_16(altro_handle* h, const double* x0, bool dev) {
 
 int32_t altro_batch_set_initial_state(altro_handle* h, const double* x0) {
   return guard(h, [&]() -> int32_t {
-    WIDE_FWD(h, set_initial_state(x0));
     if (!h || !x0) return ALTRO_ERR_INVALID_ARG;
+    WIDE_FWD(h, set_initial_state(x0));
     return set_x0_16(h, x0, false);
   });
 }
@@ -1394,7 +1348,7 @@ static int get_x0_16(altro_handle* h, double* x0, bool dev) {
   HIPCHK(h, hipSetDevice(h->device));
   const size_t cnt = (size_t)h->d.batch * h->d.n;
   if (!dev) {
-    int rc = ensure_stage(h, cnt * sizeof(double));
+    int rc = h->ensure_stage(cnt * sizeof(double));
     if (rc) return rc;
   }
   hipLaunchKernelGGL(k_unpack_x0, grid_for((size_t)h->d.batch * LW), dim3(256), 0, h->stream, dev ? x0 : h->stage, h->x0,
@@ -1408,8 +1362,8 @@ static int get_x0_16(altro_handle* h, double* x0, bool dev) {
 
 int32_t altro_batch_get_initial_state(altro_handle* h, double* x0) {
   return guard(h, [&]() -> int32_t {
-    WIDE_FWD(h, get_initial_state(x0));
     if (!h || !x0) return ALTRO_ERR_INVALID_ARG;
+    WIDE_FWD(h, get_initial_state(x0));
     return get_x0_16(h, x0, false);
   });
 }
@@ -1418,7 +1372,7 @@ static int set_ref_common(altro_handle* h, const double* Xref, const double* Ure
   const size_t B = h->d.batch, n = h->d.n, m = h->d.m;
   const size_t cx = B * Nt * n, cu = B * (Nt - 1) * m;
   const bool staged = !dev || h->dev_via_stage;
-  int rc = staged ? ensure_stage(h, (cx + cu) * sizeof(double)) : ALTRO_OK;
+  int rc = staged ? h->ensure_stage((cx + cu) * sizeof(double)) : ALTRO_OK;
   if (rc) return rc;
   if ((size_t)Nt * h->Bp * LW * sizeof(double) >= (1ull << 32)) FAIL(h, ALTRO_ERR_UNSUPPORTED, "reference trajectory too large for one handle (below 4 GiB)");
   if (h->Nt != Nt || !h->Zref) {
@@ -1448,8 +1402,8 @@ static int set_ref_common(altro_handle* h, const double* Xref, const double* Ure
 
 int32_t altro_batch_set_reference(altro_handle* h, const double* Xref, const double* Uref) {
   return guard(h, [&]() -> int32_t {
-    WIDE_FWD(h, set_reference(Xref, Uref));
     if (!h || !Xref || !Uref) return ALTRO_ERR_INVALID_ARG;
+    WIDE_FWD(h, set_reference(Xref, Uref));
     HIPCHK(h, hipSetDevice(h->device));
     return set_ref_common(h, Xref, Uref, h->d.N);
   });
@@ -1461,7 +1415,7 @@ static int set_traj_16(altro_handle* h, const double* X, const double* U, bool d
   const size_t cx = X ? B * N * n : 0, cu = B * (N - 1) * m;
   const int have_x = X ? 1 : 0;
   if (!dev) {
-    int rc = ensure_stage(h, (cx + cu) * sizeof(double));
+    int rc = h->ensure_stage((cx + cu) * sizeof(double));
     if (rc) return rc;
     if (X && (rc = upload(h, X, cx, 0))) return rc;
     if ((rc = upload(h, U, cu, cx))) return rc;
@@ -1478,16 +1432,16 @@ static int set_traj_16(altro_handle* h, const double* X, const double* U, bool d
 
 int32_t altro_batch_set_initial_trajectory(altro_handle* h, const double* X, const double* U) {
   return guard(h, [&]() -> int32_t {
-    WIDE_FWD(h, set_initial_trajectory(X, U));
     if (!h || !U) return ALTRO_ERR_INVALID_ARG;
+    WIDE_FWD(h, set_initial_trajectory(X, U));
     return set_traj_16(h, X, U, false);
   });
 }
 
 int32_t altro_batch_shift_fill(altro_handle* h, int32_t primal, int32_t dual) {
   return guard(h, [&]() -> int32_t {
-    WIDE_FWD(h, shift_fill(primal, dual));
     if (!h) return ALTRO_ERR_INVALID_ARG;
+    WIDE_FWD(h, shift_fill(primal, dual));
     HIPCHK(h, hipSetDevice(h->device));
     const size_t plane = (size_t)h->d.N * LW;
     hipLaunchKernelGGL(k_shift, grid_for((size_t)h->Bp * LW), dim3(256), 0, h->stream, h->Z, h->cur, plane, h->Lb,
@@ -1500,11 +1454,9 @@ int32_t altro_batch_shift_fill(altro_handle* h, int32_t primal, int32_t dual) {
 
 int32_t altro_batch_set_options(altro_handle* h, const altro_opts* o) {
   return guard(h, [&]() -> int32_t {
-    if (h && h->wide && o) {
-      h->wide->o = *o; h->wide->gains_valid = false; h->o = *o; return ALTRO_OK;
-    }
     if (!h || !o) return ALTRO_ERR_INVALID_ARG;
     h->o = *o;
+    if (h->wide) { h->wide->o = *o; h->wide->gains_valid = false; return ALTRO_OK; }
     HIPCHK(h, hipSetDevice(h->device));
     return drop_gains(h);
   });
@@ -1542,7 +1494,7 @@ static int launch_polish(altro_handle* h, const int* mask) {
 
 static int enqueue_solve(altro_handle* h, int first_step, int nsteps) {
   HIPCHK(h, hipSetDevice(h->device));
-  int rc = check_ready(h);
+  int rc = h->check_ready();
   if (rc) return rc;
   if ((rc = pack_constraints(h))) return rc;
   h->con_locked = true;
@@ -1572,7 +1524,7 @@ static int enqueue_solve(altro_handle* h, int first_step, int nsteps) {
       h->kref = first_step + s + 1;
       if (!rc) rc = launch_polish(h, mask);
       if (!rc && h->mlog) {
-        double* rec0 = h->mlog + (size_t)(first_step + s) * (size_t)h->d.batch * (LW + altro::MLOG_TAIL);
+        double* rec0 = h->mlog + (size_t)(first_step + s) * (size_t)h->d.batch * h->mlog_rec;
         hipLaunchKernelGGL(k_log_polished, grid_for((size_t)h->d.batch), dim3(256), 0, h->stream, rec0, h->Z, h->cur, (size_t)h->d.N * LW,
                            h->cost, h->cmax, h->status, mask, h->d.batch, h->d.N, h->d.n, h->d.m);
         if (hipGetLastError() != hipSuccess) { h->err = "launch of the log kernel failed"; rc = ALTRO_ERR_HIP; }
@@ -1594,19 +1546,16 @@ static int enqueue_solve(altro_handle* h, int first_step, int nsteps) {
 
 int32_t altro_batch_solve_async(altro_handle* h) {
   return guard(h, [&]() -> int32_t {
-    WIDE_FWD(h, enqueue(0, 0, 0));
     if (!h) return ALTRO_ERR_INVALID_ARG;
+    WIDE_FWD(h, enqueue(0, 0, 0));
     return enqueue_solve(h, 0, 0);
   });
 }
 
 int32_t altro_batch_synchronize(altro_handle* h) {
   return guard(h, [&]() -> int32_t {
-    WIDE_FWD(h, synchronize());
     if (!h) return ALTRO_ERR_INVALID_ARG;
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return ALTRO_OK;
+    return fwd(h, common(h).synchronize());
   });
 }
 
@@ -1629,7 +1578,7 @@ static int get_traj(altro_handle* h, double* X, double* U, bool dev = false) {
     HIPCHK(h, hipGetLastError());
     return ALTRO_OK;
   }
-  int rc = ensure_stage(h, (cx + cu) * sizeof(double));
+  int rc = h->ensure_stage((cx + cu) * sizeof(double));
   if (rc) return rc;
   hipLaunchKernelGGL(k_unpack_traj, grid_for(B * LW), dim3(256), 0, h->stream, X ? h->stage : nullptr,
                      U ? h->stage + cx : nullptr, h->Z, h->cur, plane, (int)B, h->Bp, (int)N, (int)n, (int)m);
@@ -1642,16 +1591,16 @@ static int get_traj(altro_handle* h, double* X, double* U, bool dev = false) {
 
 int32_t altro_batch_get_states(altro_handle* h, double* X) {
   return guard(h, [&]() -> int32_t {
-    WIDE_FWD(h, get_planes(X, nullptr));
     if (!h || !X) return ALTRO_ERR_INVALID_ARG;
+    WIDE_FWD(h, get_planes(X, nullptr));
     return get_traj(h, X, nullptr);
   });
 }
 
 int32_t altro_batch_get_controls(altro_handle* h, double* U) {
   return guard(h, [&]() -> int32_t {
-    WIDE_FWD(h, get_planes(nullptr, U));
     if (!h || !U) return ALTRO_ERR_INVALID_ARG;
+    WIDE_FWD(h, get_planes(nullptr, U));
     return get_traj(h, nullptr, U);
   });
 }
@@ -1662,7 +1611,7 @@ static int duals_xfer(altro_handle* h, int32_t con_id, double* lambda, int to_ho
     if (cb.id != con_id) continue;
     const size_t nk = cb.k1 - cb.k0 + 1;
     const size_t cnt = (size_t)h->d.batch * nk * cb.p;
-    int rc = ensure_stage(h, cnt * sizeof(double));
+    int rc = h->ensure_stage(cnt * sizeof(double));
     if (rc) return rc;
     if (!to_host && (rc = upload(h, lambda, cnt))) return rc;
     HIPCHK(h, hipMemcpyAsync(h->lanebuf, cb.lanes, LW * sizeof(int), hipMemcpyHostToDevice, h->stream));
@@ -1677,7 +1626,7 @@ static int duals_xfer(altro_handle* h, int32_t con_id, double* lambda, int to_ho
   const int nz = h->d.n + h->d.m;
   const size_t nk = h->box_k1 - h->box_k0 + 1;
   const size_t cnt = (size_t)h->d.batch * nk * 2 * nz;
-  int rc = ensure_stage(h, cnt * sizeof(double));
+  int rc = h->ensure_stage(cnt * sizeof(double));
   if (rc) return rc;
   if (!to_host && (rc = upload(h, lambda, cnt))) return rc;
   hipLaunchKernelGGL(k_duals, grid_for((size_t)h->Bp * LW), dim3(256), 0, h->stream, h->stage, h->Lb, h->bslot, h->nbp,
@@ -1690,16 +1639,16 @@ static int duals_xfer(altro_handle* h, int32_t con_id, double* lambda, int to_ho
 
 int32_t altro_batch_get_duals(altro_handle* h, int32_t con_id, double* lambda) {
   return guard(h, [&]() -> int32_t {
-    WIDE_FWD(h, duals(con_id, lambda, false));
     if (!h || !lambda) return ALTRO_ERR_INVALID_ARG;
+    WIDE_FWD(h, duals(con_id, lambda, false));
     return duals_xfer(h, con_id, lambda, 1);
   });
 }
 
 int32_t altro_batch_set_duals(altro_handle* h, int32_t con_id, const double* lambda) {
   return guard(h, [&]() -> int32_t {
-    WIDE_FWD(h, duals(con_id, const_cast<double*>(lambda), true));
     if (!h || !lambda) return ALTRO_ERR_INVALID_ARG;
+    WIDE_FWD(h, duals(con_id, const_cast<double*>(lambda), true));
     return duals_xfer(h, con_id, const_cast<double*>(lambda), 0);
   });
 }
@@ -1707,30 +1656,15 @@ int32_t altro_batch_set_duals(altro_handle* h, int32_t con_id, const double* lam
 int32_t altro_batch_get_stats(altro_handle* h, int32_t* iterations, int32_t* iterations_outer, int32_t* status,
                               double* cost, double* c_max, double* cost_trace, double* cmax_trace) {
   return guard(h, [&]() -> int32_t {
-    WIDE_FWD(h, get_stats(iterations, iterations_outer, status, cost, c_max, cost_trace, cmax_trace));
     if (!h) return ALTRO_ERR_INVALID_ARG;
-    HIPCHK(h, hipSetDevice(h->device));
-    const size_t B = h->d.batch;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (iterations) HIPCHK(h, hipMemcpy(iterations, h->iters, B * sizeof(int), hipMemcpyDeviceToHost));
-    if (iterations_outer) HIPCHK(h, hipMemcpy(iterations_outer, h->iters_outer, B * sizeof(int), hipMemcpyDeviceToHost));
-    if (status) HIPCHK(h, hipMemcpy(status, h->status, B * sizeof(int), hipMemcpyDeviceToHost));
-    if (cost) HIPCHK(h, hipMemcpy(cost, h->cost, B * sizeof(double), hipMemcpyDeviceToHost));
-    if (c_max) HIPCHK(h, hipMemcpy(c_max, h->cmax, B * sizeof(double), hipMemcpyDeviceToHost));
-    if (cost_trace) HIPCHK(h, hipMemcpy(cost_trace, h->Jtrace, B * ALTRO_TRACE_LEN * sizeof(double), hipMemcpyDeviceToHost));
-    if (cmax_trace) HIPCHK(h, hipMemcpy(cmax_trace, h->ctrace, B * ALTRO_TRACE_LEN * sizeof(double), hipMemcpyDeviceToHost));
-    return ALTRO_OK;
+    return fwd(h, common(h).get_stats(iterations, iterations_outer, status, cost, c_max, cost_trace, cmax_trace));
   });
 }
 
 int32_t altro_batch_get_alpha_trace(altro_handle* h, double* alpha_trace) {
   return guard(h, [&]() -> int32_t {
-    WIDE_FWD(h, get_alpha_trace(alpha_trace));
     if (!h || !alpha_trace) return ALTRO_ERR_INVALID_ARG;
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipMemcpy(alpha_trace, h->atrace, (size_t)h->d.batch * ALTRO_TRACE_LEN * sizeof(double), hipMemcpyDeviceToHost));
-    return ALTRO_OK;
+    return fwd(h, common(h).get_alpha_trace(alpha_trace));
   });
 }
 
@@ -1743,8 +1677,10 @@ static int fetch_kd(altro_handle* h, std::vector<double>& kd) {
 
 int32_t altro_batch_get_gains(altro_handle* h, double* K, double* d) {
   return guard(h, [&]() -> int32_t {
+    if (!h) return ALTRO_ERR_INVALID_ARG;
+    // (both null: the header says only that either may be; the 16-lane backend has always refused it, the wide one copies nothing)
+    if (!K && !d && !h->wide) return ALTRO_ERR_INVALID_ARG;
     WIDE_FWD(h, get_gains(K, d));
-    if (!h || (!K && !d)) return ALTRO_ERR_INVALID_ARG;
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     const size_t n = h->d.n, m = h->d.m, N = h->d.N, B = h->d.batch, Bp = h->Bp;
@@ -1798,132 +1734,75 @@ int32_t altro_batch_get_gain_factors(altro_handle* h, double* F) {
 
 int32_t altro_batch_last_solve_ms(altro_handle* h, float* ms) {
   return guard(h, [&]() -> int32_t {
-    WIDE_FWD(h, last_solve_ms(ms));
     if (!h || !ms) return ALTRO_ERR_INVALID_ARG;
-    if (!h->timed) FAIL(h, ALTRO_ERR_STATE, "no solve has been launched");
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipEventSynchronize(h->ev1));
-    HIPCHK(h, hipEventElapsedTime(ms, h->ev0, h->ev1));
-    return ALTRO_OK;
+    return fwd(h, common(h).last_solve_ms(ms));
   });
 }
 
 int32_t altro_batch_timing_reset(altro_handle* h) {
   return guard(h, [&]() -> int32_t {
-    WIDE_FWD(h, timing_reset());
     if (!h) return ALTRO_ERR_INVALID_ARG;
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->ring.reset();
-    HIPCHK(h, hipMemsetAsync(h->n_backward, 0, h->Bp * sizeof(long long), h->stream));
-    HIPCHK(h, hipMemsetAsync(h->n_rollout, 0, h->Bp * sizeof(long long), h->stream));
-    HIPCHK(h, hipMemsetAsync(h->n_solves, 0, h->Bp * sizeof(long long), h->stream));
-    HIPCHK(h, hipMemsetAsync(h->n_iters, 0, h->Bp * sizeof(long long), h->stream));
-    HIPCHK(h, hipMemsetAsync(h->n_ok, 0, h->Bp * sizeof(long long), h->stream));
-    HIPCHK(h, hipMemsetAsync(h->n_trials, 0, h->Bp * sizeof(long long), h->stream));
-    HIPCHK(h, hipMemsetAsync(h->n_gconf, 0, h->Bp * sizeof(long long), h->stream));
-    HIPCHK(h, hipMemsetAsync(h->n_fo, 0, h->Bp * sizeof(long long), h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return ALTRO_OK;
+    return fwd(h, common(h).timing_reset());
   });
 }
 
 int32_t altro_batch_timing_get(altro_handle* h, float* ms, int32_t capacity, int32_t* count) {
   return guard(h, [&]() -> int32_t {
-    WIDE_FWD(h, timing_get(ms, capacity, count));
-    if (!h || !count) return ALTRO_ERR_INVALID_ARG;
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    const int32_t n = (int32_t)h->ring.readable();
-    *count = n;
-    for (int32_t i = 0; ms && i < n && i < capacity; ++i) HIPCHK(h, h->ring.elapsed((size_t)i, &ms[i]));
-    return ALTRO_OK;
+    if (!h) return ALTRO_ERR_INVALID_ARG;
+    // (count null: the header is silent; the 16-lane backend has always refused it, the wide one takes it as "not asked for")
+    if (!count && !h->wide) return ALTRO_ERR_INVALID_ARG;
+    return fwd(h, common(h).timing_get(ms, capacity, count));
   });
 }
 
 int32_t altro_batch_get_solve_counters(altro_handle* h, int64_t* solves, int64_t* iterations, int64_t* succeeded) {
   return guard(h, [&]() -> int32_t {
-    if (h && h->wide) { long long* const src[3] = {h->wide->n_solves, h->wide->n_iters, h->wide->n_ok}; const int rc_ = h->wide->counters(src, solves, iterations, succeeded); if (rc_) h->err = h->wide->err; return rc_; }
     if (!h) return ALTRO_ERR_INVALID_ARG;
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    const size_t B = h->d.batch;
-    if (solves) HIPCHK(h, hipMemcpy(solves, h->n_solves, B * sizeof(long long), hipMemcpyDeviceToHost));
-    if (iterations) HIPCHK(h, hipMemcpy(iterations, h->n_iters, B * sizeof(long long), hipMemcpyDeviceToHost));
-    if (succeeded) HIPCHK(h, hipMemcpy(succeeded, h->n_ok, B * sizeof(long long), hipMemcpyDeviceToHost));
-    return ALTRO_OK;
+    altro::BackendCommon& c = common(h);
+    long long* const src[3] = {c.n_solves, c.n_iters, c.n_ok};
+    return fwd(h, c.counters(src, solves, iterations, succeeded));
   });
 }
 
 int32_t altro_batch_get_work_counters(altro_handle* h, int64_t* backward_passes, int64_t* rollouts, int64_t* trials) {
   return guard(h, [&]() -> int32_t {
-    if (h && h->wide) { long long* const src[3] = {h->wide->n_backward, h->wide->n_rollout, h->wide->n_trials}; const int rc_ = h->wide->counters(src, backward_passes, rollouts, trials); if (rc_) h->err = h->wide->err; return rc_; }
     if (!h) return ALTRO_ERR_INVALID_ARG;
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    const size_t B = h->d.batch;
-    if (backward_passes) HIPCHK(h, hipMemcpy(backward_passes, h->n_backward, B * sizeof(long long), hipMemcpyDeviceToHost));
-    if (rollouts) HIPCHK(h, hipMemcpy(rollouts, h->n_rollout, B * sizeof(long long), hipMemcpyDeviceToHost));
-    if (trials) HIPCHK(h, hipMemcpy(trials, h->n_trials, B * sizeof(long long), hipMemcpyDeviceToHost));
-    return ALTRO_OK;
+    altro::BackendCommon& c = common(h);
+    long long* const src[3] = {c.n_backward, c.n_rollout, c.n_trials};
+    return fwd(h, c.counters(src, backward_passes, rollouts, trials));
   });
 }
 
 int32_t altro_batch_get_reuse_counter(altro_handle* h, int64_t* reused) {
   return guard(h, [&]() -> int32_t {
     if (!h || !reused) return ALTRO_ERR_INVALID_ARG;
-    HIPCHK(h, hipSetDevice(h->device));
-    if (h->wide) {
-      HIPCHK(h, hipStreamSynchronize(h->wide->stream));
-      HIPCHK(h, hipMemcpy(reused, h->wide->n_gs, (size_t)h->d.batch * sizeof(long long), hipMemcpyDeviceToHost));
-      return ALTRO_OK;
-    }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipMemcpy(reused, h->n_fo, (size_t)h->d.batch * sizeof(long long), hipMemcpyDeviceToHost));
-    return ALTRO_OK;
+    long long* const src[3] = {common(h).n_reuse, nullptr, nullptr};
+    return fwd(h, common(h).counters(src, reused, nullptr, nullptr));
   });
 }
 
-// Both polish getters on both backends (pn_core.h PnOut::read): zeros while projected_newton is off, or before a handle on
-// the one-wave-per-instance backend has polished.
-static int32_t read_polish(altro_handle* h, bool stats, int32_t* ran, int32_t* failed, double* res, double* dres0, double* dres, int32_t* dfail) {
-  if (!h) return ALTRO_ERR_INVALID_ARG;
-  HIPCHK(h, hipSetDevice(h->device));
-  const altro_pn::PnOut& out = h->wide ? h->wide->pn_out : h->pn_out;
-  const hipStream_t st = h->wide ? h->wide->stream : h->stream;
-  const bool on = (h->wide ? h->wide->o : h->o).projected_newton;
-  if (stats && !on && !h->wide) {
-    // the statistics themselves go back to zero: an instance that a mask keeps out of the first polish after the option is
-    // switched on reports them
-    HIPCHK(h, hipMemsetAsync(out.ran, 0, h->Bp * sizeof(int), st));
-    HIPCHK(h, hipMemsetAsync(out.failed, 0, h->Bp * sizeof(int), st));
-    HIPCHK(h, hipMemsetAsync(out.res, 0, h->Bp * sizeof(double), st));
-  }
-  HIPCHK(h, out.read(st, on && out.ran, (size_t)h->d.batch, ran, failed, res, dres0, dres, dfail));
-  return ALTRO_OK;
-}
-
+// Both polish getters on both backends (BackendCommon::read_polish): zeros while projected_newton is off, or before a handle
+// on the one-wave-per-instance backend has polished.  (Only the 16-lane backend, whose arrays exist from create on, puts the
+// statistics back to zero when they are asked for while the option is off.)
 int32_t altro_batch_get_polish_stats(altro_handle* h, int32_t* ran, int32_t* failed, double* residual) {
-  return guard(h, [&]() -> int32_t { return read_polish(h, true, ran, failed, residual, nullptr, nullptr, nullptr); });
+  return guard(h, [&]() -> int32_t {
+    if (!h) return ALTRO_ERR_INVALID_ARG;
+    return fwd(h, common(h).read_polish(!h->wide, ran, failed, residual, nullptr, nullptr, nullptr));
+  });
 }
 
 int32_t altro_batch_get_polish_dual_residuals(altro_handle* h, double* before, double* after, int32_t* failed) {
-  return guard(h, [&]() -> int32_t { return read_polish(h, false, nullptr, nullptr, nullptr, before, after, failed); });
+  return guard(h, [&]() -> int32_t {
+    if (!h) return ALTRO_ERR_INVALID_ARG;
+    return fwd(h, common(h).read_polish(false, nullptr, nullptr, nullptr, before, after, failed));
+  });
 }
 
 int32_t altro_batch_get_confirm_counter(altro_handle* h, int64_t* confirmed) {
   return guard(h, [&]() -> int32_t {
     if (!h || !confirmed) return ALTRO_ERR_INVALID_ARG;
-    if (h->wide) {
-      HIPCHK(h, hipSetDevice(h->device));
-      HIPCHK(h, hipStreamSynchronize(h->wide->stream));
-      HIPCHK(h, hipMemcpy(confirmed, h->wide->n_gconf, (size_t)h->d.batch * sizeof(long long), hipMemcpyDeviceToHost));
-      return ALTRO_OK;
-    }
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipMemcpy(confirmed, h->n_gconf, (size_t)h->d.batch * sizeof(long long), hipMemcpyDeviceToHost));
-    return ALTRO_OK;
+    long long* const src[3] = {common(h).n_gconf, nullptr, nullptr};
+    return fwd(h, common(h).counters(src, confirmed, nullptr, nullptr));
   });
 }
 
@@ -1957,9 +1836,9 @@ int32_t altro_batch_get_wave_passes(altro_handle* h, int64_t* passes, int32_t ca
 
 int32_t altro_mpc_set_track(altro_handle* h, const double* Xtrack, const double* Utrack, int32_t Nt) {
   return guard(h, [&]() -> int32_t {
-    WIDE_FWD(h, mpc_set_track(Xtrack, Utrack, Nt));
     if (!h || !Xtrack || !Utrack) return ALTRO_ERR_INVALID_ARG;
     if (Nt < h->d.N) FAIL(h, ALTRO_ERR_INVALID_ARG, "track shorter than the horizon");
+    WIDE_FWD(h, mpc_set_track(Xtrack, Utrack, Nt));
     HIPCHK(h, hipSetDevice(h->device));
     int rc = set_ref_common(h, Xtrack, Utrack, Nt);
     if (rc) return rc;
@@ -1985,55 +1864,33 @@ int32_t altro_mpc_set_track(altro_handle* h, const double* Xtrack, const double*
 
 int32_t altro_mpc_set_noise(altro_handle* h, const double* noise, int32_t steps) {
   return guard(h, [&]() -> int32_t {
-    WIDE_FWD(h, mpc_set_noise(noise, steps));
     if (!h || !noise || steps < 1) return ALTRO_ERR_INVALID_ARG;
-    HIPCHK(h, hipSetDevice(h->device));
-    const size_t cnt = (size_t)steps * h->d.batch * h->d.n;
-    HIPCHK(h, h->pool.alloc(&h->noise, cnt, h->stream, false));
-    HIPCHK(h, hipMemcpy(h->noise, noise, cnt * sizeof(double), hipMemcpyHostToDevice));
-    h->noise_steps = steps;
-    return ALTRO_OK;
+    return fwd(h, common(h).set_noise(noise, steps));
   });
 }
 
 int32_t altro_mpc_set_noise_model(altro_handle* h, int32_t mode, const double* weights, const int32_t* groups) {
   return guard(h, [&]() -> int32_t {
-    WIDE_FWD(h, mpc_set_noise_model(mode, weights, groups));
     if (!h || !weights || mode < 0 || mode > 2) return ALTRO_ERR_INVALID_ARG;
-    HIPCHK(h, hipSetDevice(h->device));
-    std::vector<double> w(LW, 0.0);
-    std::vector<int> g(LW, 0);
-    for (int i = 0; i < h->d.n; ++i) {
-      w[i] = weights[i];
-      g[i] = groups ? groups[i] : 0;
-      if (g[i] != 0 && g[i] != 1) FAIL(h, ALTRO_ERR_INVALID_ARG, "noise groups are 0 or 1");
-    }
-    HIPCHK(h, hipMemcpyAsync(h->noise_w, w.data(), LW * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->noise_grp, g.data(), LW * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->noise_mode = mode;
-    return ALTRO_OK;
+    for (int i = 0; groups && i < h->d.n; ++i)
+      if (groups[i] != 0 && groups[i] != 1) FAIL(h, ALTRO_ERR_INVALID_ARG, "noise groups are 0 or 1");
+    return fwd(h, common(h).set_noise_model(mode, weights, groups));
   });
 }
 
 int32_t altro_mpc_set_shift(altro_handle* h, int32_t shift) {
   return guard(h, [&]() -> int32_t {
-    if (h && h->wide) { h->wide->mpc_shift = shift ? 1 : 0; return ALTRO_OK; }
     if (!h) return ALTRO_ERR_INVALID_ARG;
-    h->mpc_shift = shift ? 1 : 0;
+    common(h).mpc_shift = shift ? 1 : 0;
     return ALTRO_OK;
   });
 }
 
 int32_t altro_mpc_run_async(altro_handle* h, int32_t first_step, int32_t nsteps) {
   return guard(h, [&]() -> int32_t {
-    WIDE_FWD(h, mpc_run(first_step, nsteps));
     if (!h) return ALTRO_ERR_INVALID_ARG;
-    if (nsteps < 1 || first_step < 0) FAIL(h, ALTRO_ERR_INVALID_ARG, "bad step range");
-    if (h->noise && first_step + nsteps > h->noise_steps) FAIL(h, ALTRO_ERR_INVALID_ARG, "steps outside the uploaded noise");
-    // (under an episode clock an instance that runs off the end of its track goes idle there: altro_mpc_set_clock)
-    if (!h->clock.on && first_step + nsteps + h->d.N > h->Nt) FAIL(h, ALTRO_ERR_INVALID_ARG, "steps run past the end of the track");
-    if (h->mlog && first_step + nsteps > h->mlog_cap) FAIL(h, ALTRO_ERR_INVALID_ARG, "steps outside the capacity of the log (altro_mpc_set_log)");
+    if (int rc = fwd(h, common(h).mpc_run_rules(first_step, nsteps))) return rc;
+    WIDE_FWD(h, enqueue(1, first_step, nsteps));
     return enqueue_solve(h, first_step, nsteps);
   });
 }
@@ -2042,36 +1899,17 @@ int32_t altro_mpc_step_async(altro_handle* h, int32_t step) { return altro_mpc_r
 
 int32_t altro_mpc_set_log(altro_handle* h, int32_t capacity_steps) {
   return guard(h, [&]() -> int32_t {
-    WIDE_FWD(h, mpc_set_log(capacity_steps));
     if (!h) return ALTRO_ERR_INVALID_ARG;
     if (capacity_steps < 0) FAIL(h, ALTRO_ERR_INVALID_ARG, "negative log capacity");
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));  // a launch in flight may still be writing the old log
-    h->mlog_cap = 0;
-    HIPCHK(h, h->pool.release(&h->mlog));
-    if (capacity_steps == 0) return ALTRO_OK;
-    const size_t elems = (size_t)capacity_steps * (size_t)h->d.batch * (LW + altro::MLOG_TAIL);
-    HIPCHK(h, h->pool.alloc(&h->mlog, elems, h->stream, false));
-    HIPCHK(h, hipMemsetAsync(h->mlog, 0xFF, elems * sizeof(double), h->stream));  // never written: -1 / NaN
-    h->mlog_cap = capacity_steps;
-    return ALTRO_OK;
+    return fwd(h, common(h).set_log(capacity_steps));
   });
 }
 
 int32_t altro_mpc_get_log(altro_handle* h, int32_t first_step, int32_t nsteps, double* x0, double* u0, int32_t* iterations,
                           int32_t* iterations_outer, int32_t* status, double* cost, double* c_max) {
   return guard(h, [&]() -> int32_t {
-    WIDE_FWD(h, mpc_get_log(first_step, nsteps, x0, u0, iterations, iterations_outer, status, cost, c_max));
     if (!h) return ALTRO_ERR_INVALID_ARG;
-    if (!h->mlog) FAIL(h, ALTRO_ERR_STATE, "no log: altro_mpc_set_log has not been called");
-    if (first_step < 0 || nsteps < 0 || first_step > h->mlog_cap - nsteps) FAIL(h, ALTRO_ERR_INVALID_ARG, "steps outside the capacity of the log");
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    const size_t rec = LW + altro::MLOG_TAIL, B = h->d.batch;
-    std::vector<double> img((size_t)nsteps * B * rec);
-    if (!img.empty()) HIPCHK(h, hipMemcpy(img.data(), h->mlog + (size_t)first_step * B * rec, img.size() * sizeof(double), hipMemcpyDeviceToHost));
-    altro::mlog_unpack(img.data(), (size_t)nsteps, B, rec, h->d.n, h->d.m, x0, u0, iterations, iterations_outer, status, cost, c_max);
-    return ALTRO_OK;
+    return fwd(h, common(h).get_log(first_step, nsteps, x0, u0, iterations, iterations_outer, status, cost, c_max));
   });
 }
 
@@ -2083,20 +1921,17 @@ int32_t altro_mpc_set_dynamics_track(altro_handle* h, const double* A, const dou
       const int rc = migrate_to_wide(h);
       if (rc) return rc;
     }
-    WIDE_FWD(h, mpc_set_dynamics_track(A, B, f, nblocks, step_stride, per_instance));
-    return ALTRO_ERR_STATE;
+    return fwd(h, h->wide->mpc_set_dynamics_track(A, B, f, nblocks, step_stride, per_instance));
   });
 }
 
 int32_t altro_mpc_prepare_async(altro_handle* h, int32_t step) {
   return guard(h, [&]() -> int32_t {
-    WIDE_FWD(h, mpc_prepare(step));
     if (!h) return ALTRO_ERR_INVALID_ARG;
-    if (step < 0) FAIL(h, ALTRO_ERR_INVALID_ARG, "bad step");
-    if (h->noise && step + 1 > h->noise_steps) FAIL(h, ALTRO_ERR_INVALID_ARG, "step outside the uploaded noise");
-    if (!h->clock.on && step + 1 + h->d.N > h->Nt) FAIL(h, ALTRO_ERR_INVALID_ARG, "step runs past the end of the track");
+    WIDE_FWD(h, mpc_prepare(step));   // (the shared step rules, then its two of the dynamics track)
+    if (int rc = h->mpc_prepare_rules(step)) return rc;
     HIPCHK(h, hipSetDevice(h->device));
-    int rc = check_ready(h);
+    int rc = h->check_ready();
     if (rc) return rc;
     if ((rc = launch_solve(h, step, 1, 1))) return rc;  // the solve kernel's own plant step, nothing else
     h->kref = step + 1;
@@ -2106,11 +1941,11 @@ int32_t altro_mpc_prepare_async(altro_handle* h, int32_t step) {
 
 int32_t altro_batch_benchmark_solve(altro_handle* h, int32_t samples, int32_t evals, float* sample_ms) {
   return guard(h, [&]() -> int32_t {
-    WIDE_FWD(h, benchmark_solve(samples, evals, sample_ms));
     if (!h) return ALTRO_ERR_INVALID_ARG;
     if (samples < 1 || evals < 1) FAIL(h, ALTRO_ERR_INVALID_ARG, "samples and evals must be positive");
-    if (h->flags.on) FAIL(h, ALTRO_ERR_STATE, "altro_batch_benchmark_solve restores and repeats whole batches: clear the active mask first");
-    if (h->clock.on) FAIL(h, ALTRO_ERR_STATE, "altro_batch_benchmark_solve restores and repeats whole batches: clear the episode clock first");
+    if (common(h).flags.on) FAIL(h, ALTRO_ERR_STATE, "altro_batch_benchmark_solve restores and repeats whole batches: clear the active mask first");
+    if (common(h).clock.on) FAIL(h, ALTRO_ERR_STATE, "altro_batch_benchmark_solve restores and repeats whole batches: clear the episode clock first");
+    WIDE_FWD(h, benchmark_solve(samples, evals, sample_ms));
     HIPCHK(h, hipSetDevice(h->device));
     const size_t plane = (size_t)h->d.N * LW;
     if (!h->Zsave) HIPCHK(h, h->pool.alloc(&h->Zsave, plane * h->Bp, h->stream, false));
@@ -2212,14 +2047,10 @@ int32_t altro_batch_set_dynamics_dev(altro_handle* h, const double* A, const dou
     DEV_ARG(h, "A", A, nb * n_ * n_, double, false);
     DEV_ARG(h, "B", B, nb * n_ * m_, double, false);
     DEV_ARG(h, "f", f, nb * n_, double, true);
-    WIDE_FWD(h, set_dynamics_dev(A, B, f, per_knot, per_instance));
-    if (per_knot) {  // the first call on an (n, m) of the 16-lane set: the handle moves to the one-wave-per-instance kernel
-      const int rc = migrate_to_wide(h);
-      if (rc) return rc;
-      const int rc2 = h->wide->set_dynamics_dev(A, B, f, per_knot, per_instance);
-      if (rc2) h->err = h->wide->err;
-      return rc2;
+    if (per_knot && !h->wide) {  // the first call on an (n, m) of the 16-lane set: the handle moves to the one-wave-per-instance kernel
+      if (int rc = migrate_to_wide(h)) return rc;
     }
+    WIDE_FWD(h, set_dynamics_dev(A, B, f, per_knot, per_instance));
     return set_dynamics_16(h, A, B, f, per_instance, true);
   });
 }
@@ -2265,7 +2096,7 @@ int32_t altro_batch_get_first_knot_dev(altro_handle* h, double* u0, double* x1, 
 int32_t altro_batch_update_constraint_data_dev(altro_handle* h, int32_t con_id, const double* A, const double* b) {
   return guard(h, [&]() -> int32_t {
     DEV_ENTER(h, "altro_batch_update_constraint_data_dev");
-    const int box_id = h->wide ? h->wide->box_id : h->box_id;
+    const int box_id = common(h).box_id;
     if (box_id >= 0 && con_id == box_id) FAIL(h, ALTRO_ERR_INVALID_ARG, std::string(fn_) + ": con_id is a BOX constraint (altro_batch_set_bounds_dev)");
     altro_handle::ConBlock* cb = nullptr;
     altro_wide::WideBackend::Block* bl = nullptr;
@@ -2311,7 +2142,7 @@ int32_t altro_batch_update_constraint_data_dev(altro_handle* h, int32_t con_id, 
 int32_t altro_batch_set_bounds_dev(altro_handle* h, int32_t con_id, const double* zmin, const double* zmax, int32_t per_instance) {
   return guard(h, [&]() -> int32_t {
     DEV_ENTER(h, "altro_batch_set_bounds_dev");
-    const int box_id = h->wide ? h->wide->box_id : h->box_id;
+    const int box_id = common(h).box_id;
     if (box_id < 0 || con_id != box_id) FAIL(h, ALTRO_ERR_INVALID_ARG, std::string(fn_) + ": con_id is not a BOX constraint");
     const size_t rows = per_instance ? B_ : 1;
     DEV_ARG(h, "zmin", zmin, rows * (n_ + m_), double, false);
@@ -2352,24 +2183,14 @@ int32_t altro_batch_get_dev_refusals(altro_handle* h, int64_t* rows) {
   return guard(h, [&]() -> int32_t {
     if (!h) return dev_null_handle("altro_batch_get_dev_refusals");
     if (!rows) FAIL(h, ALTRO_ERR_INVALID_ARG, "altro_batch_get_dev_refusals: null pointer");
-    WIDE_FWD(h, get_dev_refusals(rows));
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    unsigned long long v = 0;
-    HIPCHK(h, hipMemcpy(&v, h->refusals, sizeof(v), hipMemcpyDeviceToHost));
-    *rows = (int64_t)v;
-    return ALTRO_OK;
+    return fwd(h, common(h).get_dev_refusals(rows));
   });
 }
 
 // ---- feedback policy on the device (kernels in policy.h)
 // x, knot, u, fb: device arrays (the caller's, validated; or the staged copies of the host twin).  Enqueues one kernel.
 static int eval_policy_launch(altro_handle* h, const double* x, const int32_t* knot, int32_t clamp, double* u, int32_t* fb) {
-  if (h->wide) {
-    const int rc = h->wide->eval_policy_dev(x, knot, clamp, u, fb);
-    if (rc) h->err = h->wide->err;
-    return rc;
-  }
+  if (h->wide) return fwd(h, h->wide->eval_policy_dev(x, knot, clamp, u, fb));
   hipLaunchKernelGGL(altro::k_eval_policy, grid_for((size_t)h->Bp * LW), dim3(256), 0, h->stream, u, fb, x, knot, h->Z, h->cur, h->KD, h->kmu,
                      h->zmin, h->zmax, tab_imask(h), (size_t)h->d.N * LW, h->Bp, h->d.batch, h->d.N, h->d.n, h->d.m, clamp ? 1 : 0, h->box_k0,
                      h->box_k1);
@@ -2400,12 +2221,9 @@ int32_t altro_batch_eval_policy(altro_handle* h, const double* x, const int32_t*
         FAIL(h, ALTRO_ERR_INVALID_ARG, "altro_batch_eval_policy: knot[" + std::to_string(b) + "] = " + std::to_string(knot[b]) + " is outside 0 .. N-2");
     HIPCHK(h, hipSetDevice(h->device));
     const size_t bytes = B * (n + m) * sizeof(double) + 2 * B * sizeof(int32_t);
-    if (int rc = h->wide ? h->wide->ensure_stage(bytes) : ensure_stage(h, bytes)) {
-      if (h->wide) h->err = h->wide->err;
-      return rc;
-    }
-    const hipStream_t st = h->wide ? h->wide->stream : h->stream;
-    double* sx = h->wide ? h->wide->stage : h->stage;
+    if (int rc = fwd(h, common(h).ensure_stage(bytes))) return rc;
+    const hipStream_t st = common(h).stream;
+    double* sx = common(h).stage;
     double* su = sx + B * n;
     int32_t* sk = reinterpret_cast<int32_t*>(su + B * m);
     int32_t* sf = sk + B;
@@ -2452,7 +2270,7 @@ static altro::Eval16 eval16_params(altro_handle* h) {
 // what evaluate_launch, warm_start_launch and simulate_launch check first on the 16-lane path (the one-wave-per-instance
 // backend has WideBackend::eval_ready)
 static int score_ready(altro_handle* h) {
-  if (int rc = check_ready(h)) return rc;
+  if (int rc = h->check_ready()) return rc;
   if (!h->clock.on && h->kref + h->d.N > h->Nt) FAIL(h, ALTRO_ERR_STATE, "reference window runs past the end of the stored trajectory");
   return pack_constraints(h);   // (what the next solve would do first; a no-op once the tables are packed)
 }
@@ -2466,12 +2284,9 @@ struct StageCursor : altro::StageLayout {
   char* base = nullptr;
   explicit StageCursor(altro_handle* h_) : h(h_) {}
   int open() {
-    if (int rc = h->wide ? h->wide->ensure_stage(bytes) : ensure_stage(h, bytes)) {
-      if (h->wide) h->err = h->wide->err;
-      return rc;
-    }
-    st = h->wide ? h->wide->stream : h->stream;
-    base = reinterpret_cast<char*>(h->wide ? h->wide->stage : h->stage);
+    if (int rc = fwd(h, common(h).ensure_stage(bytes))) return rc;
+    st = common(h).stream;
+    base = reinterpret_cast<char*>(common(h).stage);
     for (int i = 0; i < nslots; ++i)
       if (slot[i].in) HIPCHK(h, hipMemcpyAsync(base + slot[i].off, slot[i].in, slot[i].bytes, hipMemcpyHostToDevice, st));
     return ALTRO_OK;
@@ -2503,11 +2318,7 @@ static int evaluate_rules(altro_handle* h, const char* fn, int32_t ncand, const 
 // the rollout kernel when there is no X, then the scoring kernel; allocates only when the workspace has to grow.
 static int evaluate_launch(altro_handle* h, int32_t ncand, const double* U, const double* X, const double* x0, double* J, double* c_max,
                            double* defect, double* Xout) {
-  if (h->wide) {
-    const int rc = h->wide->evaluate_dev(ncand, U, X, x0, J, c_max, defect, Xout);
-    if (rc) h->err = h->wide->err;
-    return rc;
-  }
+  if (h->wide) return fwd(h, h->wide->evaluate_dev(ncand, U, X, x0, J, c_max, defect, Xout));
   int rc = score_ready(h);
   if (rc) return rc;
   const size_t B = h->d.batch, N = h->d.N, n = h->d.n, m = h->d.m;
@@ -2583,11 +2394,7 @@ static int warm_start_rules(altro_handle* h, const char* fn, int32_t ncand, cons
 // kernel, then the select-and-install kernel; allocates only when J or c_max is null and the merit workspace has to grow.
 static int warm_start_launch(altro_handle* h, int32_t ncand, const double* U, double rho, int32_t inc, int32_t* chosen, double* J,
                              double* c_max) {
-  if (h->wide) {
-    const int rc = h->wide->warm_start_dev(ncand, U, rho, inc, chosen, J, c_max);
-    if (rc) h->err = h->wide->err;
-    return rc;
-  }
+  if (h->wide) return fwd(h, h->wide->warm_start_dev(ncand, U, rho, inc, chosen, J, c_max));
   if (int rc = score_ready(h)) return rc;
   const size_t B = h->d.batch, N = h->d.N, n = h->d.n, m = h->d.m;
   const size_t R = B * (size_t)(ncand + inc);
@@ -2653,11 +2460,7 @@ static int simulate_rules(altro_handle* h, const char* fn, int32_t nsamp, int32_
 
 // io: device arrays (the caller's, validated; or the staged copies of the host twin).  Enqueues one kernel, allocates nothing.
 static int simulate_launch(altro_handle* h, int32_t nsamp, int32_t clamp, const altro::SimIO& io) {
-  if (h->wide) {
-    const int rc = h->wide->simulate_policy_dev(nsamp, clamp, io);
-    if (rc) h->err = h->wide->err;
-    return rc;
-  }
+  if (h->wide) return fwd(h, h->wide->simulate_policy_dev(nsamp, clamp, io));
   if (int rc = score_ready(h)) return rc;
   const size_t R = (size_t)h->d.batch * (size_t)nsamp;
   const altro::Eval16 p = eval16_params(h);
@@ -2715,7 +2518,7 @@ static int covariance_rules(altro_handle* h, const char* fn, const altro::CovIO&
   if (per_instance != 0 && per_instance != 1) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": per_instance must be 0 or 1");
   if (!(io.kappa >= 0.0) || std::isinf(io.kappa)) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": kappa must be finite and not negative");
   if ((io.zlo_t != nullptr) != (io.zhi_t != nullptr)) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": zmin_t and zmax_t go together: both or neither");
-  const int box_id = h->wide ? h->wide->box_id : h->box_id;
+  const int box_id = common(h).box_id;
   if (io.zlo_t && box_id < 0) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": zmin_t / zmax_t need a BOX constraint on the handle");
   if (con_id < 0) {
     if (con_id != -1) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": unknown constraint id");
@@ -2737,11 +2540,7 @@ static int covariance_rules(altro_handle* h, const char* fn, const altro::CovIO&
 // io: device arrays (the caller's, validated; or the staged copies of the host twin).  Enqueues one kernel, allocates nothing:
 // the covariance lives in registers (16-lane backend) or LDS (one-wave-per-instance backend).
 static int covariance_launch(altro_handle* h, const altro::CovIO& io, int32_t con_id) {
-  if (h->wide) {
-    const int rc = h->wide->propagate_covariance_dev(io, con_id);
-    if (rc) h->err = h->wide->err;
-    return rc;
-  }
+  if (h->wide) return fwd(h, h->wide->propagate_covariance_dev(io, con_id));
   if (int rc = score_ready(h)) return rc;
   altro::CovRows cr{};
   for (const auto& cb : h->cons) {
@@ -2803,10 +2602,10 @@ int32_t altro_batch_propagate_covariance(altro_handle* h, const double* Sigma0, 
 
 // ---- per-instance active mask and cold restart
 static int set_active_common(altro_handle* h, const int32_t* active, bool dev) {
-  altro::InstanceFlags& fl = h->wide ? h->wide->flags : h->flags;
-  const hipStream_t st = h->wide ? h->wide->stream : h->stream;
+  altro::InstanceFlags& fl = common(h).flags;
+  const hipStream_t st = common(h).stream;
   if (!active) { fl.on = false; return ALTRO_OK; }
-  HIPCHK(h, fl.load(false, active, dev, h->d.batch, h->wide ? h->d.batch : h->Bp, st));
+  HIPCHK(h, fl.load(false, active, dev, h->d.batch, common(h).slots, st));
   if (!dev) HIPCHK(h, hipStreamSynchronize(st));
   fl.on = true;
   return ALTRO_OK;
@@ -2832,11 +2631,11 @@ int32_t altro_batch_get_active(altro_handle* h, int32_t* active) {
   return guard(h, [&]() -> int32_t {
     if (!h) return dev_null_handle("altro_batch_get_active");
     if (!active) FAIL(h, ALTRO_ERR_INVALID_ARG, "altro_batch_get_active: null pointer");
-    const altro::InstanceFlags& fl = h->wide ? h->wide->flags : h->flags;
+    const altro::InstanceFlags& fl = common(h).flags;
     const size_t B = h->d.batch;
     if (!fl.on) { for (size_t i = 0; i < B; ++i) active[i] = 1; return ALTRO_OK; }
     HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(h->wide ? h->wide->stream : h->stream));
+    HIPCHK(h, hipStreamSynchronize(common(h).stream));
     HIPCHK(h, hipMemcpy(active, fl.active, B * sizeof(int), hipMemcpyDeviceToHost));
     return ALTRO_OK;
   });
@@ -2847,7 +2646,7 @@ static int restart_16(altro_handle* h, const int32_t* which, const double* X, co
   const size_t B = h->d.batch, N = h->d.N, n = h->d.n, m = h->d.m;
   const size_t cx = X ? B * N * n : 0, cu = B * (N - 1) * m;
   if (!dev) {
-    int rc = ensure_stage(h, (cx + cu) * sizeof(double));
+    int rc = h->ensure_stage((cx + cu) * sizeof(double));
     if (rc) return rc;
     if (X && (rc = upload(h, X, cx, 0))) return rc;
     if ((rc = upload(h, U, cu, cx))) return rc;
@@ -2886,9 +2685,9 @@ int32_t altro_batch_restart_instances_dev(altro_handle* h, const int32_t* which,
 
 // ---- per-instance episode clock
 static int set_clock_common(altro_handle* h, const int32_t* start, const int32_t* length, bool dev) {
-  altro::EpisodeClock& ck = h->wide ? h->wide->clock : h->clock;
-  const hipStream_t st = h->wide ? h->wide->stream : h->stream;
-  int& kref = h->wide ? h->wide->kref : h->kref;
+  altro::EpisodeClock& ck = common(h).clock;
+  const hipStream_t st = common(h).stream;
+  int& kref = common(h).kref;
   const size_t B = h->d.batch;
   if (!start) {   // clear: the handle goes back to ONE window, which must be the one every instance holds
     if (!ck.on) return ALTRO_OK;
@@ -2901,9 +2700,9 @@ static int set_clock_common(altro_handle* h, const int32_t* start, const int32_t
     ck.on = false;
     return ALTRO_OK;
   }
-  if ((h->wide ? h->wide->Nt : h->Nt) < 1 || !(h->wide ? h->wide->have_ref : h->have_ref))
+  if (common(h).Nt < 1 || !common(h).have_ref)
     FAIL(h, ALTRO_ERR_STATE, "altro_mpc_set_clock: no track (altro_mpc_set_track)");
-  HIPCHK(h, ck.load(start, length, dev, (int)B, h->wide ? (int)B : h->Bp, kref, st));
+  HIPCHK(h, ck.load(start, length, dev, (int)B, common(h).slots, kref, st));
   if (!dev) HIPCHK(h, hipStreamSynchronize(st));
   ck.on = true;
   return ALTRO_OK;
@@ -2930,10 +2729,10 @@ int32_t altro_mpc_get_clock(altro_handle* h, int32_t* start, int32_t* length, in
   return guard(h, [&]() -> int32_t {
     if (!h) return dev_null_handle("altro_mpc_get_clock");
     if (!start && !length && !window) FAIL(h, ALTRO_ERR_INVALID_ARG, "altro_mpc_get_clock: every output pointer is null");
-    const altro::EpisodeClock& ck = h->wide ? h->wide->clock : h->clock;
+    const altro::EpisodeClock& ck = common(h).clock;
     const size_t B = h->d.batch;
     if (!ck.on) {
-      const int kref = h->wide ? h->wide->kref : h->kref;
+      const int kref = common(h).kref;
       for (size_t i = 0; i < B; ++i) {
         if (start) start[i] = 0;
         if (length) length[i] = -1;
@@ -2942,7 +2741,7 @@ int32_t altro_mpc_get_clock(altro_handle* h, int32_t* start, int32_t* length, in
       return ALTRO_OK;
     }
     HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(h->wide ? h->wide->stream : h->stream));
+    HIPCHK(h, hipStreamSynchronize(common(h).stream));
     if (start) HIPCHK(h, hipMemcpy(start, ck.start, B * sizeof(int), hipMemcpyDeviceToHost));
     if (length) HIPCHK(h, hipMemcpy(length, ck.length, B * sizeof(int), hipMemcpyDeviceToHost));
     if (window) HIPCHK(h, hipMemcpy(window, ck.window, B * sizeof(int), hipMemcpyDeviceToHost));
@@ -2953,7 +2752,7 @@ int32_t altro_mpc_get_clock(altro_handle* h, int32_t* start, int32_t* length, in
 int32_t altro_batch_wait_stream(altro_handle* h, void* producer) {
   return guard(h, [&]() -> int32_t {
     DEV_ENTER(h, "altro_batch_wait_stream");
-    HIPCHK(h, h->link.wait(h->wide ? h->wide->stream : h->stream, (hipStream_t)producer));
+    HIPCHK(h, h->link.wait(common(h).stream, (hipStream_t)producer));
     return ALTRO_OK;
   });
 }
@@ -2961,7 +2760,7 @@ int32_t altro_batch_wait_stream(altro_handle* h, void* producer) {
 int32_t altro_batch_signal_stream(altro_handle* h, void* consumer) {
   return guard(h, [&]() -> int32_t {
     DEV_ENTER(h, "altro_batch_signal_stream");
-    HIPCHK(h, h->link.signal(h->wide ? h->wide->stream : h->stream, (hipStream_t)consumer));
+    HIPCHK(h, h->link.signal(common(h).stream, (hipStream_t)consumer));
     return ALTRO_OK;
   });
 }

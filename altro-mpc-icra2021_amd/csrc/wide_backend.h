@@ -20,6 +20,7 @@
 #include "solve_wide.h"
 #include "covariance.h"
 #include "pn_wide.h"
+#include "backend_common.h"
 
 namespace altro_wide {
 
@@ -125,52 +126,24 @@ __global__ void __launch_bounds__(64) k_restart_wide(const int* __restrict__ whi
   }
 }
 
-struct WideBackend {
-  altro_dims d{};
-  altro_opts o{};
-  int device = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  bool timed = false;
-  altro::LaunchRing ring;
-  altro::InstanceFlags flags;  // active mask and restart selection, [batch] (device_io.h)
-  altro::EpisodeClock clock;   // per-instance episode clock, [batch] (device_io.h)
-  std::string err;
-  altro::DevicePool pool;   // owns every device array below (device_pool.h); the members stay plain pointers
+struct WideBackend : altro::BackendCommon {   // (what both backends hold and do alike: backend_common.h)
   // device
   double *A = nullptr, *Bm = nullptr, *f = nullptr, *wd = nullptr, *wf = nullptr, *zmin = nullptr, *zmax = nullptr;
   double *x0 = nullptr, *Xref = nullptr, *Uref = nullptr, *X = nullptr, *U = nullptr, *Lb = nullptr, *Lc = nullptr,
-         *mu = nullptr, *Kg = nullptr, *dg = nullptr, *trash = nullptr, *AconT = nullptr, *bcon = nullptr, *stage = nullptr, *Qz = nullptr, *fac = nullptr;
+         *mu = nullptr, *Kg = nullptr, *dg = nullptr, *trash = nullptr, *AconT = nullptr, *bcon = nullptr, *Qz = nullptr, *fac = nullptr;
   unsigned char* aset = nullptr;   // [B][3][N][64] exact active sets (solve_wide.h: Params::aset)
   unsigned* bwst = nullptr;   // [B][136] per instance: the state of the gain reuse between launches (solve_wide.h: bw_*)
   int coop_mode = -1, static_mask = 7;  // altro_debug_set "wide_coop", "wide_static_mask" (before create)
   int compact_np_max = 48;  // wide_compact: the LDS carve-up with Qux and K inside W, for padded state dimensions up to this
   bool debug_keep_gains = false;  // altro_debug_set "keep_gains" (-DALTRO_DEBUG builds only): stale gains are kept (exists to show that the tests notice them)
-  // projected-Newton polish (pn_core.h): per-instance results, and the workspace slots allocated by the first solve that asks
-  altro_pn::PnOut pn_out;
-  altro_pn::PnWork pn_ws;
   bool gains_valid = false;   // nothing the stored gains depend on (model, cost, constraints, options) has changed since the last launch
   double *Xsave = nullptr, *Usave = nullptr;  // Z0 of benchmark_solve
   std::vector<hipEvent_t> bench_ev;
-  int *cur = nullptr, *ctype = nullptr, *rowk0 = nullptr, *rowk1 = nullptr, *rowc0 = nullptr, *rowcp = nullptr, *iters = nullptr, *iters_outer = nullptr,
-      *status = nullptr, *noise_grp = nullptr;
-  double *cost = nullptr, *cmax = nullptr, *Jtrace = nullptr, *ctrace = nullptr, *atrace = nullptr, *noise = nullptr,
-         *noise_w = nullptr;
-  long long *n_backward = nullptr, *n_rollout = nullptr, *n_trials = nullptr, *n_solves = nullptr, *n_iters = nullptr,
-            *n_ok = nullptr, *n_gconf = nullptr, *n_gs = nullptr;
-  size_t stage_bytes = 0;
-  double* eval_ws = nullptr;   // altro_batch_evaluate(_dev): states of a rollout without Xout, or the gathered own trajectory (grow-only)
-  size_t eval_ws_elems = 0;
-  double* ws_merit = nullptr;  // altro_batch_warm_start(_dev): J, c_max [batch * (ncand + 1)] each when the caller passes none (grow-only)
-  size_t ws_merit_elems = 0;
+  int *cur = nullptr, *ctype = nullptr, *rowk0 = nullptr, *rowk1 = nullptr, *rowc0 = nullptr, *rowcp = nullptr;
   size_t cov_lds_set = 0;      // altro_batch_propagate_covariance(_dev): the LDS bytes its kernel has been allowed (above the 64 KB a kernel gets unasked)
-  int Nt = 0, kref = 0, noise_steps = 0, noise_mode = 0, mpc_shift = 1;
-  double* mlog = nullptr;  // per-step log of the MPC loop (mpc_log.h): [mlog_cap][B][n + m + MLOG_TAIL]; null: off
-  int mlog_cap = 0;
   int dyn_blocks = 1, dyn_step_stride = 0;
   size_t dyn_table_blocks = 0;   // blocks the tables A, Bm, f have room for (set_dynamics_dev reuses them while it is unchanged)
-  bool ltv = false, dyn_per_instance = false, have_dyn = false, have_cost = false, have_ref = false;
-  int box_k0 = 0, box_k1 = -1, box_id = -1;
+  bool ltv = false;
   std::vector<bool> box_lo_fin, box_hi_fin;   // [n+m] finite sides of the BOX (host copy: polish_prepare, set_bounds)
   int w_pi = 0, b_pi = 0;                     // wd / wf, resp. zmin / zmax, hold one row per instance
   bool w_big = false, b_big = false;          // their device arrays have room for B rows
@@ -185,7 +158,6 @@ struct WideBackend {
   int Pn = 0, ncon = 0, ncone = 0;
   bool con_dirty = false, con_locked = false, con_per_instance = false;
   size_t acon_elems = (size_t)-1;
-  unsigned long long* refusals = nullptr;   // device counter: rows set_bounds_dev refused since create
 
   int np() const { return pad16(d.n); }
   int mp() const { return pad16(d.m); }
@@ -193,15 +165,13 @@ struct WideBackend {
 
   static bool supports(int n, int m) { return n >= 1 && m >= 1 && n <= kMaxN && m <= kMaxM; }
 
-  int ensure_stage(size_t bytes) {
-    WCHK(pool.reserve(reinterpret_cast<char**>(&stage), &stage_bytes, bytes));
-    return ALTRO_OK;
-  }
-
   int create(const altro_dims* dims, const altro_opts* opts, int dev) {
     d = *dims;
     o = *opts;
     device = dev;
+    slots = d.batch;
+    mlog_rec = (size_t)nz() + altro::MLOG_TAIL;
+    noise_len = kMaxN;
     // (diagnostic switches -- compact_np_max: 0 = never, 32 / 48 = up to that padded n; coop_mode: cooperative blocks 0 = never,
     //  1 = every size with n or m > 16; static_mask: which uses of time-invariant constraint tables stay in LDS;
     //  debug_keep_gains -- are members set by the caller from altro_debug_set() before create(): nothing is read from the
@@ -227,7 +197,7 @@ struct WideBackend {
                                              {&ctype, 1}, {&rowk0, 1}, {&rowk1, 1}, {&rowc0, 1}, {&rowcp, 1}};
     for (const auto& a : dbl) WCHK(pool.alloc(a.first, a.second, stream));
     for (const auto& a : ints) WCHK(pool.alloc(a.first, a.second, stream));
-    for (long long** c : {&n_backward, &n_rollout, &n_trials, &n_solves, &n_iters, &n_ok, &n_gconf, &n_gs}) WCHK(pool.alloc(c, B, stream));
+    for (long long** c : {&n_backward, &n_rollout, &n_trials, &n_solves, &n_iters, &n_ok, &n_gconf, &n_reuse}) WCHK(pool.alloc(c, B, stream));
     WCHK(pool.alloc(&bwst, B * 136, stream));
     WCHK(pool.alloc(&aset, B * 3 * N * 64, stream));
     WCHK(pool.alloc(&refusals, 1, stream));
@@ -268,7 +238,6 @@ struct WideBackend {
   }
   // blocks_per_instance knot blocks per instance (1: time-invariant)
   int upload_dynamics(const double* A_, const double* B_, const double* f_, size_t blocks_per_instance, int per_instance) {
-    if (!A_ || !B_) return ALTRO_ERR_INVALID_ARG;
     WCHK(hipSetDevice(device));
     WCHK(hipStreamSynchronize(stream));
     const size_t n = d.n, m = d.m;
@@ -285,7 +254,6 @@ struct WideBackend {
   // The same from device arrays (already validated), stream-ordered: the tables are reused while the block count is that
   // of the previous call; a call that changes it reallocates, and synchronises to do so, as the host call always does.
   int upload_dynamics_dev(const double* A_, const double* B_, const double* f_, size_t blocks_per_instance, int per_instance) {
-    if (!A_ || !B_) return ALTRO_ERR_INVALID_ARG;
     WCHK(hipSetDevice(device));
     const size_t n = d.n, m = d.m;
     const size_t blocks_ = (per_instance ? (size_t)d.batch : 1) * blocks_per_instance;
@@ -353,7 +321,6 @@ struct WideBackend {
   // rows = 1: one row for the batch; rows = B: Qd [B][n], Rd [B][m], Qfd [B][n]
   int set_cost_rows(const double* Qd, const double* Rd, const double* Qfd, double dt, size_t rows) {
     gains_valid = false;
-    if (!Qd || !Rd || !Qfd || !(dt > 0.0)) return ALTRO_ERR_INVALID_ARG;
     WCHK(hipSetDevice(device));
     const size_t n = d.n, m = d.m, z = nz();
     if ((rows > 1 && !w_big) || !wd || !wf) {   // the shared arrays hold one row: room for B rows from now on
@@ -374,10 +341,9 @@ struct WideBackend {
     return ALTRO_OK;
   }
 
-  // altro_batch_set_bounds: new values for the BOX, one row for the batch or one per instance (per_instance != 0)
-  int set_bounds(int con_id, const double* zmin_, const double* zmax_, int per_instance) {
-    if (box_id < 0 || con_id != box_id) WFAIL(ALTRO_ERR_INVALID_ARG, "altro_batch_set_bounds: con_id is not a BOX constraint");
-    if (!zmin_ || !zmax_) return ALTRO_ERR_INVALID_ARG;
+  // altro_batch_set_bounds: new values for the BOX, one row for the batch or one per instance (per_instance != 0).  (As for
+  // every host call below, the entry point has checked the null pointers, the ranges and that the id is the BOX's.)
+  int set_bounds(const double* zmin_, const double* zmax_, int per_instance) {
     const size_t rows = per_instance ? (size_t)d.batch : 1, z = nz();
     {
       bool lfb[kMaxN + kMaxM], hfb[kMaxN + kMaxM];
@@ -403,9 +369,7 @@ struct WideBackend {
                      const double* zmax_, int per_knot, int* con_id) {
     WCHK(hipSetDevice(device));
     if (con_locked) WFAIL(ALTRO_ERR_STATE, "constraints must be added before the first solve");
-    if (k_first < 0 || k_last < k_first || k_last > d.N - 1) WFAIL(ALTRO_ERR_INVALID_ARG, "bad knot range");
     if (kind == ALTRO_CON_BOX) {
-      if (!zmin_ || !zmax_) return ALTRO_ERR_INVALID_ARG;
       if (box_id >= 0) WFAIL(ALTRO_ERR_UNSUPPORTED, "one BOX constraint per problem");
       WCHK(hipMemcpy(zmin, zmin_, nz() * sizeof(double), hipMemcpyHostToDevice));
       WCHK(hipMemcpy(zmax, zmax_, nz() * sizeof(double), hipMemcpyHostToDevice));
@@ -419,9 +383,7 @@ struct WideBackend {
       if (con_id) *con_id = box_id;
       return ALTRO_OK;
     }
-    if ((kind != ALTRO_CON_LINEAR && kind != ALTRO_CON_SOC) || !A_ || !b_ || p < 1) return ALTRO_ERR_INVALID_ARG;
     if (kind == ALTRO_CON_SOC && (p < 2 || p > 4)) WFAIL(ALTRO_ERR_UNSUPPORTED, "second-order cones of dimension 2..4 only");
-    if (kind == ALTRO_CON_LINEAR && sense != ALTRO_SENSE_EQ && sense != ALTRO_SENSE_INEQ) return ALTRO_ERR_INVALID_ARG;
     if (Pn + p > kMaxP) WFAIL(ALTRO_ERR_UNSUPPORTED, "more than 64 linear constraint rows");
     // (rows a `_dev` update wrote come back while the tables still have the row count Pn they were packed with)
     if (int rcm = refresh_block_mirrors()) return rcm;
@@ -534,14 +496,6 @@ struct WideBackend {
     gains_valid = false;
     return ALTRO_OK;
   }
-  int get_dev_refusals(int64_t* rows) {
-    WCHK(hipSetDevice(device));
-    WCHK(hipStreamSynchronize(stream));
-    unsigned long long v = 0;
-    WCHK(hipMemcpy(&v, refusals, sizeof(v), hipMemcpyDeviceToHost));
-    *rows = (int64_t)v;
-    return ALTRO_OK;
-  }
 
   int update_constraint_data(int con_id, const double* A_, const double* b_) {
     gains_valid = false;
@@ -609,14 +563,12 @@ struct WideBackend {
   }
 
   int set_initial_state(const double* x) {
-    if (!x) return ALTRO_ERR_INVALID_ARG;
     WCHK(hipSetDevice(device));
     WCHK(hipMemcpyAsync(x0, x, (size_t)d.batch * d.n * sizeof(double), hipMemcpyHostToDevice, stream));
     WCHK(hipStreamSynchronize(stream));
     return ALTRO_OK;
   }
   int get_initial_state(double* x) {
-    if (!x) return ALTRO_ERR_INVALID_ARG;
     WCHK(hipSetDevice(device));
     WCHK(hipStreamSynchronize(stream));
     WCHK(hipMemcpy(x, x0, (size_t)d.batch * d.n * sizeof(double), hipMemcpyDeviceToHost));
@@ -678,7 +630,6 @@ struct WideBackend {
     return ALTRO_OK;
   }
   int set_reference(const double* Xr, const double* Ur) {
-    if (!Xr || !Ur) return ALTRO_ERR_INVALID_ARG;
     return set_ref_common(Xr, Ur, d.N);
   }
 
@@ -700,7 +651,6 @@ struct WideBackend {
     return ALTRO_OK;
   }
   int set_initial_trajectory(const double* Xh, const double* Uh) {
-    if (!Uh) return ALTRO_ERR_INVALID_ARG;
     WCHK(hipSetDevice(device));
     return put_planes(Xh, Uh);
   }
@@ -742,9 +692,7 @@ struct WideBackend {
   }
   // what evaluate_dev, warm_start_dev and simulate_policy_dev check first ...
   int eval_ready() {
-    if (!have_dyn) WFAIL(ALTRO_ERR_STATE, "altro_batch_set_dynamics has not been called");
-    if (!have_cost) WFAIL(ALTRO_ERR_STATE, "altro_batch_set_tracking_cost has not been called");
-    if (!have_ref) WFAIL(ALTRO_ERR_STATE, "no reference trajectory (altro_batch_set_reference / altro_mpc_set_track)");
+    if (int rc = check_ready()) return rc;
     if (!clock.on && kref + d.N > Nt) WFAIL(ALTRO_ERR_STATE, "reference window runs past the end of the stored trajectory");
     if (!clock.on && !dyn_covers(kref)) WFAIL(ALTRO_ERR_STATE, "the dynamics track ends before the window");
     if (int rc = pack_constraints()) return rc;   // (what the next solve would do first; a no-op once the tables are packed)
@@ -889,7 +837,7 @@ struct WideBackend {
     p.x0 = x0; p.Xref = Xref; p.Uref = Uref; p.X = X; p.U = U; p.cur = cur; p.Lb = Lb; p.Lc = Lc; p.mu = mu; p.Kg = Kg; p.dg = dg; p.trash = trash;
     p.iters = iters; p.iters_outer = iters_outer; p.status = status; p.cost = cost; p.cmax = cmax;
     p.Jtrace = Jtrace; p.ctrace = ctrace; p.atrace = atrace;
-    p.n_backward = n_backward; p.n_rollout = n_rollout; p.n_trials = n_trials; p.n_solves = n_solves; p.n_iters = n_iters; p.n_ok = n_ok; p.n_gconf = n_gconf; p.n_gs = n_gs; p.Qz = Qz; p.fac = fac; p.bwst = bwst; p.aset = aset; p.reuse_ok = (gains_valid || debug_keep_gains) ? 1 : 0;
+    p.n_backward = n_backward; p.n_rollout = n_rollout; p.n_trials = n_trials; p.n_solves = n_solves; p.n_iters = n_iters; p.n_ok = n_ok; p.n_gconf = n_gconf; p.n_gs = n_reuse; p.Qz = Qz; p.fac = fac; p.bwst = bwst; p.aset = aset; p.reuse_ok = (gains_valid || debug_keep_gains) ? 1 : 0;
     p.noise = noise; p.noise_w = noise_w; p.noise_grp = noise_grp; p.noise_mode = noise_mode; p.mpc_shift = mpc_shift;
     p.kref = kref;
     p.dyn_blocks = dyn_blocks; p.dyn_step_stride = dyn_step_stride;
@@ -938,11 +886,8 @@ struct WideBackend {
   size_t lds_bytes() const { return (size_t)lds_layout(d.n, d.m, Pn, compact()).total * sizeof(double); }
 
   int prepare_launch() {
-    if (!have_dyn) WFAIL(ALTRO_ERR_STATE, "altro_batch_set_dynamics has not been called");
-    if (!have_cost) WFAIL(ALTRO_ERR_STATE, "altro_batch_set_tracking_cost has not been called");
-    if (!have_ref) WFAIL(ALTRO_ERR_STATE, "no reference trajectory (altro_batch_set_reference / altro_mpc_set_track)");
-    int rc = pack_constraints();
-    if (rc) return rc;
+    int rc = check_ready();
+    if (rc || (rc = pack_constraints())) return rc;
     con_locked = true;
     const size_t bytes = lds_bytes();
     if (bytes > 160 * 1024) WFAIL(ALTRO_ERR_UNSUPPORTED, "problem does not fit the 160 KB of LDS of one CU");
@@ -998,7 +943,7 @@ struct WideBackend {
         kref = first_step + s + 1;
         if (!rc) rc = polish_launch(mask);
         if (!rc && mlog) {
-          double* rec0 = mlog + (size_t)(first_step + s) * (size_t)d.batch * mlog_rec();
+          double* rec0 = mlog + (size_t)(first_step + s) * (size_t)d.batch * mlog_rec;
           hipLaunchKernelGGL(k_log_polished_wide, dim3((unsigned)((d.batch + 255) / 256)), dim3(256), 0, stream, rec0, U, cur, cost, cmax, status,
                              mask, d.batch, d.N, d.n, d.m);
           if (hipGetLastError() != hipSuccess) { err = "launch of the log kernel failed"; rc = ALTRO_ERR_HIP; }
@@ -1022,9 +967,7 @@ struct WideBackend {
 
   // altro_mpc_prepare_async: plant step + noise -> x0, reference window <- step + 1 (no shift, no solve)
   int mpc_prepare(int step) {
-    if (step < 0) WFAIL(ALTRO_ERR_INVALID_ARG, "bad step");
-    if (noise && step + 1 > noise_steps) WFAIL(ALTRO_ERR_INVALID_ARG, "step outside the uploaded noise");
-    if (!clock.on && step + 1 + d.N > Nt) WFAIL(ALTRO_ERR_INVALID_ARG, "step runs past the end of the track");
+    if (int rcs = mpc_prepare_rules(step)) return rcs;
     if (ltv && dyn_step_stride == 0) WFAIL(ALTRO_ERR_UNSUPPORTED, "the device plant step over per-knot dynamics needs altro_mpc_set_dynamics_track");
     if (!clock.on && !dyn_covers(step + 1)) WFAIL(ALTRO_ERR_STATE, "the dynamics track ends before this step's window");
     WCHK(hipSetDevice(device));
@@ -1038,9 +981,6 @@ struct WideBackend {
 
   // benchmark_solve!(solver; samples, evals): see include/altro_batch.h
   int benchmark_solve(int samples, int evals, float* sample_ms) {
-    if (samples < 1 || evals < 1) WFAIL(ALTRO_ERR_INVALID_ARG, "samples and evals must be positive");
-    if (flags.on) WFAIL(ALTRO_ERR_STATE, "altro_batch_benchmark_solve restores and repeats whole batches: clear the active mask first");
-    if (clock.on) WFAIL(ALTRO_ERR_STATE, "altro_batch_benchmark_solve restores and repeats whole batches: clear the episode clock first");
     WCHK(hipSetDevice(device));
     const size_t B = d.batch, lx = (size_t)d.N * d.n, lu = (size_t)(d.N - 1) * d.m;
     if (!Xsave) WCHK(pool.alloc(&Xsave, B * lx, stream, false));
@@ -1097,12 +1037,6 @@ struct WideBackend {
     return ALTRO_OK;
   }
 
-  int synchronize() {
-    WCHK(hipSetDevice(device));
-    WCHK(hipStreamSynchronize(stream));
-    return ALTRO_OK;
-  }
-
   int duals(int con_id, double* lam, bool set) {
     WCHK(hipSetDevice(device));
     WCHK(hipStreamSynchronize(stream));
@@ -1132,25 +1066,6 @@ struct WideBackend {
     return ALTRO_OK;
   }
 
-  int get_stats(int32_t* it, int32_t* ito, int32_t* st, double* J, double* c, double* Jt, double* ct) {
-    WCHK(hipSetDevice(device));
-    WCHK(hipStreamSynchronize(stream));
-    const size_t B = d.batch;
-    if (it) WCHK(hipMemcpy(it, iters, B * sizeof(int), hipMemcpyDeviceToHost));
-    if (ito) WCHK(hipMemcpy(ito, iters_outer, B * sizeof(int), hipMemcpyDeviceToHost));
-    if (st) WCHK(hipMemcpy(st, status, B * sizeof(int), hipMemcpyDeviceToHost));
-    if (J) WCHK(hipMemcpy(J, cost, B * sizeof(double), hipMemcpyDeviceToHost));
-    if (c) WCHK(hipMemcpy(c, cmax, B * sizeof(double), hipMemcpyDeviceToHost));
-    if (Jt) WCHK(hipMemcpy(Jt, Jtrace, B * ALTRO_TRACE_LEN * sizeof(double), hipMemcpyDeviceToHost));
-    if (ct) WCHK(hipMemcpy(ct, ctrace, B * ALTRO_TRACE_LEN * sizeof(double), hipMemcpyDeviceToHost));
-    return ALTRO_OK;
-  }
-  int get_alpha_trace(double* a) {
-    WCHK(hipSetDevice(device));
-    WCHK(hipStreamSynchronize(stream));
-    WCHK(hipMemcpy(a, atrace, (size_t)d.batch * ALTRO_TRACE_LEN * sizeof(double), hipMemcpyDeviceToHost));
-    return ALTRO_OK;
-  }
   int get_gains(double* K, double* dd) {
     WCHK(hipSetDevice(device));
     WCHK(hipStreamSynchronize(stream));
@@ -1158,41 +1073,8 @@ struct WideBackend {
     if (dd) WCHK(hipMemcpy(dd, dg, (size_t)d.batch * (d.N - 1) * d.m * sizeof(double), hipMemcpyDeviceToHost));
     return ALTRO_OK;
   }
-  int last_solve_ms(float* ms) {
-    if (!timed) WFAIL(ALTRO_ERR_STATE, "no solve has been launched");
-    WCHK(hipSetDevice(device));
-    WCHK(hipEventSynchronize(ev1));
-    WCHK(hipEventElapsedTime(ms, ev0, ev1));
-    return ALTRO_OK;
-  }
-  int timing_reset() {
-    WCHK(hipSetDevice(device));
-    WCHK(hipStreamSynchronize(stream));
-    ring.reset();
-    const size_t B = d.batch;
-    for (long long* p : {n_backward, n_rollout, n_trials, n_solves, n_iters, n_ok, n_gconf, n_gs}) WCHK(hipMemset(p, 0, B * sizeof(long long)));
-    return ALTRO_OK;
-  }
-  int timing_get(float* ms, int capacity, int* count) {
-    WCHK(hipSetDevice(device));
-    WCHK(hipStreamSynchronize(stream));
-    const int nl = (int)ring.readable();
-    if (count) *count = nl;
-    for (int i = 0; i < nl && i < capacity && ms; ++i) WCHK(ring.elapsed((size_t)i, &ms[i]));
-    return ALTRO_OK;
-  }
-  int counters(long long* const src[3], int64_t* a, int64_t* b, int64_t* c) {
-    WCHK(hipSetDevice(device));
-    WCHK(hipStreamSynchronize(stream));
-    int64_t* dst[3] = {a, b, c};
-    for (int i = 0; i < 3; ++i)
-      if (dst[i]) WCHK(hipMemcpy(dst[i], src[i], (size_t)d.batch * sizeof(long long), hipMemcpyDeviceToHost));
-    return ALTRO_OK;
-  }
 
   int mpc_set_track(const double* Xt, const double* Ut, int Nt_) {
-    if (!Xt || !Ut) return ALTRO_ERR_INVALID_ARG;
-    if (Nt_ < d.N) WFAIL(ALTRO_ERR_INVALID_ARG, "track shorter than the horizon");
     int rc = set_ref_common(Xt, Ut, Nt_);
     if (rc) return rc;
     // initial_trajectory!(prob, Z): the first window of the track; x0 = its first knot (mpc.jl:19-20,45)
@@ -1205,64 +1087,6 @@ struct WideBackend {
     }
     if ((rc = put_planes(Xw.data(), Uw.data()))) return rc;
     return set_initial_state(xs.data());
-  }
-  int mpc_set_noise(const double* nzv, int steps) {
-    if (!nzv || steps < 1) return ALTRO_ERR_INVALID_ARG;
-    WCHK(hipSetDevice(device));
-    const size_t cnt = (size_t)steps * d.batch * d.n;
-    WCHK(pool.alloc(&noise, cnt, stream, false));
-    WCHK(hipMemcpy(noise, nzv, cnt * sizeof(double), hipMemcpyHostToDevice));
-    noise_steps = steps;
-    return ALTRO_OK;
-  }
-  int mpc_set_noise_model(int mode, const double* w, const int32_t* g) {
-    if (!w || mode < 0 || mode > 2) return ALTRO_ERR_INVALID_ARG;
-    WCHK(hipSetDevice(device));
-    std::vector<double> wv(kMaxN, 0.0);
-    std::vector<int> gv(kMaxN, 0);
-    for (int i = 0; i < d.n; ++i) {
-      wv[i] = w[i];
-      gv[i] = g ? g[i] : 0;
-    }
-    WCHK(hipMemcpy(noise_w, wv.data(), kMaxN * sizeof(double), hipMemcpyHostToDevice));
-    WCHK(hipMemcpy(noise_grp, gv.data(), kMaxN * sizeof(int), hipMemcpyHostToDevice));
-    noise_mode = mode;
-    return ALTRO_OK;
-  }
-  // per-step log of the MPC loop (include/altro_batch.h: altro_mpc_set_log / altro_mpc_get_log)
-  size_t mlog_rec() const { return (size_t)nz() + altro::MLOG_TAIL; }
-  int mpc_set_log(int capacity_steps) {
-    if (capacity_steps < 0) WFAIL(ALTRO_ERR_INVALID_ARG, "negative log capacity");
-    WCHK(hipSetDevice(device));
-    WCHK(hipStreamSynchronize(stream));  // a launch in flight may still be writing the old log
-    mlog_cap = 0;
-    WCHK(pool.release(&mlog));
-    if (capacity_steps == 0) return ALTRO_OK;
-    const size_t elems = (size_t)capacity_steps * (size_t)d.batch * mlog_rec();
-    WCHK(pool.alloc(&mlog, elems, stream, false));
-    WCHK(hipMemsetAsync(mlog, 0xFF, elems * sizeof(double), stream));  // never written: -1 / NaN
-    mlog_cap = capacity_steps;
-    return ALTRO_OK;
-  }
-  int mpc_get_log(int first_step, int nsteps, double* x0h, double* u0h, int32_t* it, int32_t* ito, int32_t* st, double* J, double* c) {
-    if (!mlog) WFAIL(ALTRO_ERR_STATE, "no log: altro_mpc_set_log has not been called");
-    if (first_step < 0 || nsteps < 0 || first_step > mlog_cap - nsteps) WFAIL(ALTRO_ERR_INVALID_ARG, "steps outside the capacity of the log");
-    WCHK(hipSetDevice(device));
-    WCHK(hipStreamSynchronize(stream));
-    const size_t rec = mlog_rec(), B = d.batch;
-    std::vector<double> img((size_t)nsteps * B * rec);
-    if (!img.empty()) WCHK(hipMemcpy(img.data(), mlog + (size_t)first_step * B * rec, img.size() * sizeof(double), hipMemcpyDeviceToHost));
-    altro::mlog_unpack(img.data(), (size_t)nsteps, B, rec, d.n, d.m, x0h, u0h, it, ito, st, J, c);
-    return ALTRO_OK;
-  }
-
-  int mpc_run(int first_step, int nsteps) {
-    if (nsteps < 1 || first_step < 0) WFAIL(ALTRO_ERR_INVALID_ARG, "bad step range");
-    if (noise && first_step + nsteps > noise_steps) WFAIL(ALTRO_ERR_INVALID_ARG, "steps outside the uploaded noise");
-    // (under an episode clock an instance that runs off the end of its track goes idle there: altro_mpc_set_clock)
-    if (!clock.on && first_step + nsteps + d.N > Nt) WFAIL(ALTRO_ERR_INVALID_ARG, "steps run past the end of the track");
-    if (mlog && first_step + nsteps > mlog_cap) WFAIL(ALTRO_ERR_INVALID_ARG, "steps outside the capacity of the log (altro_mpc_set_log)");
-    return enqueue(1, first_step, nsteps);
   }
 };
 

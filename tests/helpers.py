@@ -9,6 +9,58 @@ REF_OPTS = dict(cost_tolerance=1e-4, cost_tolerance_intermediate=1e-4, constrain
 """run_random_linear.jl:41-49"""
 
 
+def D(a):
+    """a double array (or None) as the C-ABI takes it"""
+    import ctypes as C
+    return None if a is None else np.ascontiguousarray(a, dtype=np.float64).ctypes.data_as(C.POINTER(C.c_double))
+
+
+def I(a):
+    """an int32 array (or None) as the C-ABI takes it"""
+    import ctypes as C
+    return None if a is None else np.ascontiguousarray(a, dtype=np.int32).ctypes.data_as(C.POINTER(C.c_int32))
+
+
+class Handle:
+    """A handle of the raw C-ABI.  h.set_dynamics(...) calls altro_batch_set_dynamics(h, ...) (or altro_mpc_*) and asserts
+    ALTRO_OK; h.rc(name, ...) returns the code instead; h.error() is altro_last_error."""
+
+    def __init__(self, n, m, batch=5, N=8, **opts):
+        import ctypes as C
+        import altro_mpc_icra2021_amd as altro
+        from altro_mpc_icra2021_amd import _lib, mpc
+        self.L, self.n, self.m = _lib.lib(), n, m
+        self.opts = altro.SolverOptions(**dict(mpc.REF_OPTS, iterations=60, **opts))
+        self.h = C.c_void_p()
+        dims = _lib.Dims(batch, n, m, N)
+        assert self.L.altro_batch_create(C.byref(dims), C.byref(self.opts), 0, C.byref(self.h)) == _lib.OK
+
+    def rc(self, name, *args):
+        fn = getattr(self.L, "altro_batch_" + name, None) or getattr(self.L, "altro_mpc_" + name)
+        return fn(self.h, *args)
+
+    def error(self):
+        return (self.L.altro_last_error(self.h) or b"").decode()
+
+    def __getattr__(self, name):
+        if name.startswith("_"):
+            raise AttributeError(name)
+
+        def call(*args):
+            rc = self.rc(name, *args)
+            assert rc == 0, (name, rc, self.error())
+        return call
+
+    def polish(self, on):
+        import ctypes as C
+        self.opts.projected_newton = 1 if on else 0
+        self.set_options(C.byref(self.opts))
+
+    def destroy(self):
+        rc, self.h = self.L.altro_batch_destroy(self.h), None
+        return rc
+
+
 def make_oracle(O, pb, b, opts=None, bounded=True):
     n, m, N = pb.n, pb.m, pb.N
     s = O.OracleSolver(n, m, N, pb.dt)

@@ -12,22 +12,13 @@ from types import SimpleNamespace as NS
 import numpy as np
 import pytest
 
-import altro_mpc_icra2021_amd as altro
-from altro_mpc_icra2021_amd import _lib, mpc, problems
+from altro_mpc_icra2021_amd import _lib, problems
+from helpers import D, I, Handle   # (Handle: batch 5, N = 8 unless told otherwise -- B and N below)
 
 pytestmark = pytest.mark.gpu
 OK, INV, UNSUP, STATE = _lib.OK, _lib.ERR_INVALID_ARG, _lib.ERR_UNSUPPORTED, _lib.ERR_STATE
 B, N, STEPS = 5, 8, 2
 DIMS = {"16-lane": (12, 4), "wide": (3, 2)}
-dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-
-
-def D(a):
-    return None if a is None else np.ascontiguousarray(a, dtype=np.float64).ctypes.data_as(dp)
-
-
-def I(a):
-    return None if a is None else np.ascontiguousarray(a, dtype=np.int32).ctypes.data_as(ip)
 
 
 @pytest.fixture(autouse=True)
@@ -37,39 +28,6 @@ def switches_of_the_environment():
     _lib.sync_debug_env()
     yield
     _lib.sync_debug_env()
-
-
-class Handle:
-    """h.set_dynamics(...) calls altro_batch_set_dynamics(h, ...) (or altro_mpc_*) and asserts ALTRO_OK; h.rc(name, ...)
-    returns the code instead"""
-
-    def __init__(self, n, m, **opts):
-        self.L, self.n, self.m = _lib.lib(), n, m
-        self.opts = altro.SolverOptions(**dict(mpc.REF_OPTS, iterations=60, **opts))
-        self.h = C.c_void_p()
-        dims = _lib.Dims(B, n, m, N)
-        assert self.L.altro_batch_create(C.byref(dims), C.byref(self.opts), 0, C.byref(self.h)) == OK
-
-    def rc(self, name, *args):
-        fn = getattr(self.L, "altro_batch_" + name, None) or getattr(self.L, "altro_mpc_" + name)
-        return fn(self.h, *args)
-
-    def __getattr__(self, name):
-        if name.startswith("_"):
-            raise AttributeError(name)
-
-        def call(*args):
-            rc = self.rc(name, *args)
-            assert rc == OK, (name, rc, (self.L.altro_last_error(self.h) or b"").decode())
-        return call
-
-    def polish(self, on):
-        self.opts.projected_newton = 1 if on else 0
-        self.set_options(C.byref(self.opts))
-
-    def destroy(self):
-        rc, self.h = self.L.altro_batch_destroy(self.h), None
-        return rc
 
 
 @functools.lru_cache(maxsize=None)
