@@ -1052,6 +1052,129 @@ def evaluate(solver, U=None, X=None, x0=None, out=None, Xout=None):
     return out
 
 
+def _evaluate_grad_shapes(solver, U, name):
+    """(ncand, shapes of J and P / U and gU / gx0 / Xout / x0) from U, by evaluate's rule for U"""
+    if U is None:
+        raise ValueError(f"{name}: U is required")
+    ncand, lead, su, sx, s0 = _evaluate_shapes(solver, U, None, None, name)
+    return ncand, lead, su, lead + (solver.n,), sx, s0
+
+
+def _evaluate_grad_out(out, name):
+    out = tuple(out)
+    if len(out) != 4 or all(o is None for o in out):
+        raise ValueError(f"{name}: out is (J, P, gU, gx0); any may be None, not all")
+    return out
+
+
+def _check_rho(rho, name):
+    rho = float(rho)
+    if not (rho >= 0.0) or rho == float("inf"):
+        raise ValueError(f"{name}: rho must be finite and not negative")
+    return rho
+
+
+def _evaluate_grad_dev(solver, U, x0=None, rho=0.0, out=None, Xout=None):
+    """device form of evaluate_grad: every tensor is validated (shape, dtype, strides, device) before the library is called"""
+    import torch
+    dev = torch.device("cuda", solver.device)
+    ncand, lead, su, sg, sx, s0 = _evaluate_grad_shapes(solver, U, "evaluate_grad")
+    rho = _check_rho(rho, "evaluate_grad")
+    check_device_tensor(U, su, solver.device, "U")
+    if x0 is not None:
+        check_device_tensor(x0, s0, solver.device, "x0")
+    if Xout is not None:
+        check_device_tensor(Xout, sx, solver.device, "Xout")
+    shapes = (lead, lead, su, sg)
+    if out is None:
+        out = tuple(torch.empty(s, dtype=torch.float64, device=dev) for s in shapes)
+    out = _evaluate_grad_out(out, "evaluate_grad")
+    for o, s, nm in zip(out, shapes, ("J", "P", "gU", "gx0")):
+        if o is not None:
+            check_device_tensor(o, s, solver.device, nm)
+    solver._chk(solver._L.altro_batch_evaluate_grad_dev(solver.h, ncand, _addr(U), _addr(x0), rho, _addr(out[0]), _addr(out[1]),
+                                                        _addr(out[2]), _addr(out[3]), _addr(Xout)))
+    return out
+
+
+def evaluate_grad(solver, U, x0=None, rho=0.0, out=None, Xout=None):
+    """The merit of control sequences the solver did not make and its gradient, against the problem the next solve would see
+    (altro_batch_evaluate_grad / _dev): returns (J, P, gU, gx0) -- the plain tracking cost evaluate returns, the penalty
+    P = 1/2 sum r^2 of the signed constraint residuals (BOX, LINEAR, SOC: the distance of every row to its feasible set), and
+    the gradient of M = J + rho P with respect to the controls and to the initial state, by one rollout and one costate sweep.
+    U (B, N-1, m): one candidate per instance, J and P (B,), gx0 (B, n); U (B, ncand, N-1, m): J and P (B, ncand), gx0
+    (B, ncand, n); gU has the shape of U.  The states are rolled out from x0 (B, n) (None: the solver's initial state) and
+    written to Xout (shape of U with (N, n)) when given.  With rho = 0 the gradient is that of J alone.
+    With GPU tensors (float64, contiguous) the call is stream-ordered and nothing synchronises; out = (J, P, gU, gx0) are
+    tensors to write into (any may be None, not all; default: four new ones).  With numpy the host twin runs: the same bytes."""
+    args = (U, x0, Xout) + (tuple(out) if out is not None else ())
+    if any(_on_gpu(a) for a in args):
+        if not all(a is None or _on_gpu(a) for a in args):
+            raise ValueError("evaluate_grad: U, x0, Xout and out must all be GPU tensors (or None), or none of them")
+        with _bracket(solver):
+            return _evaluate_grad_dev(solver, U, x0, rho, out, Xout)
+    U = None if U is None else _c(U)
+    x0 = None if x0 is None else _c(x0)
+    ncand, lead, su, sg, sx, s0 = _evaluate_grad_shapes(solver, U, "evaluate_grad")
+    rho = _check_rho(rho, "evaluate_grad")
+    for a, shp, nm in ((U, su, "U"), (x0, s0, "x0")):
+        if a is not None and a.shape != shp:
+            raise ValueError(f"evaluate_grad: {nm}: shape {a.shape}, expected {shp}")
+    shapes = (lead, lead, su, sg)
+    if out is None:
+        out = tuple(np.empty(s) for s in shapes)
+    out = _evaluate_grad_out(out, "evaluate_grad")
+    for o, shp, nm in tuple(zip(out, shapes, ("J", "P", "gU", "gx0"))) + ((Xout, sx, "Xout"),):
+        if o is not None and not (isinstance(o, np.ndarray) and o.dtype == np.float64 and o.flags.c_contiguous and o.shape == shp):
+            raise ValueError(f"evaluate_grad: {nm} must be a C-contiguous float64 array of shape {shp}")
+    solver._chk(solver._L.altro_batch_evaluate_grad(solver.h, ncand, _p(U), _p(x0), rho, _p(out[0]), _p(out[1]), _p(out[2]), _p(out[3]),
+                                                    _p(Xout)))
+    return out
+
+
+_merit_fn = None
+
+
+def _merit_function():
+    """the torch.autograd.Function behind merit, made on first use (the package imports without torch)"""
+    global _merit_fn
+    if _merit_fn is not None:
+        return _merit_fn
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class Merit(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, solver, U, x0, rho):
+            J, P, gU, gx0 = evaluate_grad(solver, U.detach(), None if x0 is None else x0.detach(), rho)
+            ctx.save_for_backward(J, P, gU, gx0)
+            return J + rho * P
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad_out):
+            J, P, gU, gx0 = ctx.saved_tensors
+            dU = grad_out[..., None, None] * gU if ctx.needs_input_grad[1] else None
+            dx0 = None
+            if ctx.needs_input_grad[2]:
+                dx0 = grad_out[..., None] * gx0
+                if dx0.dim() == 3:
+                    dx0 = dx0.sum(dim=1)
+            return None, dU, dx0, None
+
+    _merit_fn = Merit
+    return Merit
+
+
+def merit(solver, U, x0=None, rho=0.0):
+    """M = J + rho P of evaluate_grad as a tensor torch can differentiate once: U (and x0, when it is a tensor that requires
+    grad) are GPU tensors, M has the shape of J and a grad_fn.  The single device call happens in forward; backward hands
+    grad[..., None, None] * gU to U and grad[..., None] * gx0, summed over the candidates, to x0."""
+    if not _on_gpu(U) or not (x0 is None or _on_gpu(x0)):
+        raise ValueError("merit: U (and x0, if given) must be GPU tensors")
+    return _merit_function().apply(solver, U, x0, _check_rho(rho, "merit"))
+
+
 def rollout(solver, U, x0=None, out=None):
     """rollout!(prob): the states of the model under the controls U from x0 (None: the solver's initial state), on the device
     (the rollout form of altro_batch_evaluate).  U (B, N-1, m) -> X (B, N, n); U (B, ncand, N-1, m) -> X (B, ncand, N, n).  GPU

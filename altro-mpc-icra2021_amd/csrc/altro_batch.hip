@@ -17,6 +17,7 @@
 #include "device_io.h"
 #include "device_pool.h"
 #include "evaluate.h"
+#include "evaluate_grad.h"
 #include "launch_ring.h"
 #include "pn_polish.h"
 #include "policy.h"
@@ -2374,6 +2375,69 @@ int32_t altro_batch_evaluate(altro_handle* h, int32_t ncand, const double* U, co
     if (int rc = evaluate_launch(h, ncand, sc.f64(altro::EV_U), sc.f64(altro::EV_X), sc.f64(altro::EV_X0),
                                  sc.f64(altro::EV_J), sc.f64(altro::EV_CMAX), sc.f64(altro::EV_DEFECT),
                                  sc.f64(altro::EV_XOUT)))
+      return rc;
+    return sc.close();
+  });
+}
+
+// ---- gradient of a candidate's merit with respect to its controls and initial state (kernels in evaluate_grad.h)
+// the argument rules both forms share, checked before anything else
+static int evaluate_grad_rules(altro_handle* h, const char* fn, int32_t ncand, const double* U, double rho, double* J, double* P, double* gU,
+                               double* gx0) {
+  const std::string f(fn);
+  if (!U) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": U is required");
+  if (ncand < 1) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": ncand must be at least 1");
+  if (!(rho >= 0.0) || std::isinf(rho)) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": rho must be finite and not negative");
+  if (!J && !P && !gU && !gx0) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": J, P, gU and gx0 are all null");
+  return ALTRO_OK;
+}
+
+// U, x0, J, P, gU, gx0, Xout: device arrays (the caller's, validated; or the staged copies of the host twin).  Enqueues one
+// kernel; allocates only when there is no Xout and the state workspace has to grow.
+static int evaluate_grad_launch(altro_handle* h, int32_t ncand, const double* U, const double* x0, double rho, double* J, double* P, double* gU,
+                                double* gx0, double* Xout) {
+  if (h->wide) return fwd(h, h->wide->evaluate_grad_dev(ncand, U, x0, rho, J, P, gU, gx0, Xout));
+  if (int rc = score_ready(h)) return rc;
+  const size_t B = h->d.batch, N = h->d.N, n = h->d.n;
+  const size_t R = B * (size_t)ncand;
+  if (!Xout) HIPCHK(h, h->pool.reserve(&h->eval_ws, &h->eval_ws_elems, R * N * n));
+  const altro::Eval16 p = eval16_params(h);
+  const size_t rows = (R + 3) & ~(size_t)3;   // whole waves of four rows
+  const altro::GradIO io{U, x0 ? x0 : h->x0, J, P, gU, gx0, Xout ? Xout : h->eval_ws, rho};
+  hipLaunchKernelGGL(altro::k_eval_grad16, grid_for(rows * LW), dim3(256), 0, h->stream, io, x0 ? (int)n : LW, p, (int)ncand, R, rows);
+  HIPCHK(h, hipGetLastError());
+  return ALTRO_OK;
+}
+
+int32_t altro_batch_evaluate_grad_dev(altro_handle* h, int32_t ncand, const double* U, const double* x0, double rho, double* J, double* P,
+                                      double* gU, double* gx0, double* Xout) {
+  return guard(h, [&]() -> int32_t {
+    DEV_ENTER(h, "altro_batch_evaluate_grad_dev");
+    if (int rc = evaluate_grad_rules(h, fn_, ncand, U, rho, J, P, gU, gx0)) return rc;
+    const size_t R = B_ * (size_t)ncand;
+    DEV_ARG(h, "U", U, R * (N_ - 1) * m_, double, false);
+    DEV_ARG(h, "x0", x0, B_ * n_, double, true);
+    DEV_ARG(h, "J", J, R, double, true);
+    DEV_ARG(h, "P", P, R, double, true);
+    DEV_ARG(h, "gU", gU, R * (N_ - 1) * m_, double, true);
+    DEV_ARG(h, "gx0", gx0, R * n_, double, true);
+    DEV_ARG(h, "Xout", Xout, R * N_ * n_, double, true);
+    return evaluate_grad_launch(h, ncand, U, x0, rho, J, P, gU, gx0, Xout);
+  });
+}
+
+// The host twin (StageCursor)
+int32_t altro_batch_evaluate_grad(altro_handle* h, int32_t ncand, const double* U, const double* x0, double rho, double* J, double* P,
+                                  double* gU, double* gx0, double* Xout) {
+  return guard(h, [&]() -> int32_t {
+    if (!h) return dev_null_handle("altro_batch_evaluate_grad");
+    if (int rc = evaluate_grad_rules(h, "altro_batch_evaluate_grad", ncand, U, rho, J, P, gU, gx0)) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    StageCursor sc(h);
+    altro::stage_evaluate_grad(sc, h->d.batch, h->d.N, h->d.n, h->d.m, ncand, U, x0, J, P, gU, gx0, Xout);
+    if (int rc = sc.open()) return rc;
+    if (int rc = evaluate_grad_launch(h, ncand, sc.f64(altro::EG_U), sc.f64(altro::EG_X0), rho, sc.f64(altro::EG_J), sc.f64(altro::EG_P),
+                                      sc.f64(altro::EG_GU), sc.f64(altro::EG_GX0), sc.f64(altro::EG_XOUT)))
       return rc;
     return sc.close();
   });

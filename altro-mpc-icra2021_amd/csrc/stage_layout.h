@@ -54,6 +54,19 @@ inline void stage_evaluate(StageLayout& L, size_t B, size_t N, size_t n, size_t 
   L.add<double>(cx, nullptr, Xout, StageLayout::OPTIONAL);
 }
 
+enum { EG_J, EG_P, EG_GU, EG_GX0, EG_U, EG_X0, EG_XOUT };
+inline void stage_evaluate_grad(StageLayout& L, size_t B, size_t N, size_t n, size_t m, size_t ncand, const double* U, const double* x0,
+                                double* J, double* P, double* gU, double* gx0, double* Xout) {
+  const size_t R = B * ncand, cu = R * (N - 1) * m;
+  L.add<double>(R, nullptr, J, StageLayout::RESERVED);
+  L.add<double>(R, nullptr, P, StageLayout::RESERVED);
+  L.add<double>(cu, nullptr, gU, StageLayout::OPTIONAL);
+  L.add<double>(R * n, nullptr, gx0, StageLayout::OPTIONAL);
+  L.add<double>(cu, U, nullptr, StageLayout::OPTIONAL);
+  L.add<double>(B * n, x0, nullptr, StageLayout::OPTIONAL);
+  L.add<double>(R * N * n, nullptr, Xout, StageLayout::OPTIONAL);
+}
+
 enum { WS_J, WS_CMAX, WS_U, WS_CHOSEN };
 inline void stage_warm_start(StageLayout& L, size_t B, size_t N, size_t m, size_t ncand, size_t inc, const double* U, int32_t* chosen,
                              double* J, double* c_max) {

@@ -13,6 +13,7 @@
 #include "device_io.h"
 #include "device_pool.h"
 #include "evaluate.h"
+#include "evaluate_grad.h"
 #include "warm_start.h"
 #include "simulate.h"
 #include "launch_ring.h"
@@ -737,6 +738,23 @@ struct WideBackend : altro::BackendCommon {   // (what both backends hold and do
       given = 0;
     }
     hipLaunchKernelGGL(altro::k_eval_score_wide, grid, block, (dd && given) ? lds : 0, stream, Jd, cd, dd, Xd, Ud, p, ncand, R, given);
+    WCHK(hipGetLastError());
+    return ALTRO_OK;
+  }
+  // altro_batch_evaluate_grad_dev (evaluate_grad.h; pointers and argument rules checked by the caller, the host twin passes
+  // staged copies): one kernel over batch * ncand waves.  Reads what the next solve would read; writes the caller's outputs and
+  // eval_ws only.
+  int evaluate_grad_dev(int ncand, const double* Ud, const double* x0d, double rho, double* Jd, double* Pd, double* gUd, double* gx0d,
+                        double* Xout) {
+    WCHK(hipSetDevice(device));
+    if (int rc = eval_ready()) return rc;
+    const size_t R = (size_t)d.batch * ncand;
+    if (!Xout) WCHK(pool.reserve(&eval_ws, &eval_ws_elems, R * (size_t)d.N * d.n));
+    const altro::EvalW p = eval_params();
+    const bool use_lds = altro::gradw_lds_fits(d.n, d.m, ltv);
+    const altro::GradIO io{Ud, x0d ? x0d : x0, Jd, Pd, gUd, gx0d, Xout ? Xout : eval_ws, rho};
+    hipLaunchKernelGGL(altro::k_eval_grad_wide, dim3((unsigned)((R * 64 + 255) / 256)), dim3(256), use_lds ? altro::gradw_lds_bytes(d.n, d.m) : 0,
+                       stream, io, p, ncand, R, use_lds ? 1 : 0);
     WCHK(hipGetLastError());
     return ALTRO_OK;
   }

@@ -346,6 +346,11 @@ class ExternalMPC:
         stream reaches this point (api.evaluate): a pass-through, GPU tensors or numpy."""
         return api.evaluate(self.solver, U, X=X, x0=x0, out=out, Xout=Xout)
 
+    def merit(self, U, x0=None, rho=0.0):
+        """M = J + rho P of candidate control sequences against the problem the next tick's solve would see, as a tensor torch
+        differentiates once with respect to U and x0 (api.merit): a pass-through, GPU tensors."""
+        return api.merit(self.solver, U, x0=x0, rho=rho)
+
     def warm_start(self, U, rho=0.0, include_current=True, out=None):
         """(chosen, J, c_max) of api.warm_start: the best of the candidates U (and the trajectory held, when include_current)
         becomes the initial trajectory of the next tick's solve once the solver's stream reaches this point: a pass-through,

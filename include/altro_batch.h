@@ -582,6 +582,51 @@ int32_t altro_batch_evaluate_dev(altro_handle* h, int32_t ncand, const double* U
 int32_t altro_batch_evaluate(altro_handle* h, int32_t ncand, const double* U, const double* X, const double* x0, double* J,
                              double* c_max, double* defect, double* Xout);
 
+/* ---- gradient of a candidate's merit with respect to its controls and its initial state, on the device.  The calls above say
+ * how good a control sequence is for the problem the next solve will see; this one says which way it should move: what a
+ * trained warm-start generator needs to learn against the handle's own cost and constraints, and what a few gradient steps on
+ * the candidates of altro_batch_warm_start_dev need, without the host.  The rollout form of altro_batch_evaluate_dev only.
+ * altro_batch_evaluate_grad_dev: every pointer is a device pointer under the rules of the device-pointer block (validated before
+ * anything is enqueued, stream-ordered, no host synchronisation, no caller pointer kept).  ncand >= 1 candidates per instance:
+ *   U      [batch][ncand][N-1][m]   required
+ *   x0     [batch][n]               NULL: the initial state the handle holds
+ *   rho    >= 0, finite             the weight of P in the merit M = J + rho P (the library does not form M)
+ *   J, P   [batch][ncand]           outputs
+ *   gU     [batch][ncand][N-1][m]   dM/dU
+ *   gx0    [batch][ncand][n]        dM/dx0
+ *   Xout   [batch][ncand][N][n]     the states; NULL: they go to the grow-only workspace altro_batch_evaluate_dev uses (the one
+ *                                   allocation, on the first call or when batch * ncand grows)
+ * Any of J, P, gU, gx0 may be NULL, not all four; which of them are NULL changes no other output.
+ * The window, the dynamics blocks, the weights, the bounds and the constraint tables are those altro_batch_evaluate_dev sees at
+ * that point of the stream (under an episode clock the instance's own window); like it the call first packs constraint tables
+ * a HOST edit has left unpacked.
+ *   X (Xout) the rollout of altro_batch_evaluate_dev: the same bytes.
+ *   J      the plain tracking cost of altro_batch_evaluate_dev: the same bytes.
+ *   P      = 1/2 sum r^2 over every constraint, every knot of its range and every row, r the signed distance of the row to its
+ *          feasible set: BOX finite side max(0, z - zmax), max(0, zmin - z), state columns only at knot N-1; LINEAR v for an
+ *          equality row, max(0, v) for an inequality row; SOC the vector v - Proj(v) (0 inside the cone, v in the polar cone,
+ *          ((1 - c) s, t - c |s|) with c = (1 + t / |s|) / 2 otherwise).  It is the augmented-Lagrangian penalty of the solver
+ *          with zero multipliers and unit penalty.
+ *   gU, gx0   the gradient of M by one costate sweep, with c_k = sum_rows a_r r_r (BOX: r on the element, signed), e = z - zref
+ *          and the weights as altro_batch_evaluate_dev applies them (wd = dt Q, dt R; wf = Qf):
+ *            lambda_{N-1} = wf e_x + rho c_x;  gU_k = wd e_u + rho c_u + B_k' lambda_{k+1};
+ *            lambda_k = wd e_x + rho c_x + A_k' lambda_{k+1};  gx0 = lambda_0.
+ *          With rho == 0 no constraint term enters the gradient, not even as a product with zero; P is still computed.
+ *          M is piecewise quadratic and once differentiable; where a row value sits exactly on its kink the gradient is that of
+ *          the side the comparison above picks.
+ * No masking, no status; a NaN stays a NaN.  Nothing the library owns changes.  Candidate c of instance b gets the bytes it would
+ * get alone (ncand = 1) or on a batch-1 handle holding instance b's data; x0 == NULL and the handle's state passed explicitly
+ * give the same bytes.  Summation orders: csrc/evaluate_grad.h.
+ * altro_batch_evaluate_grad: the same with host arrays, through the handle's staging buffer; synchronises; writes the bytes the
+ * `_dev` call writes.
+ * ALTRO_ERR_INVALID_ARG (nothing enqueued, the handle unchanged and usable): NULL handle; NULL U; ncand < 1; rho negative, NaN
+ * or infinite; J, P, gU and gx0 all NULL; _dev: what the device-pointer block refuses.  ALTRO_ERR_STATE: as
+ * altro_batch_evaluate_dev. */
+int32_t altro_batch_evaluate_grad_dev(altro_handle* h, int32_t ncand, const double* U, const double* x0, double rho, double* J,
+                                      double* P, double* gU, double* gx0, double* Xout);
+int32_t altro_batch_evaluate_grad(altro_handle* h, int32_t ncand, const double* U, const double* x0, double rho, double* J, double* P,
+                                  double* gU, double* gx0, double* Xout);
+
 /* ---- warm start from the best of several candidates, chosen on the device.  The closed loops of the reference start every
  * solve from ONE guess (the shifted previous solution: random_linear_problem.jl:136, simple_rocket.jl:160); a loop that also
  * holds the reference controls and a learned or sampled guess wants the best of them, and the 20-step launch lasts as long as

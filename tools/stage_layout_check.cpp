@@ -53,6 +53,26 @@ int main() {
       slot_is(L, altro::EV_XOUT, s, Xo ? cx * D : 0, Xo, D, "evaluate: Xout", c);
       expect((L.slot[altro::EV_U].in == U) && (L.slot[altro::EV_J].out == J) && (L.slot[altro::EV_XOUT].out == Xo), "evaluate: copies", c);
     }
+    // altro_batch_evaluate_grad: elems = 2 R + (gU ? cu : 0) + (gx0 ? R n : 0) + (U ? cu : 0) + (x0 ? B n : 0) + (Xout ? cx : 0); J, P first
+    for (int c = 0; c < 128; ++c) {
+      const double *U = c & 1 ? d : nullptr, *x0 = c & 2 ? d : nullptr;
+      double *J = c & 4 ? d : nullptr, *P = c & 8 ? d : nullptr, *gU = c & 16 ? d : nullptr, *g0 = c & 32 ? d : nullptr, *Xo = c & 64 ? d : nullptr;
+      const size_t R = B * nc, cu = R * (N - 1) * m, cx = R * N * n;
+      StageLayout L;
+      altro::stage_evaluate_grad(L, B, N, n, m, nc, U, x0, J, P, gU, g0, Xo);
+      expect(L.nslots == 7, "evaluate_grad: slots", c);
+      size_t s = 0;
+      slot_is(L, altro::EG_J, s, R * D, J, D, "evaluate_grad: J", c); s += R * D;
+      slot_is(L, altro::EG_P, s, R * D, P, D, "evaluate_grad: P", c); s += R * D;
+      slot_is(L, altro::EG_GU, s, gU ? cu * D : 0, gU, D, "evaluate_grad: gU", c); s += gU ? cu * D : 0;
+      slot_is(L, altro::EG_GX0, s, g0 ? R * n * D : 0, g0, D, "evaluate_grad: gx0", c); s += g0 ? R * n * D : 0;
+      slot_is(L, altro::EG_U, s, U ? cu * D : 0, U, D, "evaluate_grad: U", c); s += U ? cu * D : 0;
+      slot_is(L, altro::EG_X0, s, x0 ? B * n * D : 0, x0, D, "evaluate_grad: x0", c); s += x0 ? B * n * D : 0;
+      slot_is(L, altro::EG_XOUT, s, Xo ? cx * D : 0, Xo, D, "evaluate_grad: Xout", c); s += Xo ? cx * D : 0;
+      expect(L.bytes == s, "evaluate_grad: size", c);
+      expect(L.slot[altro::EG_U].in == U && L.slot[altro::EG_X0].in == x0 && L.slot[altro::EG_GU].out == gU && L.slot[altro::EG_XOUT].out == Xo,
+             "evaluate_grad: copies", c);
+    }
     // altro_batch_warm_start: bytes = (2 R1 + cu) doubles + B ints; J, c_max, U, chosen, all handed to the kernels
     for (int c = 0; c < 16; ++c) {
       const size_t inc = c & 1;
