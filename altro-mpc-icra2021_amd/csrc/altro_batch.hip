@@ -2188,6 +2188,33 @@ int32_t altro_batch_get_dev_refusals(altro_handle* h, int64_t* rows) {
   });
 }
 
+// The arrays of a host twin in the staging buffer of whichever backend the handle runs on (their layout: stage_layout.h).
+// open() makes room and copies in what the caller passed, f64() / i32() are what the launch gets, close() copies the outputs back and
+// synchronises once: the SAME kernels run on the staged copies, so the bytes are those of the `_dev` call by construction.
+struct StageCursor : altro::StageLayout {
+  altro_handle* h;
+  hipStream_t st = nullptr;
+  char* base = nullptr;
+  explicit StageCursor(altro_handle* h_) : h(h_) {}
+  int open() {
+    if (int rc = fwd(h, common(h).ensure_stage(bytes))) return rc;
+    st = common(h).stream;
+    base = reinterpret_cast<char*>(common(h).stage);
+    for (int i = 0; i < nslots; ++i)
+      if (slot[i].in) HIPCHK(h, hipMemcpyAsync(base + slot[i].off, slot[i].in, slot[i].bytes, hipMemcpyHostToDevice, st));
+    return ALTRO_OK;
+  }
+  void* dev(int i) const { return slot[i].dev ? base + slot[i].off : nullptr; }
+  double* f64(int i) const { return static_cast<double*>(dev(i)); }
+  int32_t* i32(int i) const { return static_cast<int32_t*>(dev(i)); }
+  int close() {
+    for (int i = 0; i < nslots; ++i)
+      if (slot[i].out) HIPCHK(h, hipMemcpyAsync(slot[i].out, base + slot[i].off, slot[i].bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    return ALTRO_OK;
+  }
+};
+
 // ---- feedback policy on the device (kernels in policy.h)
 // x, knot, u, fb: device arrays (the caller's, validated; or the staged copies of the host twin).  Enqueues one kernel.
 static int eval_policy_launch(altro_handle* h, const double* x, const int32_t* knot, int32_t clamp, double* u, int32_t* fb) {
@@ -2210,31 +2237,21 @@ int32_t altro_batch_eval_policy_dev(altro_handle* h, const double* x, const int3
   });
 }
 
-// The host twin: knot is checked here, then x and knot go through the staging buffer, the SAME kernel runs on the staged
-// copies and u, fb come back -- the bytes are those of the `_dev` call by construction.
+// The host twin (StageCursor): x and u are required and knot is checked here, before anything is staged
 int32_t altro_batch_eval_policy(altro_handle* h, const double* x, const int32_t* knot, int32_t clamp, double* u, int32_t* fb) {
   return guard(h, [&]() -> int32_t {
     if (!h) return dev_null_handle("altro_batch_eval_policy");
     if (!x || !u) FAIL(h, ALTRO_ERR_INVALID_ARG, "altro_batch_eval_policy: x and u are required");
-    const size_t B = h->d.batch, N = h->d.N, n = h->d.n, m = h->d.m;
+    const size_t B = h->d.batch, N = h->d.N;
     for (size_t b = 0; knot && b < B; ++b)
       if (knot[b] < 0 || knot[b] > (int32_t)N - 2)
         FAIL(h, ALTRO_ERR_INVALID_ARG, "altro_batch_eval_policy: knot[" + std::to_string(b) + "] = " + std::to_string(knot[b]) + " is outside 0 .. N-2");
     HIPCHK(h, hipSetDevice(h->device));
-    const size_t bytes = B * (n + m) * sizeof(double) + 2 * B * sizeof(int32_t);
-    if (int rc = fwd(h, common(h).ensure_stage(bytes))) return rc;
-    const hipStream_t st = common(h).stream;
-    double* sx = common(h).stage;
-    double* su = sx + B * n;
-    int32_t* sk = reinterpret_cast<int32_t*>(su + B * m);
-    int32_t* sf = sk + B;
-    HIPCHK(h, hipMemcpyAsync(sx, x, B * n * sizeof(double), hipMemcpyHostToDevice, st));
-    if (knot) HIPCHK(h, hipMemcpyAsync(sk, knot, B * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    if (int rc = eval_policy_launch(h, sx, knot ? sk : nullptr, clamp, su, fb ? sf : nullptr)) return rc;
-    HIPCHK(h, hipMemcpyAsync(u, su, B * m * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (fb) HIPCHK(h, hipMemcpyAsync(fb, sf, B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    return ALTRO_OK;
+    StageCursor sc(h);
+    altro::stage_eval_policy(sc, B, h->d.n, h->d.m, x, knot, u, fb);
+    if (int rc = sc.open()) return rc;
+    if (int rc = eval_policy_launch(h, sc.f64(altro::EP_X), sc.i32(altro::EP_KNOT), clamp, sc.f64(altro::EP_U), sc.i32(altro::EP_FB))) return rc;
+    return sc.close();
   });
 }
 
@@ -2275,33 +2292,6 @@ static int score_ready(altro_handle* h) {
   if (!h->clock.on && h->kref + h->d.N > h->Nt) FAIL(h, ALTRO_ERR_STATE, "reference window runs past the end of the stored trajectory");
   return pack_constraints(h);   // (what the next solve would do first; a no-op once the tables are packed)
 }
-
-// The arrays of a host twin in the staging buffer of whichever backend the handle runs on (their layout: stage_layout.h).
-// open() makes room and copies in what the caller passed, f64() / i32() are what the launch gets, close() copies the outputs back and
-// synchronises once: the SAME kernels run on the staged copies, so the bytes are those of the `_dev` call by construction.
-struct StageCursor : altro::StageLayout {
-  altro_handle* h;
-  hipStream_t st = nullptr;
-  char* base = nullptr;
-  explicit StageCursor(altro_handle* h_) : h(h_) {}
-  int open() {
-    if (int rc = fwd(h, common(h).ensure_stage(bytes))) return rc;
-    st = common(h).stream;
-    base = reinterpret_cast<char*>(common(h).stage);
-    for (int i = 0; i < nslots; ++i)
-      if (slot[i].in) HIPCHK(h, hipMemcpyAsync(base + slot[i].off, slot[i].in, slot[i].bytes, hipMemcpyHostToDevice, st));
-    return ALTRO_OK;
-  }
-  void* dev(int i) const { return slot[i].dev ? base + slot[i].off : nullptr; }
-  double* f64(int i) const { return static_cast<double*>(dev(i)); }
-  int32_t* i32(int i) const { return static_cast<int32_t*>(dev(i)); }
-  int close() {
-    for (int i = 0; i < nslots; ++i)
-      if (slot[i].out) HIPCHK(h, hipMemcpyAsync(slot[i].out, base + slot[i].off, slot[i].bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    return ALTRO_OK;
-  }
-};
 
 // the argument rules both forms share, checked before anything else
 static int evaluate_rules(altro_handle* h, const char* fn, int32_t ncand, const double* U, const double* X, const double* x0, double* J,

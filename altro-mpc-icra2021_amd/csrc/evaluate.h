@@ -6,15 +6,20 @@
 // it wrote gives the bytes a direct scoring of the same arrays gives.  The kernels read the tables the solve kernels read --
 // dynamics, cost rows, bounds rows, reference window, constraint rows -- and write nothing the library owns.  No
 // synchronisation between waves; LDS only as a wave-private copy of time-invariant dynamics on the one-wave-per-instance backend.
-// THE SCORING CORE.  This file also holds, once per backend, what every kernel that scores a trajectory is made
-// of -- the kernels here and those of warm_start.h and simulate.h: the context of a row / wave (Ctx16, CtxW), the per-knot
-// score (score16_knot, scorew_knot: cost term, box test, constraint rows), its reduction (score_reduce) and the step of the
-// recurrence (eval16_step, evalw_advance).  Contraction is off in every function that holds a product followed by a sum and
-// each fused multiply-add is written out, so the order of every sum is the one stated here, and here only:
+// THE SCORING CORE.  This file also holds, once per backend, what every kernel that scores a trajectory is
+// made of -- the kernels here and those of warm_start.h, simulate.h and evaluate_grad.h: the context of a row / wave (Ctx16,
+// CtxW), the value of a constraint row (con16_row, conw_row) with what the maximum (con16_max, conw_max) and the penalty
+// (con16_residual, conw_residual) make of it, the two sides of a box (box_sides), the per-knot cost (cost16_knot, costw_knot)
+// and score (score16_knot, scorew_knot: cost, box test, constraint rows), its reduction (score_reduce), the dynamics of a wave
+// forwards and transposed (EvalWDyn) and the step of the recurrence (eval16_step, evalw_advance).  Contraction is off in every
+// function that holds a product followed by a sum and each fused multiply-add is written out, so the order of every sum is
+// the one stated here (evaluate_grad.h adds those of its reverse sweep):
 //   dynamics / constraint row   acc = f_i (b_r); acc = fma(coefficient_j, z_j, acc) for j = 0, 1, ..., n + m - 1 in turn
 //   cost                        every lane adds its own w e^2 (product e * e rounded, then w * (e e), then the addition) knot
 //                               after knot, k = 0 .. N-1; the lanes are then added by an xor butterfly (strides 8, 4, 2, 1, and
 //                               32, 16 first on the one-wave-per-instance backend); J = 0.5 * that sum
+//   SOC residual                n2 = v_0^2 + v_1^2 + .. in turn (products rounded), nv = sqrt(n2), c = 0.5 * (1 + t / nv);
+//                               element q < p - 1: v_q - c * v_q; element p - 1: t - c * nv; the violation is its fabs
 //   c_max, defect               maxima (exact in any order); a NaN stays a NaN
 #pragma once
 #include <hip/hip_runtime.h>
@@ -50,18 +55,33 @@ __device__ __forceinline__ double cost_term(double w, double z, double zref) {
   return q;
 }
 
-// one element's box test (the solve kernels' test for a finite side); on = the lane holds the element
+// max(0, v) that keeps a NaN
+__device__ __forceinline__ double grad_pos(double v) { return (v > 0.0 || v != v) ? v : 0.0; }
+
+// the two sides of one element's box: whether the side is there (the solve kernels' test for a finite side; on = the lane
+// holds the element) and the signed distances over() = z - hi, under() = lo - z.  box_max takes their maxima, the penalty
+// max(0, .) of them.  (The distances are formed where they are used: formed ahead, box_max's second subtraction moved up in
+// the knot loop of k_ws_score_wide and cost that kernel 2 %)
+struct BoxSides {
+  bool has_hi, has_lo;
+  double z, lo, hi;
+  __device__ __forceinline__ double over() const { return z - hi; }
+  __device__ __forceinline__ double under() const { return lo - z; }
+  __device__ __forceinline__ double res_hi() const { return has_hi ? grad_pos(over()) : 0.0; }
+  __device__ __forceinline__ double res_lo() const { return has_lo ? grad_pos(under()) : 0.0; }
+};
+__device__ __forceinline__ BoxSides box_sides(bool on, double z, double lo, double hi) { return {on && hi < 1e300, on && lo > -1e300, z, lo, hi}; }
 __device__ __forceinline__ double box_max(double viol, bool on, double z, double lo, double hi) {
-  const bool has_hi = hi < 1e300, has_lo = lo > -1e300;
-  if (on && has_hi) viol = eval_max(viol, z - hi);
-  if (on && has_lo) viol = eval_max(viol, lo - z);
+  const BoxSides s = box_sides(on, z, lo, hi);
+  if (s.has_hi) viol = eval_max(viol, s.over());
+  if (s.has_lo) viol = eval_max(viol, s.under());
   return viol;
 }
 
-// |Proj(v) - v| of element `pos` of a second-order cone of dimension p (2..4) whose values are v[0..p-1] (v[q] = 0 for
-// q >= p): the oracle's soc_project / con_violation.  Inside the cone 0, in the polar cone |v_pos|, otherwise the distance to
-// the boundary point c (s, |s|), c = (1 + t / |s|) / 2.
-__device__ __forceinline__ double soc_row_violation(const double (&v)[4], int p, int pos) {
+// v - Proj(v) of element `pos` of a second-order cone of dimension p (2..4) whose values are v[0..p-1] (v[q] = 0 for
+// q >= p): the oracle's soc_project.  Inside the cone 0, in the polar cone v_pos, otherwise the step from the boundary point
+// c (s, |s|), c = (1 + t / |s|) / 2.  The violation (the oracle's con_violation) is its magnitude, exactly.
+__device__ __forceinline__ double soc_row_residual(const double (&v)[4], int p, int pos) {
 #pragma clang fp contract(off)
   const int pt = p - 1;
   double n2 = 0.0, t = 0.0, mine = 0.0;
@@ -73,10 +93,27 @@ __device__ __forceinline__ double soc_row_violation(const double (&v)[4], int p,
   }
   const double nv = sqrt(n2);
   if (nv <= t) return 0.0;
-  if (nv <= -t) return fabs(mine);
+  if (nv <= -t) return mine;
   const double c = 0.5 * (1.0 + t / nv);
   const double proj = pos == pt ? c * nv : c * mine;
-  return fabs(proj - mine);   // (a NaN anywhere in the cone fails both tests above and comes out here)
+  return mine - proj;   // (a NaN anywhere in the cone fails both tests above and comes out here)
+}
+__device__ __forceinline__ double soc_row_violation(const double (&v)[4], int p, int pos) { return fabs(soc_row_residual(v, p, pos)); }
+
+// What a lane has of the constraint row it owns at a knot (con16_row, conw_row): the row's value v, whether the row is on (a
+// lane without an active row: v is 0 or unused), its kind, and for a cone its dimension p, the row's place pos in it and the
+// cone's values vq (0 beyond p).  The maximum takes |Proj - v| / |v| / v of it, the penalty the signed residual.
+struct ConRow {
+  double v, vq[4];
+  int p, pos;
+  bool on, soc, eq;
+};
+__device__ __forceinline__ double row_violation(const ConRow& r) {
+  return r.soc ? soc_row_violation(r.vq, r.p, r.pos) : (r.eq ? fabs(r.v) : r.v);
+}
+__device__ __forceinline__ double row_residual(const ConRow& r) {
+  const double res = r.soc ? soc_row_residual(r.vq, r.p, r.pos) : (r.eq ? r.v : grad_pos(r.v));
+  return r.on ? res : 0.0;
 }
 
 // what a scoring kernel accumulates knot after knot, per lane, and what its row / wave has in the end
@@ -169,45 +206,55 @@ struct Ctx16 {
   }
 };
 
-// the constraint rows of knot k: lane r owns row r of the knot's table (Ac, bc: the lane's row and offset of knot 0); viol comes
-// in and goes out by value
-__device__ __forceinline__ double con16_max(double viol, const Eval16& P, const double* Ac, const double* bc, int pos, int lane, int k,
-                                            double z) {
+// the constraint row of knot k that lane r owns: row r of the knot's table (c.Ac, c.bc: the lane's row and offset of knot 0).
+// Every lane of the row is here (the broadcasts read live lanes); P.ncrows > 0.
+__device__ __forceinline__ ConRow con16_row(const Eval16& P, const Ctx16& c, int k, double z) {
   const int n = P.n, m = P.m;
+  const int* cm = P.cmeta + ((size_t)k * 16 + c.lane) * 4;
+  const int type = cm[0], p = cm[3];
+  const bool act = type != CT_NONE && k >= cm[1] && k <= cm[2];
+  double a[16], v = 0.0;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) a[j] = 0.0;
+  if (act) {
+    const double* ar = c.Ac + (size_t)k * 256;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) a[j] = j < n + m ? ar[j] : 0.0;
+    v = c.bc[(size_t)k * 16];
+  }
+  ConRow r;
+  r.v = row_affine(a, v, z);
+  r.p = p; r.pos = c.pos; r.soc = type == CT_SOC; r.eq = type == CT_EQ;
+  r.on = act && (!r.soc || c.pos < p);   // (a linear row may sit in a spare lane of a cone's quad)
+  const double vv = (r.on && r.soc) ? r.v : 0.0;
+  r.vq[0] = quad_bcast<0>(vv); r.vq[1] = quad_bcast<1>(vv); r.vq[2] = quad_bcast<2>(vv); r.vq[3] = quad_bcast<3>(vv);
+  return r;
+}
+// the running maximum with the knot's rows (in and out by value), and the lane's signed residual (0 without an active row)
+__device__ __forceinline__ double con16_max(double viol, const Eval16& P, const Ctx16& c, int k, double z) {
   if (P.ncrows > 0) {
-    const int* cm = P.cmeta + ((size_t)k * 16 + lane) * 4;
-    const int type = cm[0], p = cm[3];
-    const bool act = type != CT_NONE && k >= cm[1] && k <= cm[2];
-    double a[16], v = 0.0;
-#pragma unroll
-    for (int c = 0; c < 16; ++c) a[c] = 0.0;
-    if (act) {
-      const double* ar = Ac + (size_t)k * 256;
-#pragma unroll
-      for (int c = 0; c < 16; ++c) a[c] = c < n + m ? ar[c] : 0.0;
-      v = bc[(size_t)k * 16];
-    }
-    v = row_affine(a, v, z);
-    const bool is_soc = type == CT_SOC;
-    const bool row_on = act && (!is_soc || pos < p);   // (a linear row may sit in a spare lane of a cone's quad)
-    const double vv = (row_on && is_soc) ? v : 0.0;
-    double vq[4];
-    vq[0] = quad_bcast<0>(vv); vq[1] = quad_bcast<1>(vv); vq[2] = quad_bcast<2>(vv); vq[3] = quad_bcast<3>(vv);
-    const double cv = is_soc ? soc_row_violation(vq, p, pos) : (type == CT_EQ ? fabs(v) : v);
-    if (row_on) viol = eval_max(viol, cv);
+    const ConRow r = con16_row(P, c, k, z);
+    if (r.on) viol = eval_max(viol, row_violation(r));
   }
   return viol;
 }
+__device__ __forceinline__ double con16_residual(const Eval16& P, const Ctx16& c, int k, double z) { return row_residual(con16_row(P, c, k, z)); }
 
-// knot k of the row: z = the lane's element (0 where the row holds none), zr = the lane's element of the knot's reference row
-// (an argument: k_sim16 loads it a knot ahead)
-__device__ __forceinline__ void score16_knot(Score& s, const Eval16& P, const Ctx16& c, int k, double z, double zr) {
+// the cost of knot k of the row added to the lane's sum: z = the lane's element (0 where the row holds none), zr = the lane's
+// element of the knot's reference row (an argument: k_sim16 loads it a knot ahead)
+__device__ __forceinline__ double cost16_knot(double cost, const Eval16& P, const Ctx16& c, int k, double z, double zr) {
   const bool term = k == P.N - 1;
-  const bool on = c.isx || (c.isu && !term);
+  const bool on = c.isx | (c.isu & !term);
   const double q = cost_term(term ? c.wf : c.wd, z, zr);
-  s.cost = on ? s.cost + q : s.cost;
+  return on ? cost + q : cost;
+}
+
+// knot k of the row: cost, box, constraint rows
+__device__ __forceinline__ void score16_knot(Score& s, const Eval16& P, const Ctx16& c, int k, double z, double zr) {
+  const bool on = c.isx | (c.isu & (k != P.N - 1));
+  s.cost = cost16_knot(s.cost, P, c, k, z, zr);
   if (on && k >= P.box_k0 && k <= P.box_k1) s.viol = box_max(s.viol, true, z, c.zlo, c.zhi);
-  s.viol = con16_max(s.viol, P, c.Ac, c.bc, c.pos, c.lane, k, z);
+  s.viol = con16_max(s.viol, P, c, k, z);
 }
 
 // Rollout: Xw [R][N][n] <- x_0 = x0[b] (x0s = its row stride: n for a caller's array, 16 for the handle's own), then the
@@ -251,16 +298,15 @@ __global__ void k_eval_score16(double* __restrict__ J, double* __restrict__ cmax
   double dfc = 0.0;
   for (int k = 0; k < N; ++k) {
     const bool term = k == N - 1;
-    const bool on = isx || (isu && !term);
+    const bool on = isx | (isu & !term);   // (cost16_knot's form of it: the two are then one value to the compiler)
     const double z = isx ? Xr[(size_t)k * n + lane] : (on ? Ur[(size_t)k * m + (lane - n)] : 0.0);
-    const double q = cost_term(term ? c.wf : c.wd, z, c.Zr[(size_t)k * 16]);
-    s.cost = on ? s.cost + q : s.cost;
+    s.cost = cost16_knot(s.cost, P, c, k, z, c.Zr[(size_t)k * 16]);
     if (on && k >= P.box_k0 && k <= P.box_k1) s.viol = box_max(s.viol, true, z, c.zlo, c.zhi);
     if (want_defect && !term) {
       const double pred = row_affine(g, fv, z);
       if (isx) dfc = eval_max(dfc, fabs(pred - Xr[(size_t)(k + 1) * n + lane]));
     }
-    s.viol = con16_max(s.viol, P, c.Ac, c.bc, c.pos, lane, k, z);
+    s.viol = con16_max(s.viol, P, c, k, z);
   }
   double Jr, cr;
   score_reduce<16>(s, Jr, cr);
@@ -287,12 +333,14 @@ struct EvalW {
   int lds_dyn;   // 1: time-invariant dynamics whose [A | B] block fits: every wave keeps its instance's block in its slice of LDS
 };
 
-// LDS doubles a wave needs for lds_dyn, the bytes a 256-thread block of four waves asks for, and the rule for it: inside the
-// 64 KB a kernel gets without asking for more (n (n + m) <= 2048: up to (32, 32), (40, 11), ...).  Larger blocks are read
-// from memory at every knot.
-__host__ __device__ inline size_t evalw_lds_doubles(int n, int m) { return (size_t)n * (n + m); }
-__host__ __device__ inline size_t evalw_lds_bytes(int n, int m) { return 4 * evalw_lds_doubles(n, m) * sizeof(double); }
-__host__ __device__ inline bool evalw_lds_fits(int n, int m, int ltv) { return !ltv && evalw_lds_bytes(n, m) <= 65536; }
+// The leading dimension ld of a wave's LDS copy of [A | B] (n, or n | 1 for a kernel that also reads it transposed: EvalWDyn),
+// the LDS doubles a wave needs for it, the bytes a 256-thread block of four waves asks for, and the rule for it: inside the
+// 64 KB a kernel gets without asking for more (ld (n + m) <= 2048: up to (32, 32), (40, 11), ...; padded (32, 16), (30, 25)).
+// Larger blocks are read from memory at every knot.
+__host__ __device__ inline int evalw_ld(int n, bool pad) { return pad ? n | 1 : n; }
+__host__ __device__ inline size_t evalw_lds_doubles(int ld, int n, int m) { return (size_t)ld * (n + m); }
+__host__ __device__ inline size_t evalw_lds_bytes(int ld, int n, int m) { return 4 * evalw_lds_doubles(ld, n, m) * sizeof(double); }
+__host__ __device__ inline bool evalw_lds_fits(int ld, int n, int m, int ltv) { return !ltv && evalw_lds_bytes(ld, n, m) <= 65536; }
 
 __device__ __forceinline__ double eval_readlane(double v, int j) {
   const int lo = __builtin_amdgcn_readlane(__double2loint(v), j), hi = __builtin_amdgcn_readlane(__double2hiint(v), j);
@@ -322,33 +370,40 @@ __device__ __forceinline__ double evalw_dot(const double* col, size_t stride, do
   return acc;
 }
 
-// row Tn of A x + B u + f0: Acol / Bcol point at element Tn of the first column; xs / us are the lane's own elements
-__device__ __forceinline__ double evalw_step(const double* Acol, const double* Bcol, double f0, int n, int m, double xs, double us) {
-  const double acc = evalw_dot(Acol, (size_t)n, xs, n, f0, true);
-  return evalw_dot(Bcol, (size_t)n, us, m, acc, true);
+// row Tn of A x + B u + f0: Acol / Bcol point at element Tn of the first column, the next column is ld doubles on; xs / us
+// are the lane's own elements
+__device__ __forceinline__ double evalw_step(const double* Acol, const double* Bcol, int ld, double f0, int n, int m, double xs, double us) {
+  const double acc = evalw_dot(Acol, (size_t)ld, xs, n, f0, true);
+  return evalw_dot(Bcol, (size_t)ld, us, m, acc, true);
 }
 
-// The dynamics of instance b as one wave reads them at knot k.  Time-invariant blocks that fit (lds_dyn) are copied once into
-// the wave's own slice of LDS -- every knot of every candidate would otherwise read the same n (n + m) doubles from memory
-// again, and at (32, 16), batch 8192, ncand 8 that traffic (12 KB per knot and wave) was the whole run time.  The slice is
-// written and read by the same wave only: LDS instructions of a wave execute in order, so the hand-over needs a wave-level
-// fence for the compiler and no barrier.  The values and the order of every sum are the same either way.
-struct EvalWDyn {
+// The dynamics of instance b as one wave reads them at knot k, forwards (step: row T of [A | B]) and transposed (tstep: column
+// T).  Time-invariant blocks that fit are copied once into the wave's own slice of LDS -- every knot of every candidate would
+// otherwise read the same n (n + m) doubles from memory again, and at (32, 16), batch 8192, ncand 8 that traffic (12 KB per
+// knot and wave) was the whole run time.  The slice is written and read by the same wave only: LDS instructions of a wave
+// execute in order, so the hand-over needs a wave-level fence for the compiler and no barrier.  The values and the order of
+// every sum are the same either way.  PAD: the kernel also reads the slice transposed, so its leading dimension is padded to
+// an odd number of doubles: lane j's transposed run starts at j * ld, and a ds_read_b64 of 32 lanes is conflict-free exactly
+// when j * ld mod 32 takes 32 values (MI355X: 64 banks of 4 bytes, a double takes two).  The forward reads
+// (element T + j * ld, j uniform) are consecutive either way.
+template <bool PAD>
+struct EvalWDynT {
   const EvalW& P;
   size_t b;
-  int kref, Tn;
+  int kref, Tn, Tm;
   const double* lds;   // the wave's [A | B] in LDS, or null
   double f0;
-  // T: the lane; `wanted` = false: the kernel will not step (no copy)
-  __device__ __forceinline__ EvalWDyn(const EvalW& p, size_t b_, int kref_, int T, bool wanted)
-      : P(p), b(b_), kref(kref_), Tn(T < p.n ? T : p.n - 1), lds(nullptr), f0(0.0) {
-    if (!wanted || !P.lds_dyn) return;
+  // T: the lane; `copy` = false: no slice (the kernel will not step, or the block does not fit: the launch decides)
+  __device__ __forceinline__ EvalWDynT(const EvalW& p, size_t b_, int kref_, int T, bool copy)
+      : P(p), b(b_), kref(kref_), Tn(T < p.n ? T : p.n - 1), Tm(T < p.m ? T : p.m - 1), lds(nullptr), f0(0.0) {
+    if (!copy) return;
     extern __shared__ double eval_lds[];
-    double* slice = eval_lds + (threadIdx.x >> 6) * evalw_lds_doubles(P.n, P.m);
+    const int n = P.n, na = P.n * P.n, nb = P.n * P.m, ld = evalw_ld(P.n, PAD);
+    double* slice = eval_lds + (threadIdx.x >> 6) * evalw_lds_doubles(ld, P.n, P.m);
     const size_t blk = evalw_block(P, b, kref, 0);
-    const int na = P.n * P.n, nb = P.n * P.m;
-    for (int e = T; e < na; e += 64) slice[e] = P.A[blk * na + e];
-    for (int e = T; e < nb; e += 64) slice[na + e] = P.Bm[blk * nb + e];
+    auto at = [&](int e) { return PAD ? (e / n) * ld + e % n : e; };   // element e of the column-major [A | B]
+    for (int e = T; e < na; e += 64) slice[at(e)] = P.A[blk * na + e];
+    for (int e = T; e < nb; e += 64) slice[at(na + e)] = P.Bm[blk * nb + e];
     f0 = P.f != nullptr ? P.f[blk * P.n + Tn] : 0.0;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -356,15 +411,25 @@ struct EvalWDyn {
     lds = slice;
   }
   __device__ __forceinline__ double step(int k, double xs, double us) const {
-    const int n = P.n, m = P.m;
-    if (lds != nullptr) return evalw_step(lds + Tn, lds + n * n + Tn, f0, n, m, xs, us);
+    const int n = P.n, m = P.m, ld = evalw_ld(P.n, PAD);
+    if (lds != nullptr) return evalw_step(lds + Tn, lds + n * ld + Tn, ld, f0, n, m, xs, us);
     const size_t blk = evalw_block(P, b, kref, k);
-    return evalw_step(P.A + blk * n * n + Tn, P.Bm + blk * n * m + Tn, P.f != nullptr ? P.f[blk * n + Tn] : 0.0, n, m, xs, us);
+    return evalw_step(P.A + blk * n * n + Tn, P.Bm + blk * n * m + Tn, n, P.f != nullptr ? P.f[blk * n + Tn] : 0.0, n, m, xs, us);
+  }
+  // acc + column Tn of A_k (bt: column Tm of B_k) times lambda, i = 0 .. n-1 in turn
+  __device__ __forceinline__ double tstep(int k, bool bt, double lam, double acc, bool on) const {
+    const int n = P.n, m = P.m;
+    if (lds != nullptr) return evalw_dot(lds + (size_t)(bt ? n + Tm : Tn) * evalw_ld(n, PAD), 1, lam, n, acc, on);
+    const size_t blk = evalw_block(P, b, kref, k);
+    const double* col = bt ? P.Bm + blk * n * m + (size_t)Tm * n : P.A + blk * n * n + (size_t)Tn * n;
+    return evalw_dot(col, 1, lam, n, acc, on);
   }
 };
+using EvalWDyn = EvalWDynT<false>;
 
 // the step of the recurrence: (x, u) of knot k -> x_{k+1} on the state lanes, 0 elsewhere
-__device__ __forceinline__ double evalw_advance(const EvalWDyn& dyn, int k, double x, double u, bool isx) {
+template <bool PAD>
+__device__ __forceinline__ double evalw_advance(const EvalWDynT<PAD>& dyn, int k, double x, double u, bool isx) {
   const double nx = dyn.step(k, x, u);
   return isx ? nx : 0.0;
 }
@@ -387,46 +452,59 @@ struct CtxW {
         ulo(P.zmin[b * (size_t)P.b_pi * (P.n + P.m) + P.n + Tm]), uhi(P.zmax[b * (size_t)P.b_pi * (P.n + P.m) + P.n + Tm]),
         Xf(P.Xref + (b * (size_t)P.Nt + (size_t)kref) * P.n), Uf(P.Uref + (b * (size_t)(P.Nt - 1) + (size_t)kref) * P.m),
         At(P.AconT + b * P.con_istride + (isr ? T_ : 0)), bc(P.bcon + b * P.bcon_istride + (isr ? T_ : 0)),
-        c0(isr ? P.rowc0[T_] : 0), cp(isr ? P.rowcp[T_] : 0), dyn(P, b, kref, T_, want_dyn) {}
+        c0(isr ? P.rowc0[T_] : 0), cp(isr ? P.rowcp[T_] : 0), dyn(P, b, kref, T_, want_dyn && P.lds_dyn) {}
 };
 
-// the constraint rows of knot k: lane T < Pn owns row T (At, bc: the lane's row and offset of knot 0; c0, cp: its cone); viol
-// comes in and goes out by value
-__device__ __forceinline__ double conw_max(double viol, const EvalW& P, const double* At, const double* bc, int c0, int cp, bool isr, int T,
-                                           int k, double x, double u) {
+// the constraint row of knot k that lane T < Pn owns (c.At, c.bc: the lane's row and offset of knot 0; c.c0, c.cp: its cone).
+// Every lane of the wave is here (the shuffles read live lanes); P.Pn > 0.
+__device__ __forceinline__ ConRow conw_row(const EvalW& P, const CtxW& c, int k, double x, double u) {
   const int n = P.n, m = P.m, nz = P.n + P.m, Pn = P.Pn;
   const bool term = k == P.N - 1;
-  if (Pn > 0) {
-    const int ct = isr ? P.ctype[(size_t)k * Pn + T] : 0;
-    const bool on = ct != 0;
-    const double* Ak = At + (size_t)k * nz * Pn;
-    double v = on ? bc[(size_t)k * Pn] : 0.0;
-    v = evalw_dot(Ak, (size_t)Pn, x, n, v, on);
-    if (!term) v = evalw_dot(Ak + (size_t)n * Pn, (size_t)Pn, u, m, v, on);
-    double vq[4];   // (every lane of the wave is here: the shuffles read live lanes)
+  const int ct = c.isr ? P.ctype[(size_t)k * Pn + c.T] : 0;
+  ConRow r;
+  r.on = ct != CT_NONE; r.soc = ct == CT_SOC; r.eq = ct == CT_EQ; r.p = c.cp; r.pos = c.T - c.c0;
+  const double* Ak = c.At + (size_t)k * nz * Pn;
+  double v = r.on ? c.bc[(size_t)k * Pn] : 0.0;
+  v = evalw_dot(Ak, (size_t)Pn, x, n, v, r.on);
+  if (!term) v = evalw_dot(Ak + (size_t)n * Pn, (size_t)Pn, u, m, v, r.on);
+  r.v = v;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const double s = __shfl(v, (c0 + q) & 63, 64);
-      vq[q] = q < cp ? s : 0.0;
-    }
-    const double cv = ct == 3 ? soc_row_violation(vq, cp, T - c0) : (ct == 1 ? fabs(v) : v);
-    if (on) viol = eval_max(viol, cv);
+  for (int q = 0; q < 4; ++q) {
+    const double s = __shfl(v, (c.c0 + q) & 63, 64);
+    r.vq[q] = q < c.cp ? s : 0.0;
+  }
+  return r;
+}
+// the running maximum with the knot's rows (in and out by value), and the lane's signed residual (0 without an active row)
+__device__ __forceinline__ double conw_max(double viol, const EvalW& P, const CtxW& c, int k, double x, double u) {
+  if (P.Pn > 0) {
+    const ConRow r = conw_row(P, c, k, x, u);
+    if (r.on) viol = eval_max(viol, row_violation(r));
   }
   return viol;
 }
+__device__ __forceinline__ double conw_residual(const EvalW& P, const CtxW& c, int k, double x, double u) {
+  return row_residual(conw_row(P, c, k, x, u));
+}
 
-// knot k of the wave: x, u = the lane's elements (0 where it owns none, u = 0 at the terminal knot)
-__device__ __forceinline__ void scorew_knot(Score& s, const EvalW& P, const CtxW& c, int k, double x, double u) {
-  const int T = c.T;
+// the cost of knot k of the wave added to the lane's sum: x, u = the lane's elements (0 where it owns none, u = 0 at the
+// terminal knot)
+__device__ __forceinline__ double costw_knot(double cost, const EvalW& P, const CtxW& c, int k, double x, double u) {
   const bool term = k == P.N - 1;
-  const bool uon = c.isu && !term;
-  if (c.isx) s.cost += cost_term(term ? c.wfx : c.wx, x, c.Xf[(size_t)k * P.n + T]);
-  if (uon) s.cost += cost_term(c.wu, u, c.Uf[(size_t)k * P.m + T]);
+  if (c.isx) cost += cost_term(term ? c.wfx : c.wx, x, c.Xf[(size_t)k * P.n + c.T]);
+  if (c.isu && !term) cost += cost_term(c.wu, u, c.Uf[(size_t)k * P.m + c.T]);
+  return cost;
+}
+
+// knot k of the wave: cost, box, constraint rows
+__device__ __forceinline__ void scorew_knot(Score& s, const EvalW& P, const CtxW& c, int k, double x, double u) {
+  const bool uon = c.isu && k != P.N - 1;
+  s.cost = costw_knot(s.cost, P, c, k, x, u);
   if (k >= P.box_k0 && k <= P.box_k1) {
     s.viol = box_max(s.viol, c.isx, x, c.xlo, c.xhi);
     s.viol = box_max(s.viol, uon, u, c.ulo, c.uhi);
   }
-  s.viol = conw_max(s.viol, P, c.At, c.bc, c.c0, c.cp, c.isr, T, k, x, u);
+  s.viol = conw_max(s.viol, P, c, k, x, u);
 }
 
 __global__ void k_eval_rollout_wide(double* __restrict__ Xw, const double* __restrict__ U, const double* __restrict__ x0, EvalW P, int ncand,
@@ -440,7 +518,7 @@ __global__ void k_eval_rollout_wide(double* __restrict__ Xw, const double* __res
   const bool isx = T < n, isu = T < m;
   double* Xr = Xw + r * (size_t)N * n;
   const double* Ur = U + r * (size_t)(N - 1) * m;
-  const EvalWDyn dyn(P, b, eval_window(P.window, P.kref, b, N, P.Nt), T, true);
+  const EvalWDyn dyn(P, b, eval_window(P.window, P.kref, b, N, P.Nt), T, P.lds_dyn != 0);
   double x = isx ? x0[b * (size_t)n + T] : 0.0;
   for (int k = 0;; ++k) {
     if (isx) Xr[(size_t)k * n + T] = x;
@@ -471,8 +549,7 @@ __global__ void k_eval_score_wide(double* __restrict__ J, double* __restrict__ c
     const bool uon = c.isu && !term;
     const double u = uon ? Ur[(size_t)k * m + T] : 0.0;
     // scorew_knot's terms with the defect between the box and the constraint rows, where it always stood
-    if (isx) s.cost += cost_term(term ? c.wfx : c.wx, x, c.Xf[(size_t)k * n + T]);
-    if (uon) s.cost += cost_term(c.wu, u, c.Uf[(size_t)k * m + T]);
+    s.cost = costw_knot(s.cost, P, c, k, x, u);
     if (k >= P.box_k0 && k <= P.box_k1) {
       s.viol = box_max(s.viol, isx, x, c.xlo, c.xhi);
       s.viol = box_max(s.viol, uon, u, c.ulo, c.uhi);
@@ -481,7 +558,7 @@ __global__ void k_eval_score_wide(double* __restrict__ J, double* __restrict__ c
       const double pred = c.dyn.step(k, x, u);
       if (isx) dfc = eval_max(dfc, fabs(pred - Xr[(size_t)(k + 1) * n + T]));
     }
-    s.viol = conw_max(s.viol, P, c.At, c.bc, c.c0, c.cp, c.isr, T, k, x, u);
+    s.viol = conw_max(s.viol, P, c, k, x, u);
   }
   double Jr, cr;
   score_reduce<64>(s, Jr, cr);

@@ -1,6 +1,7 @@
-// stage_layout.h -- where the arrays of a host twin (altro_batch_evaluate, altro_batch_warm_start, altro_batch_simulate_policy,
-// altro_batch_propagate_covariance) sit in the handle's staging buffer.  Plain host arithmetic, no HIP: altro_batch.hip's StageCursor adds the copies, and
-// tools/stage_layout_check.cpp runs this file alone on the CPU against the sizes and offsets written out by hand.
+// stage_layout.h -- where the arrays of a host twin (altro_batch_eval_policy, altro_batch_evaluate, altro_batch_evaluate_grad,
+// altro_batch_warm_start, altro_batch_simulate_policy, altro_batch_propagate_covariance) sit in the handle's staging buffer.
+// Plain host arithmetic, no HIP: altro_batch.hip's StageCursor adds the copies, and tools/stage_layout_check.cpp runs this
+// file alone on the CPU against the sizes and offsets written out by hand.
 #pragma once
 #include <cassert>
 #include <cstddef>
@@ -41,6 +42,14 @@ struct StageLayout {
 };
 
 // the slots of each twin, in the order of its layout
+enum { EP_X, EP_U, EP_KNOT, EP_FB };
+inline void stage_eval_policy(StageLayout& L, size_t B, size_t n, size_t m, const double* x, const int32_t* knot, double* u, int32_t* fb) {
+  L.add<double>(B * n, x, nullptr, StageLayout::OPTIONAL);   // (x and u are required: the twin has checked them)
+  L.add<double>(B * m, nullptr, u, StageLayout::OPTIONAL);
+  L.add<int32_t>(B, knot, nullptr, StageLayout::RESERVED);
+  L.add<int32_t>(B, nullptr, fb, StageLayout::RESERVED);
+}
+
 enum { EV_J, EV_CMAX, EV_DEFECT, EV_U, EV_X, EV_X0, EV_XOUT };
 inline void stage_evaluate(StageLayout& L, size_t B, size_t N, size_t n, size_t m, size_t ncand, const double* U, const double* X,
                            const double* x0, double* J, double* c_max, double* defect, double* Xout) {

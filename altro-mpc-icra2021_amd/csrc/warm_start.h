@@ -181,7 +181,7 @@ __global__ void k_ws_install_wide(int* __restrict__ chosen, const double* __rest
   const size_t pl = b * 2 + (size_t)cur[b];
   double* Xd = Xp + pl * (size_t)N * n;
   double* Ud = Up + pl * (size_t)(N - 1) * m;
-  const EvalWDyn dyn(P, b, eval_window(P.window, P.kref, b, N, P.Nt), T, true);
+  const EvalWDyn dyn(P, b, eval_window(P.window, P.kref, b, N, P.Nt), T, P.lds_dyn != 0);
   double x = isx ? x0[b * (size_t)n + T] : 0.0;
   for (int k = 0;; ++k) {
     if (isx) Xd[(size_t)k * n + T] = x;

@@ -708,11 +708,16 @@ struct WideBackend : altro::BackendCommon {   // (what both backends hold and do
     p.bcon_istride = con_per_instance ? (size_t)d.N * Pn : 0;
     p.w_pi = w_pi; p.b_pi = b_pi; p.ltv = ltv; p.dyn_pi = dyn_per_instance; p.dyn_blocks = dyn_blocks; p.dyn_stride = dyn_step_stride;
     p.Pn = Pn; p.N = d.N; p.Nt = Nt; p.n = d.n; p.m = d.m; p.kref = kref; p.box_k0 = box_k0; p.box_k1 = box_k1;
-    p.lds_dyn = altro::evalw_lds_fits(d.n, d.m, ltv) ? 1 : 0;
+    p.lds_dyn = altro::evalw_lds_fits(d.n, d.n, d.m, ltv) ? 1 : 0;
     return p;
   }
-  // the LDS a block of their kernels asks for
-  static size_t eval_lds(const altro::EvalW& p) { return p.lds_dyn ? altro::evalw_lds_bytes(p.n, p.m) : 0; }
+  // the LDS a block of their kernels asks for: the wave's dynamics when p.lds_dyn says they are kept there, else 0 ...
+  static size_t eval_lds(const altro::EvalW& p) { return p.lds_dyn ? altro::evalw_lds_bytes(p.n, p.n, p.m) : 0; }
+  // ... and for k_eval_grad_wide, whose slice has the odd leading dimension of its transposed reads and its own rule for fitting
+  static size_t eval_grad_lds(const altro::EvalW& p) {
+    const int ld = altro::evalw_ld(p.n, true);
+    return altro::evalw_lds_fits(ld, p.n, p.m, p.ltv) ? altro::evalw_lds_bytes(ld, p.n, p.m) : 0;
+  }
   // altro_batch_evaluate_dev (evaluate.h; pointers and argument rules checked by the caller, the host twin passes staged
   // copies): the rollout kernel when there is no X, then the scoring kernel on states and controls in memory.  Reads what the
   // next solve would read; writes the caller's outputs and eval_ws only.
@@ -751,10 +756,9 @@ struct WideBackend : altro::BackendCommon {   // (what both backends hold and do
     const size_t R = (size_t)d.batch * ncand;
     if (!Xout) WCHK(pool.reserve(&eval_ws, &eval_ws_elems, R * (size_t)d.N * d.n));
     const altro::EvalW p = eval_params();
-    const bool use_lds = altro::gradw_lds_fits(d.n, d.m, ltv);
+    const size_t lds = eval_grad_lds(p);
     const altro::GradIO io{Ud, x0d ? x0d : x0, Jd, Pd, gUd, gx0d, Xout ? Xout : eval_ws, rho};
-    hipLaunchKernelGGL(altro::k_eval_grad_wide, dim3((unsigned)((R * 64 + 255) / 256)), dim3(256), use_lds ? altro::gradw_lds_bytes(d.n, d.m) : 0,
-                       stream, io, p, ncand, R, use_lds ? 1 : 0);
+    hipLaunchKernelGGL(altro::k_eval_grad_wide, dim3((unsigned)((R * 64 + 255) / 256)), dim3(256), lds, stream, io, p, ncand, R, lds ? 1 : 0);
     WCHK(hipGetLastError());
     return ALTRO_OK;
   }

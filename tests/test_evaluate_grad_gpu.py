@@ -22,6 +22,7 @@ from altro_mpc_icra2021_amd import api, mpc
 import evaluate_ref as ER
 import evaluate_grad_ref as GR
 import test_evaluate_gpu as TE
+import warm_start_ref as WR
 
 pytestmark = pytest.mark.gpu
 INV, STATE = altro._lib.ERR_INVALID_ARG, altro._lib.ERR_STATE
@@ -118,6 +119,40 @@ def test_parity_with_evaluate_and_with_the_yardstick(name):
         assert (y.gUb <= 1e-9 * np.abs(y.gU).max()).all()                 # (bounds of rounding size: a wrong term cannot hide)
     assert same(r.g[0.0].P, r.g[10.0].P) and (r.g[10.0].P[:, 1:3] > 0).any(axis=0).all()
     assert not same(r.g[0.0].gU, r.g[1.0].gU) and not same(r.g[1.0].gU, r.g[10.0].gU)
+
+
+def residual_terms(cs):
+    """how many residuals r one candidate's P = 1/2 sum r^2 has: per constraint and knot of its range, the two sides of every
+    column a box holds there (state columns only at knot N-1), resp. the rows of a LINEAR / SOC block"""
+    return sum(2 * (cs.n if k == cs.N - 1 else cs.n + cs.m) if c.kind == "box" else c.A.shape[2]
+               for c in cs.cons for k in range(c.k0, c.k1 + 1))
+
+
+@pytest.mark.parametrize("name", list(WR.CASES))
+def test_largest_residual_behind_P_is_the_value_behind_c_max(name):
+    """evaluate_dev (rollout form) and evaluate_grad_dev on the same U: c_max is the largest |r| and P = 1/2 sum r^2 over the
+    same rows, so, with NO tolerance, c_max^2 <= 2 P (a sum of rounded non-negative squares never falls below its largest term,
+    the halving is exact): it holds exactly when the largest |r| behind P is bit for bit the value behind c_max.  P == 0
+    exactly where c_max == 0, and 2 P <= T c_max^2 (1 + (T + 2) u) for the T residual terms of the case (each square rounds
+    once, at most T - 1 additions of two non-zero terms).  Not vacuous: at least a third of the rows have c_max > 0."""
+    make, kw = WR.CASES[name]
+    cs = make()
+    U = GR.candidates_with_polar(cs, 5)
+    sv = solver_of(cs, kw)
+    try:
+        J, c, d = TE.ev(sv, U)
+        g = eg(sv, U, rho=10.0, want=(1, 1, 0, 0), Xout=False)
+    finally:
+        sv.close()
+    assert same(g.J, J)
+    assert np.isfinite(c).all() and np.isfinite(g.P).all()
+    c2, P2, Tn = c * c, 2.0 * g.P, residual_terms(cs)
+    print(name, "rows with c_max > 0:", int((c > 0).sum()), "of", c.size, "T", Tn, "min 2P / c_max^2", (P2[c > 0] / c2[c > 0]).min(),
+          "max", (P2[c > 0] / c2[c > 0]).max())
+    assert 3 * int((c > 0).sum()) >= c.size
+    assert (c2 <= P2).all()
+    assert ((g.P == 0.0) == (c == 0.0)).all()
+    assert (P2 <= Tn * c2 * (1.0 + (Tn + 2) * U_)).all()
 
 
 # ---------------------------------------------------------------------------------------------- 2: invariances

@@ -1,8 +1,11 @@
-"""Do two builds of the library score, warm-start, simulate and evaluate the policy to the same bytes?
+"""Do two builds of the library score, differentiate, warm-start, simulate and evaluate the policy to the same bytes (DESIGN.md
+7l, 7q)?
 For each of the two libraries -- the parent's first, then this build's -- one fresh child process (ALTRO_HIP_LIB selects the
 library, as in the other A/B tools) builds the seven cases of tests/evaluate_ref.py plus (12, 4) forced onto the
 one-wave-per-instance backend, solves each once and records SHA-256 of the raw bytes of
   evaluate_dev          given form: J, c_max, defect; rollout form: J, c_max, defect, Xout
+  evaluate_grad_dev     rho 0 and 10, the candidates of evaluate_grad_ref.candidates_with_polar (on the cone case all three
+                        branches of the cone): J, P, gU, gx0, Xout
   warm_start_dev        six candidates + incumbent, rho 0 and 1e3: chosen, J, c_max, the installed states and controls
   simulate_policy_dev   nsamp 3, with and without w, clamp 0 and 1: J, c_max, dx_max, fb, Xout, Uout
   eval_policy_dev       at every knot: u, fb
@@ -24,6 +27,7 @@ def child(path):
     import altro_mpc_icra2021_amd as altro
     from altro_mpc_icra2021_amd import mpc
     import evaluate_ref as ER
+    import evaluate_grad_ref as GR
     import simulate_ref as SR
     import warm_start_ref as WR
     dev = torch.device("cuda", 0)
@@ -56,6 +60,13 @@ def child(path):
         J, c, d = E(B, 3), E(B, 3), E(B, 3)
         altro.evaluate(sv, U3, X=Xo, out=(J, c, d))
         rec(case, "evaluate given", J=J, c_max=c, defect=d)
+        # evaluate_grad_dev, without and with the pullback of the rows
+        Ug = T(GR.candidates_with_polar(cs, 5))
+        nc = Ug.shape[1]
+        for rho in (0.0, 10.0):
+            J, P, gU, g0, Xo = E(B, nc), E(B, nc), E(B, nc, N - 1, m), E(B, nc, n), E(B, nc, N, n)
+            altro.evaluate_grad(sv, Ug, rho=rho, out=(J, P, gU, g0), Xout=Xo)
+            rec(case, "evaluate_grad rho %g" % rho, J=J, P=P, gU=gU, gx0=g0, Xout=Xo)
         # simulate_policy_dev
         x0 = SR.disturbed_starts(Xbar[:, 0], S, 71)
         x0[:, -1] = SR.disturbed_starts(Xbar[:, 0], 1, 72, rel=3.0)[:, 0]

@@ -1,4 +1,4 @@
-// Stand-alone CPU check of csrc/stage_layout.h (DESIGN.md 7l): for every null / non-null combination of the arguments of the
+// Stand-alone CPU check of csrc/stage_layout.h (DESIGN.md 7l, 7q): for every null / non-null combination of the arguments of the
 // host twins, the total size and the offset of every sub-array against the sums altro_batch.hip wrote out by hand
 // before the layout was shared.  No GPU, no library:
 //   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -o /tmp/stage_layout_check \
@@ -34,6 +34,22 @@ int main() {
   const size_t dims[][5] = {{5, 9, 12, 4, 1}, {5, 9, 12, 4, 17}, {2, 4, 64, 32, 3}, {1, 2, 1, 1, 1}, {8192, 50, 12, 4, 8}};
   for (const auto& q : dims) {
     const size_t B = q[0], N = q[1], n = q[2], m = q[3], nc = q[4];
+    // altro_batch_eval_policy: bytes = B (n + m) doubles + 2 B ints either way; x, u, knot, fb; x and u are required
+    for (int c = 0; c < 4; ++c) {
+      const int32_t* kn = c & 1 ? i32 : nullptr;
+      int32_t* fb = c & 2 ? i32 : nullptr;
+      StageLayout L;
+      altro::stage_eval_policy(L, B, n, m, d, kn, d, fb);
+      expect(L.nslots == 4, "eval_policy: slots", c);
+      expect(L.bytes == B * (n + m) * D + 2 * B * I, "eval_policy: size", c);
+      slot_is(L, altro::EP_X, 0, B * n * D, true, D, "eval_policy: x", c);
+      slot_is(L, altro::EP_U, B * n * D, B * m * D, true, D, "eval_policy: u", c);
+      slot_is(L, altro::EP_KNOT, B * (n + m) * D, B * I, kn, I, "eval_policy: knot", c);
+      slot_is(L, altro::EP_FB, B * (n + m) * D + B * I, B * I, fb, I, "eval_policy: fb", c);
+      expect(L.slot[altro::EP_X].in == d && L.slot[altro::EP_KNOT].in == kn && L.slot[altro::EP_U].out == d && L.slot[altro::EP_FB].out == fb &&
+                 !L.slot[altro::EP_X].out && !L.slot[altro::EP_U].in && !L.slot[altro::EP_KNOT].out && !L.slot[altro::EP_FB].in,
+             "eval_policy: copies", c);
+    }
     // altro_batch_evaluate: elems = 3 R + (U ? cu : 0) + (X ? cx : 0) + (x0 ? B n : 0) + (Xout ? cx : 0); J, c_max, defect first
     for (int c = 0; c < 128; ++c) {
       const double *U = c & 1 ? d : nullptr, *X = c & 2 ? d : nullptr, *x0 = c & 4 ? d : nullptr;
