@@ -49,6 +49,7 @@ EXPORTS = [
     "altro_batch_eval_policy_dev", "altro_batch_eval_policy", "altro_batch_get_gains_dev",
     "altro_batch_evaluate_dev", "altro_batch_evaluate",
     "altro_batch_evaluate_grad_dev", "altro_batch_evaluate_grad",
+    "altro_batch_evaluate_al_dev", "altro_batch_evaluate_al", "altro_batch_get_penalty_dev", "altro_batch_get_penalty",
     "altro_batch_warm_start_dev", "altro_batch_warm_start",
     "altro_batch_simulate_policy_dev", "altro_batch_simulate_policy",
     "altro_batch_propagate_covariance_dev", "altro_batch_propagate_covariance",
@@ -74,6 +75,14 @@ class Opts(C.Structure):
         [(k, C.c_double) for k in ("projected_newton_tolerance", "active_set_tolerance_pn", "rho_chol", "rho_primal", "r_threshold")]
 
 
+AL_OUT_FIELDS = ("LA", "J", "gU", "gx0", "gXref", "gUref", "gQ", "gQf", "gR", "gzmin", "gzmax", "Xout")
+
+
+class ALOut(C.Structure):
+    """altro_al_out: twelve nullable pointers (device addresses for the _dev call, host addresses for the host twin)"""
+    _fields_ = [(k, C.c_void_p) for k in AL_OUT_FIELDS]
+
+
 class AltroError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libaltro_hip error {code}: {msg}")
@@ -84,7 +93,7 @@ def build(force=False, verbose=False):
     """Generate the DPP block include and compile the HIP library for gfx950, in tree.  The library is several translation
     units (altro_batch.hip: the C-ABI, the 16-lane kernels, the polish; wide_inst.hip once per group of one-wave-per-instance
     kernels, solve_wide.h ALTRO_WIDE_KERNELS) compiled side by side -- one after the other they take ~6 minutes."""
-    srcs = [os.path.join(CSRC, f) for f in ("altro_batch.hip", "wide_inst.hip", "solve_dpp16.h", "solve_wide.h", "wide_backend.h", "backend_common.h", "launch_ring.h", "pn_core.h", "pn_polish.h", "pn_wide.h", "mpc_log.h", "device_io.h", "device_pool.h", "episode_clock.h", "policy.h", "evaluate.h", "evaluate_grad.h", "warm_start.h", "simulate.h", "covariance.h", "stage_layout.h", "gen_dpp_blocks.py")]
+    srcs = [os.path.join(CSRC, f) for f in ("altro_batch.hip", "wide_inst.hip", "solve_dpp16.h", "solve_wide.h", "wide_backend.h", "backend_common.h", "launch_ring.h", "pn_core.h", "pn_polish.h", "pn_wide.h", "mpc_log.h", "device_io.h", "device_pool.h", "episode_clock.h", "policy.h", "evaluate.h", "evaluate_grad.h", "evaluate_al.h", "warm_start.h", "simulate.h", "covariance.h", "stage_layout.h", "gen_dpp_blocks.py")]
     srcs.append(os.path.join(os.path.dirname(_HERE), "include", "altro_batch.h"))
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):
         return LIB_PATH
@@ -181,6 +190,11 @@ def lib():
     if hasattr(L, "altro_batch_evaluate_grad_dev"):   # gradient of a candidate's merit w.r.t. its controls and initial state
         L.altro_batch_evaluate_grad_dev.argtypes = [H, C.c_int32, C.c_void_p, C.c_void_p, C.c_double] + [C.c_void_p] * 5
         L.altro_batch_evaluate_grad.argtypes = [H, C.c_int32, dp, dp, C.c_double] + [dp] * 5
+    if hasattr(L, "altro_batch_evaluate_al_dev"):   # the solver's augmented Lagrangian, its gradient and data derivatives
+        L.altro_batch_evaluate_al_dev.argtypes = [H, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(ALOut)]
+        L.altro_batch_evaluate_al.argtypes = [H, C.c_int32, dp, dp, C.POINTER(ALOut)]
+        L.altro_batch_get_penalty_dev.argtypes = [H, C.c_void_p]
+        L.altro_batch_get_penalty.argtypes = [H, dp]
     if hasattr(L, "altro_batch_warm_start_dev"):   # warm start from the best of several candidates
         L.altro_batch_warm_start_dev.argtypes = [H, C.c_int32, C.c_void_p, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.altro_batch_warm_start.argtypes = [H, C.c_int32, dp, C.c_double, C.c_int32, ip, dp, dp]

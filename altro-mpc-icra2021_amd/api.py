@@ -1175,6 +1175,160 @@ def merit(solver, U, x0=None, rho=0.0):
     return _merit_function().apply(solver, U, x0, _check_rho(rho, "merit"))
 
 
+def _evaluate_al_shapes(solver, U, name):
+    """(ncand, shape of x0, {output name: shape}) from U by evaluate's rule; U None: the controls the solver holds, one candidate"""
+    B, N, n, m = solver.B, solver.N, solver.n, solver.m
+    if U is None:
+        ncand, lead = 1, (B,)
+    else:
+        ncand, lead = _evaluate_shapes(solver, U, None, None, name)[:2]
+    su, sx = lead + (N - 1, m), lead + (N, n)
+    shapes = dict(LA=lead, J=lead, gU=su, gx0=lead + (n,), gXref=sx, gUref=su, gQ=lead + (n,), gQf=lead + (n,), gR=lead + (m,),
+                  gzmin=lead + (n + m,), gzmax=lead + (n + m,), Xout=sx)
+    return ncand, su, (B, n), shapes
+
+
+def _evaluate_al_out(out, shapes, make, name):
+    """the dict of outputs: out None -> all twelve made new; a sequence of names -> those made new; a dict name -> array (None
+    entries and missing names are skipped)"""
+    if out is None:
+        out = tuple(_lib.AL_OUT_FIELDS)
+    if not isinstance(out, dict):
+        names = tuple(out)
+        if any(not isinstance(k, str) for k in names):
+            raise ValueError(f"{name}: out is a dict of arrays or a sequence of names out of {_lib.AL_OUT_FIELDS}")
+        out = {k: None for k in names}
+        fill = True
+    else:
+        fill = False
+    unknown = [k for k in out if k not in shapes]
+    if unknown:
+        raise ValueError(f"{name}: out: unknown output {unknown[0]!r}; the outputs are {_lib.AL_OUT_FIELDS}")
+    res = {k: (make(shapes[k]) if fill else out[k]) for k in _lib.AL_OUT_FIELDS if k in out and (fill or out[k] is not None)}
+    if not any(k != "Xout" for k in res):
+        raise ValueError(f"{name}: out needs at least one output other than Xout")
+    return res
+
+
+def _al_struct(res, addr):
+    return _lib.ALOut(**{k: (addr(res[k]) if k in res else None) for k in _lib.AL_OUT_FIELDS})
+
+
+def evaluate_al(solver, U=None, x0=None, out=None):
+    """The solver's own augmented Lagrangian L_A(U; lambda, mu) -- the function a solve minimises, with the duals and the penalty
+    the solver holds -- of control sequences, its gradient and its partial derivatives with respect to the problem data
+    (altro_batch_evaluate_al / _dev), as a dict: LA, J; gU = dL_A/dU and gx0 = dL_A/dx0 by one costate sweep; gXref, gUref; gQ, gQf,
+    gR (with respect to the arguments of the tracking objective); gzmin, gzmax (the shadow prices of the box bounds); Xout (the
+    states).  U None: the controls the solver holds -- after a solve gU is then the stationarity residual the solve stopped at,
+    and by the envelope theorem the other derivatives are those of the optimal cost, up to that residual.  U (B, N-1, m) or
+    (B, ncand, N-1, m) as in evaluate; x0 (B, n), None: the solver's initial state.  out: None (all twelve outputs), a sequence
+    of names (those, made new), or a dict name -> array to write into; an output left out costs nothing.  With GPU tensors
+    (float64, contiguous) the call is stream-ordered and nothing synchronises; with numpy the host twin runs: the same bytes.
+    Nothing the solver holds changes."""
+    given = (U, x0) + (tuple(out.values()) if isinstance(out, dict) else ())
+    ncand, su, s0, shapes = _evaluate_al_shapes(solver, U, "evaluate_al")
+    if any(_on_gpu(a) for a in given):
+        if not all(a is None or _on_gpu(a) for a in given):
+            raise ValueError("evaluate_al: U, x0 and the arrays of out must all be GPU tensors (or None), or none of them")
+        import torch
+        dev = torch.device("cuda", solver.device)
+        if U is not None:
+            check_device_tensor(U, su, solver.device, "U")
+        if x0 is not None:
+            check_device_tensor(x0, s0, solver.device, "x0")
+        res = _evaluate_al_out(out, shapes, lambda s: torch.empty(s, dtype=torch.float64, device=dev), "evaluate_al")
+        for k, t in res.items():
+            if not _on_gpu(t):
+                raise ValueError(f"evaluate_al: {k} must be a GPU tensor")
+            check_device_tensor(t, shapes[k], solver.device, k)
+        st = _al_struct(res, lambda t: t.data_ptr())
+        with _bracket(solver):
+            solver._chk(solver._L.altro_batch_evaluate_al_dev(solver.h, ncand, _addr(U), _addr(x0), C.byref(st)))
+        return res
+    U = None if U is None else _c(U)
+    x0 = None if x0 is None else _c(x0)
+    for a, shp, nm in ((U, su, "U"), (x0, s0, "x0")):
+        if a is not None and a.shape != shp:
+            raise ValueError(f"evaluate_al: {nm}: shape {a.shape}, expected {shp}")
+    res = _evaluate_al_out(out, shapes, np.empty, "evaluate_al")
+    for k, a in res.items():
+        if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and a.shape == shapes[k]):
+            raise ValueError(f"evaluate_al: {k} must be a C-contiguous float64 array of shape {shapes[k]}")
+    st = _al_struct(res, lambda a: a.ctypes.data)
+    solver._chk(solver._L.altro_batch_evaluate_al(solver.h, ncand, _p(U), _p(x0), C.byref(st)))
+    return res
+
+
+def penalty(solver, out=None):
+    """the penalty mu of every instance, (B,): the one evaluate_al uses (altro_batch_get_penalty); out = a GPU tensor of that
+    shape: written on the device, stream-ordered, and returned"""
+    if out is not None:
+        if not _on_gpu(out):
+            raise ValueError("penalty: out must be a GPU tensor")
+        check_device_tensor(out, (solver.B,), solver.device, "out")
+        with _bracket(solver):
+            solver._chk(solver._L.altro_batch_get_penalty_dev(solver.h, _addr(out)))
+        return out
+    mu = np.empty(solver.B)
+    solver._chk(solver._L.altro_batch_get_penalty(solver.h, _p(mu)))
+    return mu
+
+
+_optimal_cost_fn = None
+
+
+def _optimal_cost_function():
+    """the torch.autograd.Function behind optimal_cost, made on first use (the package imports without torch)"""
+    global _optimal_cost_fn
+    if _optimal_cost_fn is not None:
+        return _optimal_cost_fn
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class OptimalCost(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, solver, x0, Xref, Uref):
+            # all three validated before the first setter: a refused tensor leaves the solver as it was
+            check_device_tensor(x0, (solver.B, solver.n), solver.device, "x0")
+            check_device_tensor(Xref, (solver.B, solver.N, solver.n), solver.device, "Xref")
+            check_device_tensor(Uref, (solver.B, solver.N - 1, solver.m), solver.device, "Uref")
+            with _bracket(solver):
+                _set_initial_state_dev(solver, x0.detach())
+                _update_trajectory_dev(solver, Xref.detach(), Uref.detach())
+                solver._chk(solver._L.altro_batch_solve_async(solver.h))
+            r = evaluate_al(solver, out={k: torch.empty(s, dtype=torch.float64, device=x0.device) for k, s in
+                                         (("LA", (solver.B,)), ("gx0", (solver.B, solver.n)), ("gXref", (solver.B, solver.N, solver.n)),
+                                          ("gUref", (solver.B, solver.N - 1, solver.m)))})
+            ctx.save_for_backward(r["gx0"], r["gXref"], r["gUref"])
+            return r["LA"]
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad_out):
+            gx0, gXref, gUref = ctx.saved_tensors
+            need = ctx.needs_input_grad
+            return (None, grad_out[:, None] * gx0 if need[1] else None, grad_out[:, None, None] * gXref if need[2] else None,
+                    grad_out[:, None, None] * gUref if need[3] else None)
+
+    _optimal_cost_fn = OptimalCost
+    return OptimalCost
+
+
+def optimal_cost(solver, x0, Xref, Uref):
+    """The cost a solve ends at as a tensor torch can differentiate once with respect to what a learned component produces: the
+    initial state x0 (B, n) and the reference Xref (B, N, n), Uref (B, N-1, m): GPU tensors on the solver's device, float64,
+    contiguous, of exactly these shapes (nothing is cast, copied or moved; a tensor that is not is refused with ValueError before
+    anything is installed, the solver unchanged).  Forward CHANGES THE SOLVER: it
+    installs the three on it (the device setters), solves, and returns L_A (B,) of the controls the solve left, with the duals
+    and the penalty it left (evaluate_al with U None); all of it stream-ordered.  Backward hands grad * gx0, grad * gXref and
+    grad * gUref back.  By the envelope theorem these are the derivatives of the optimal cost min_U L_A, EXACT UP TO THE
+    STATIONARITY RESIDUAL the solve stopped at (gU of evaluate_al(solver): the tolerances of the solver bound it); the duals
+    and the penalty are held fixed, no KKT system is solved."""
+    if not (_on_gpu(x0) and _on_gpu(Xref) and _on_gpu(Uref)):
+        raise ValueError("optimal_cost: x0, Xref and Uref must be GPU tensors")
+    return _optimal_cost_function().apply(solver, x0, Xref, Uref)
+
+
 def rollout(solver, U, x0=None, out=None):
     """rollout!(prob): the states of the model under the controls U from x0 (None: the solver's initial state), on the device
     (the rollout form of altro_batch_evaluate).  U (B, N-1, m) -> X (B, N, n); U (B, ncand, N-1, m) -> X (B, ncand, N, n).  GPU

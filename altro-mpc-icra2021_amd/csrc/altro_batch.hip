@@ -18,6 +18,7 @@
 #include "device_pool.h"
 #include "evaluate.h"
 #include "evaluate_grad.h"
+#include "evaluate_al.h"
 #include "launch_ring.h"
 #include "pn_polish.h"
 #include "policy.h"
@@ -2430,6 +2431,107 @@ int32_t altro_batch_evaluate_grad(altro_handle* h, int32_t ncand, const double* 
                                       sc.f64(altro::EG_GU), sc.f64(altro::EG_GX0), sc.f64(altro::EG_XOUT)))
       return rc;
     return sc.close();
+  });
+}
+
+// ---- the solver's augmented Lagrangian of a control sequence, its gradient and its data derivatives (kernels in
+// evaluate_al.h).  The argument rules both forms share, checked before anything else
+static int evaluate_al_rules(altro_handle* h, const char* fn, int32_t ncand, const double* U, const altro_al_out* out) {
+  const std::string f(fn);
+  if (!out) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": out is required");
+  if (ncand < 1) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": ncand must be at least 1");
+  if (!U && ncand != 1) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": the controls the handle holds (U null) are one candidate: ncand must be 1");
+  if (!out->LA && !out->J && !out->gU && !out->gx0 && !out->gXref && !out->gUref && !out->gQ && !out->gQf && !out->gR && !out->gzmin &&
+      !out->gzmax)
+    FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": every output other than Xout is null");
+  return ALTRO_OK;
+}
+
+// U, x0 and the pointers of o: device arrays (the caller's, validated; or the staged copies of the host twin).  Enqueues one
+// kernel (after the unpack of the held controls into the workspace when U is null); allocates only when the workspace has to grow.
+static int evaluate_al_launch(altro_handle* h, int32_t ncand, const double* U, const double* x0, const altro_al_out& o) {
+  if (h->wide) return fwd(h, h->wide->evaluate_al_dev(ncand, U, x0, o));
+  if (int rc = score_ready(h)) return rc;
+  const size_t B = h->d.batch, N = h->d.N, n = h->d.n, m = h->d.m;
+  const size_t R = B * (size_t)ncand, lx = N * n, lu = (N - 1) * m;
+  const size_t need = (o.Xout ? 0 : R * lx) + (U ? 0 : R * lu);
+  if (need) HIPCHK(h, h->pool.reserve(&h->eval_ws, &h->eval_ws_elems, need));
+  if (!U) {   // the controls held: the current plane, unpacked behind the workspace's states in the caller's layout
+    double* Uw = h->eval_ws + (o.Xout ? 0 : R * lx);
+    if (int rc = get_traj(h, nullptr, Uw, true)) return rc;
+    U = Uw;
+  }
+  const altro::Eval16 p = eval16_params(h);
+  const size_t rows = (R + 3) & ~(size_t)3;   // whole waves of four rows
+  const altro::ALIO io{U, x0 ? x0 : h->x0, o.LA, o.J, o.gU, o.gx0, o.gXref, o.gUref, o.gQ, o.gQf, o.gR, o.gzmin, o.gzmax,
+                       o.Xout ? o.Xout : h->eval_ws, h->Lb, h->Lc, h->mu, h->bslot, h->nbp, 0.5 * h->dt};
+  hipLaunchKernelGGL(altro::k_eval_al16, grid_for(rows * LW), dim3(256), 0, h->stream, io, x0 ? (int)n : LW, p, (int)ncand, R, rows);
+  HIPCHK(h, hipGetLastError());
+  return ALTRO_OK;
+}
+
+int32_t altro_batch_evaluate_al_dev(altro_handle* h, int32_t ncand, const double* U, const double* x0, const altro_al_out* out) {
+  return guard(h, [&]() -> int32_t {
+    DEV_ENTER(h, "altro_batch_evaluate_al_dev");
+    if (int rc = evaluate_al_rules(h, fn_, ncand, U, out)) return rc;
+    const size_t R = B_ * (size_t)ncand, cu = R * (N_ - 1) * m_, cx = R * N_ * n_;
+    DEV_ARG(h, "U", U, cu, double, true);
+    DEV_ARG(h, "x0", x0, B_ * n_, double, true);
+    DEV_ARG(h, "LA", out->LA, R, double, true);
+    DEV_ARG(h, "J", out->J, R, double, true);
+    DEV_ARG(h, "gU", out->gU, cu, double, true);
+    DEV_ARG(h, "gx0", out->gx0, R * n_, double, true);
+    DEV_ARG(h, "gXref", out->gXref, cx, double, true);
+    DEV_ARG(h, "gUref", out->gUref, cu, double, true);
+    DEV_ARG(h, "gQ", out->gQ, R * n_, double, true);
+    DEV_ARG(h, "gQf", out->gQf, R * n_, double, true);
+    DEV_ARG(h, "gR", out->gR, R * m_, double, true);
+    DEV_ARG(h, "gzmin", out->gzmin, R * (n_ + m_), double, true);
+    DEV_ARG(h, "gzmax", out->gzmax, R * (n_ + m_), double, true);
+    DEV_ARG(h, "Xout", out->Xout, cx, double, true);
+    return evaluate_al_launch(h, ncand, U, x0, *out);
+  });
+}
+
+// The host twin (StageCursor)
+int32_t altro_batch_evaluate_al(altro_handle* h, int32_t ncand, const double* U, const double* x0, const altro_al_out* out) {
+  return guard(h, [&]() -> int32_t {
+    if (!h) return dev_null_handle("altro_batch_evaluate_al");
+    if (int rc = evaluate_al_rules(h, "altro_batch_evaluate_al", ncand, U, out)) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    // (readiness before the staging buffer is touched: like the `_dev` form, ALTRO_ERR_STATE allocates and copies nothing)
+    if (int rc = h->wide ? fwd(h, h->wide->eval_ready()) : score_ready(h)) return rc;
+    StageCursor sc(h);
+    double* const po[12] = {out->LA, out->J, out->gU, out->gx0, out->gXref, out->gUref, out->gQ, out->gQf, out->gR, out->gzmin, out->gzmax,
+                            out->Xout};
+    altro::stage_evaluate_al(sc, h->d.batch, h->d.N, h->d.n, h->d.m, ncand, U, x0, po);
+    if (int rc = sc.open()) return rc;
+    const altro_al_out so{sc.f64(altro::AL_LA), sc.f64(altro::AL_J), sc.f64(altro::AL_GU), sc.f64(altro::AL_GX0), sc.f64(altro::AL_GXREF),
+                          sc.f64(altro::AL_GUREF), sc.f64(altro::AL_GQ), sc.f64(altro::AL_GQF), sc.f64(altro::AL_GR), sc.f64(altro::AL_GZMIN),
+                          sc.f64(altro::AL_GZMAX), sc.f64(altro::AL_XOUT)};
+    if (int rc = evaluate_al_launch(h, ncand, sc.f64(altro::AL_U), sc.f64(altro::AL_X0), so)) return rc;
+    return sc.close();
+  });
+}
+
+// the penalty of every instance: the mu altro_batch_evaluate_al uses
+int32_t altro_batch_get_penalty_dev(altro_handle* h, double* mu) {
+  return guard(h, [&]() -> int32_t {
+    DEV_ENTER(h, "altro_batch_get_penalty_dev");
+    DEV_ARG(h, "mu", mu, B_, double, false);
+    HIPCHK(h, hipMemcpyAsync(mu, h->wide ? h->wide->mu : h->mu, B_ * sizeof(double), hipMemcpyDeviceToDevice, common(h).stream));
+    return ALTRO_OK;
+  });
+}
+
+int32_t altro_batch_get_penalty(altro_handle* h, double* mu) {
+  return guard(h, [&]() -> int32_t {
+    if (!h) return dev_null_handle("altro_batch_get_penalty");
+    if (!mu) FAIL(h, ALTRO_ERR_INVALID_ARG, "altro_batch_get_penalty: null pointer");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipMemcpyAsync(mu, h->wide ? h->wide->mu : h->mu, (size_t)h->d.batch * sizeof(double), hipMemcpyDeviceToHost, common(h).stream));
+    HIPCHK(h, hipStreamSynchronize(common(h).stream));
+    return ALTRO_OK;
   });
 }
 

@@ -1,5 +1,5 @@
 // stage_layout.h -- where the arrays of a host twin (altro_batch_eval_policy, altro_batch_evaluate, altro_batch_evaluate_grad,
-// altro_batch_warm_start, altro_batch_simulate_policy, altro_batch_propagate_covariance) sit in the handle's staging buffer.
+// altro_batch_evaluate_al, altro_batch_warm_start, altro_batch_simulate_policy, altro_batch_propagate_covariance) sit in the handle's staging buffer.
 // Plain host arithmetic, no HIP: altro_batch.hip's StageCursor adds the copies, and tools/stage_layout_check.cpp runs this
 // file alone on the CPU against the sizes and offsets written out by hand.
 #pragma once
@@ -22,7 +22,7 @@ struct StageLayout {
     void* out;           // copied back after it, or null
     bool dev;            // the kernels get the sub-array
   };
-  static constexpr int MAX_SLOTS = 10;
+  static constexpr int MAX_SLOTS = 14;
   Slot slot[MAX_SLOTS] = {};
   int nslots = 0;
   size_t bytes = 0;
@@ -74,6 +74,17 @@ inline void stage_evaluate_grad(StageLayout& L, size_t B, size_t N, size_t n, si
   L.add<double>(cu, U, nullptr, StageLayout::OPTIONAL);
   L.add<double>(B * n, x0, nullptr, StageLayout::OPTIONAL);
   L.add<double>(R * N * n, nullptr, Xout, StageLayout::OPTIONAL);
+}
+
+// out[AL_LA .. AL_XOUT]: the twelve pointers of altro_al_out in the order of the struct; every sub-array only when given
+enum { AL_LA, AL_J, AL_GU, AL_GX0, AL_GXREF, AL_GUREF, AL_GQ, AL_GQF, AL_GR, AL_GZMIN, AL_GZMAX, AL_XOUT, AL_U, AL_X0, AL_SLOTS };
+inline void stage_evaluate_al(StageLayout& L, size_t B, size_t N, size_t n, size_t m, size_t ncand, const double* U, const double* x0,
+                              double* const (&out)[12]) {
+  const size_t R = B * ncand, cu = R * (N - 1) * m, cx = R * N * n;
+  const size_t count[12] = {R, R, cu, R * n, cx, cu, R * n, R * n, R * m, R * (n + m), R * (n + m), cx};
+  for (int i = 0; i < 12; ++i) L.add<double>(count[i], nullptr, out[i], StageLayout::OPTIONAL);
+  L.add<double>(cu, U, nullptr, StageLayout::OPTIONAL);
+  L.add<double>(B * n, x0, nullptr, StageLayout::OPTIONAL);
 }
 
 enum { WS_J, WS_CMAX, WS_U, WS_CHOSEN };

@@ -14,6 +14,7 @@
 #include "device_pool.h"
 #include "evaluate.h"
 #include "evaluate_grad.h"
+#include "evaluate_al.h"
 #include "warm_start.h"
 #include "simulate.h"
 #include "launch_ring.h"
@@ -147,6 +148,7 @@ struct WideBackend : altro::BackendCommon {   // (what both backends hold and do
   bool ltv = false;
   std::vector<bool> box_lo_fin, box_hi_fin;   // [n+m] finite sides of the BOX (host copy: polish_prepare, set_bounds)
   int w_pi = 0, b_pi = 0;                     // wd / wf, resp. zmin / zmax, hold one row per instance
+  double cost_dt = 0.0;                       // the dt of altro_batch_set_tracking_cost (evaluate_al_dev: gQ, gR)
   bool w_big = false, b_big = false;          // their device arrays have room for B rows
   struct Block {
     int id, sense, k0, k1, p, per_knot, r0;
@@ -338,6 +340,7 @@ struct WideBackend : altro::BackendCommon {   // (what both backends hold and do
     WCHK(hipMemcpy(wd, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice));
     WCHK(hipMemcpy(wf, Qfd, rows * n * sizeof(double), hipMemcpyHostToDevice));
     w_pi = rows > 1 ? 1 : 0;
+    cost_dt = dt;
     have_cost = true;
     return ALTRO_OK;
   }
@@ -759,6 +762,28 @@ struct WideBackend : altro::BackendCommon {   // (what both backends hold and do
     const size_t lds = eval_grad_lds(p);
     const altro::GradIO io{Ud, x0d ? x0d : x0, Jd, Pd, gUd, gx0d, Xout ? Xout : eval_ws, rho};
     hipLaunchKernelGGL(altro::k_eval_grad_wide, dim3((unsigned)((R * 64 + 255) / 256)), dim3(256), lds, stream, io, p, ncand, R, lds ? 1 : 0);
+    WCHK(hipGetLastError());
+    return ALTRO_OK;
+  }
+  // altro_batch_evaluate_al_dev (evaluate_al.h; pointers and argument rules checked by the caller, the host twin passes staged
+  // copies): one kernel over batch * ncand waves (after the gather of the held controls into the workspace when Ud is null).
+  // Reads what the next solve would read, the duals and the penalty included; writes the caller's outputs and eval_ws only.
+  int evaluate_al_dev(int ncand, const double* Ud, const double* x0d, const altro_al_out& o) {
+    WCHK(hipSetDevice(device));
+    if (int rc = eval_ready()) return rc;
+    const size_t R = (size_t)d.batch * ncand, lx = (size_t)d.N * d.n, lu = (size_t)(d.N - 1) * d.m;
+    const size_t need = (o.Xout ? 0 : R * lx) + (Ud ? 0 : R * lu);
+    if (need) WCHK(pool.reserve(&eval_ws, &eval_ws_elems, need));
+    if (!Ud) {
+      double* Uw = eval_ws + (o.Xout ? 0 : R * lx);
+      if (int rc = get_planes_dev(nullptr, Uw)) return rc;
+      Ud = Uw;
+    }
+    const altro::EvalW p = eval_params();
+    const size_t lds = eval_grad_lds(p);
+    const altro::ALIO io{Ud, x0d ? x0d : x0, o.LA, o.J, o.gU, o.gx0, o.gXref, o.gUref, o.gQ, o.gQf, o.gR, o.gzmin, o.gzmax,
+                         o.Xout ? o.Xout : eval_ws, Lb, Lc, mu, nullptr, 0, 0.5 * cost_dt};
+    hipLaunchKernelGGL(altro::k_eval_al_wide, dim3((unsigned)((R * 64 + 255) / 256)), dim3(256), lds, stream, io, p, ncand, R, lds ? 1 : 0);
     WCHK(hipGetLastError());
     return ALTRO_OK;
   }

@@ -351,6 +351,12 @@ class ExternalMPC:
         differentiates once with respect to U and x0 (api.merit): a pass-through, GPU tensors."""
         return api.merit(self.solver, U, x0=x0, rho=rho)
 
+    def sensitivity(self, **kw):
+        """the solver's augmented Lagrangian of the controls it holds (or of U=...), its stationarity residual gU and the
+        derivatives of the optimal cost with respect to x0, the reference, the cost weights and the box bounds, against the
+        problem the next tick's solve would see (api.evaluate_al): a pass-through, GPU tensors or numpy."""
+        return api.evaluate_al(self.solver, **kw)
+
     def warm_start(self, U, rho=0.0, include_current=True, out=None):
         """(chosen, J, c_max) of api.warm_start: the best of the candidates U (and the trajectory held, when include_current)
         becomes the initial trajectory of the next tick's solve once the solver's stream reaches this point: a pass-through,

@@ -627,6 +627,59 @@ int32_t altro_batch_evaluate_grad_dev(altro_handle* h, int32_t ncand, const doub
 int32_t altro_batch_evaluate_grad(altro_handle* h, int32_t ncand, const double* U, const double* x0, double rho, double* J, double* P,
                                   double* gU, double* gx0, double* Xout);
 
+/* ---- the solver's own augmented Lagrangian L_A(U; lambda, mu) of a control sequence, on the device: the function a solve
+ * minimises, with the multipliers the handle holds (altro_batch_get_duals) and the penalty of every instance
+ * (altro_batch_get_penalty), where altro_batch_evaluate_grad_dev scores a stand-in with zero multipliers.  Three uses: the
+ * stationarity residual dL_A/dU at the trajectory a solve left (an optimality certificate: U == NULL); by the envelope theorem
+ * the derivative of the optimal cost with respect to a problem datum is the partial derivative of L_A at the optimum, so the
+ * same sweep gives dJ-star/dx0, the derivatives with respect to the reference and the cost weights and the shadow prices of the
+ * box bounds -- exact up to that stationarity residual, no KKT solve; and with them a differentiable layer over x0 and the
+ * reference.
+ * altro_batch_evaluate_al_dev: every pointer is a device pointer under the rules of the device-pointer block (validated before
+ * anything is enqueued, stream-ordered, no host synchronisation, no caller pointer kept).  ncand >= 1 candidates per instance:
+ *   U      [batch][ncand][N-1][m]   NULL: the controls the handle holds (ncand must be 1)
+ *   x0     [batch][n]               NULL: the initial state the handle holds
+ *   out    a struct of output pointers, each may be NULL, not all of those other than Xout:
+ *     LA, J        [batch][ncand]
+ *     gU           [batch][ncand][N-1][m]   dL_A/dU
+ *     gx0          [batch][ncand][n]        dL_A/dx0
+ *     gXref        [batch][ncand][N][n]     dL_A/dXref_k = -(w e_x)_k (w = dt Q, Qf at knot N-1): the cost term only
+ *     gUref        [batch][ncand][N-1][m]   dL_A/dUref_k = -(dt R e_u)_k
+ *     gQ, gQf      [batch][ncand][n]        dt/2 sum_{k<N-1} e_x^2;  e_{x,N-1}^2 / 2   (the arguments of altro_batch_set_tracking_cost)
+ *     gR           [batch][ncand][m]        dt/2 sum e_u^2
+ *     gzmin, gzmax [batch][ncand][n+m]      + sum_k g_lo;  - sum_k g_hi; 0 on infinite sides
+ *     Xout         [batch][ncand][N][n]     the states; NULL: the grow-only workspace altro_batch_evaluate_dev uses
+ *   The data derivatives are partial derivatives of L_A per (instance, candidate), also where the handle shares the datum
+ *   across the batch (the derivative with respect to a shared datum is their sum).
+ * Which pointers are NULL changes no other output.  X (Xout) and J are altro_batch_evaluate_dev's bytes.  With e = z - zref:
+ *   L_A = J + sum over every constraint, every knot of its range and every row:
+ *     BOX finite side, value c = z - zmax resp. zmin - z (state columns only at knot N-1), and LINEAR inequality row,
+ *     c = a'z + b, dual l:   l c + [a] mu c^2 / 2 with a = (c >= 0) | (l > 0);   g = l + [a] mu c
+ *     LINEAR equality row:   the same with a = true
+ *     SOC, v = A z + b, duals l:   (|y|^2 - |l|^2) / (2 mu), y = Proj_K(l - mu v)
+ *   pulled back to z as + g on the element (upper side), - g (lower side), a_r g (row), - A' y (cone): c_k their sum, then
+ *     lam_{N-1} = Qf e_x + c_x;  gU_k = dt R e_u + c_u + B_k' lam_{k+1};  lam_k = dt Q e_x + c_x + A_k' lam_{k+1};  gx0 = lam_0.
+ *   It is the oracle's con_cost / cost_expansion.  L_A is once differentiable everywhere: at c == 0 with l == 0 both sides give
+ *   the same g.  Duals on infinite box sides are not read.
+ * The window, the dynamics, the weights, the bounds and the constraint tables are those altro_batch_evaluate_dev sees at that
+ * point of the stream (under an episode clock the instance's own window).  No masking, no status; a NaN stays a NaN.  Nothing
+ * the library owns changes.  Candidate c of instance b gets the bytes it would get alone or on a batch-1 handle holding
+ * instance b's data; x0 == NULL / U == NULL and the held state / altro_batch_get_controls_dev's array passed explicitly give
+ * the same bytes.  Summation orders: csrc/evaluate_al.h.
+ * altro_batch_evaluate_al: the same with host arrays, through the handle's staging buffer; synchronises; the same bytes.
+ * ALTRO_ERR_INVALID_ARG (nothing enqueued, the handle unchanged and usable): NULL handle; NULL out; ncand < 1; U NULL with
+ * ncand != 1; every output other than Xout NULL; _dev: what the device-pointer block refuses.  ALTRO_ERR_STATE: as
+ * altro_batch_evaluate_dev.
+ * altro_batch_get_penalty(_dev): mu [batch], the penalty every instance holds (1 on a new or restarted handle; after a solve
+ * the penalty its last inner solve ran with); _dev is stream-ordered, the host form synchronises. */
+typedef struct altro_al_out {
+  double *LA, *J, *gU, *gx0, *gXref, *gUref, *gQ, *gQf, *gR, *gzmin, *gzmax, *Xout;
+} altro_al_out;
+int32_t altro_batch_evaluate_al_dev(altro_handle* h, int32_t ncand, const double* U, const double* x0, const altro_al_out* out);
+int32_t altro_batch_evaluate_al(altro_handle* h, int32_t ncand, const double* U, const double* x0, const altro_al_out* out);
+int32_t altro_batch_get_penalty_dev(altro_handle* h, double* mu);
+int32_t altro_batch_get_penalty(altro_handle* h, double* mu);
+
 /* ---- warm start from the best of several candidates, chosen on the device.  The closed loops of the reference start every
  * solve from ONE guess (the shifted previous solution: random_linear_problem.jl:136, simple_rocket.jl:160); a loop that also
  * holds the reference controls and a learned or sampled guess wants the best of them, and the 20-step launch lasts as long as

@@ -9,6 +9,7 @@ one-wave-per-instance backend, solves each once and records SHA-256 of the raw b
   warm_start_dev        six candidates + incumbent, rho 0 and 1e3: chosen, J, c_max, the installed states and controls
   simulate_policy_dev   nsamp 3, with and without w, clamp 0 and 1: J, c_max, dx_max, fb, Xout, Uout
   eval_policy_dev       at every knot: u, fb
+  propagate_covariance_dev   W = 0.01 I: sx, su, dJ, fb and, where the case has a box, zmin_t, zmax_t at kappa = 1
 The parent's child ends before the other starts; each has its own time limit; a child that ends abnormally ends the tool and
 nothing more is started.  The result is the table of digests and whether every one is equal; exit status 1 when one differs.
 Usage: gpu_score_bytes_ab.py out.json <parent libaltro_hip.so>"""
@@ -82,6 +83,10 @@ def child(path):
             u, fb = E(B, m), E(B, dtype=torch.int32)
             altro.eval_policy(sv, T(Xbar[:, k] + (x0[:, -1] - Xbar[:, 0])), knot=torch.full((B,), k, dtype=torch.int32, device=dev), clamp=True, out=u, fb=fb)
             rec(case, "eval_policy knot %d" % k, u=u, fb=fb)
+        # propagate_covariance_dev: W = 0.01 I, Sigma0 = 0; the box tightened by one deviation where the case has a box
+        Wc = T(0.01 * np.eye(n))
+        cov = altro.propagate_covariance(sv, None, Wc, None, 1.0 if any(c.kind == "box" for c in cs.cons) else None)
+        rec(case, "propagate_covariance", **cov)
         # warm_start_dev (last: it rewrites the plane)
         U6 = T(WR.six_candidates(cs, Ubar))
         for rho in (0.0, 1e3):

@@ -89,6 +89,27 @@ int main() {
       expect(L.slot[altro::EG_U].in == U && L.slot[altro::EG_X0].in == x0 && L.slot[altro::EG_GU].out == gU && L.slot[altro::EG_XOUT].out == Xo,
              "evaluate_grad: copies", c);
     }
+    // altro_batch_evaluate_al: every one of the fourteen sub-arrays only when given, the twelve outputs of altro_al_out in the
+    // order of the struct, then U, then x0
+    for (int c = 0; c < (1 << 14); ++c) {
+      const size_t R = B * nc, cu = R * (N - 1) * m, cx = R * N * n;
+      const size_t cnt[14] = {R, R, cu, R * n, cx, cu, R * n, R * n, R * m, R * (n + m), R * (n + m), cx, cu, B * n};
+      double* out[12];
+      for (int i = 0; i < 12; ++i) out[i] = (c >> i) & 1 ? d : nullptr;
+      const double *U = (c >> 12) & 1 ? d : nullptr, *x0 = (c >> 13) & 1 ? d : nullptr;
+      StageLayout L;
+      altro::stage_evaluate_al(L, B, N, n, m, nc, U, x0, out);
+      expect(L.nslots == altro::AL_SLOTS && L.nslots <= StageLayout::MAX_SLOTS, "evaluate_al: slots", c);
+      size_t s = 0;
+      for (int i = 0; i < 14; ++i) {
+        const bool on = (c >> i) & 1;
+        slot_is(L, i, s, on ? cnt[i] * D : 0, on, D, "evaluate_al: sub-array", c);
+        s += on ? cnt[i] * D : 0;
+        expect(L.slot[i].out == (i < 12 ? out[i] : nullptr) && L.slot[i].in == (i == 12 ? U : i == 13 ? x0 : nullptr), "evaluate_al: copies", c);
+      }
+      expect(L.bytes == s, "evaluate_al: size", c);
+      expect(altro::AL_LA == 0 && altro::AL_XOUT == 11 && altro::AL_U == 12 && altro::AL_X0 == 13, "evaluate_al: order", c);
+    }
     // altro_batch_warm_start: bytes = (2 R1 + cu) doubles + B ints; J, c_max, U, chosen, all handed to the kernels
     for (int c = 0; c < 16; ++c) {
       const size_t inc = c & 1;
