@@ -586,7 +586,9 @@ struct PnCore {
       R.res[inst] = viol;
       V.P.cost[inst] = J;
       V.P.cmax[inst] = cm;
-      if (cm < ctol) V.P.status[inst] = ALTRO_SOLVE_SUCCEEDED;
+      // (need: the AL stage left UNSOLVED or SOLVE_SUCCEEDED -- judged at ITS tolerance, projected_newton_tolerance.  A polish
+      //  that failed or stopped above constraint_tolerance must not keep that SOLVE_SUCCEEDED: oracle orc_solve)
+      V.P.status[inst] = cm < ctol ? ALTRO_SOLVE_SUCCEEDED : ALTRO_UNSOLVED;
     }
   }
 };

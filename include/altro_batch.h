@@ -138,7 +138,9 @@ typedef struct altro_opts {
    * m <= 32, per-knot dynamics) -- primal projection first, then
    * Altro's multiplier projection (altro_batch_get_polish_dual_residuals).  Inside the device-resident MPC loop
    * (altro_mpc_step_async / altro_mpc_run_async) every step is then a one-step solve kernel followed by the polish kernel:
-   * the next step shifts the polished trajectory and the projected multipliers.
+   * the next step shifts the polished trajectory and the AL duals (the projected multipliers stay inside the polish).
+   * Where the polish ran, the status is SOLVE_SUCCEEDED only if the violation it left is below constraint_tolerance, and
+   * UNSOLVED otherwise (it failed, or stopped above the tolerance) -- whatever the AL stage reported at its looser one.
    * PARITY UNPINNED: the reference stores no polished trajectory. */
   int32_t projected_newton;
   double projected_newton_tolerance;   /* 1e-3 */

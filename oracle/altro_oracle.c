@@ -15,6 +15,7 @@
 #include <string.h>
 
 #define MAXCON 16
+#define ORC_NZ_MAX 96   /* n + m of the largest problem (n <= 64, m <= 32): a BOX evaluates into 2 nz values on the stack */
 
 typedef struct {
   int kind, sense, k0, k1, p, per_knot, nk;
@@ -403,7 +404,7 @@ static void cost_expansion(orc_solver* s) {
       double* lx = s->lx + (size_t)k * n;
       double* lu = s->lu + (size_t)k * m;
       if (c->kind == ORC_BOX) {
-        double cb[2 * 64];
+        double cb[2 * ORC_NZ_MAX];
         con_eval(s, c, k, x, u, cb);
         for (int j = 0; j < nz; ++j) {
           if (j >= n && terminal) continue;
@@ -767,7 +768,7 @@ static void dbg_rejected_trial(orc_solver* s, const double* X, const double* U, 
       ck[k] = l;
     }
   }
-  double cv[2 * 64];
+  double cv[2 * ORC_NZ_MAX];
   for (int ci = 0; ci < s->ncon; ++ci) {
     con_t* c = &s->con[ci];
     int rows = c->p;
@@ -953,7 +954,7 @@ static double* pn_hdiag(const orc_solver* s, int k, double* h) {
 static double pn_row(const orc_solver* s, int ci, int r, int k, const double* x, const double* u, double* E) {
   const con_t* c = &s->con[ci];
   int n = s->n, nz = s->nz, terminal = (k == s->N - 1);
-  double cv[64];
+  double cv[2 * ORC_NZ_MAX];   /* a BOX has 2 nz rows */
   con_eval(s, c, k, x, u, cv);
   if (E) memset(E, 0, nz * sizeof(double));
   if (c->kind == ORC_BOX) {
@@ -1281,7 +1282,7 @@ static int projected_newton(orc_solver* s, double* viol_out) {
   double *lam = dalloc((size_t)N * bm), *res = dalloc((size_t)N * bm), *cor = dalloc((size_t)N * bm), *Sv = dalloc((size_t)N * bm);
   double *tz = dalloc((size_t)N * nz), *dz = dalloc((size_t)N * nz), *dtrial = dalloc((size_t)N * bm);
   for (int k = 0; k < N; ++k) {
-    double h[128];
+    double h[ORC_NZ_MAX];
     pn_hdiag(s, k, h);
     for (int j = 0; j < nz; ++j) w.hinv[(size_t)k * nz + j] = 1.0 / h[j];
   }
@@ -1338,6 +1339,8 @@ static int projected_newton(orc_solver* s, double* viol_out) {
     s->stats.pn_dual_failed = multiplier_projection(s, &w, &r0, &r1);
     s->stats.pn_dual_residual0 = r0;
     s->stats.pn_dual_residual = r1;
+  } else {
+    s->stats.pn_dual_failed = 1;   /* no trajectory to project multipliers at: pn_core.h reports the dual half failed, residuals 0 */
   }
   free(w.nb); free(w.nst); free(w.rcon); free(w.rrow); free(w.E); free(w.dv); free(w.Ld); free(w.Lo); free(w.hinv);
   free(lam); free(res); free(cor); free(Sv); free(tz); free(dz); free(dtrial);
