@@ -835,8 +835,10 @@ def wave_cycles(solver):
 
 def wave_passes(solver):
     """(waves, 8) per wave of the last solve launch (16-lane kernels): column 0 (every build) backward passes run in the
-    pair form; in the -DALTRO_PHASE_STAMPS build also 1-3 four-row passes with 2, 3 and 4 rows needing them, 4-6 their
-    ticks, 7 the ticks of the pair passes."""
+    pair form; columns 1-3 (shipped build, box-only kernels) the open-loop rollouts, closed-loop rollouts and first-order
+    sweeps that ran in the four-row form: bits 0-15 the ones that took the wave-uniform variant, the bits above the ones
+    in the generic form.  The -DALTRO_PHASE_STAMPS build fills instead 1-3 four-row passes with 2, 3 and 4 rows needing
+    them, 4-6 their ticks, 7 the ticks of the pair passes."""
     cnt = C.c_int32(0)
     solver._chk(solver._L.altro_batch_get_wave_passes(solver.h, None, 0, C.byref(cnt)))
     out = np.zeros(cnt.value, dtype=np.int64)

@@ -26,8 +26,10 @@
 //     A row that converges starts its next MPC step in the next turn while its wave-mates keep
 //     iterating, so a row never idles waiting for a slower neighbour (measured before this:
 //     56 wave-iterations per 42 instance-iterations).  Branches are wave-uniform (ballot), so
-//     EXEC is all ones wherever a DPP instruction executes; rows that sit out a phase have their
-//     stores redirected to a trash slot.  Waves never synchronise with each other.
+//     EXEC is all ones wherever a DPP instruction executes; rows that sit out a phase run it as
+//     exact clones of a row that takes part (box-only kernels: clone_flag; same stores, same
+//     values) or have their stores redirected to a trash slot.  Waves never synchronise with
+//     each other.
 //   * row state (costs, tolerances, counters, phase) lives in LDS between phases, so that it
 //     does not occupy VGPRs during the register-hungry backward pass.
 //
@@ -85,6 +87,11 @@
 #endif
 #ifndef ALTRO_PRIO_LAG
 #define ALTRO_PRIO_LAG 0  // measured 4 and 8 on the headline: within run-to-run noise of 0 (off)
+#endif
+#ifndef ALTRO_UNIFORM
+// which phases have a wave-uniform variant (Solver::uniform_phase): bit 0 the open-loop rollout, bit 1 the closed-loop
+// rollout, bit 2 the first-order sweep.  0 compiles the variants out (A/B builds).
+#define ALTRO_UNIFORM 7
 #endif
 #ifndef ALTRO_WAVES_PER_SIMD
 #define ALTRO_WAVES_PER_SIMD 2  // register budget: 512 / this
@@ -290,6 +297,22 @@ __device__ __forceinline__ void stg(double* base, unsigned idx, double v) {
   *reinterpret_cast<double*>(reinterpret_cast<char*>(base) + (idx << 3)) = v;
 }
 
+// The wave-uniform variants of the knot loops (Solver::rollout UNI) access (array + knot's offset)[lane's offset of the phase].
+// p is that uniform first part.  Left to itself the optimiser regroups the sum: the lane's offset is loop-invariant, so it is
+// added to the array FIRST and hoisted as a 64-bit pointer per lane, and the knot's offset then costs a 64-bit VALU add per
+// access.  The empty asm (the idiom of phase_begin and landed: no instruction, no address is written by hand) pins p in an
+// SGPR pair as it is; the access becomes `global_load v, v_lane_offset, s[base:base+1]`.  (readfirstlane is folded away
+// before that regrouping and does not help.)  The other half is lane_offsets_here(): instruction selection works block by
+// block and takes the `base in SGPRs + 32-bit offset in a VGPR` form only where it sees the offset being widened, so the
+// lane's offsets are made opaque once at the top of each loop body -- again no instruction -- and widened there.
+template <class T>
+__device__ __forceinline__ T* uniform_base(T* p) {
+  typedef T __attribute__((address_space(1))) GT;   // (an address of global memory still, not a flat one)
+  GT* g = (GT*)p;
+  asm("" : "+s"(g));
+  return (T*)g;
+}
+
 // 1/x to full FP64 accuracy: v_rcp_f64 + two Newton steps (x > 0, normal range)
 __device__ __forceinline__ double rcp_nr(double x) {
   double y = __builtin_amdgcn_rcp(x);
@@ -458,6 +481,13 @@ struct Solver {
   unsigned wave_slot = 0;
   int turns = 0;           // turns of the wave loop so far
   int n_pair = 0;          // backward passes of this launch that ran as backward_split<2> (altro_batch_get_wave_passes [0])
+  // four-row phases of this launch by form (altro_batch_get_wave_passes [1..3]): open-loop rollouts, closed-loop rollouts,
+  // first-order sweeps -- each word counts the ones that ran as the wave-uniform variant in its low 16 bits and the ones in
+  // the generic form in the bits above.  In LDS: the kernel has no register to spare for them (every lane writes the same word)
+  static __device__ __forceinline__ unsigned* form_words() {
+    __shared__ unsigned w[3];
+    return w;
+  }
   int n_lone = 0;          // backward passes of this launch that ran as backward_split<4> (diagnostic, wave_cycles[7])
   ASet* ah;    // this lane's active set of the backward pass that left the gains in KD (LDS; kept in P.ahash between launches)
   ASet* qhs;   // this lane's active set of the trajectory in Qz (LDS)
@@ -478,6 +508,11 @@ struct Solver {
   };
 
   __device__ Solver(const SolveParams& p, RowState* rows, double* tiles, ASet* hashes) : P(p) {
+    {
+      unsigned zero = 0u;   // (made here: see aset_clear)
+      asm volatile("" : "+v"(zero));
+      form_words()[0] = form_words()[1] = form_words()[2] = zero;
+    }
     lane = threadIdx.x & 63;
     ah = hashes + (threadIdx.x & 63);
     qhs = hashes + 64 + (threadIdx.x & 63);
@@ -579,6 +614,15 @@ struct Solver {
     }
   }
 
+  // lane offsets made opaque at knot k (wave-uniform): see uniform_base()
+  template <int M, int I = 0>
+  static __device__ __forceinline__ void opaque_at(unsigned (&a)[M], int k) {
+    if constexpr (I < M) {
+      asm("" : "+v"(a[I]) : "s"(k));
+      opaque_at<M, I + 1>(a, k);
+    }
+  }
+
   // INSTANCE-MAJOR arrays (DESIGN.md "Data layout"): everything an instance owns in one array is contiguous, row after
   // row of 16 lanes, so a sweep over the knots walks one 128-byte line after the other (one DRAM page, one TLB entry per
   // array) and a row index becomes an address with a shift -- with the knots outermost every knot of every array sat in
@@ -665,7 +709,11 @@ struct Solver {
   // so the backward pass (descending), the rollouts (ascending) and the lone rollouts (four rows at once, each its own
   // knots, into the SAME set: hence the atomic) arrive at the same words.
   static __device__ __forceinline__ void aset_clear(ASet* t) {
-    sfor<0, ASET_WORDS>([&](auto q) { t->w[decltype(q)::value] = 0u; });
+    // (the zero is made here: as a constant it was hoisted to the kernel's entry as a 128-bit vector of zeros, four registers
+    //  held -- and spilled -- for the whole kernel)
+    unsigned zero = 0u;
+    asm volatile("" : "+v"(zero));
+    sfor<0, ASET_WORDS>([&](auto q) { t->w[decltype(q)::value] = zero; });
   }
   static __device__ __forceinline__ void aset_add(ASet* t, unsigned code, int k) {
     atomicOr(&t->w[imin(k >> 4, ASET_WORDS - 1)], code << ((k & 15) * 2));
@@ -758,10 +806,23 @@ struct Solver {
   //   !OPEN: closed-loop rollout with gains KD and step alpha = 1 from plane cur into plane
   //          cur^1 (dead storage for every row that is not iterating, so stores need no mask).
   //          storeq: rows whose gradient plane Qz this rollout refreshes (the rows that are searching).
-  template <bool OPEN>
+  //   UNI  : the wave-uniform variant (box-only kernels; run() chooses it with a wave-uniform test in front of the phase).
+  //          Every lane is a row that takes part or an exact clone of one (clone_flag) and the rows agree on `shift`:
+  //          take = storeq = true, `shift` is a scalar, no store needs a trash slot, and every knot index is k or a clamp
+  //          of k on the scalar unit.  Each access is written as (array + scalar knot offset)[per-lane offset of the phase]:
+  //          the lane's part -- instance, lane, and the plane `cur`, which may differ between rows -- is formed once in
+  //          front of the loop, the knot's part is added to the array's base in SGPRs, and the loop body forms no address
+  //          on the VALU.  Same loads, same arithmetic, same values stored to the same places as the generic form.
+  template <bool OPEN, bool UNI = false>
   __device__ RollOut rollout(bool take, bool shift, bool storeq = false) {
+    static_assert(!UNI || !CONES, "the wave-uniform variant: box-only kernels");
     phase_begin();
     prio_serial();  // latency-bound phase: see ALTRO_PRIO_SERIAL
+    if constexpr (UNI) {
+      take = true;
+      storeq = true;
+      shift = OPEN && (__builtin_amdgcn_readfirstlane(shift ? 1 : 0) != 0);  // (the caller's test: the same on every lane)
+    }
     const LaneConst lc = consts();
     const double mu = rs->mu;
     const int cur = rs->cur, kref = rs->kref;
@@ -801,10 +862,40 @@ struct Solver {
     bool kval[KS] = {};
     if constexpr (!OPEN) gain_slots(kofs, kval);  // slot order of the gain rows, and d in slot 0 of the control lanes
 
+    // UNI: the lane's part of every address of the phase (element offsets of knot 0) and the scalar strides of a knot
+    unsigned u_zs = zs + zat(0), u_zd = zd + zat(0), u_zr = rat(kref), u_lb = lb_at(0, 0), u_qz = qat(0);
+    const unsigned u_nbp = (unsigned)P.nbp;
+    unsigned u_kd[KS] = {};
+    if constexpr (UNI && !OPEN) sfor<0, KS>([&](auto c) { u_kd[decltype(c)::value] = kd_at(0, 0) + kofs[decltype(c)::value]; });
+    auto lane_offsets_here = [&](int k) {   // see uniform_base()
+      if constexpr (UNI) {
+        asm("" : "+v"(u_zs), "+v"(u_zd), "+v"(u_zr), "+v"(u_lb), "+v"(u_qz) : "s"(k));
+        if constexpr (!OPEN) opaque_at(u_kd, k);
+      }
+    };
+    auto sk = [](int k) { return (size_t)((unsigned)k * (unsigned)LW); };                       // a knot's row of 16 lanes
+    auto sl = [&](int k, unsigned side) { return (size_t)(((unsigned)k * 2u + side) * u_nbp); };  // a knot's dual row, one side
+
     // operands of stage knot k (k clamped to 0..N-2 by the callers)
     auto load = [&](int k, KnotIn& in, ConK& ck) {
       const int ku = imin(k + 1, N - 2);
       const int kl = imax(imin(k + 1, k1), 0);
+      if constexpr (UNI) {
+        // (the open-loop rollout reads z on its control lanes only -- stage: zb = is_x ? xb : in.z -- so with `shift` the state
+        //  lanes may load the row one knot ahead as well: the per-lane select of the generic form has nothing left to choose)
+        in.z = ldg(uniform_base(P.Z + sk(shift ? ku : k)), u_zs);
+        in.zr = ldg(uniform_base(P.Zref + sk(k)), u_zr);
+        const int kk = shift ? kl : k;
+        in.lhi = ldg(uniform_base(P.Lb + sl(kk, 0u)), u_lb);
+        in.llo = ldg(uniform_base(P.Lb + sl(kk, 1u)), u_lb);
+        if constexpr (!OPEN) {
+          sfor<0, KS>([&](auto c) { in.kcol[decltype(c)::value] = ldg(uniform_base(P.KD + sk(k) * NU), u_kd[decltype(c)::value]); });
+          if constexpr (!DKD) in.dff = ldg(uniform_base(P.Dff + sk(k)), u_qz);
+        }
+        in.lc = 0.0;
+        in.lcn = 0.0;
+        return;
+      }
       in.z = ldg(P.Z, zs + zat(shu ? ku : k));
       in.zr = ldg(P.Zref, rat(kref + k));
       const int kk = shl ? kl : k;
@@ -832,7 +923,18 @@ struct Solver {
       const bool bx = box_at(k);
       const double lhi = bx ? in.lhi : 0.0, llo = bx ? in.llo : 0.0;
       double zb;
-      if constexpr (OPEN) {
+      if constexpr (OPEN && UNI) {
+        zb = is_x ? xb : in.z;
+        stg(uniform_base(P.Z + sk(k)), u_zd, zb);
+        // The shifted duals go back to knot k from EVERY lane.  A lane without a bound has slot 0 (lslot): it loaded what the
+        // owner of slot 0 loaded, holds the value that lane holds (bx ? in.lhi : 0) and stores it to the address that lane
+        // stores to, in the same instruction -- a clone of it, where the generic form sends it to the trash row.  (No lane
+        // owns slot 0 only when nothing is bounded: the slot then holds zeros and zeros are what is written.)  Without
+        // `shift` every lane writes the trash row, as in the generic form.
+        const int kl_ = shift ? k : P.N;
+        stg(uniform_base(P.Lb + sl(kl_, 0u)), u_lb, lhi);
+        stg(uniform_base(P.Lb + sl(kl_, 1u)), u_lb, llo);
+      } else if constexpr (OPEN) {
         zb = is_x ? xb : in.z;
         stg(P.Z, zat(take ? cur * N + k : 2 * N), zb);
         const int kl_ = wl ? k : P.N;  // knot N of Lb is the trash row
@@ -881,14 +983,16 @@ struct Solver {
         zb = is_x ? xb : ub;
         changed = changed | ((is_x | is_u) & (zb != in.z));
         big = big | ((is_x | is_u) & !(fabs(zb - in.z) <= 1e-7 * (1.0 + fabs(in.z))));
-        stg(P.Z, zd + zat(k), zb);
+        if constexpr (UNI) stg(uniform_base(P.Z + sk(k)), u_zd, zb);
+        else stg(P.Z, zd + zat(k), zb);
       }
       if constexpr (!CONES) {
         double qz;
         unsigned code;
         Jacc += lane_cost_grad<true>(lc, mu, zb, in.zr, lc.wd, OPEN ? lhi : in.lhi, OPEN ? llo : in.llo, bx, viol, qz, code);
         aset_add(tq, code, k);
-        stg(P.Qz, qat(storeq ? k : N), qz);
+        if constexpr (UNI) stg(uniform_base(P.Qz + sk(k)), u_qz, qz);
+        else stg(P.Qz, qat(storeq ? k : N), qz);
       } else {
         Jacc += lane_cost(lc, mu, zb, in.zr, lc.wd, lhi, llo, bx, viol);
       }
@@ -943,6 +1047,7 @@ struct Solver {
     const int ngroups = (N - 1) / PD;
     int k = 0;
     for (int g = 0; g < ngroups; ++g, k += PD) {
+      lane_offsets_here(k);
       sfor<0, PD>([&](auto u) {
         constexpr int U = decltype(u)::value;
         stage(u, k + U, ring[U], cring[U]);
@@ -1745,9 +1850,15 @@ struct Solver {
   // Writes d where store_gains puts it (rows with live: one store per knot, only the NU lanes that change), returns dV and
   // the tiny-feedforward flag of backward().  54 % of the backward passes of the headline workload are of this kind
   // (tools/gpu_reuse_diag.py).
+  // UNI: the wave-uniform variant (see rollout()): live on every lane, the knot's part of each address in SGPRs.  A lane that
+  // is no control lane has no d to store; the generic form sends its zero to the trash block, here it is a clone of control
+  // lane NX + 1 -- the solve for d runs on every lane, it holds that lane's d[1] -- and stores it to that lane's slot.
+  template <bool UNI = false>
   __device__ void fosweep(bool live, double& dV1, double& dV2, bool& dtiny) {
+    static_assert(!UNI || !CONES, "the wave-uniform variant: box-only kernels");
     phase_begin();
     prio_serial();
+    if constexpr (UNI) live = true;
     double g[NX];
     sfor<0, NX>([&](auto c) {
       constexpr int C = decltype(c)::value;
@@ -1763,7 +1874,15 @@ struct Solver {
     struct In {
       double qz, z, kr[NU];
     };
+    unsigned u_qz = qat(0), u_zs = zs + zat(0), u_kd = kd_at(0, 0);   // UNI: the lane's part of the addresses
+    auto sk = [](int k) { return (size_t)((unsigned)k * (unsigned)LW); };      // a knot's row of 16 lanes
     auto load = [&](int k, In& in) {
+      if constexpr (UNI) {
+        in.qz = ldg(uniform_base(P.Qz + sk(k)), u_qz);
+        in.z = ldg(uniform_base(P.Z + sk(k)), u_zs);
+        sfor<0, NU>([&](auto a) { in.kr[decltype(a)::value] = ldg(uniform_base(P.KD + sk(k) * NU) + decltype(a)::value * LW, u_kd); });
+        return;
+      }
       in.qz = ldg(P.Qz, qat(k));
       in.z = ldg(P.Z, zs + zat(k));
       sfor<0, NU>([&](auto a) { in.kr[decltype(a)::value] = ldg(P.KD, kd_at(k, decltype(a)::value)); });
@@ -1778,11 +1897,19 @@ struct Solver {
     // as well -- issued a few instructions earlier, that was a full store round trip per group of PD knots.
     double dst_[PD];
     const unsigned dofs = DKD ? d_ofs() : 0u;
+    // UNI, DKD: where this lane's store of a knot goes inside the knot's gain block -- its own d, or that of lane NX + 1
+    unsigned u_dst = is_u ? u_kd + dofs : u_kd - (unsigned)j + (unsigned)(NX + 1);
     int kst = N;  // first knot of the pending stores (N: none yet -> the trash row)
     sfor<0, PD>([&](auto u) { dst_[decltype(u)::value] = 0.0; });
     auto flush = [&]() {
       sfor<0, PD>([&](auto u) {
         constexpr int U = decltype(u)::value;
+        if constexpr (UNI) {
+          const bool on_s = (kst - U >= 0) & (kst < N);   // scalar
+          if constexpr (DKD) stg(uniform_base(P.KD + sk(on_s ? kst - U : N - 1) * NU), u_dst, dst_[U]);
+          else stg(uniform_base(P.Dff + sk(on_s ? kst - U : N)), u_qz, dst_[U]);
+          return;
+        }
         const bool on = live & (kst - U >= 0) & (kst < N);
         // DKD: a control lane sends its d to its slot of the knot's gain rows, every other lane a zero to the trash block
         if constexpr (DKD) stg(P.KD, kd_at((on & is_u) ? kst - U : N - 1, 0) + dofs, dst_[U]);
@@ -1790,6 +1917,7 @@ struct Solver {
       });
     };
     auto group = [&](In (&cur_)[PD], In (&nxt)[PD]) {
+      if constexpr (UNI) asm("" : "+v"(u_qz), "+v"(u_zs), "+v"(u_kd), "+v"(u_dst) : "s"(k));   // see uniform_base()
       sfor<0, PD>([&](auto u) { load(imax(k - PD - decltype(u)::value, 0), nxt[decltype(u)::value]); });
       landed_in(cur_[0].qz);   // the wait for this group's operands goes here, BEFORE the previous group's stores
       flush();
@@ -1827,6 +1955,7 @@ struct Solver {
           dk[I] = v;
         });
         double t1 = 0.0, dm = 0.0, dl = 0.0;
+        if constexpr (UNI && DKD) dl = -dk[1];   // (the other lanes: clones of control lane NX + 1, see above)
         sfor<0, NU>([&](auto a) {
           constexpr int A = decltype(a)::value;
           dk[A] = -dk[A];
@@ -1954,8 +2083,8 @@ struct Solver {
   // own instance: real loads of operands nobody needs (a fifth of the kernel's HBM traffic).  It now takes the identity of a
   // row that does take part, exactly as in a lone phase: its loads hit the lines that row loads in the same instruction,
   // and what it stores is either that row's values over again (same inputs, same instructions) or goes to that row's
-  // trash slots (its own flags still say "not mine").  Results cannot change: the caller reads a phase's outputs only for
-  // the rows that asked for it.
+  // trash slots (conic kernels: its own flags still say "not mine"; box-only kernels: it takes that row's flags too, see
+  // clone_flag).  Results cannot change: the caller reads a phase's outputs only for the rows that asked for it.
   __device__ __forceinline__ LoneCtx shadow_enter(bool active) {
     LoneCtx c{inst, rowoff, rs, sm, ah, qhs};
     if (P.shadow == 0) return c;
@@ -1972,6 +2101,29 @@ struct Solver {
     //  write the transpose tile of the row they shadow)
     qhs = active ? qhs : c.qhs - lane + lrow * LW + j;
     return c;
+  }
+  // Clones (box-only kernels).  A shadow row used to keep its own flags -- take, shift, storeq, live: "not mine" -- and with
+  // them sent its stores to the trash slots; those per-row flags were the only reason the knot index of every access was a
+  // per-lane value.  It now takes the FLAGS of the row it shadows as well: clone_flag(f, active) is f on a row that takes
+  // part and, on a row that sits out, the f of the row shadow_enter(active) points it at.  Such a row is an exact clone:
+  // the same loads, the same arithmetic, and the same values stored to the same addresses in the same instruction.
+  // Several lanes of one store instruction writing ONE value to ONE address is well defined (whichever lane's write lands
+  // last, the bytes are the same; nothing reads the location in between, the instruction is one memory operation of the
+  // wave), and the ds_or of the active set is idempotent.  What the caller does after the phase stays guarded by the row's
+  // OWN flag.  Without shadow rows (no_shadow), or when no row takes part, the flag is returned as it is.
+  __device__ __forceinline__ bool clone_flag(bool f, bool active) const {
+    if (CONES || P.shadow == 0) return f;
+    const unsigned long long bm = __ballot(active);
+    if (bm == 0ull) return f;
+    const unsigned long long fb = __ballot(f);
+    return active ? f : (((fb >> (first_row(bm) * LW)) & 1ull) != 0ull);
+  }
+  // The wave-uniform test in front of a phase: every lane is a participant or a clone (shadow rows on; the caller has
+  // checked that a row takes part) and the rows agree on the flag f (in effect `shift`; pass false where there is none).
+  __device__ __forceinline__ bool uniform_phase(bool f) const {
+    if (CONES || P.shadow == 0) return false;
+    const unsigned long long fb = __ballot(f);
+    return fb == 0ull || fb == ~0ull;
   }
   // the row of the wave (0..3) a wave-uniform ballot of a per-row flag names, and how many rows it names
   static __device__ __forceinline__ int rows_in(unsigned long long b) {
@@ -2370,8 +2522,17 @@ struct Solver {
               lone_leave(ctx);
             }
           } else {
+            const bool ob_c = clone_flag(ob, ob), shift_c = clone_flag(ob_shift, ob);  // a row that sits out: a clone of one that begins
             const LoneCtx sh = shadow_enter(ob);
-            r0 = rollout<true>(ob, ob_shift, ob);
+            bool uni = false;
+            if constexpr (!CONES && (ALTRO_UNIFORM & 1)) uni = uniform_phase(shift_c);   // (rows disagree when one begins a later AL outer iteration)
+            form_words()[0] += uni ? 1u : 0x10000u;
+            if constexpr (!CONES) {
+              if (uni) r0 = rollout<true, true>(true, shift_c, true);
+              else r0 = rollout<true>(ob_c, shift_c, ob_c);
+            } else {
+              r0 = rollout<true>(ob, ob_shift, ob);
+            }
             lone_leave(sh);
           }
           ALTRO_STAMP(t_ro += stamp() - ts;)
@@ -2478,8 +2639,12 @@ struct Solver {
               double f1, f2;
               bool ft;
               ALTRO_STAMP(long long ts = stamp();)
+              const bool fo_c = clone_flag(fo, fo);
               const LoneCtx sh = shadow_enter(fo);
-              fosweep(fo, f1, f2, ft);
+              const bool uni = (ALTRO_UNIFORM & 4) ? uniform_phase(false) : false;
+              form_words()[2] += uni ? 1u : 0x10000u;
+              if (uni) fosweep<true>(true, f1, f2, ft);
+              else fosweep(fo_c, f1, f2, ft);
               lone_leave(sh);
               ALTRO_STAMP(t_fo += stamp() - ts; c_fo++;)
               if (fo) {
@@ -2549,18 +2714,19 @@ struct Solver {
             } else {
               double b1, b2;
               bool bt;
+              const bool bw_c = clone_flag(bwrow, bwrow);   // `live` of a row that sits out: that of the row it shadows
               const LoneCtx sh = shadow_enter(bwrow);
               // the Qz form of the pass: every row that takes part holds a trajectory a rollout has just produced
               bool useq = false;
               if constexpr (!CONES) useq = (P.useqz != 0) && !with_rho && (P.N <= ASET_MAXN) && !wave_any(bwrow && (rs->qvalid == 0));
               if (o.strict) {
-                if (with_rho) backward<true, true>(b1, b2, fail, bt, bwrow);
-                else if constexpr (!CONES) { if (useq) backward<false, true, true>(b1, b2, fail, bt, bwrow); else backward<false, true>(b1, b2, fail, bt, bwrow); }
-                else backward<false, true>(b1, b2, fail, bt, bwrow);
+                if (with_rho) backward<true, true>(b1, b2, fail, bt, bw_c);
+                else if constexpr (!CONES) { if (useq) backward<false, true, true>(b1, b2, fail, bt, bw_c); else backward<false, true>(b1, b2, fail, bt, bw_c); }
+                else backward<false, true>(b1, b2, fail, bt, bw_c);
               } else {
-                if (with_rho) backward<true, false>(b1, b2, fail, bt, bwrow);
-                else if constexpr (!CONES) { if (useq) backward<false, false, true>(b1, b2, fail, bt, bwrow); else backward<false, false>(b1, b2, fail, bt, bwrow); }
-                else backward<false, false>(b1, b2, fail, bt, bwrow);
+                if (with_rho) backward<true, false>(b1, b2, fail, bt, bw_c);
+                else if constexpr (!CONES) { if (useq) backward<false, false, true>(b1, b2, fail, bt, bw_c); else backward<false, false>(b1, b2, fail, bt, bw_c); }
+                else backward<false, false>(b1, b2, fail, bt, bw_c);
               }
               lone_leave(sh);
               if (bwrow) {
@@ -2660,8 +2826,17 @@ struct Solver {
                 lone_leave(ctx);
               }
             } else {
+              const bool sq_c = clone_flag(searching, searching);
               const LoneCtx sh = shadow_enter(searching);
-              rr = rollout<false>(true, false, searching);
+              bool uni = false;
+              if constexpr (!CONES && (ALTRO_UNIFORM & 2)) uni = uniform_phase(false);
+              form_words()[1] += uni ? 1u : 0x10000u;
+              if constexpr (!CONES) {
+                if (uni) rr = rollout<false, true>(true, false, true);
+                else rr = rollout<false>(true, false, sq_c);
+              } else {
+                rr = rollout<false>(true, false, searching);
+              }
               lone_leave(sh);
             }
             ALTRO_STAMP(t_rc += stamp() - ts; c_rc++;)
@@ -2893,6 +3068,9 @@ __global__ void __launch_bounds__(64, (CONES || NU > 4) ? 1 : ALTRO_WAVES_PER_SI
     // the pass records behind the cycle records and the trace: [wave][8]
     long long* wp = p.wave_cycles + (size_t)gridDim.x * 16 + 4096 + (size_t)blockIdx.x * 8;
     wp[0] = s.n_pair;
+#ifndef ALTRO_PHASE_STAMPS
+    wp[1] = s.form_words()[0]; wp[2] = s.form_words()[1]; wp[3] = s.form_words()[2];
+#endif
     ALTRO_STAMP(wp[1] = s.c_b2; wp[2] = s.c_b3; wp[3] = s.c_b4; wp[4] = s.t_b2; wp[5] = s.t_b3; wp[6] = s.t_b4; wp[7] = s.t_bp;)
 #ifdef ALTRO_PHASE_STAMPS
     {  // which SIMD the wave ran on (HW_ID: simd 5:4, cu 11:8, sh 12, se 15:13; XCC_ID 3:0): who shares a SIMD with whom

@@ -329,9 +329,12 @@ int32_t altro_batch_get_polish_dual_residuals(altro_handle* h, double* before, d
 int32_t altro_batch_get_wave_cycles(altro_handle* h, int64_t* cycles, int32_t capacity, int32_t* count);
 
 /* Pass records of the last solve launch (16-lane kernels), 8 words per wave.  [0] (every build) backward passes that ran
- * in the pair form (two rows of the wave needed one; "no_pair" keeps the four-row form).  Diagnostic builds
- * (-DALTRO_PHASE_STAMPS) also fill [1..3] four-row passes with 2, 3 and 4 rows needing them, [4..6] their ticks and
- * [7] the ticks of the pair passes.  count = 8 * waves; 0 for the one-wave-per-instance backend. */
+ * in the pair form (two rows of the wave needed one; "no_pair" keeps the four-row form).  The shipped build also fills
+ * the four-row phases by form (box-only kernels): [1] open-loop rollouts, [2] closed-loop rollouts, [3] first-order sweeps;
+ * each word holds the ones that ran as the wave-uniform variant in bits 0-15 and the ones that ran in the generic form in
+ * the bits above ("no_shadow": none is uniform).
+ * Diagnostic builds (-DALTRO_PHASE_STAMPS) fill instead [1..3] four-row passes with 2, 3 and 4 rows needing them,
+ * [4..6] their ticks and [7] the ticks of the pair passes.  count = 8 * waves; 0 for the one-wave-per-instance backend. */
 int32_t altro_batch_get_wave_passes(altro_handle* h, int64_t* passes, int32_t capacity, int32_t* count);
 
 /* ---- device-resident MPC harness (reference random_linear_problem.jl:121-139, mpc.jl:11-47).
