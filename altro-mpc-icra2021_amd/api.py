@@ -1331,6 +1331,210 @@ def optimal_cost(solver, x0, Xref, Uref):
     return _optimal_cost_function().apply(solver, x0, Xref, Uref)
 
 
+def get_gain_factors_dev(solver, out=None):
+    """altro_batch_get_gain_factors into a GPU tensor (B, N-1, m, m), stream-ordered and without a host synchronisation:
+    1 / D on the diagonal, L below it, 0 above (Quu = L D L').  Also on the one-wave-per-instance kernels with m <= 16, where
+    gain_factors is not available.  out: the tensor to write into (default: a new one); returned."""
+    import torch
+    shp = (solver.B, solver.N - 1, solver.m, solver.m)
+    if out is None:
+        out = torch.empty(shp, dtype=torch.float64, device=torch.device("cuda", solver.device))
+    if not _on_gpu(out):
+        raise ValueError("get_gain_factors_dev: out must be a GPU tensor")
+    check_device_tensor(out, shp, solver.device, "out")
+    with _bracket(solver):
+        solver._chk(solver._L.altro_batch_get_gain_factors_dev(solver.h, _addr(out)))
+    return out
+
+
+def _sens_kinds(solver):
+    """the trailing shape of every array of solution_vjp / solution_jvp"""
+    sx, su, s0 = (solver.N, solver.n), (solver.N - 1, solver.m), (solver.n,)
+    return dict(gX=sx, gU=su, gx0=s0, gXref=sx, gUref=su, vx0=s0, vXref=sx, vUref=su, dX=sx, dU=su)
+
+
+def _sens_lead(solver, arrs, name):
+    """(nseed, leading shape) from the arrays given ({name: array}): (B,) + trailing shape is one seed per instance (a seed
+    axis is added for the call and dropped from the results), (B, nseed) + trailing shape is nseed of them; all must agree"""
+    kinds = _sens_kinds(solver)
+    lead = None
+    for k, a in arrs.items():
+        if a is None:
+            continue
+        shp, tail = tuple(int(v) for v in a.shape), kinds[k]
+        ok = len(shp) in (1 + len(tail), 2 + len(tail)) and shp[len(shp) - len(tail):] == tail and shp[0] == solver.B
+        if not ok:
+            raise ValueError(f"{name}: {k}: shape {shp}, expected {(solver.B,) + tail} or {(solver.B, 'nseed') + tail}")
+        ld = shp[:len(shp) - len(tail)]
+        if len(ld) == 2 and ld[1] < 1:
+            raise ValueError(f"{name}: {k}: nseed must be at least 1")
+        if lead is not None and ld != lead:
+            raise ValueError(f"{name}: {k}: leading shape {ld}, the other arrays have {lead}")
+        lead = ld
+    return (lead[1] if len(lead) == 2 else 1), lead
+
+
+def _sens_out(out, names, name):
+    """the outputs asked for: None -> all of `names`; a sequence of names; a dict name -> array to write into ('fb' may be among
+    them).  Returns ({name: array or None}, fb or None)"""
+    if out is None:
+        out = names
+    if not isinstance(out, dict):
+        out = {k: None for k in out}
+    out = dict(out)
+    fb = out.pop("fb", None)
+    unknown = [k for k in out if k not in names]
+    if unknown:
+        raise ValueError(f"{name}: out: unknown output {unknown[0]!r}; the outputs are {names} and 'fb'")
+    if not out:
+        raise ValueError(f"{name}: out needs at least one of {names}")
+    return out, fb
+
+
+def _solution_sens(solver, name, ins, out, names, call):
+    """what solution_vjp and solution_jvp share: shapes, the device / host split, the outputs.  call(dev, nseed, ins, res, fb)
+    makes the C call from {name: array or None} dicts whose arrays are addressed by the function it is given."""
+    if all(a is None for a in ins.values()):
+        raise ValueError(f"{name}: at least one of {tuple(ins)} is required")
+    want, fb = _sens_out(out, names, name)
+    given = tuple(ins.values()) + tuple(want.values()) + (fb,)
+    gpu = any(_on_gpu(a) for a in given)
+    if gpu and not all(a is None or _on_gpu(a) for a in given):
+        raise ValueError(f"{name}: the inputs and the arrays of out must all be GPU tensors (or None), or none of them")
+    if not gpu:
+        ins = {k: (None if a is None else _c(a)) for k, a in ins.items()}
+    nseed, lead = _sens_lead(solver, ins, name)
+    kinds = _sens_kinds(solver)
+    if gpu:
+        import torch
+        dev = torch.device("cuda", solver.device)
+        for k, a in ins.items():
+            if a is not None:
+                check_device_tensor(a, lead + kinds[k], solver.device, k)
+        res = {k: (torch.empty(lead + kinds[k], dtype=torch.float64, device=dev) if a is None else a) for k, a in want.items()}
+        for k, t in res.items():
+            check_device_tensor(t, lead + kinds[k], solver.device, k)
+        if fb is None:
+            fb = torch.empty((solver.B,), dtype=torch.int32, device=dev)
+        check_device_tensor(fb, (solver.B,), solver.device, "fb", dtype="torch.int32")
+        with _bracket(solver):
+            solver._chk(call(True, nseed, ins, res, fb, lambda t: None if t is None else t.data_ptr()))
+    else:
+        res = {k: (np.empty(lead + kinds[k]) if a is None else a) for k, a in want.items()}
+        for k, a in res.items():
+            if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and a.shape == lead + kinds[k]):
+                raise ValueError(f"{name}: {k} must be a C-contiguous float64 array of shape {lead + kinds[k]}")
+        if fb is None:
+            fb = np.empty(solver.B, dtype=np.int32)
+        if not (isinstance(fb, np.ndarray) and fb.dtype == np.int32 and fb.flags.c_contiguous and fb.shape == (solver.B,)):
+            raise ValueError(f"{name}: fb must be a C-contiguous int32 array of shape ({solver.B},)")
+        solver._chk(call(False, nseed, ins, res, fb, lambda a: None if a is None else a.ctypes.data))
+    res["fb"] = fb
+    return res
+
+
+def solution_vjp(solver, gX=None, gU=None, out=None):
+    """Reverse-mode sensitivity of the SOLUTION of the last solve through the stored gains (altro_batch_solution_vjp / _dev):
+    for seeds gX = dl/dX* (B, N, n) and gU = dl/dU* (B, N-1, m) -- or (B, nseed, ...) for several seeds per instance; None is
+    zero -- the gradients of l with respect to the initial state and the reference, as a dict: gx0 (B[, nseed], n), gXref,
+    gUref (the shapes of gX, gU), and fb (B,) int32: 1 where the instance holds valid gains of an unregularised backward pass,
+    0 where it does not -- every row of that instance is then NaN.  Exact for the minimiser of the augmented Lagrangian at the
+    multipliers, penalty and active set of the stored pass.  out: None (all three), a sequence of names, or a
+    dict name -> array to write into ('fb' too); an output left out costs nothing (gx0 alone runs one sweep and needs no factors
+    of Quu).  With GPU tensors (float64, contiguous; fb int32) the call is stream-ordered and nothing synchronises; with numpy
+    the host twin runs: the same bytes.  Nothing the solver holds changes."""
+    def call(dev, nseed, ins, res, fb, addr):
+        st = _lib.SensOut(**{k: addr(res.get(k)) for k in _lib.SENS_OUT_FIELDS})
+        if dev:
+            return solver._L.altro_batch_solution_vjp_dev(solver.h, nseed, addr(ins["gX"]), addr(ins["gU"]), C.byref(st), addr(fb))
+        return solver._L.altro_batch_solution_vjp(solver.h, nseed, _p(ins["gX"]), _p(ins["gU"]), C.byref(st), fb.ctypes.data_as(_IP))
+    return _solution_sens(solver, "solution_vjp", dict(gX=gX, gU=gU), out, _lib.SENS_OUT_FIELDS, call)
+
+
+def solution_jvp(solver, vx0=None, vXref=None, vUref=None, out=None):
+    """Forward-mode sensitivity of the SOLUTION of the last solve through the stored gains (altro_batch_solution_jvp / _dev):
+    for tangents vx0 (B, n), vXref (B, N, n), vUref (B, N-1, m) -- or (B, nseed, ...); None is zero -- the directional
+    derivatives of the solution, as a dict: dX, dU (the shapes of vXref, vUref) and fb as in solution_vjp.  vx0 = e_j alone
+    gives dU[:, 0] = column j of the first gain.  out: None (both), a sequence of names, or a dict name -> array ('fb' too).
+    GPU tensors: stream-ordered; numpy: the host twin, the same bytes.  Nothing the solver holds changes."""
+    def call(dev, nseed, ins, res, fb, addr):
+        if dev:
+            return solver._L.altro_batch_solution_jvp_dev(solver.h, nseed, addr(ins["vx0"]), addr(ins["vXref"]), addr(ins["vUref"]),
+                                                          addr(res.get("dX")), addr(res.get("dU")), addr(fb))
+        return solver._L.altro_batch_solution_jvp(solver.h, nseed, _p(ins["vx0"]), _p(ins["vXref"]), _p(ins["vUref"]), _p(res.get("dX")),
+                                                  _p(res.get("dU")), fb.ctypes.data_as(_IP))
+    return _solution_sens(solver, "solution_jvp", dict(vx0=vx0, vXref=vXref, vUref=vUref), out, ("dX", "dU"), call)
+
+
+_solution_fn = None
+
+
+def _solution_function():
+    """the torch.autograd.Function behind solution, made on first use (the package imports without torch)"""
+    global _solution_fn
+    if _solution_fn is not None:
+        return _solution_fn
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class Solution(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, solver, x0, Xref, Uref, invalid):
+            # all three validated before the first setter: a refused tensor leaves the solver as it was
+            check_device_tensor(x0, (solver.B, solver.n), solver.device, "x0")
+            check_device_tensor(Xref, (solver.B, solver.N, solver.n), solver.device, "Xref")
+            check_device_tensor(Uref, (solver.B, solver.N - 1, solver.m), solver.device, "Uref")
+            X = torch.empty((solver.B, solver.N, solver.n), dtype=torch.float64, device=x0.device)
+            U = torch.empty((solver.B, solver.N - 1, solver.m), dtype=torch.float64, device=x0.device)
+            with _bracket(solver):
+                _set_initial_state_dev(solver, x0.detach())
+                _update_trajectory_dev(solver, Xref.detach(), Uref.detach())
+                solver._chk(solver._L.altro_batch_solve_async(solver.h))
+                solver._chk(solver._L.altro_batch_get_states_dev(solver.h, _addr(X)))
+                solver._chk(solver._L.altro_batch_get_controls_dev(solver.h, _addr(U)))
+            # the validity of the gains the backward will go through, read once (x0-only: one sweep, no factors needed)
+            fb = solution_jvp(solver, vx0=torch.zeros_like(x0), out=("dU",))["fb"]
+            bad = (fb == 0).nonzero().flatten().tolist()
+            if bad and invalid != "zero":
+                raise AltroError(_lib.ERR_STATE, f"solution: instances {bad} hold no valid gains of an unregularised backward pass: "
+                                 "the solution is not differentiable through them (invalid='zero' zeroes their gradients)")
+            ctx.solver = solver
+            ctx.bad = (fb == 0) if bad else None
+            return X, U
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, gX, gU):
+            solver, need = ctx.solver, ctx.needs_input_grad
+            names = tuple(k for k, nd in (("gx0", need[1]), ("gXref", need[2]), ("gUref", need[3])) if nd)
+            if not names:
+                return None, None, None, None, None
+            r = solution_vjp(solver, gX.contiguous(), gU.contiguous(), out=names)
+            if ctx.bad is not None:
+                for k in names:
+                    r[k][ctx.bad] = 0.0
+            return None, r.get("gx0"), r.get("gXref"), r.get("gUref"), None
+
+    _solution_fn = Solution
+    return Solution
+
+
+def solution(solver, x0, Xref, Uref, invalid="raise"):
+    """The solution (X, U) of a solve as tensors torch can differentiate once with respect to the initial state x0 (B, n) and
+    the reference Xref (B, N, n), Uref (B, N-1, m): GPU tensors on the solver's device, float64, contiguous, of exactly these
+    shapes (a tensor that is not is refused with ValueError before anything is installed).  Forward CHANGES THE SOLVER: it
+    installs the three on it, solves, and returns the trajectory the solver holds.  Backward is one solution_vjp call through
+    the gains the solve stored: the exact derivative of the minimiser of the augmented Lagrangian at the multipliers, penalty
+    and active set of the last backward pass, so the solver must not be changed between forward and backward.
+    The forward reads the validity of the stored gains once (it synchronises): with an instance that holds none, or whose last
+    pass was regularised, it raises AltroError -- unless invalid="zero", which zeroes the gradient rows of those instances."""
+    if invalid not in ("raise", "zero"):
+        raise ValueError("solution: invalid must be 'raise' or 'zero'")
+    if not (_on_gpu(x0) and _on_gpu(Xref) and _on_gpu(Uref)):
+        raise ValueError("solution: x0, Xref and Uref must be GPU tensors")
+    return _solution_function().apply(solver, x0, Xref, Uref, invalid)
+
+
 def rollout(solver, U, x0=None, out=None):
     """rollout!(prob): the states of the model under the controls U from x0 (None: the solver's initial state), on the device
     (the rollout form of altro_batch_evaluate).  U (B, N-1, m) -> X (B, N, n); U (B, ncand, N-1, m) -> X (B, ncand, N, n).  GPU

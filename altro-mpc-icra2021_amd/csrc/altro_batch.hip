@@ -2756,6 +2756,122 @@ int32_t altro_batch_propagate_covariance(altro_handle* h, const double* Sigma0, 
   });
 }
 
+// ---- sensitivity of the solution through the stored gains (kernels in sensitivity.h)
+// The argument rules the VJP and the JVP share with their twins, checked before anything else.  io: the call's arrays as the
+// kernels name them (VJP: inx = gX, inu = gU, o0 = gx0, ox = gXref, ou = gUref; JVP: inx = vXref, inu = vUref, in0 = vx0,
+// ox = dX, ou = dU).
+static int sens_rules(altro_handle* h, const char* fn, int32_t nseed, const altro::SensIO& io, bool have_out) {
+  const std::string f(fn);
+  if (nseed < 1) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": nseed must be at least 1");
+  if (io.jvp) {
+    if (!io.in0 && !io.inx && !io.inu) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": vx0, vXref and vUref are all null");
+    if (!io.ox && !io.ou) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": dX and dU are both null");
+  } else {
+    if (!io.inx && !io.inu) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": gX and gU are both null");
+    if (!have_out) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": out is required");
+    if (!io.o0 && !io.ox && !io.ou) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": gx0, gXref and gUref are all null");
+  }
+  if (h->wide && h->d.m > 16 && io.bwd && io.fwd)   // (what needs d_k: a seed AND an output of the forward sweep)
+    FAIL(h, ALTRO_ERR_UNSUPPORTED, f + ": the one-wave-per-instance kernels keep no factors of Quu for m > 16: only the x0-only sensitivities "
+                                       "(gx0 alone, vx0 alone) are available");
+  return ALTRO_OK;
+}
+// which sweeps a call needs: the backward one when there is a seed, the forward one when xi or nu is asked for
+static altro::SensIO sens_io(bool jvp, const double* inx, const double* inu, const double* in0, double* o0, double* ox, double* ou, int32_t* fb) {
+  altro::SensIO io{inx, inu, in0, o0, ox, ou, nullptr, fb, jvp ? 1 : 0, 0, 0};
+  io.bwd = (inx || inu) ? 1 : 0;
+  io.fwd = (ox || ou) ? 1 : 0;
+  return io;
+}
+
+// io: device arrays (the caller's, validated; or the staged copies of the host twin).  Enqueues one kernel; allocates only
+// when both sweeps run and the workspace that carries d_k between them has to grow.
+static int sens_launch(altro_handle* h, int32_t nseed, altro::SensIO io) {
+  if (h->wide) return fwd(h, h->wide->solution_sens_dev(nseed, io));
+  if (int rc = score_ready(h)) return rc;
+  const size_t B = h->d.batch, N = h->d.N, m = h->d.m;
+  const size_t R = B * (size_t)nseed;
+  if (io.bwd && io.fwd) {
+    HIPCHK(h, h->pool.reserve(&h->eval_ws, &h->eval_ws_elems, R * (N - 1) * m));
+    io.dws = h->eval_ws;
+  }
+  const size_t rows = (R + 3) & ~(size_t)3;   // whole waves of four rows
+  hipLaunchKernelGGL(altro::k_sens16, grid_for(rows * LW), dim3(256), 0, h->stream, io, h->KD, h->kmu, eval16_params(h), (int)nseed, R, rows);
+  HIPCHK(h, hipGetLastError());
+  return ALTRO_OK;
+}
+
+static int sens_dev(altro_handle* h, const char* fn, int32_t nseed, const altro::SensIO& io, bool have_out) {
+  DEV_ENTER(h, fn);
+  if (int rc = sens_rules(h, fn_, nseed, io, have_out)) return rc;
+  const size_t R = B_ * (size_t)nseed;
+  DEV_ARG(h, io.jvp ? "vXref" : "gX", io.inx, R * N_ * n_, double, true);
+  DEV_ARG(h, io.jvp ? "vUref" : "gU", io.inu, R * (N_ - 1) * m_, double, true);
+  DEV_ARG(h, "vx0", io.in0, R * n_, double, true);
+  DEV_ARG(h, "gx0", io.o0, R * n_, double, true);
+  DEV_ARG(h, io.jvp ? "dX" : "gXref", io.ox, R * N_ * n_, double, true);
+  DEV_ARG(h, io.jvp ? "dU" : "gUref", io.ou, R * (N_ - 1) * m_, double, true);
+  DEV_ARG(h, "fb", io.fb, B_, int32_t, true);
+  return sens_launch(h, nseed, io);
+}
+
+// The host twins (StageCursor)
+static int sens_host(altro_handle* h, const char* fn, int32_t nseed, const altro::SensIO& io, bool have_out) {
+  if (!h) return dev_null_handle(fn);
+  if (int rc = sens_rules(h, fn, nseed, io, have_out)) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  StageCursor sc(h);
+  altro::stage_solution_sens(sc, h->d.batch, h->d.N, h->d.n, h->d.m, nseed, io.inx, io.inu, io.in0, io.o0, io.ox, io.ou, io.fb);
+  if (int rc = sc.open()) return rc;
+  altro::SensIO st = io;
+  st.inx = sc.f64(altro::SS_INX); st.inu = sc.f64(altro::SS_INU); st.in0 = sc.f64(altro::SS_IN0);
+  st.o0 = sc.f64(altro::SS_O0); st.ox = sc.f64(altro::SS_OX); st.ou = sc.f64(altro::SS_OU); st.fb = sc.i32(altro::SS_FB);
+  if (int rc = sens_launch(h, nseed, st)) return rc;
+  return sc.close();
+}
+
+int32_t altro_batch_solution_vjp_dev(altro_handle* h, int32_t nseed, const double* gX, const double* gU, const altro_sens_out* out, int32_t* fb) {
+  return guard(h, [&]() -> int32_t {
+    return sens_dev(h, "altro_batch_solution_vjp_dev", nseed,
+                    sens_io(false, gX, gU, nullptr, out ? out->gx0 : nullptr, out ? out->gXref : nullptr, out ? out->gUref : nullptr, fb), out != nullptr);
+  });
+}
+
+int32_t altro_batch_solution_vjp(altro_handle* h, int32_t nseed, const double* gX, const double* gU, const altro_sens_out* out, int32_t* fb) {
+  return guard(h, [&]() -> int32_t {
+    return sens_host(h, "altro_batch_solution_vjp", nseed,
+                     sens_io(false, gX, gU, nullptr, out ? out->gx0 : nullptr, out ? out->gXref : nullptr, out ? out->gUref : nullptr, fb), out != nullptr);
+  });
+}
+
+int32_t altro_batch_solution_jvp_dev(altro_handle* h, int32_t nseed, const double* vx0, const double* vXref, const double* vUref, double* dX,
+                                     double* dU, int32_t* fb) {
+  return guard(h, [&]() -> int32_t {
+    return sens_dev(h, "altro_batch_solution_jvp_dev", nseed, sens_io(true, vXref, vUref, vx0, nullptr, dX, dU, fb), true);
+  });
+}
+
+int32_t altro_batch_solution_jvp(altro_handle* h, int32_t nseed, const double* vx0, const double* vXref, const double* vUref, double* dX,
+                                 double* dU, int32_t* fb) {
+  return guard(h, [&]() -> int32_t {
+    return sens_host(h, "altro_batch_solution_jvp", nseed, sens_io(true, vXref, vUref, vx0, nullptr, dX, dU, fb), true);
+  });
+}
+
+// altro_batch_get_gain_factors on the device: the unpack that call does in a loop on the host (k_unpack_factors16), resp. the
+// unpack of the packed triangles of the one-wave-per-instance kernels
+int32_t altro_batch_get_gain_factors_dev(altro_handle* h, double* F) {
+  return guard(h, [&]() -> int32_t {
+    DEV_ENTER(h, "altro_batch_get_gain_factors_dev");
+    DEV_ARG(h, "F", F, B_ * (N_ - 1) * m_ * m_, double, false);
+    WIDE_FWD(h, get_gain_factors_dev(F));
+    hipLaunchKernelGGL(altro::k_unpack_factors16, grid_for(B_ * (N_ - 1) * m_ * m_), dim3(256), 0, h->stream, F, h->KD, (int)B_, (int)N_, (int)n_,
+                       (int)m_);
+    HIPCHK(h, hipGetLastError());
+    return ALTRO_OK;
+  });
+}
+
 // ---- per-instance active mask and cold restart
 static int set_active_common(altro_handle* h, const int32_t* active, bool dev) {
   altro::InstanceFlags& fl = common(h).flags;

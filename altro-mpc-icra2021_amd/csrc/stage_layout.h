@@ -1,5 +1,6 @@
 // stage_layout.h -- where the arrays of a host twin (altro_batch_eval_policy, altro_batch_evaluate, altro_batch_evaluate_grad,
-// altro_batch_evaluate_al, altro_batch_warm_start, altro_batch_simulate_policy, altro_batch_propagate_covariance) sit in the handle's staging buffer.
+// altro_batch_evaluate_al, altro_batch_warm_start, altro_batch_simulate_policy, altro_batch_propagate_covariance,
+// altro_batch_solution_vjp, altro_batch_solution_jvp) sit in the handle's staging buffer.
 // Plain host arithmetic, no HIP: altro_batch.hip's StageCursor adds the copies, and tools/stage_layout_check.cpp runs this
 // file alone on the CPU against the sizes and offsets written out by hand.
 #pragma once
@@ -125,6 +126,20 @@ inline void stage_covariance(StageLayout& L, size_t B, size_t N, size_t n, size_
   L.add<double>(B * (n + m), nullptr, zmin_t, StageLayout::OPTIONAL);
   L.add<double>(B * (n + m), nullptr, zmax_t, StageLayout::OPTIONAL);
   L.add<double>(B * N * n * n, nullptr, Sout, StageLayout::OPTIONAL);
+  L.add<int32_t>(B, nullptr, fb, StageLayout::RESERVED);
+}
+
+// altro_batch_solution_vjp / _jvp (one layout: the JVP has no s_0, the VJP no xi_0)
+enum { SS_INX, SS_INU, SS_IN0, SS_O0, SS_OX, SS_OU, SS_FB };
+inline void stage_solution_sens(StageLayout& L, size_t B, size_t N, size_t n, size_t m, size_t nseed, const double* inx, const double* inu,
+                                const double* in0, double* o0, double* ox, double* ou, int32_t* fb) {
+  const size_t R = B * nseed;
+  L.add<double>(R * N * n, inx, nullptr, StageLayout::OPTIONAL);
+  L.add<double>(R * (N - 1) * m, inu, nullptr, StageLayout::OPTIONAL);
+  L.add<double>(R * n, in0, nullptr, StageLayout::OPTIONAL);
+  L.add<double>(R * n, nullptr, o0, StageLayout::OPTIONAL);
+  L.add<double>(R * N * n, nullptr, ox, StageLayout::OPTIONAL);
+  L.add<double>(R * (N - 1) * m, nullptr, ou, StageLayout::OPTIONAL);
   L.add<int32_t>(B, nullptr, fb, StageLayout::RESERVED);
 }
 

@@ -14,6 +14,7 @@
 #include "device_pool.h"
 #include "evaluate.h"
 #include "evaluate_grad.h"
+#include "sensitivity.h"
 #include "evaluate_al.h"
 #include "warm_start.h"
 #include "simulate.h"
@@ -841,6 +842,38 @@ struct WideBackend : altro::BackendCommon {   // (what both backends hold and do
     }
     hipLaunchKernelGGL(altro::k_cov_wide, dim3((unsigned)d.batch), dim3(64), lds, stream, io, cr, Kg, bwst,
                        (gains_valid || debug_keep_gains) ? 1 : 0, eval_params());
+    WCHK(hipGetLastError());
+    return ALTRO_OK;
+  }
+  // altro_batch_solution_vjp_dev / _jvp_dev (sensitivity.h; pointers and argument rules checked by the caller, the host twins
+  // pass staged copies): one kernel over batch * nseed waves.  Reads what the next solve and eval_policy_dev would read and the
+  // factors of Quu; writes the caller's outputs and eval_ws (d_k between the sweeps) only.  m > 16: no factors are kept, so
+  // what needs both sweeps is refused before anything is enqueued.
+  int solution_sens_dev(int nseed, altro::SensIO io) {
+    WCHK(hipSetDevice(device));
+    const bool need_d = io.bwd && io.fwd;
+    if (need_d && d.m > 16)
+      WFAIL(ALTRO_ERR_UNSUPPORTED, "the one-wave-per-instance kernels keep no factors of Quu for m > 16: only the x0-only sensitivities (gx0 alone, vx0 alone) are available");
+    if (int rc = eval_ready()) return rc;
+    const size_t R = (size_t)d.batch * nseed;
+    if (need_d) {
+      WCHK(pool.reserve(&eval_ws, &eval_ws_elems, R * (size_t)(d.N - 1) * d.m));
+      io.dws = eval_ws;
+    }
+    const altro::EvalW p = eval_params();
+    const size_t lds = eval_grad_lds(p);
+    hipLaunchKernelGGL(altro::k_sens_wide, dim3((unsigned)((R * 64 + 255) / 256)), dim3(256), lds, stream, io, Kg, d.m <= 16 ? fac : nullptr,
+                       d.m <= 16 ? wide_fac_size(d.m) : 0, bwst, (gains_valid || debug_keep_gains) ? 1 : 0, p, nseed, R, lds ? 1 : 0);
+    WCHK(hipGetLastError());
+    return ALTRO_OK;
+  }
+  // altro_batch_get_gain_factors_dev: the packed triangles of fac, unpacked in the host getter's convention (m <= 16)
+  int get_gain_factors_dev(double* Fd) {
+    WCHK(hipSetDevice(device));
+    if (d.m > 16) WFAIL(ALTRO_ERR_UNSUPPORTED, "the one-wave-per-instance kernels keep no factors of Quu for m > 16");
+    const size_t thr = (size_t)d.batch * (d.N - 1) * d.m * d.m;
+    hipLaunchKernelGGL(altro::k_unpack_factors_wide, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, stream, Fd, fac, wide_fac_size(d.m), d.batch,
+                       d.N, d.m);
     WCHK(hipGetLastError());
     return ALTRO_OK;
   }

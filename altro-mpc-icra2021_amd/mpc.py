@@ -357,6 +357,16 @@ class ExternalMPC:
         problem the next tick's solve would see (api.evaluate_al): a pass-through, GPU tensors or numpy."""
         return api.evaluate_al(self.solver, **kw)
 
+    def solution_vjp(self, gX=None, gU=None, out=None):
+        """the gradients of a loss on the solution the solver holds with respect to x0 and the reference, through the stored
+        gains (api.solution_vjp): a pass-through, GPU tensors or numpy."""
+        return api.solution_vjp(self.solver, gX=gX, gU=gU, out=out)
+
+    def solution_jvp(self, vx0=None, vXref=None, vUref=None, out=None):
+        """the directional derivatives of the solution the solver holds along tangents of x0 and the reference, through the
+        stored gains (api.solution_jvp): a pass-through, GPU tensors or numpy."""
+        return api.solution_jvp(self.solver, vx0=vx0, vXref=vXref, vUref=vUref, out=out)
+
     def warm_start(self, U, rho=0.0, include_current=True, out=None):
         """(chosen, J, c_max) of api.warm_start: the best of the candidates U (and the trajectory held, when include_current)
         becomes the initial trajectory of the next tick's solve once the solver's stream reaches this point: a pass-through,

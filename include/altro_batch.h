@@ -685,6 +685,55 @@ int32_t altro_batch_evaluate_al(altro_handle* h, int32_t ncand, const double* U,
 int32_t altro_batch_get_penalty_dev(altro_handle* h, double* mu);
 int32_t altro_batch_get_penalty(altro_handle* h, double* mu);
 
+/* ---- sensitivity of the SOLUTION of the last solve, through the stored gains, on the device.  Inside the
+ * active set and penalty of the last backward pass the problem the solve minimised is an LQ problem and the stored gains are
+ * its exact Riccati solution; the derivative of its minimiser (X*, U*) with respect to x0 and the reference is two sweeps with
+ * what the solve left in memory: the gains K_k (altro_batch_get_gains), the factors Quu_k = L D L'
+ * (altro_batch_get_gain_factors_dev) and the dynamics blocks (A_k, B_k) of the window altro_batch_evaluate_dev sees at that
+ * point of the stream.  For g = (gx [N][n], gu [N-1][m]) define  Lin(g, xi_0) -> (s_0, xi, nu):
+ *   backward  s_{N-1} = gx_{N-1};  k = N-2 .. 0:  q_x = gx_k + A_k' s_{k+1},  q_u = gu_k + B_k' s_{k+1},
+ *             d_k = -Quu_k^-1 q_u,  s_k = q_x + K_k' q_u
+ *   forward   xi_0 given;  k = 0 .. N-2:  nu_k = K_k xi_k + d_k,  xi_{k+1} = A_k xi_k + B_k nu_k
+ * With w = dt Q (Qf at knot N-1) and dt R as altro_batch_evaluate_dev applies them (per instance where the handle holds them so):
+ *   altro_batch_solution_vjp_dev (reverse mode): seeds gX = dl/dX*, gU = dl/dU*;  (s_0, xi, nu) = Lin((gX, gU), 0);
+ *     out->gx0 = s_0,  out->gXref_k = -(w xi)_k,  out->gUref_k = -(dt R nu)_k
+ *   altro_batch_solution_jvp_dev (forward mode): tangents vx0, vXref, vUref;  (., xi, nu) = Lin((-w vXref, -dt R vUref), vx0);
+ *     dX = xi,  dU = nu
+ * nseed >= 1 seeds per instance.  gX, vXref, dX, gXref: [batch][nseed][N][n];  gU, vUref, dU, gUref: [batch][nseed][N-1][m];
+ * vx0, gx0: [batch][nseed][n];  fb: [batch] (may be NULL).  A NULL input is zero; any output may be NULL, not all of them.
+ * The result is the exact derivative of the minimiser of the augmented Lagrangian at the multipliers and the penalty of the
+ * stored pass, inside its active set; it differs from the derivative of the constrained optimum by O(1 / mu) on active rows.
+ * For conic handles the gains are those of the last quadratic model (soc_second_order as set).
+ * fb[b] = 1 iff altro_batch_eval_policy_dev would report valid gains AND the stored pass ran without regularisation;
+ * otherwise fb[b] = 0 and every output row of that instance is a quiet NaN.  No masking, no clamp, no status; a NaN stays a
+ * NaN.  Nothing the library owns changes: the stored gains stay, and every later solve, step, counter and log record is that of
+ * a handle that never made the call.  Row (b, s) gets the bytes it would get alone (nseed = 1) or on a batch-1 handle holding
+ * instance b's data; which outputs are NULL changes no other output.  Summation orders: csrc/sensitivity.h.
+ * The _dev forms follow the rules of the device-pointer block (validated before anything is enqueued, stream-ordered behind
+ * the solve that wrote the gains, no host synchronisation, no caller pointer kept); the only allocation is a grow-only
+ * workspace of batch * nseed * (N-1) * m doubles that carries d_k between the sweeps.  The host twins go through the staging
+ * buffer, synchronise and write the same bytes.
+ * ALTRO_ERR_INVALID_ARG (nothing enqueued, the handle unchanged and usable): NULL handle; nseed < 1; vjp: gX and gU both NULL,
+ * out NULL or its three members all NULL; jvp: vx0, vXref and vUref all NULL, or dX and dU both NULL; _dev: what the
+ * device-pointer block refuses.  ALTRO_ERR_STATE: as altro_batch_evaluate_dev.  ALTRO_ERR_UNSUPPORTED (nothing enqueued): the
+ * one-wave-per-instance kernels with m > 16 keep no factors of Quu, so what needs d_k is refused there -- out->gXref,
+ * out->gUref, vXref, vUref; the x0-only paths (gx0 alone; vx0 alone) need K alone and work.
+ * altro_batch_get_gain_factors_dev: F [batch][N-1][m][m] on the device, stream-ordered, in the layout of
+ * altro_batch_get_gain_factors: (a, a) = 1 / D_a, (a, c < a) = L[a][c], 0 above.  16-lane kernels: that call's bytes;
+ * one-wave-per-instance kernels: m <= 16 unpacked from the packed triangles, m > 16 ALTRO_ERR_UNSUPPORTED. */
+typedef struct altro_sens_out {
+  double *gx0, *gXref, *gUref;
+} altro_sens_out;
+int32_t altro_batch_solution_vjp_dev(altro_handle* h, int32_t nseed, const double* gX, const double* gU, const altro_sens_out* out,
+                                     int32_t* fb);
+int32_t altro_batch_solution_vjp(altro_handle* h, int32_t nseed, const double* gX, const double* gU, const altro_sens_out* out,
+                                 int32_t* fb);
+int32_t altro_batch_solution_jvp_dev(altro_handle* h, int32_t nseed, const double* vx0, const double* vXref, const double* vUref,
+                                     double* dX, double* dU, int32_t* fb);
+int32_t altro_batch_solution_jvp(altro_handle* h, int32_t nseed, const double* vx0, const double* vXref, const double* vUref,
+                                 double* dX, double* dU, int32_t* fb);
+int32_t altro_batch_get_gain_factors_dev(altro_handle* h, double* F);
+
 /* ---- warm start from the best of several candidates, chosen on the device.  The closed loops of the reference start every
  * solve from ONE guess (the shifted previous solution: random_linear_problem.jl:136, simple_rocket.jl:160); a loop that also
  * holds the reference controls and a learned or sampled guess wants the best of them, and the 20-step launch lasts as long as

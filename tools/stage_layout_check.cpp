@@ -173,6 +173,27 @@ int main() {
       expect(L.slot[altro::COV_S0].in == S0 && L.slot[altro::COV_W].in == W && L.slot[altro::COV_FB].out == fb && L.slot[altro::COV_SOUT].out == So,
              "covariance: copies", c);
     }
+    // altro_batch_solution_vjp / _jvp: three inputs and three outputs only when given, fb has room either way; fb last (ints)
+    for (int c = 0; c < 128; ++c) {
+      const double *ix = c & 1 ? d : nullptr, *iu = c & 2 ? d : nullptr, *i0 = c & 4 ? d : nullptr;
+      double *o0 = c & 8 ? d : nullptr, *ox = c & 16 ? d : nullptr, *ou = c & 32 ? d : nullptr;
+      int32_t* fb = c & 64 ? i32 : nullptr;
+      const size_t R = B * nc, cx = R * N * n, cu = R * (N - 1) * m, c0 = R * n;
+      StageLayout L;
+      altro::stage_solution_sens(L, B, N, n, m, nc, ix, iu, i0, o0, ox, ou, fb);
+      expect(L.nslots == 7 && L.nslots <= StageLayout::MAX_SLOTS, "solution sens: slots", c);
+      size_t s = 0;
+      slot_is(L, altro::SS_INX, s, ix ? cx * D : 0, ix, D, "solution sens: inx", c); s += ix ? cx * D : 0;
+      slot_is(L, altro::SS_INU, s, iu ? cu * D : 0, iu, D, "solution sens: inu", c); s += iu ? cu * D : 0;
+      slot_is(L, altro::SS_IN0, s, i0 ? c0 * D : 0, i0, D, "solution sens: in0", c); s += i0 ? c0 * D : 0;
+      slot_is(L, altro::SS_O0, s, o0 ? c0 * D : 0, o0, D, "solution sens: o0", c); s += o0 ? c0 * D : 0;
+      slot_is(L, altro::SS_OX, s, ox ? cx * D : 0, ox, D, "solution sens: ox", c); s += ox ? cx * D : 0;
+      slot_is(L, altro::SS_OU, s, ou ? cu * D : 0, ou, D, "solution sens: ou", c); s += ou ? cu * D : 0;
+      slot_is(L, altro::SS_FB, s, B * I, fb, I, "solution sens: fb", c); s += B * I;
+      expect(L.bytes == s, "solution sens: size", c);
+      expect(L.slot[altro::SS_INX].in == ix && L.slot[altro::SS_IN0].in == i0 && L.slot[altro::SS_OU].out == ou && L.slot[altro::SS_FB].out == fb,
+             "solution sens: copies", c);
+    }
   }
   std::printf("stage_layout_check: %ld checks passed\n", checks);
   return 0;
