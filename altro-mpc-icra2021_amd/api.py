@@ -67,6 +67,22 @@ def _on_gpu(a):
     return _is_tensor(a) and a.device.type != "cpu"
 
 
+def _gpu_form(what, args, nreq=0):
+    """Which form of a twin pair the arrays of a call select: True when they are GPU tensors (or None; the first nreq may not be
+    None), the device form; False when none is a GPU tensor, the host twin.  A mix is refused: nothing is converted."""
+    if not any(_on_gpu(a) for a in args):
+        return False
+    if not all(_on_gpu(a) or (a is None and i >= nreq) for i, a in enumerate(args)):
+        raise ValueError(f"{what} must all be GPU tensors (or None), or none of them")
+    return True
+
+
+def _check_np_out(fn, nm, o, shp, dt=np.float64):
+    """o is an array a host twin can write into as it is"""
+    if not (isinstance(o, np.ndarray) and o.dtype == dt and o.flags.c_contiguous and o.shape == shp):
+        raise ValueError(f"{fn}: {nm} must be a C-contiguous {np.dtype(dt).name} array of shape {shp}")
+
+
 def _dense_strides(shape, colmajor=False):
     """element strides of a dense array of `shape`; colmajor: the last two dimensions stored transposed (column-major blocks)"""
     shape = list(shape)
@@ -929,22 +945,17 @@ def eval_policy(solver, x, knot=None, clamp=True, out=None, fb=None):
     With numpy the host twin runs (the same bytes), and fb may be a (B,) int32 array to fill.  fb: 1 feedback applied, 0 no
     valid stored gains (u = u_k), -1 knot outside 0 .. N-2 (device path only: the row of u is left as it was; the host path
     raises).  Returns u."""
-    if _on_gpu(x):
-        if not ((knot is None or _on_gpu(knot)) and (out is None or _on_gpu(out)) and (fb is None or _on_gpu(fb))):
-            raise ValueError("eval_policy: x, knot, out and fb must all be GPU tensors (or None), or none of them")
+    if _gpu_form("eval_policy: x, knot, out and fb", (x, knot, out, fb), nreq=1):
         with _bracket(solver):
             return _eval_policy_dev(solver, x, knot, clamp, out, fb)
-    if _on_gpu(knot) or _on_gpu(out) or _on_gpu(fb):
-        raise ValueError("eval_policy: x, knot, out and fb must all be GPU tensors (or None), or none of them")
     x = _c(x)
     assert x.shape == (solver.B, solver.n)
     kn = None if knot is None else _clock_i32(knot, solver.B, "knot")
     if out is None:
         out = np.empty((solver.B, solver.m))
-    if not (isinstance(out, np.ndarray) and out.dtype == np.float64 and out.flags.c_contiguous and out.shape == (solver.B, solver.m)):
-        raise ValueError(f"eval_policy: out must be a C-contiguous float64 array of shape ({solver.B}, {solver.m})")
-    if fb is not None and not (isinstance(fb, np.ndarray) and fb.dtype == np.int32 and fb.flags.c_contiguous and fb.shape == (solver.B,)):
-        raise ValueError(f"eval_policy: fb must be a C-contiguous int32 array of shape ({solver.B},)")
+    _check_np_out("eval_policy", "out", out, (solver.B, solver.m))
+    if fb is not None:
+        _check_np_out("eval_policy", "fb", fb, (solver.B,), np.int32)
     solver._chk(solver._L.altro_batch_eval_policy(solver.h, _p(x), None if kn is None else kn.ctypes.data_as(_IP), int(bool(clamp)),
                                                   _p(out), None if fb is None else fb.ctypes.data_as(_IP)))
     return out
@@ -1028,9 +1039,7 @@ def evaluate(solver, U=None, X=None, x0=None, out=None, Xout=None):
     With GPU tensors (float64, contiguous) the call is stream-ordered and nothing synchronises; out = (J, c_max, defect) are
     tensors to write into (any may be None, not all; default: three new ones).  With numpy the host twin runs: the same bytes."""
     args = (U, X, x0, Xout) + (tuple(out) if out is not None else ())
-    if any(_on_gpu(a) for a in args):
-        if not all(a is None or _on_gpu(a) for a in args):
-            raise ValueError("evaluate: U, X, x0, Xout and out must all be GPU tensors (or None), or none of them")
+    if _gpu_form("evaluate: U, X, x0, Xout and out", args):
         with _bracket(solver):
             return _evaluate_dev(solver, U, X, x0, out, Xout)
     U = None if U is None else _c(U)
@@ -1048,8 +1057,8 @@ def evaluate(solver, U=None, X=None, x0=None, out=None, Xout=None):
     if len(out) != 3 or all(o is None for o in out):
         raise ValueError("evaluate: out is (J, c_max, defect); any may be None, not all")
     for o, shp, nm in tuple(zip(out, (lead,) * 3, ("J", "c_max", "defect"))) + ((Xout, sx, "Xout"),):
-        if o is not None and not (isinstance(o, np.ndarray) and o.dtype == np.float64 and o.flags.c_contiguous and o.shape == shp):
-            raise ValueError(f"evaluate: {nm} must be a C-contiguous float64 array of shape {shp}")
+        if o is not None:
+            _check_np_out("evaluate", nm, o, shp)
     solver._chk(solver._L.altro_batch_evaluate(solver.h, ncand, _p(U), _p(X), _p(x0), _p(out[0]), _p(out[1]), _p(out[2]), _p(Xout)))
     return out
 
@@ -1110,9 +1119,7 @@ def evaluate_grad(solver, U, x0=None, rho=0.0, out=None, Xout=None):
     With GPU tensors (float64, contiguous) the call is stream-ordered and nothing synchronises; out = (J, P, gU, gx0) are
     tensors to write into (any may be None, not all; default: four new ones).  With numpy the host twin runs: the same bytes."""
     args = (U, x0, Xout) + (tuple(out) if out is not None else ())
-    if any(_on_gpu(a) for a in args):
-        if not all(a is None or _on_gpu(a) for a in args):
-            raise ValueError("evaluate_grad: U, x0, Xout and out must all be GPU tensors (or None), or none of them")
+    if _gpu_form("evaluate_grad: U, x0, Xout and out", args):
         with _bracket(solver):
             return _evaluate_grad_dev(solver, U, x0, rho, out, Xout)
     U = None if U is None else _c(U)
@@ -1127,8 +1134,8 @@ def evaluate_grad(solver, U, x0=None, rho=0.0, out=None, Xout=None):
         out = tuple(np.empty(s) for s in shapes)
     out = _evaluate_grad_out(out, "evaluate_grad")
     for o, shp, nm in tuple(zip(out, shapes, ("J", "P", "gU", "gx0"))) + ((Xout, sx, "Xout"),):
-        if o is not None and not (isinstance(o, np.ndarray) and o.dtype == np.float64 and o.flags.c_contiguous and o.shape == shp):
-            raise ValueError(f"evaluate_grad: {nm} must be a C-contiguous float64 array of shape {shp}")
+        if o is not None:
+            _check_np_out("evaluate_grad", nm, o, shp)
     solver._chk(solver._L.altro_batch_evaluate_grad(solver.h, ncand, _p(U), _p(x0), rho, _p(out[0]), _p(out[1]), _p(out[2]), _p(out[3]),
                                                     _p(Xout)))
     return out
@@ -1229,9 +1236,7 @@ def evaluate_al(solver, U=None, x0=None, out=None):
     Nothing the solver holds changes."""
     given = (U, x0) + (tuple(out.values()) if isinstance(out, dict) else ())
     ncand, su, s0, shapes = _evaluate_al_shapes(solver, U, "evaluate_al")
-    if any(_on_gpu(a) for a in given):
-        if not all(a is None or _on_gpu(a) for a in given):
-            raise ValueError("evaluate_al: U, x0 and the arrays of out must all be GPU tensors (or None), or none of them")
+    if _gpu_form("evaluate_al: U, x0 and the arrays of out", given):
         import torch
         dev = torch.device("cuda", solver.device)
         if U is not None:
@@ -1254,8 +1259,7 @@ def evaluate_al(solver, U=None, x0=None, out=None):
             raise ValueError(f"evaluate_al: {nm}: shape {a.shape}, expected {shp}")
     res = _evaluate_al_out(out, shapes, np.empty, "evaluate_al")
     for k, a in res.items():
-        if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and a.shape == shapes[k]):
-            raise ValueError(f"evaluate_al: {k} must be a C-contiguous float64 array of shape {shapes[k]}")
+        _check_np_out("evaluate_al", k, a, shapes[k])
     st = _al_struct(res, lambda a: a.ctypes.data)
     solver._chk(solver._L.altro_batch_evaluate_al(solver.h, ncand, _p(U), _p(x0), C.byref(st)))
     return res
@@ -1398,9 +1402,7 @@ def _solution_sens(solver, name, ins, out, names, call):
         raise ValueError(f"{name}: at least one of {tuple(ins)} is required")
     want, fb = _sens_out(out, names, name)
     given = tuple(ins.values()) + tuple(want.values()) + (fb,)
-    gpu = any(_on_gpu(a) for a in given)
-    if gpu and not all(a is None or _on_gpu(a) for a in given):
-        raise ValueError(f"{name}: the inputs and the arrays of out must all be GPU tensors (or None), or none of them")
+    gpu = _gpu_form(f"{name}: the inputs and the arrays of out", given)
     if not gpu:
         ins = {k: (None if a is None else _c(a)) for k, a in ins.items()}
     nseed, lead = _sens_lead(solver, ins, name)
@@ -1422,12 +1424,10 @@ def _solution_sens(solver, name, ins, out, names, call):
     else:
         res = {k: (np.empty(lead + kinds[k]) if a is None else a) for k, a in want.items()}
         for k, a in res.items():
-            if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and a.shape == lead + kinds[k]):
-                raise ValueError(f"{name}: {k} must be a C-contiguous float64 array of shape {lead + kinds[k]}")
+            _check_np_out(name, k, a, lead + kinds[k])
         if fb is None:
             fb = np.empty(solver.B, dtype=np.int32)
-        if not (isinstance(fb, np.ndarray) and fb.dtype == np.int32 and fb.flags.c_contiguous and fb.shape == (solver.B,)):
-            raise ValueError(f"{name}: fb must be a C-contiguous int32 array of shape ({solver.B},)")
+        _check_np_out(name, "fb", fb, (solver.B,), np.int32)
         solver._chk(call(False, nseed, ins, res, fb, lambda a: None if a is None else a.ctypes.data))
     res["fb"] = fb
     return res
@@ -1628,9 +1628,7 @@ def simulate_policy(solver, x0=None, w=None, nsamp=None, clamp=True, out=None, f
     dx_max) are tensors to write into (any may be None; default: three new ones).  With numpy -- or with no array at all --
     the host twin runs: the same bytes."""
     args = (x0, w, fb, Xout, Uout) + (tuple(out) if out is not None else ())
-    if any(_on_gpu(a) for a in args):
-        if not all(a is None or _on_gpu(a) for a in args):
-            raise ValueError("simulate_policy: x0, w, out, fb, Xout and Uout must all be GPU tensors (or None), or none of them")
+    if _gpu_form("simulate_policy: x0, w, out, fb, Xout and Uout", args):
         with _bracket(solver):
             return _simulate_policy_dev(solver, x0, w, nsamp, clamp, out, fb, Xout, Uout)
     x0 = None if x0 is None else _c(x0)
@@ -1648,8 +1646,8 @@ def simulate_policy(solver, x0=None, w=None, nsamp=None, clamp=True, out=None, f
         raise ValueError("simulate_policy: J, c_max, dx_max, fb, Xout and Uout are all None")
     for o, shp, dt, nm in zip(out + (fb, Xout, Uout), (lead,) * 3 + ((solver.B,), sx, su), (np.float64,) * 3 + (np.int32, np.float64, np.float64),
                               ("J", "c_max", "dx_max", "fb", "Xout", "Uout")):
-        if o is not None and not (isinstance(o, np.ndarray) and o.dtype == dt and o.flags.c_contiguous and o.shape == shp):
-            raise ValueError(f"simulate_policy: {nm} must be a C-contiguous {np.dtype(dt).name} array of shape {shp}")
+        if o is not None:
+            _check_np_out("simulate_policy", nm, o, shp, dt)
     solver._chk(solver._L.altro_batch_simulate_policy(solver.h, ns, _p(x0), _p(w), int(bool(clamp)), _p(out[0]), _p(out[1]), _p(out[2]),
                                                       None if fb is None else fb.ctypes.data_as(_IP), _p(Xout), _p(Uout)))
     return out
@@ -1729,9 +1727,7 @@ def propagate_covariance(solver, Sigma0=None, W=None, con_id=None, kappa=None, o
     changes.  With GPU tensors (float64, contiguous; fb int32) the call is stream-ordered and nothing synchronises; with numpy
     the host twin runs: the same bytes.  Nothing is converted: a mix of the two is refused."""
     args = (Sigma0, W) + (tuple(out.values()) if isinstance(out, dict) else ())
-    if any(_on_gpu(a) for a in args):
-        if not all(a is None or _on_gpu(a) for a in args):
-            raise ValueError("propagate_covariance: Sigma0, W and the arrays of out must all be GPU tensors (or None), or none of them")
+    if _gpu_form("propagate_covariance: Sigma0, W and the arrays of out", args):
         with _bracket(solver):
             return _propagate_covariance_dev(solver, Sigma0, W, con_id, kappa, out)
     for a, nm in ((Sigma0, "Sigma0"), (W, "W")):
@@ -1741,9 +1737,7 @@ def propagate_covariance(solver, Sigma0=None, W=None, con_id=None, kappa=None, o
     if out is None:
         out = {k: np.empty(shapes[k], dtype=np.int32 if k == "fb" else np.float64) for k in default}
     for k, o in out.items():
-        dt = np.int32 if k == "fb" else np.float64
-        if not (isinstance(o, np.ndarray) and o.dtype == dt and o.flags.c_contiguous and o.shape == shapes[k]):
-            raise ValueError(f"propagate_covariance: {k} must be a C-contiguous {np.dtype(dt).name} array of shape {shapes[k]}")
+        _check_np_out("propagate_covariance", k, o, shapes[k], np.int32 if k == "fb" else np.float64)
     ptr = lambda k: None if k not in out else out[k].ctypes.data_as(_IP) if k == "fb" else _p(out[k])
     solver._chk(solver._L.altro_batch_propagate_covariance(solver.h, _p(Sigma0), _p(W), pi, cid, kap, *(ptr(k) for k in COV_OUTPUTS)))
     return out
@@ -1804,9 +1798,7 @@ def warm_start(solver, U, rho=0.0, include_current=True, out=None):
     synchronises; out = (chosen, J, c_max) are tensors to write into (any may be None; default: three new ones).  With numpy
     the host twin runs: the same bytes."""
     args = (U,) + (tuple(out) if out is not None else ())
-    if any(_on_gpu(a) for a in args):
-        if not all(a is None or _on_gpu(a) for a in args):
-            raise ValueError("warm_start: U and out must all be GPU tensors (or None), or none of them")
+    if _gpu_form("warm_start: U and out", args):
         with _bracket(solver):
             return _warm_start_dev(solver, U, rho, include_current, out)
     U = None if U is None else _c(U)
@@ -1819,8 +1811,8 @@ def warm_start(solver, U, rho=0.0, include_current=True, out=None):
     if len(out) != 3:
         raise ValueError("warm_start: out is (chosen, J, c_max); any may be None")
     for o, shp, dt, nm in zip(out, ((solver.B,), lead, lead), (np.int32, np.float64, np.float64), ("chosen", "J", "c_max")):
-        if o is not None and not (isinstance(o, np.ndarray) and o.dtype == dt and o.flags.c_contiguous and o.shape == shp):
-            raise ValueError(f"warm_start: {nm} must be a C-contiguous {np.dtype(dt).name} array of shape {shp}")
+        if o is not None:
+            _check_np_out("warm_start", nm, o, shp, dt)
     ch = None if out[0] is None else out[0].ctypes.data_as(_IP)
     solver._chk(solver._L.altro_batch_warm_start(solver.h, ncand, _p(U), rho, 1 if include_current else 0, ch, _p(out[1]), _p(out[2])))
     return out

@@ -2189,14 +2189,23 @@ int32_t altro_batch_get_dev_refusals(altro_handle* h, int64_t* rows) {
   });
 }
 
-// The arrays of a host twin in the staging buffer of whichever backend the handle runs on (their layout: stage_layout.h).
-// open() makes room and copies in what the caller passed, f64() / i32() are what the launch gets, close() copies the outputs back and
-// synchronises once: the SAME kernels run on the staged copies, so the bytes are those of the `_dev` call by construction.
-struct StageCursor : altro::StageLayout {
+// ---- host/device twin pairs: a `_dev` form on the caller's device arrays and a host twin on host arrays
+// The array arguments of one call of either form, as the pair's table names them (stage_layout.h).  f64() / i32() are what the launch
+// gets.  `_dev` form: validate() checks every pointer against its extent, and the launch gets the caller's own pointers.  Host twin:
+// open() makes room in the staging buffer of whichever backend the handle runs on and copies in what the caller passed, the launch
+// gets the staged sub-arrays, close() copies the outputs back and synchronises once: the SAME kernels run on the staged copies, so
+// the bytes are those of the `_dev` call by construction.
+struct TwinArgs : altro::StageLayout {
   altro_handle* h;
+  const bool host;
   hipStream_t st = nullptr;
   char* base = nullptr;
-  explicit StageCursor(altro_handle* h_) : h(h_) {}
+  TwinArgs(altro_handle* h_, bool host_) : h(h_), host(host_) {}
+  int validate(const char* fn) {
+    for (int i = 0; i < nslots; ++i)
+      if (int rc = dev_arg(h, fn, slot[i].name, slot[i].arg(), slot[i].extent, !slot[i].required)) return rc;
+    return ALTRO_OK;
+  }
   int open() {
     if (int rc = fwd(h, common(h).ensure_stage(bytes))) return rc;
     st = common(h).stream;
@@ -2205,7 +2214,7 @@ struct StageCursor : altro::StageLayout {
       if (slot[i].in) HIPCHK(h, hipMemcpyAsync(base + slot[i].off, slot[i].in, slot[i].bytes, hipMemcpyHostToDevice, st));
     return ALTRO_OK;
   }
-  void* dev(int i) const { return slot[i].dev ? base + slot[i].off : nullptr; }
+  void* dev(int i) const { return !host ? const_cast<void*>(slot[i].arg()) : slot[i].dev ? base + slot[i].off : nullptr; }
   double* f64(int i) const { return static_cast<double*>(dev(i)); }
   int32_t* i32(int i) const { return static_cast<int32_t*>(dev(i)); }
   int close() {
@@ -2215,6 +2224,39 @@ struct StageCursor : altro::StageLayout {
     return ALTRO_OK;
   }
 };
+
+// what the launches of the scoring pairs check first on the 16-lane path (the one-wave-per-instance backend has
+// WideBackend::eval_ready)
+static int score_ready(altro_handle* h) {
+  if (int rc = h->check_ready()) return rc;
+  if (!h->clock.on && h->kref + h->d.N > h->Nt) FAIL(h, ALTRO_ERR_STATE, "reference window runs past the end of the stored trajectory");
+  return pack_constraints(h);   // (what the next solve would do first; a no-op once the tables are packed)
+}
+
+// Both forms of every pair: the handle, the pair's argument rules, the device, then the caller's pointers validated (`_dev`) or the
+// handle found ready and the arrays staged (host twin), the launch, and for the twin the copies back.  `ready`: the pair's launch
+// opens with score_ready / WideBackend::eval_ready; the twin asks first, so that ALTRO_ERR_STATE allocates and copies nothing.
+extern "C++" {   // (a template, inside the extern "C" of the entry points)
+template <class Rules, class Table, class Launch>
+static int32_t twin_call(altro_handle* h, const char* fn, bool host, bool ready, Rules&& rules, Table&& table, Launch&& launch) {
+  return guard(h, [&]() -> int32_t {
+    if (!h) return dev_null_handle(fn);
+    if (int rc = rules()) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    TwinArgs a(h, host);
+    table(a);
+    if (!host) {
+      if (int rc = a.validate(fn)) return rc;
+      return launch(a);
+    }
+    if (ready)
+      if (int rc = h->wide ? fwd(h, h->wide->eval_ready()) : score_ready(h)) return rc;
+    if (int rc = a.open()) return rc;
+    if (int rc = launch(a)) return rc;
+    return a.close();
+  });
+}
+}   // extern "C++"
 
 // ---- feedback policy on the device (kernels in policy.h)
 // x, knot, u, fb: device arrays (the caller's, validated; or the staged copies of the host twin).  Enqueues one kernel.
@@ -2227,33 +2269,32 @@ static int eval_policy_launch(altro_handle* h, const double* x, const int32_t* k
   return ALTRO_OK;
 }
 
-int32_t altro_batch_eval_policy_dev(altro_handle* h, const double* x, const int32_t* knot, int32_t clamp, double* u, int32_t* fb) {
-  return guard(h, [&]() -> int32_t {
-    DEV_ENTER(h, "altro_batch_eval_policy_dev");
-    DEV_ARG(h, "x", x, B_ * n_, double, false);
-    DEV_ARG(h, "knot", knot, B_, int32_t, true);
-    DEV_ARG(h, "u", u, B_ * m_, double, false);
-    DEV_ARG(h, "fb", fb, B_, int32_t, true);
-    return eval_policy_launch(h, x, knot, clamp, u, fb);
-  });
+// the host twin alone: x and u are required and knot is checked on the host, before anything is staged (the `_dev` form cannot
+// read knot: its kernel reports an out-of-range knot through fb)
+static int eval_policy_host_rules(altro_handle* h, const char* fn, const double* x, const int32_t* knot, const double* u) {
+  const std::string f(fn);
+  if (!x || !u) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": x and u are required");
+  const size_t B = h->d.batch, N = h->d.N;
+  for (size_t b = 0; knot && b < B; ++b)
+    if (knot[b] < 0 || knot[b] > (int32_t)N - 2)
+      FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": knot[" + std::to_string(b) + "] = " + std::to_string(knot[b]) + " is outside 0 .. N-2");
+  return ALTRO_OK;
 }
 
-// The host twin (StageCursor): x and u are required and knot is checked here, before anything is staged
+static int32_t eval_policy_call(altro_handle* h, const char* fn, bool host, const double* x, const int32_t* knot, int32_t clamp, double* u,
+                                int32_t* fb) {
+  return twin_call(
+      h, fn, host, false, [&] { return host ? eval_policy_host_rules(h, fn, x, knot, u) : ALTRO_OK; },
+      [&](TwinArgs& a) { altro::stage_eval_policy(a, h->d.batch, h->d.n, h->d.m, x, knot, u, fb); },
+      [&](const TwinArgs& a) {
+        return eval_policy_launch(h, a.f64(altro::EP_X), a.i32(altro::EP_KNOT), clamp, a.f64(altro::EP_U), a.i32(altro::EP_FB));
+      });
+}
+int32_t altro_batch_eval_policy_dev(altro_handle* h, const double* x, const int32_t* knot, int32_t clamp, double* u, int32_t* fb) {
+  return eval_policy_call(h, "altro_batch_eval_policy_dev", false, x, knot, clamp, u, fb);
+}
 int32_t altro_batch_eval_policy(altro_handle* h, const double* x, const int32_t* knot, int32_t clamp, double* u, int32_t* fb) {
-  return guard(h, [&]() -> int32_t {
-    if (!h) return dev_null_handle("altro_batch_eval_policy");
-    if (!x || !u) FAIL(h, ALTRO_ERR_INVALID_ARG, "altro_batch_eval_policy: x and u are required");
-    const size_t B = h->d.batch, N = h->d.N;
-    for (size_t b = 0; knot && b < B; ++b)
-      if (knot[b] < 0 || knot[b] > (int32_t)N - 2)
-        FAIL(h, ALTRO_ERR_INVALID_ARG, "altro_batch_eval_policy: knot[" + std::to_string(b) + "] = " + std::to_string(knot[b]) + " is outside 0 .. N-2");
-    HIPCHK(h, hipSetDevice(h->device));
-    StageCursor sc(h);
-    altro::stage_eval_policy(sc, B, h->d.n, h->d.m, x, knot, u, fb);
-    if (int rc = sc.open()) return rc;
-    if (int rc = eval_policy_launch(h, sc.f64(altro::EP_X), sc.i32(altro::EP_KNOT), clamp, sc.f64(altro::EP_U), sc.i32(altro::EP_FB))) return rc;
-    return sc.close();
-  });
+  return eval_policy_call(h, "altro_batch_eval_policy", true, x, knot, clamp, u, fb);
 }
 
 // altro_batch_get_gains on the device: the unpack of KD / Dff that the host call does in a loop (k_unpack_gains), resp. two
@@ -2284,14 +2325,6 @@ static altro::Eval16 eval16_params(altro_handle* h) {
   p.con_istride = h->con_per_instance ? N * LW * LW : 0; p.ncrows = h->ncrows;
   p.N = (int)N; p.Nt = h->Nt; p.n = h->d.n; p.m = h->d.m; p.kref = h->kref; p.box_k0 = h->box_k0; p.box_k1 = h->box_k1;
   return p;
-}
-
-// what evaluate_launch, warm_start_launch and simulate_launch check first on the 16-lane path (the one-wave-per-instance
-// backend has WideBackend::eval_ready)
-static int score_ready(altro_handle* h) {
-  if (int rc = h->check_ready()) return rc;
-  if (!h->clock.on && h->kref + h->d.N > h->Nt) FAIL(h, ALTRO_ERR_STATE, "reference window runs past the end of the stored trajectory");
-  return pack_constraints(h);   // (what the next solve would do first; a no-op once the tables are packed)
 }
 
 // the argument rules both forms share, checked before anything else
@@ -2336,39 +2369,23 @@ static int evaluate_launch(altro_handle* h, int32_t ncand, const double* U, cons
   return ALTRO_OK;
 }
 
+static int32_t evaluate_call(altro_handle* h, const char* fn, bool host, int32_t ncand, const double* U, const double* X, const double* x0,
+                             double* J, double* c_max, double* defect, double* Xout) {
+  return twin_call(
+      h, fn, host, true, [&] { return evaluate_rules(h, fn, ncand, U, X, x0, J, c_max, defect, Xout); },
+      [&](TwinArgs& a) { altro::stage_evaluate(a, h->d.batch, h->d.N, h->d.n, h->d.m, ncand, U, X, x0, J, c_max, defect, Xout); },
+      [&](const TwinArgs& a) {
+        return evaluate_launch(h, ncand, a.f64(altro::EV_U), a.f64(altro::EV_X), a.f64(altro::EV_X0), a.f64(altro::EV_J),
+                               a.f64(altro::EV_CMAX), a.f64(altro::EV_DEFECT), a.f64(altro::EV_XOUT));
+      });
+}
 int32_t altro_batch_evaluate_dev(altro_handle* h, int32_t ncand, const double* U, const double* X, const double* x0, double* J, double* c_max,
                                  double* defect, double* Xout) {
-  return guard(h, [&]() -> int32_t {
-    DEV_ENTER(h, "altro_batch_evaluate_dev");
-    if (int rc = evaluate_rules(h, fn_, ncand, U, X, x0, J, c_max, defect, Xout)) return rc;
-    const size_t R = B_ * (size_t)ncand;
-    DEV_ARG(h, "U", U, R * (N_ - 1) * m_, double, true);
-    DEV_ARG(h, "X", X, R * N_ * n_, double, true);
-    DEV_ARG(h, "x0", x0, B_ * n_, double, true);
-    DEV_ARG(h, "J", J, R, double, true);
-    DEV_ARG(h, "c_max", c_max, R, double, true);
-    DEV_ARG(h, "defect", defect, R, double, true);
-    DEV_ARG(h, "Xout", Xout, R * N_ * n_, double, true);
-    return evaluate_launch(h, ncand, U, X, x0, J, c_max, defect, Xout);
-  });
+  return evaluate_call(h, "altro_batch_evaluate_dev", false, ncand, U, X, x0, J, c_max, defect, Xout);
 }
-
-// The host twin (StageCursor)
 int32_t altro_batch_evaluate(altro_handle* h, int32_t ncand, const double* U, const double* X, const double* x0, double* J, double* c_max,
                              double* defect, double* Xout) {
-  return guard(h, [&]() -> int32_t {
-    if (!h) return dev_null_handle("altro_batch_evaluate");
-    if (int rc = evaluate_rules(h, "altro_batch_evaluate", ncand, U, X, x0, J, c_max, defect, Xout)) return rc;
-    HIPCHK(h, hipSetDevice(h->device));
-    StageCursor sc(h);
-    altro::stage_evaluate(sc, h->d.batch, h->d.N, h->d.n, h->d.m, ncand, U, X, x0, J, c_max, defect, Xout);
-    if (int rc = sc.open()) return rc;
-    if (int rc = evaluate_launch(h, ncand, sc.f64(altro::EV_U), sc.f64(altro::EV_X), sc.f64(altro::EV_X0),
-                                 sc.f64(altro::EV_J), sc.f64(altro::EV_CMAX), sc.f64(altro::EV_DEFECT),
-                                 sc.f64(altro::EV_XOUT)))
-      return rc;
-    return sc.close();
-  });
+  return evaluate_call(h, "altro_batch_evaluate", true, ncand, U, X, x0, J, c_max, defect, Xout);
 }
 
 // ---- gradient of a candidate's merit with respect to its controls and initial state (kernels in evaluate_grad.h)
@@ -2400,38 +2417,23 @@ static int evaluate_grad_launch(altro_handle* h, int32_t ncand, const double* U,
   return ALTRO_OK;
 }
 
+static int32_t evaluate_grad_call(altro_handle* h, const char* fn, bool host, int32_t ncand, const double* U, const double* x0, double rho,
+                                  double* J, double* P, double* gU, double* gx0, double* Xout) {
+  return twin_call(
+      h, fn, host, true, [&] { return evaluate_grad_rules(h, fn, ncand, U, rho, J, P, gU, gx0); },
+      [&](TwinArgs& a) { altro::stage_evaluate_grad(a, h->d.batch, h->d.N, h->d.n, h->d.m, ncand, U, x0, J, P, gU, gx0, Xout); },
+      [&](const TwinArgs& a) {
+        return evaluate_grad_launch(h, ncand, a.f64(altro::EG_U), a.f64(altro::EG_X0), rho, a.f64(altro::EG_J), a.f64(altro::EG_P),
+                                    a.f64(altro::EG_GU), a.f64(altro::EG_GX0), a.f64(altro::EG_XOUT));
+      });
+}
 int32_t altro_batch_evaluate_grad_dev(altro_handle* h, int32_t ncand, const double* U, const double* x0, double rho, double* J, double* P,
                                       double* gU, double* gx0, double* Xout) {
-  return guard(h, [&]() -> int32_t {
-    DEV_ENTER(h, "altro_batch_evaluate_grad_dev");
-    if (int rc = evaluate_grad_rules(h, fn_, ncand, U, rho, J, P, gU, gx0)) return rc;
-    const size_t R = B_ * (size_t)ncand;
-    DEV_ARG(h, "U", U, R * (N_ - 1) * m_, double, false);
-    DEV_ARG(h, "x0", x0, B_ * n_, double, true);
-    DEV_ARG(h, "J", J, R, double, true);
-    DEV_ARG(h, "P", P, R, double, true);
-    DEV_ARG(h, "gU", gU, R * (N_ - 1) * m_, double, true);
-    DEV_ARG(h, "gx0", gx0, R * n_, double, true);
-    DEV_ARG(h, "Xout", Xout, R * N_ * n_, double, true);
-    return evaluate_grad_launch(h, ncand, U, x0, rho, J, P, gU, gx0, Xout);
-  });
+  return evaluate_grad_call(h, "altro_batch_evaluate_grad_dev", false, ncand, U, x0, rho, J, P, gU, gx0, Xout);
 }
-
-// The host twin (StageCursor)
 int32_t altro_batch_evaluate_grad(altro_handle* h, int32_t ncand, const double* U, const double* x0, double rho, double* J, double* P,
                                   double* gU, double* gx0, double* Xout) {
-  return guard(h, [&]() -> int32_t {
-    if (!h) return dev_null_handle("altro_batch_evaluate_grad");
-    if (int rc = evaluate_grad_rules(h, "altro_batch_evaluate_grad", ncand, U, rho, J, P, gU, gx0)) return rc;
-    HIPCHK(h, hipSetDevice(h->device));
-    StageCursor sc(h);
-    altro::stage_evaluate_grad(sc, h->d.batch, h->d.N, h->d.n, h->d.m, ncand, U, x0, J, P, gU, gx0, Xout);
-    if (int rc = sc.open()) return rc;
-    if (int rc = evaluate_grad_launch(h, ncand, sc.f64(altro::EG_U), sc.f64(altro::EG_X0), rho, sc.f64(altro::EG_J), sc.f64(altro::EG_P),
-                                      sc.f64(altro::EG_GU), sc.f64(altro::EG_GX0), sc.f64(altro::EG_XOUT)))
-      return rc;
-    return sc.close();
-  });
+  return evaluate_grad_call(h, "altro_batch_evaluate_grad", true, ncand, U, x0, rho, J, P, gU, gx0, Xout);
 }
 
 // ---- the solver's augmented Lagrangian of a control sequence, its gradient and its data derivatives (kernels in
@@ -2470,48 +2472,27 @@ static int evaluate_al_launch(altro_handle* h, int32_t ncand, const double* U, c
   return ALTRO_OK;
 }
 
-int32_t altro_batch_evaluate_al_dev(altro_handle* h, int32_t ncand, const double* U, const double* x0, const altro_al_out* out) {
-  return guard(h, [&]() -> int32_t {
-    DEV_ENTER(h, "altro_batch_evaluate_al_dev");
-    if (int rc = evaluate_al_rules(h, fn_, ncand, U, out)) return rc;
-    const size_t R = B_ * (size_t)ncand, cu = R * (N_ - 1) * m_, cx = R * N_ * n_;
-    DEV_ARG(h, "U", U, cu, double, true);
-    DEV_ARG(h, "x0", x0, B_ * n_, double, true);
-    DEV_ARG(h, "LA", out->LA, R, double, true);
-    DEV_ARG(h, "J", out->J, R, double, true);
-    DEV_ARG(h, "gU", out->gU, cu, double, true);
-    DEV_ARG(h, "gx0", out->gx0, R * n_, double, true);
-    DEV_ARG(h, "gXref", out->gXref, cx, double, true);
-    DEV_ARG(h, "gUref", out->gUref, cu, double, true);
-    DEV_ARG(h, "gQ", out->gQ, R * n_, double, true);
-    DEV_ARG(h, "gQf", out->gQf, R * n_, double, true);
-    DEV_ARG(h, "gR", out->gR, R * m_, double, true);
-    DEV_ARG(h, "gzmin", out->gzmin, R * (n_ + m_), double, true);
-    DEV_ARG(h, "gzmax", out->gzmax, R * (n_ + m_), double, true);
-    DEV_ARG(h, "Xout", out->Xout, cx, double, true);
-    return evaluate_al_launch(h, ncand, U, x0, *out);
-  });
+static int32_t evaluate_al_call(altro_handle* h, const char* fn, bool host, int32_t ncand, const double* U, const double* x0,
+                                const altro_al_out* out) {
+  return twin_call(
+      h, fn, host, true, [&] { return evaluate_al_rules(h, fn, ncand, U, out); },
+      [&](TwinArgs& a) {
+        double* const po[12] = {out->LA, out->J, out->gU, out->gx0, out->gXref, out->gUref, out->gQ, out->gQf, out->gR, out->gzmin, out->gzmax,
+                                out->Xout};
+        altro::stage_evaluate_al(a, h->d.batch, h->d.N, h->d.n, h->d.m, ncand, U, x0, po);
+      },
+      [&](const TwinArgs& a) {
+        const altro_al_out o{a.f64(altro::AL_LA), a.f64(altro::AL_J), a.f64(altro::AL_GU), a.f64(altro::AL_GX0), a.f64(altro::AL_GXREF),
+                             a.f64(altro::AL_GUREF), a.f64(altro::AL_GQ), a.f64(altro::AL_GQF), a.f64(altro::AL_GR), a.f64(altro::AL_GZMIN),
+                             a.f64(altro::AL_GZMAX), a.f64(altro::AL_XOUT)};
+        return evaluate_al_launch(h, ncand, a.f64(altro::AL_U), a.f64(altro::AL_X0), o);
+      });
 }
-
-// The host twin (StageCursor)
+int32_t altro_batch_evaluate_al_dev(altro_handle* h, int32_t ncand, const double* U, const double* x0, const altro_al_out* out) {
+  return evaluate_al_call(h, "altro_batch_evaluate_al_dev", false, ncand, U, x0, out);
+}
 int32_t altro_batch_evaluate_al(altro_handle* h, int32_t ncand, const double* U, const double* x0, const altro_al_out* out) {
-  return guard(h, [&]() -> int32_t {
-    if (!h) return dev_null_handle("altro_batch_evaluate_al");
-    if (int rc = evaluate_al_rules(h, "altro_batch_evaluate_al", ncand, U, out)) return rc;
-    HIPCHK(h, hipSetDevice(h->device));
-    // (readiness before the staging buffer is touched: like the `_dev` form, ALTRO_ERR_STATE allocates and copies nothing)
-    if (int rc = h->wide ? fwd(h, h->wide->eval_ready()) : score_ready(h)) return rc;
-    StageCursor sc(h);
-    double* const po[12] = {out->LA, out->J, out->gU, out->gx0, out->gXref, out->gUref, out->gQ, out->gQf, out->gR, out->gzmin, out->gzmax,
-                            out->Xout};
-    altro::stage_evaluate_al(sc, h->d.batch, h->d.N, h->d.n, h->d.m, ncand, U, x0, po);
-    if (int rc = sc.open()) return rc;
-    const altro_al_out so{sc.f64(altro::AL_LA), sc.f64(altro::AL_J), sc.f64(altro::AL_GU), sc.f64(altro::AL_GX0), sc.f64(altro::AL_GXREF),
-                          sc.f64(altro::AL_GUREF), sc.f64(altro::AL_GQ), sc.f64(altro::AL_GQF), sc.f64(altro::AL_GR), sc.f64(altro::AL_GZMIN),
-                          sc.f64(altro::AL_GZMAX), sc.f64(altro::AL_XOUT)};
-    if (int rc = evaluate_al_launch(h, ncand, sc.f64(altro::AL_U), sc.f64(altro::AL_X0), so)) return rc;
-    return sc.close();
-  });
+  return evaluate_al_call(h, "altro_batch_evaluate_al", true, ncand, U, x0, out);
 }
 
 // the penalty of every instance: the mu altro_batch_evaluate_al uses
@@ -2572,45 +2553,32 @@ static int warm_start_launch(altro_handle* h, int32_t ncand, const double* U, do
   return ALTRO_OK;
 }
 
+static int32_t warm_start_call(altro_handle* h, const char* fn, bool host, int32_t ncand, const double* U, double rho, int32_t include_current,
+                               int32_t* chosen, double* J, double* c_max) {
+  return twin_call(
+      h, fn, host, true, [&] { return warm_start_rules(h, fn, ncand, U, rho, include_current); },
+      [&](TwinArgs& a) { altro::stage_warm_start(a, h->d.batch, h->d.N, h->d.m, ncand, include_current, U, chosen, J, c_max); },
+      [&](const TwinArgs& a) {
+        return warm_start_launch(h, ncand, a.f64(altro::WS_U), rho, include_current, a.i32(altro::WS_CHOSEN), a.f64(altro::WS_J),
+                                 a.f64(altro::WS_CMAX));
+      });
+}
 int32_t altro_batch_warm_start_dev(altro_handle* h, int32_t ncand, const double* U, double rho, int32_t include_current, int32_t* chosen,
                                    double* J, double* c_max) {
-  return guard(h, [&]() -> int32_t {
-    DEV_ENTER(h, "altro_batch_warm_start_dev");
-    if (int rc = warm_start_rules(h, fn_, ncand, U, rho, include_current)) return rc;
-    const size_t R1 = B_ * (size_t)(ncand + include_current);
-    DEV_ARG(h, "U", U, B_ * (size_t)ncand * (N_ - 1) * m_, double, false);
-    DEV_ARG(h, "chosen", chosen, B_, int32_t, true);
-    DEV_ARG(h, "J", J, R1, double, true);
-    DEV_ARG(h, "c_max", c_max, R1, double, true);
-    return warm_start_launch(h, ncand, U, rho, include_current, chosen, J, c_max);
-  });
+  return warm_start_call(h, "altro_batch_warm_start_dev", false, ncand, U, rho, include_current, chosen, J, c_max);
 }
-
-// The host twin (StageCursor)
 int32_t altro_batch_warm_start(altro_handle* h, int32_t ncand, const double* U, double rho, int32_t include_current, int32_t* chosen,
                                double* J, double* c_max) {
-  return guard(h, [&]() -> int32_t {
-    if (!h) return dev_null_handle("altro_batch_warm_start");
-    if (int rc = warm_start_rules(h, "altro_batch_warm_start", ncand, U, rho, include_current)) return rc;
-    HIPCHK(h, hipSetDevice(h->device));
-    StageCursor sc(h);
-    altro::stage_warm_start(sc, h->d.batch, h->d.N, h->d.m, ncand, include_current, U, chosen, J, c_max);
-    if (int rc = sc.open()) return rc;
-    if (int rc = warm_start_launch(h, ncand, sc.f64(altro::WS_U), rho, include_current, sc.i32(altro::WS_CHOSEN),
-                                   sc.f64(altro::WS_J), sc.f64(altro::WS_CMAX)))
-      return rc;
-    return sc.close();
-  });
+  return warm_start_call(h, "altro_batch_warm_start", true, ncand, U, rho, include_current, chosen, J, c_max);
 }
 
 // ---- closed-loop simulation of the stored policy under disturbances (kernels in simulate.h)
 // the argument rules both forms share, checked before anything else
-static int simulate_rules(altro_handle* h, const char* fn, int32_t nsamp, int32_t clamp, const altro::SimIO& io) {
+static int simulate_rules(altro_handle* h, const char* fn, int32_t nsamp, int32_t clamp, bool any_out) {
   const std::string f(fn);
   if (nsamp < 1) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": nsamp must be at least 1");
   if (clamp != 0 && clamp != 1) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": clamp must be 0 or 1");
-  if (!io.J && !io.cmax && !io.dxmax && !io.fb && !io.Xout && !io.Uout)
-    FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": J, c_max, dx_max, fb, Xout and Uout are all null");
+  if (!any_out) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": J, c_max, dx_max, fb, Xout and Uout are all null");
   return ALTRO_OK;
 }
 
@@ -2627,58 +2595,43 @@ static int simulate_launch(altro_handle* h, int32_t nsamp, int32_t clamp, const 
   return ALTRO_OK;
 }
 
+static int32_t simulate_call(altro_handle* h, const char* fn, bool host, int32_t nsamp, const double* x0, const double* w, int32_t clamp,
+                             double* J, double* c_max, double* dx_max, int32_t* fb, double* Xout, double* Uout) {
+  return twin_call(
+      h, fn, host, true, [&] { return simulate_rules(h, fn, nsamp, clamp, J || c_max || dx_max || fb || Xout || Uout); },
+      [&](TwinArgs& a) { altro::stage_simulate(a, h->d.batch, h->d.N, h->d.n, h->d.m, nsamp, x0, w, J, c_max, dx_max, fb, Xout, Uout); },
+      [&](const TwinArgs& a) {
+        const altro::SimIO io{a.f64(altro::SIM_X0), a.f64(altro::SIM_W), a.f64(altro::SIM_J), a.f64(altro::SIM_CMAX),
+                              a.f64(altro::SIM_DXMAX), a.i32(altro::SIM_FB), a.f64(altro::SIM_XOUT), a.f64(altro::SIM_UOUT)};
+        return simulate_launch(h, nsamp, clamp, io);
+      });
+}
 int32_t altro_batch_simulate_policy_dev(altro_handle* h, int32_t nsamp, const double* x0, const double* w, int32_t clamp, double* J,
                                         double* c_max, double* dx_max, int32_t* fb, double* Xout, double* Uout) {
-  return guard(h, [&]() -> int32_t {
-    DEV_ENTER(h, "altro_batch_simulate_policy_dev");
-    const altro::SimIO io{x0, w, J, c_max, dx_max, fb, Xout, Uout};
-    if (int rc = simulate_rules(h, fn_, nsamp, clamp, io)) return rc;
-    const size_t R = B_ * (size_t)nsamp;
-    DEV_ARG(h, "x0", x0, R * n_, double, true);
-    DEV_ARG(h, "w", w, R * (N_ - 1) * n_, double, true);
-    DEV_ARG(h, "J", J, R, double, true);
-    DEV_ARG(h, "c_max", c_max, R, double, true);
-    DEV_ARG(h, "dx_max", dx_max, R, double, true);
-    DEV_ARG(h, "fb", fb, B_, int32_t, true);
-    DEV_ARG(h, "Xout", Xout, R * N_ * n_, double, true);
-    DEV_ARG(h, "Uout", Uout, R * (N_ - 1) * m_, double, true);
-    return simulate_launch(h, nsamp, clamp, io);
-  });
+  return simulate_call(h, "altro_batch_simulate_policy_dev", false, nsamp, x0, w, clamp, J, c_max, dx_max, fb, Xout, Uout);
 }
-
-// The host twin (StageCursor)
 int32_t altro_batch_simulate_policy(altro_handle* h, int32_t nsamp, const double* x0, const double* w, int32_t clamp, double* J,
                                     double* c_max, double* dx_max, int32_t* fb, double* Xout, double* Uout) {
-  return guard(h, [&]() -> int32_t {
-    if (!h) return dev_null_handle("altro_batch_simulate_policy");
-    if (int rc = simulate_rules(h, "altro_batch_simulate_policy", nsamp, clamp, altro::SimIO{x0, w, J, c_max, dx_max, fb, Xout, Uout})) return rc;
-    HIPCHK(h, hipSetDevice(h->device));
-    StageCursor sc(h);
-    altro::stage_simulate(sc, h->d.batch, h->d.N, h->d.n, h->d.m, nsamp, x0, w, J, c_max, dx_max, fb, Xout, Uout);
-    if (int rc = sc.open()) return rc;
-    const altro::SimIO io{sc.f64(altro::SIM_X0), sc.f64(altro::SIM_W), sc.f64(altro::SIM_J), sc.f64(altro::SIM_CMAX),
-                          sc.f64(altro::SIM_DXMAX), sc.i32(altro::SIM_FB), sc.f64(altro::SIM_XOUT), sc.f64(altro::SIM_UOUT)};
-    if (int rc = simulate_launch(h, nsamp, clamp, io)) return rc;
-    return sc.close();
-  });
+  return simulate_call(h, "altro_batch_simulate_policy", true, nsamp, x0, w, clamp, J, c_max, dx_max, fb, Xout, Uout);
 }
 
 // ---- closed-loop covariance of the stored policy (kernels in covariance.h)
 // The argument rules both forms share, checked before anything else; nsc <- the doubles of sc per instance (nk * p of con_id).
-static int covariance_rules(altro_handle* h, const char* fn, const altro::CovIO& io, int32_t per_instance, int32_t con_id, size_t* nsc) {
+// any_in: Sigma0 or W is given; any_out: one of the eight outputs is.
+static int covariance_rules(altro_handle* h, const char* fn, bool any_in, bool any_out, int32_t per_instance, int32_t con_id, double kappa,
+                            const double* sc, const double* zmin_t, const double* zmax_t, size_t* nsc) {
   const std::string f(fn);
   *nsc = 0;
-  if (!io.S0 && !io.W) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": Sigma0 and W are both null");
-  if (!io.sx && !io.su && !io.sc && !io.dJ && !io.fb && !io.zlo_t && !io.zhi_t && !io.Sout)
-    FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": sx, su, sc, dJ, fb, zmin_t, zmax_t and Sout are all null");
+  if (!any_in) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": Sigma0 and W are both null");
+  if (!any_out) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": sx, su, sc, dJ, fb, zmin_t, zmax_t and Sout are all null");
   if (per_instance != 0 && per_instance != 1) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": per_instance must be 0 or 1");
-  if (!(io.kappa >= 0.0) || std::isinf(io.kappa)) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": kappa must be finite and not negative");
-  if ((io.zlo_t != nullptr) != (io.zhi_t != nullptr)) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": zmin_t and zmax_t go together: both or neither");
+  if (!(kappa >= 0.0) || std::isinf(kappa)) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": kappa must be finite and not negative");
+  if ((zmin_t != nullptr) != (zmax_t != nullptr)) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": zmin_t and zmax_t go together: both or neither");
   const int box_id = common(h).box_id;
-  if (io.zlo_t && box_id < 0) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": zmin_t / zmax_t need a BOX constraint on the handle");
+  if (zmin_t && box_id < 0) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": zmin_t / zmax_t need a BOX constraint on the handle");
   if (con_id < 0) {
     if (con_id != -1) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": unknown constraint id");
-    if (io.sc) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": sc needs the id of a LINEAR or SOC constraint (con_id = -1)");
+    if (sc) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": sc needs the id of a LINEAR or SOC constraint (con_id = -1)");
     return ALTRO_OK;
   }
   if (con_id == box_id) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": con_id is a BOX constraint: its deviations are sx and su");
@@ -2689,7 +2642,7 @@ static int covariance_rules(altro_handle* h, const char* fn, const altro::CovIO&
       if (cb.id == con_id) *nsc = (size_t)(cb.k1 - cb.k0 + 1) * cb.p;
   }
   if (!*nsc) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": unknown constraint id");
-  if (!io.sc) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": con_id is given without sc");
+  if (!sc) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": con_id is given without sc");
   return ALTRO_OK;
 }
 
@@ -2711,49 +2664,37 @@ static int covariance_launch(altro_handle* h, const altro::CovIO& io, int32_t co
   return ALTRO_OK;
 }
 
+static int32_t covariance_call(altro_handle* h, const char* fn, bool host, const double* Sigma0, const double* W, int32_t per_instance,
+                               int32_t con_id, double kappa, double* sx, double* su, double* sc, double* dJ, int32_t* fb, double* zmin_t,
+                               double* zmax_t, double* Sout) {
+  size_t nsc = 0;
+  return twin_call(
+      h, fn, host, true,
+      [&] {
+        return covariance_rules(h, fn, Sigma0 || W, sx || su || sc || dJ || fb || zmin_t || zmax_t || Sout, per_instance, con_id, kappa, sc,
+                                zmin_t, zmax_t, &nsc);
+      },
+      [&](TwinArgs& a) {
+        altro::stage_covariance(a, h->d.batch, h->d.N, h->d.n, h->d.m, per_instance, nsc, Sigma0, W, sx, su, sc, dJ, fb, zmin_t, zmax_t, Sout);
+      },
+      [&](const TwinArgs& a) {
+        const altro::CovIO io{a.f64(altro::COV_S0), a.f64(altro::COV_W), per_instance, kappa, a.f64(altro::COV_SX), a.f64(altro::COV_SU),
+                              a.f64(altro::COV_SC), a.f64(altro::COV_DJ), a.i32(altro::COV_FB), a.f64(altro::COV_ZLO), a.f64(altro::COV_ZHI),
+                              a.f64(altro::COV_SOUT)};
+        return covariance_launch(h, io, con_id);
+      });
+}
 int32_t altro_batch_propagate_covariance_dev(altro_handle* h, const double* Sigma0, const double* W, int32_t per_instance, int32_t con_id,
                                              double kappa, double* sx, double* su, double* sc, double* dJ, int32_t* fb, double* zmin_t,
                                              double* zmax_t, double* Sout) {
-  return guard(h, [&]() -> int32_t {
-    DEV_ENTER(h, "altro_batch_propagate_covariance_dev");
-    const altro::CovIO io{Sigma0, W, per_instance, kappa, sx, su, sc, dJ, fb, zmin_t, zmax_t, Sout};
-    size_t nsc = 0;
-    if (int rc = covariance_rules(h, fn_, io, per_instance, con_id, &nsc)) return rc;
-    const size_t mat = (per_instance ? B_ : 1) * n_ * n_;
-    DEV_ARG(h, "Sigma0", Sigma0, mat, double, true);
-    DEV_ARG(h, "W", W, mat, double, true);
-    DEV_ARG(h, "sx", sx, B_ * N_ * n_, double, true);
-    DEV_ARG(h, "su", su, B_ * (N_ - 1) * m_, double, true);
-    DEV_ARG(h, "sc", sc, B_ * nsc, double, true);
-    DEV_ARG(h, "dJ", dJ, B_, double, true);
-    DEV_ARG(h, "fb", fb, B_, int32_t, true);
-    DEV_ARG(h, "zmin_t", zmin_t, B_ * (n_ + m_), double, true);
-    DEV_ARG(h, "zmax_t", zmax_t, B_ * (n_ + m_), double, true);
-    DEV_ARG(h, "Sout", Sout, B_ * N_ * n_ * n_, double, true);
-    return covariance_launch(h, io, con_id);
-  });
+  return covariance_call(h, "altro_batch_propagate_covariance_dev", false, Sigma0, W, per_instance, con_id, kappa, sx, su, sc, dJ, fb, zmin_t,
+                         zmax_t, Sout);
 }
-
-// The host twin (StageCursor)
 int32_t altro_batch_propagate_covariance(altro_handle* h, const double* Sigma0, const double* W, int32_t per_instance, int32_t con_id,
                                          double kappa, double* sx, double* su, double* sc, double* dJ, int32_t* fb, double* zmin_t,
                                          double* zmax_t, double* Sout) {
-  return guard(h, [&]() -> int32_t {
-    if (!h) return dev_null_handle("altro_batch_propagate_covariance");
-    size_t nsc = 0;
-    if (int rc = covariance_rules(h, "altro_batch_propagate_covariance",
-                                  altro::CovIO{Sigma0, W, per_instance, kappa, sx, su, sc, dJ, fb, zmin_t, zmax_t, Sout}, per_instance, con_id, &nsc))
-      return rc;
-    HIPCHK(h, hipSetDevice(h->device));
-    StageCursor sc_(h);
-    altro::stage_covariance(sc_, h->d.batch, h->d.N, h->d.n, h->d.m, per_instance, nsc, Sigma0, W, sx, su, sc, dJ, fb, zmin_t, zmax_t, Sout);
-    if (int rc = sc_.open()) return rc;
-    const altro::CovIO io{sc_.f64(altro::COV_S0), sc_.f64(altro::COV_W), per_instance, kappa, sc_.f64(altro::COV_SX), sc_.f64(altro::COV_SU),
-                          sc_.f64(altro::COV_SC), sc_.f64(altro::COV_DJ), sc_.i32(altro::COV_FB), sc_.f64(altro::COV_ZLO),
-                          sc_.f64(altro::COV_ZHI), sc_.f64(altro::COV_SOUT)};
-    if (int rc = covariance_launch(h, io, con_id)) return rc;
-    return sc_.close();
-  });
+  return covariance_call(h, "altro_batch_propagate_covariance", true, Sigma0, W, per_instance, con_id, kappa, sx, su, sc, dJ, fb, zmin_t,
+                         zmax_t, Sout);
 }
 
 // ---- sensitivity of the solution through the stored gains (kernels in sensitivity.h)
@@ -2801,61 +2742,34 @@ static int sens_launch(altro_handle* h, int32_t nseed, altro::SensIO io) {
   return ALTRO_OK;
 }
 
-static int sens_dev(altro_handle* h, const char* fn, int32_t nseed, const altro::SensIO& io, bool have_out) {
-  DEV_ENTER(h, fn);
-  if (int rc = sens_rules(h, fn_, nseed, io, have_out)) return rc;
-  const size_t R = B_ * (size_t)nseed;
-  DEV_ARG(h, io.jvp ? "vXref" : "gX", io.inx, R * N_ * n_, double, true);
-  DEV_ARG(h, io.jvp ? "vUref" : "gU", io.inu, R * (N_ - 1) * m_, double, true);
-  DEV_ARG(h, "vx0", io.in0, R * n_, double, true);
-  DEV_ARG(h, "gx0", io.o0, R * n_, double, true);
-  DEV_ARG(h, io.jvp ? "dX" : "gXref", io.ox, R * N_ * n_, double, true);
-  DEV_ARG(h, io.jvp ? "dU" : "gUref", io.ou, R * (N_ - 1) * m_, double, true);
-  DEV_ARG(h, "fb", io.fb, B_, int32_t, true);
-  return sens_launch(h, nseed, io);
+// io: the caller's arrays in the kernels' order (sens_io), which is the order of the table
+static int32_t sens_call(altro_handle* h, const char* fn, bool host, int32_t nseed, const altro::SensIO& io, bool have_out) {
+  return twin_call(
+      h, fn, host, true, [&] { return sens_rules(h, fn, nseed, io, have_out); },
+      [&](TwinArgs& a) {
+        altro::stage_solution_sens(a, h->d.batch, h->d.N, h->d.n, h->d.m, nseed, io.jvp != 0, io.inx, io.inu, io.in0, io.o0, io.ox, io.ou, io.fb);
+      },
+      [&](const TwinArgs& a) {
+        return sens_launch(h, nseed, sens_io(io.jvp != 0, a.f64(altro::SS_INX), a.f64(altro::SS_INU), a.f64(altro::SS_IN0), a.f64(altro::SS_O0),
+                                             a.f64(altro::SS_OX), a.f64(altro::SS_OU), a.i32(altro::SS_FB)));
+      });
 }
-
-// The host twins (StageCursor)
-static int sens_host(altro_handle* h, const char* fn, int32_t nseed, const altro::SensIO& io, bool have_out) {
-  if (!h) return dev_null_handle(fn);
-  if (int rc = sens_rules(h, fn, nseed, io, have_out)) return rc;
-  HIPCHK(h, hipSetDevice(h->device));
-  StageCursor sc(h);
-  altro::stage_solution_sens(sc, h->d.batch, h->d.N, h->d.n, h->d.m, nseed, io.inx, io.inu, io.in0, io.o0, io.ox, io.ou, io.fb);
-  if (int rc = sc.open()) return rc;
-  altro::SensIO st = io;
-  st.inx = sc.f64(altro::SS_INX); st.inu = sc.f64(altro::SS_INU); st.in0 = sc.f64(altro::SS_IN0);
-  st.o0 = sc.f64(altro::SS_O0); st.ox = sc.f64(altro::SS_OX); st.ou = sc.f64(altro::SS_OU); st.fb = sc.i32(altro::SS_FB);
-  if (int rc = sens_launch(h, nseed, st)) return rc;
-  return sc.close();
+static altro::SensIO vjp_io(const double* gX, const double* gU, const altro_sens_out* out, int32_t* fb) {
+  return sens_io(false, gX, gU, nullptr, out ? out->gx0 : nullptr, out ? out->gXref : nullptr, out ? out->gUref : nullptr, fb);
 }
-
 int32_t altro_batch_solution_vjp_dev(altro_handle* h, int32_t nseed, const double* gX, const double* gU, const altro_sens_out* out, int32_t* fb) {
-  return guard(h, [&]() -> int32_t {
-    return sens_dev(h, "altro_batch_solution_vjp_dev", nseed,
-                    sens_io(false, gX, gU, nullptr, out ? out->gx0 : nullptr, out ? out->gXref : nullptr, out ? out->gUref : nullptr, fb), out != nullptr);
-  });
+  return sens_call(h, "altro_batch_solution_vjp_dev", false, nseed, vjp_io(gX, gU, out, fb), out != nullptr);
 }
-
 int32_t altro_batch_solution_vjp(altro_handle* h, int32_t nseed, const double* gX, const double* gU, const altro_sens_out* out, int32_t* fb) {
-  return guard(h, [&]() -> int32_t {
-    return sens_host(h, "altro_batch_solution_vjp", nseed,
-                     sens_io(false, gX, gU, nullptr, out ? out->gx0 : nullptr, out ? out->gXref : nullptr, out ? out->gUref : nullptr, fb), out != nullptr);
-  });
+  return sens_call(h, "altro_batch_solution_vjp", true, nseed, vjp_io(gX, gU, out, fb), out != nullptr);
 }
-
 int32_t altro_batch_solution_jvp_dev(altro_handle* h, int32_t nseed, const double* vx0, const double* vXref, const double* vUref, double* dX,
                                      double* dU, int32_t* fb) {
-  return guard(h, [&]() -> int32_t {
-    return sens_dev(h, "altro_batch_solution_jvp_dev", nseed, sens_io(true, vXref, vUref, vx0, nullptr, dX, dU, fb), true);
-  });
+  return sens_call(h, "altro_batch_solution_jvp_dev", false, nseed, sens_io(true, vXref, vUref, vx0, nullptr, dX, dU, fb), true);
 }
-
 int32_t altro_batch_solution_jvp(altro_handle* h, int32_t nseed, const double* vx0, const double* vXref, const double* vUref, double* dX,
                                  double* dU, int32_t* fb) {
-  return guard(h, [&]() -> int32_t {
-    return sens_host(h, "altro_batch_solution_jvp", nseed, sens_io(true, vXref, vUref, vx0, nullptr, dX, dU, fb), true);
-  });
+  return sens_call(h, "altro_batch_solution_jvp", true, nseed, sens_io(true, vXref, vUref, vx0, nullptr, dX, dU, fb), true);
 }
 
 // altro_batch_get_gain_factors on the device: the unpack that call does in a loop on the host (k_unpack_factors16), resp. the

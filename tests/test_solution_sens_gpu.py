@@ -408,6 +408,59 @@ def test_c_abi_refuses_before_anything_is_enqueued(name):
         Lb.altro_batch_destroy(h2)
 
 
+@pytest.mark.parametrize("force_wide", [False, True])
+def test_an_output_one_double_short_is_refused(monkeypatch, force_wide):
+    """both `_dev` forms with one output one double short of its extent (gXref of the VJP, dU of the JVP; the last doubles of the
+    tensor's own allocation, hipMemGetAddressRange): INVALID_ARG with "shorter" in the message, the sentinel in every output
+    untouched, and the next solve equals a twin handle's.  (n, m) = (6, 3) at batch 5, N = 9: the smallest shape of
+    tests/test_evaluate_gpu.py, on the backend it picks and on the one-wave-per-instance backend"""
+    import ctypes as C
+    import test_evaluate_gpu as TE
+    if force_wide:
+        monkeypatch.setenv("ALTRO_FORCE_WIDE", "1")
+    INV = altro._lib.ERR_INVALID_ARG
+    prob = mpc.gen_tracking_problem(TE.random_linear(5, 6, 3, 41))
+    sv, tw = (altro.ALTROSolver(prob, altro.SolverOptions(**mpc.REF_OPTS)) for _ in range(2))
+    try:
+        altro.solve(sv), altro.solve(tw)
+        L, h, B, N, n, m = sv._L, sv.h, sv.B, sv.N, sv.n, sv.m
+        full = lambda *s: torch.full(s, SENT, dtype=torch.float64, device=dev())
+        gX, gU, v0 = T(np.ones((B, 1, N, n))), T(np.ones((B, 1, N - 1, m))), T(np.ones((B, 1, n)))
+        o0, oX, oU = full(B, 1, n), full(B, 1, N, n), full(B, 1, N - 1, m)
+        fb = torch.full((B,), -77, dtype=torch.int32, device=dev())
+        paths = altro._lib.hip_runtimes()
+        assert len(paths) == 1, paths
+        rt = C.CDLL(paths[0])
+        rt.hipMemGetAddressRange.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p]
+
+        def short(t):
+            base, size = C.c_void_p(), C.c_size_t()
+            assert rt.hipMemGetAddressRange(C.byref(base), C.byref(size), C.c_void_p(t.data_ptr())) == 0
+            return base.value + size.value - (t.numel() * 8 - 8)             # the last numel - 1 doubles of t's allocation
+
+        p = lambda t: t.data_ptr()
+        out = altro._lib.SensOut(gx0=p(o0), gXref=short(oX), gUref=p(oU))
+        calls = [lambda: L.altro_batch_solution_vjp_dev(h, 1, p(gX), p(gU), C.byref(out), p(fb)),
+                 lambda: L.altro_batch_solution_jvp_dev(h, 1, p(v0), p(gX), p(gU), p(oX), short(oU), p(fb))]
+        for i, call_ in enumerate(calls):
+            rc = call_()
+            msg = (L.altro_last_error(h) or b"").decode()
+            assert rc == INV and "shorter" in msg, (i, rc, msg)
+        torch.cuda.synchronize()
+        altro.synchronize(sv)
+        for t in (o0, oX, oU):
+            assert (t == SENT).all()
+        assert (fb == -77).all()
+        assert L.altro_batch_solution_jvp_dev(h, 1, p(v0), p(gX), p(gU), p(oX), p(oU), p(fb)) == 0     # the whole dU is fine
+        altro.solve(sv), altro.solve(tw)
+        ea, eb = TE.everything(sv, prob.x0), TE.everything(tw, prob.x0)
+        for k in ea:
+            assert np.array_equal(ea[k], eb[k], equal_nan=True), k
+        assert (oU != SENT).any()
+    finally:
+        sv.close(), tw.close()
+
+
 def test_api_solution_with_an_invalid_instance():
     """6: with instances whose stored pass was regularised (one iteration with bp_reg_initial > 0 on the one-wave-per-instance
     backend: the regularisation has not decayed to zero yet when the solve stops) the forward raises; with invalid="zero" their

@@ -1,10 +1,12 @@
-// Stand-alone CPU check of csrc/stage_layout.h (DESIGN.md 7l, 7q): for every null / non-null combination of the arguments of the
-// host twins, the total size and the offset of every sub-array against the sums altro_batch.hip wrote out by hand
-// before the layout was shared.  No GPU, no library:
+// Stand-alone CPU check of csrc/stage_layout.h (DESIGN.md 7u): for every null / non-null combination of the arguments of the
+// host/device twin pairs, the total size and the offset of every sub-array against the sums altro_batch.hip wrote out by hand
+// before the layout was shared, and the name, the required flag and the extent the `_dev` form validates against the sizes
+// include/altro_batch.h documents.  No GPU, no library:
 //   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -o /tmp/stage_layout_check \
 //       tools/stage_layout_check.cpp && /tmp/stage_layout_check
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 #include "../altro-mpc-icra2021_amd/csrc/stage_layout.h"
 
@@ -25,6 +27,14 @@ static void slot_is(const StageLayout& L, int i, size_t off, size_t bytes, bool 
   expect(bytes == 0 || s.off == off, what, combo);
   expect(s.dev == dev, what, combo);
   expect(!dev || s.off % align == 0, what, combo);
+}
+
+// slot i as the `_dev` form sees it: the argument's name, whether null is refused, and the bytes validated (present or not)
+static void arg_is(const StageLayout& L, int i, const char* name, bool required, size_t extent, const char* what, int combo) {
+  const StageLayout::Slot& s = L.slot[i];
+  expect(s.name && std::strcmp(s.name, name) == 0, what, combo);
+  expect(s.required == required, what, combo);
+  expect(s.extent == extent, what, combo);
 }
 
 int main() {
@@ -49,6 +59,10 @@ int main() {
       expect(L.slot[altro::EP_X].in == d && L.slot[altro::EP_KNOT].in == kn && L.slot[altro::EP_U].out == d && L.slot[altro::EP_FB].out == fb &&
                  !L.slot[altro::EP_X].out && !L.slot[altro::EP_U].in && !L.slot[altro::EP_KNOT].out && !L.slot[altro::EP_FB].in,
              "eval_policy: copies", c);
+      arg_is(L, altro::EP_X, "x", true, B * n * D, "eval_policy: arg x", c);
+      arg_is(L, altro::EP_U, "u", true, B * m * D, "eval_policy: arg u", c);
+      arg_is(L, altro::EP_KNOT, "knot", false, B * I, "eval_policy: arg knot", c);
+      arg_is(L, altro::EP_FB, "fb", false, B * I, "eval_policy: arg fb", c);
     }
     // altro_batch_evaluate: elems = 3 R + (U ? cu : 0) + (X ? cx : 0) + (x0 ? B n : 0) + (Xout ? cx : 0); J, c_max, defect first
     for (int c = 0; c < 128; ++c) {
@@ -68,6 +82,13 @@ int main() {
       slot_is(L, altro::EV_X0, s, x0 ? B * n * D : 0, x0, D, "evaluate: x0", c); s += x0 ? B * n * D : 0;
       slot_is(L, altro::EV_XOUT, s, Xo ? cx * D : 0, Xo, D, "evaluate: Xout", c);
       expect((L.slot[altro::EV_U].in == U) && (L.slot[altro::EV_J].out == J) && (L.slot[altro::EV_XOUT].out == Xo), "evaluate: copies", c);
+      arg_is(L, altro::EV_U, "U", false, B * nc * (N - 1) * m * D, "evaluate: arg U", c);
+      arg_is(L, altro::EV_X, "X", false, B * nc * N * n * D, "evaluate: arg X", c);
+      arg_is(L, altro::EV_X0, "x0", false, B * n * D, "evaluate: arg x0", c);
+      arg_is(L, altro::EV_J, "J", false, B * nc * D, "evaluate: arg J", c);
+      arg_is(L, altro::EV_CMAX, "c_max", false, B * nc * D, "evaluate: arg c_max", c);
+      arg_is(L, altro::EV_DEFECT, "defect", false, B * nc * D, "evaluate: arg defect", c);
+      arg_is(L, altro::EV_XOUT, "Xout", false, B * nc * N * n * D, "evaluate: arg Xout", c);
     }
     // altro_batch_evaluate_grad: elems = 2 R + (gU ? cu : 0) + (gx0 ? R n : 0) + (U ? cu : 0) + (x0 ? B n : 0) + (Xout ? cx : 0); J, P first
     for (int c = 0; c < 128; ++c) {
@@ -88,6 +109,13 @@ int main() {
       expect(L.bytes == s, "evaluate_grad: size", c);
       expect(L.slot[altro::EG_U].in == U && L.slot[altro::EG_X0].in == x0 && L.slot[altro::EG_GU].out == gU && L.slot[altro::EG_XOUT].out == Xo,
              "evaluate_grad: copies", c);
+      arg_is(L, altro::EG_U, "U", true, B * nc * (N - 1) * m * D, "evaluate_grad: arg U", c);
+      arg_is(L, altro::EG_X0, "x0", false, B * n * D, "evaluate_grad: arg x0", c);
+      arg_is(L, altro::EG_J, "J", false, B * nc * D, "evaluate_grad: arg J", c);
+      arg_is(L, altro::EG_P, "P", false, B * nc * D, "evaluate_grad: arg P", c);
+      arg_is(L, altro::EG_GU, "gU", false, B * nc * (N - 1) * m * D, "evaluate_grad: arg gU", c);
+      arg_is(L, altro::EG_GX0, "gx0", false, B * nc * n * D, "evaluate_grad: arg gx0", c);
+      arg_is(L, altro::EG_XOUT, "Xout", false, B * nc * N * n * D, "evaluate_grad: arg Xout", c);
     }
     // altro_batch_evaluate_al: every one of the fourteen sub-arrays only when given, the twelve outputs of altro_al_out in the
     // order of the struct, then U, then x0
@@ -108,6 +136,20 @@ int main() {
         expect(L.slot[i].out == (i < 12 ? out[i] : nullptr) && L.slot[i].in == (i == 12 ? U : i == 13 ? x0 : nullptr), "evaluate_al: copies", c);
       }
       expect(L.bytes == s, "evaluate_al: size", c);
+      arg_is(L, altro::AL_LA, "LA", false, B * nc * D, "evaluate_al: arg LA", c);
+      arg_is(L, altro::AL_J, "J", false, B * nc * D, "evaluate_al: arg J", c);
+      arg_is(L, altro::AL_GU, "gU", false, B * nc * (N - 1) * m * D, "evaluate_al: arg gU", c);
+      arg_is(L, altro::AL_GX0, "gx0", false, B * nc * n * D, "evaluate_al: arg gx0", c);
+      arg_is(L, altro::AL_GXREF, "gXref", false, B * nc * N * n * D, "evaluate_al: arg gXref", c);
+      arg_is(L, altro::AL_GUREF, "gUref", false, B * nc * (N - 1) * m * D, "evaluate_al: arg gUref", c);
+      arg_is(L, altro::AL_GQ, "gQ", false, B * nc * n * D, "evaluate_al: arg gQ", c);
+      arg_is(L, altro::AL_GQF, "gQf", false, B * nc * n * D, "evaluate_al: arg gQf", c);
+      arg_is(L, altro::AL_GR, "gR", false, B * nc * m * D, "evaluate_al: arg gR", c);
+      arg_is(L, altro::AL_GZMIN, "gzmin", false, B * nc * (n + m) * D, "evaluate_al: arg gzmin", c);
+      arg_is(L, altro::AL_GZMAX, "gzmax", false, B * nc * (n + m) * D, "evaluate_al: arg gzmax", c);
+      arg_is(L, altro::AL_XOUT, "Xout", false, B * nc * N * n * D, "evaluate_al: arg Xout", c);
+      arg_is(L, altro::AL_U, "U", false, B * nc * (N - 1) * m * D, "evaluate_al: arg U", c);
+      arg_is(L, altro::AL_X0, "x0", false, B * n * D, "evaluate_al: arg x0", c);
       expect(altro::AL_LA == 0 && altro::AL_XOUT == 11 && altro::AL_U == 12 && altro::AL_X0 == 13, "evaluate_al: order", c);
     }
     // altro_batch_warm_start: bytes = (2 R1 + cu) doubles + B ints; J, c_max, U, chosen, all handed to the kernels
@@ -125,6 +167,10 @@ int main() {
       slot_is(L, altro::WS_U, 2 * R1 * D, cu * D, true, D, "warm_start: U", c);
       slot_is(L, altro::WS_CHOSEN, (2 * R1 + cu) * D, B * I, true, I, "warm_start: chosen", c);
       expect(L.slot[altro::WS_U].in == d && L.slot[altro::WS_CHOSEN].out == ch && L.slot[altro::WS_J].out == J, "warm_start: copies", c);
+      arg_is(L, altro::WS_U, "U", true, B * nc * (N - 1) * m * D, "warm_start: arg U", c);
+      arg_is(L, altro::WS_CHOSEN, "chosen", false, B * I, "warm_start: arg chosen", c);
+      arg_is(L, altro::WS_J, "J", false, B * (nc + inc) * D, "warm_start: arg J", c);
+      arg_is(L, altro::WS_CMAX, "c_max", false, B * (nc + inc) * D, "warm_start: arg c_max", c);
     }
     // altro_batch_simulate_policy: elems = 3 R + (x0 ? c0 : 0) + (w ? cw : 0) + (Xout ? cx : 0) + (Uout ? cu : 0) doubles + B ints
     for (int c = 0; c < 256; ++c) {
@@ -146,6 +192,14 @@ int main() {
       slot_is(L, altro::SIM_UOUT, s, Uo ? cu * D : 0, Uo, D, "simulate: Uout", c); s += Uo ? cu * D : 0;
       slot_is(L, altro::SIM_FB, s, B * I, fb, I, "simulate: fb", c);
       expect(L.slot[altro::SIM_X0].in == x0 && L.slot[altro::SIM_W].in == w && L.slot[altro::SIM_FB].out == fb, "simulate: copies", c);
+      arg_is(L, altro::SIM_X0, "x0", false, B * nc * n * D, "simulate: arg x0", c);
+      arg_is(L, altro::SIM_W, "w", false, B * nc * (N - 1) * n * D, "simulate: arg w", c);
+      arg_is(L, altro::SIM_J, "J", false, B * nc * D, "simulate: arg J", c);
+      arg_is(L, altro::SIM_CMAX, "c_max", false, B * nc * D, "simulate: arg c_max", c);
+      arg_is(L, altro::SIM_DXMAX, "dx_max", false, B * nc * D, "simulate: arg dx_max", c);
+      arg_is(L, altro::SIM_FB, "fb", false, B * I, "simulate: arg fb", c);
+      arg_is(L, altro::SIM_XOUT, "Xout", false, B * nc * N * n * D, "simulate: arg Xout", c);
+      arg_is(L, altro::SIM_UOUT, "Uout", false, B * nc * (N - 1) * m * D, "simulate: arg Uout", c);
     }
     // altro_batch_propagate_covariance: dJ and fb have room either way, the eight others only when given; fb last (ints)
     for (int c = 0; c < 2048; ++c) {
@@ -172,15 +226,26 @@ int main() {
       expect(L.bytes == s, "covariance: size", c);
       expect(L.slot[altro::COV_S0].in == S0 && L.slot[altro::COV_W].in == W && L.slot[altro::COV_FB].out == fb && L.slot[altro::COV_SOUT].out == So,
              "covariance: copies", c);
+      arg_is(L, altro::COV_S0, "Sigma0", false, (pi ? B : 1) * n * n * D, "covariance: arg Sigma0", c);
+      arg_is(L, altro::COV_W, "W", false, (pi ? B : 1) * n * n * D, "covariance: arg W", c);
+      arg_is(L, altro::COV_SX, "sx", false, B * N * n * D, "covariance: arg sx", c);
+      arg_is(L, altro::COV_SU, "su", false, B * (N - 1) * m * D, "covariance: arg su", c);
+      arg_is(L, altro::COV_SC, "sc", false, B * nsc * D, "covariance: arg sc", c);
+      arg_is(L, altro::COV_DJ, "dJ", false, B * D, "covariance: arg dJ", c);
+      arg_is(L, altro::COV_FB, "fb", false, B * I, "covariance: arg fb", c);
+      arg_is(L, altro::COV_ZLO, "zmin_t", false, B * (n + m) * D, "covariance: arg zmin_t", c);
+      arg_is(L, altro::COV_ZHI, "zmax_t", false, B * (n + m) * D, "covariance: arg zmax_t", c);
+      arg_is(L, altro::COV_SOUT, "Sout", false, B * N * n * n * D, "covariance: arg Sout", c);
     }
     // altro_batch_solution_vjp / _jvp: three inputs and three outputs only when given, fb has room either way; fb last (ints)
-    for (int c = 0; c < 128; ++c) {
+    for (int c = 0; c < 256; ++c) {
+      const bool jvp = c & 128;   // the layout is one; the names are those of the form
       const double *ix = c & 1 ? d : nullptr, *iu = c & 2 ? d : nullptr, *i0 = c & 4 ? d : nullptr;
       double *o0 = c & 8 ? d : nullptr, *ox = c & 16 ? d : nullptr, *ou = c & 32 ? d : nullptr;
       int32_t* fb = c & 64 ? i32 : nullptr;
       const size_t R = B * nc, cx = R * N * n, cu = R * (N - 1) * m, c0 = R * n;
       StageLayout L;
-      altro::stage_solution_sens(L, B, N, n, m, nc, ix, iu, i0, o0, ox, ou, fb);
+      altro::stage_solution_sens(L, B, N, n, m, nc, jvp, ix, iu, i0, o0, ox, ou, fb);
       expect(L.nslots == 7 && L.nslots <= StageLayout::MAX_SLOTS, "solution sens: slots", c);
       size_t s = 0;
       slot_is(L, altro::SS_INX, s, ix ? cx * D : 0, ix, D, "solution sens: inx", c); s += ix ? cx * D : 0;
@@ -193,6 +258,13 @@ int main() {
       expect(L.bytes == s, "solution sens: size", c);
       expect(L.slot[altro::SS_INX].in == ix && L.slot[altro::SS_IN0].in == i0 && L.slot[altro::SS_OU].out == ou && L.slot[altro::SS_FB].out == fb,
              "solution sens: copies", c);
+      arg_is(L, altro::SS_INX, jvp ? "vXref" : "gX", false, B * nc * N * n * D, "solution sens: arg gX / vXref", c);
+      arg_is(L, altro::SS_INU, jvp ? "vUref" : "gU", false, B * nc * (N - 1) * m * D, "solution sens: arg gU / vUref", c);
+      arg_is(L, altro::SS_IN0, "vx0", false, B * nc * n * D, "solution sens: arg vx0", c);
+      arg_is(L, altro::SS_O0, "gx0", false, B * nc * n * D, "solution sens: arg gx0", c);
+      arg_is(L, altro::SS_OX, jvp ? "dX" : "gXref", false, B * nc * N * n * D, "solution sens: arg gXref / dX", c);
+      arg_is(L, altro::SS_OU, jvp ? "dU" : "gUref", false, B * nc * (N - 1) * m * D, "solution sens: arg gUref / dU", c);
+      arg_is(L, altro::SS_FB, "fb", false, B * I, "solution sens: arg fb", c);
     }
   }
   std::printf("stage_layout_check: %ld checks passed\n", checks);
