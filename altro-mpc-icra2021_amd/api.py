@@ -1466,6 +1466,117 @@ def solution_jvp(solver, vx0=None, vXref=None, vUref=None, out=None):
     return _solution_sens(solver, "solution_jvp", dict(vx0=vx0, vXref=vXref, vUref=vUref), out, ("dX", "dU"), call)
 
 
+def solution_vjp_data(solver, gX=None, gU=None, per_knot=False, out=None):
+    """Reverse-mode sensitivity of the SOLUTION of the last solve with respect to the problem data
+    (altro_batch_solution_vjp_data / _dev): for seeds gX = dl/dX* (B, N, n) and gU = dl/dU* (B, N-1, m) -- or
+    (B, nseed, ...); None is zero -- the gradients of l, as a dict: gQ, gQf (B[, nseed], n) and gR (.., m) with respect to the
+    arguments of set_tracking_cost; gzmin, gzmax (.., n+m) with respect to the box bounds; gA (.., n, n), gB (.., n, m), gf (.., n)
+    with respect to the dynamics, summed over the knots, or with per_knot=True one block per knot, (.., N-1, n, n) and so on; and
+    fb (B,) int32: 1 where solution_vjp reports 1 and the instance still holds the penalty of the stored pass, else 0 and every
+    row of the instance is NaN.  gA[..., i, j] = dl/dA[i, j]; the blocks are stored column-major, as set_dynamics_dev takes them, so
+    gA and gB are the transpose(-1, -2) of contiguous arrays (one given in out must be such a view).  Exact for the
+    minimiser of the augmented Lagrangian at the multipliers, penalty and active set of the stored pass.  gzmin, gzmax, gA, gB, gf
+    need a box-only problem (AltroError UNSUPPORTED otherwise); gQ, gQf, gR do not.  out: None (all eight), a sequence of names,
+    or a dict name -> array to write into ('fb' too); gQ, gQf, gR alone never read the active set.  GPU tensors: stream-ordered,
+    nothing synchronises; numpy: the host twin, the same bytes.  Nothing the solver holds changes."""
+    name = "solution_vjp_data"
+    n, m, N = solver.n, solver.m, solver.N
+    if gX is None and gU is None:
+        raise ValueError(f"{name}: at least one of ('gX', 'gU') is required")
+    want, fb = _sens_out(out, _lib.SENS_DATA_OUT_FIELDS, name)
+    ins = dict(gX=gX, gU=gU)
+    gpu = _gpu_form(f"{name}: the inputs and the arrays of out", tuple(ins.values()) + tuple(want.values()) + (fb,))
+    if not gpu:
+        ins = {k: (None if a is None else _c(a)) for k, a in ins.items()}
+    nseed, lead = _sens_lead(solver, ins, name)
+    kn = (N - 1,) if per_knot else ()
+    tail = dict(gQ=(n,), gQf=(n,), gR=(m,), gzmin=(n + m,), gzmax=(n + m,), gA=kn + (n, n), gB=kn + (n, m), gf=kn + (n,))
+    mats = ("gA", "gB")   # column-major blocks: an array given or returned is the transpose(-1, -2) of a contiguous one
+    st = _lib.SensDataOut()
+    if gpu:
+        import torch
+        dev = torch.device("cuda", solver.device)
+        kinds = _sens_kinds(solver)
+        for k, a in ins.items():
+            if a is not None:
+                check_device_tensor(a, lead + kinds[k], solver.device, k)
+        new = lambda k: torch.empty(lead + tail[k][:-2] + tail[k][:-3:-1], dtype=torch.float64, device=dev).transpose(-1, -2) if k in mats else \
+            torch.empty(lead + tail[k], dtype=torch.float64, device=dev)
+        res = {k: (new(k) if a is None else a) for k, a in want.items()}
+        for k, t in res.items():
+            check_device_tensor(t, lead + tail[k], solver.device, k, colmajor=k in mats)
+        if fb is None:
+            fb = torch.empty((solver.B,), dtype=torch.int32, device=dev)
+        check_device_tensor(fb, (solver.B,), solver.device, "fb", dtype="torch.int32")
+        for k, t in res.items():
+            setattr(st, k, t.data_ptr())
+        with _bracket(solver):
+            solver._chk(solver._L.altro_batch_solution_vjp_data_dev(solver.h, nseed, _addr(ins["gX"]), _addr(ins["gU"]), 1 if per_knot else 0,
+                                                                    C.byref(st), _addr(fb)))
+    else:
+        new = lambda k: np.swapaxes(np.empty(lead + tail[k][:-2] + tail[k][:-3:-1]), -1, -2) if k in mats else np.empty(lead + tail[k])
+        res = {k: (new(k) if a is None else a) for k, a in want.items()}
+        for k, a in res.items():
+            if not (isinstance(a, np.ndarray) and a.shape == lead + tail[k]):
+                raise ValueError(f"{name}: {k} must be a float64 array of shape {lead + tail[k]}")
+            raw = np.swapaxes(a, -1, -2) if k in mats else a
+            _check_np_out(name, k + (" (transposed: the blocks are column-major)" if k in mats else ""), raw, raw.shape)
+            setattr(st, k, raw.ctypes.data)
+        if fb is None:
+            fb = np.empty(solver.B, dtype=np.int32)
+        _check_np_out(name, "fb", fb, (solver.B,), np.int32)
+        solver._chk(solver._L.altro_batch_solution_vjp_data(solver.h, nseed, _p(ins["gX"]), _p(ins["gU"]), 1 if per_knot else 0, C.byref(st),
+                                                            fb.ctypes.data_as(_IP)))
+    res["fb"] = fb
+    return res
+
+
+def gain_active_set(solver, out=None):
+    """The active set and the penalty of the backward pass that left the stored gains (altro_batch_get_gain_active_set / _dev), as a
+    dict: codes (B, N, n+m) uint8 -- bit 0: the upper side of the element entered that pass's Hessian at the knot, bit 1: the
+    lower side; the region of the piecewise-affine solution map the instance is in -- mu_pass (B,) and fb (B,) int32 (0: no valid
+    gains of an unregularised pass at the penalty held; codes 0, mu_pass NaN).  out: None -> new GPU tensors; a dict name -> array
+    to write into chooses the form: GPU tensors (stream-ordered) or numpy arrays (the host twin, the same bytes); "numpy" -> new
+    numpy arrays.  Box-only problems (AltroError UNSUPPORTED otherwise).  Nothing the solver holds changes."""
+    name = "gain_active_set"
+    shp = dict(codes=(solver.B, solver.N, solver.n + solver.m), mu_pass=(solver.B,), fb=(solver.B,))
+    if isinstance(out, str):
+        if out != "numpy":
+            raise ValueError(f"{name}: out: {out!r}; a dict of arrays, None or 'numpy'")
+        out = dict(codes=np.empty(shp["codes"], dtype=np.uint8), mu_pass=np.empty(shp["mu_pass"]), fb=np.empty(shp["fb"], dtype=np.int32))
+    out = dict(out or {})
+    unknown = [k for k in out if k not in shp]
+    if unknown:
+        raise ValueError(f"{name}: out: unknown output {unknown[0]!r}; the outputs are ('codes', 'mu_pass', 'fb')")
+    gpu = not out or _gpu_form(f"{name}: the arrays of out", tuple(out.values()))
+    if gpu:
+        import torch
+        dev = torch.device("cuda", solver.device)
+        if not out:
+            out = dict(codes=None, mu_pass=None)
+        if "codes" not in out and "mu_pass" not in out:
+            raise ValueError(f"{name}: out needs 'codes' or 'mu_pass'")
+        dt = dict(codes=torch.uint8, mu_pass=torch.float64, fb=torch.int32)
+        out.setdefault("fb", None)
+        res = {k: (torch.empty(shp[k], dtype=dt[k], device=dev) if a is None else a) for k, a in out.items()}
+        for k, t in res.items():
+            check_device_tensor(t, shp[k], solver.device, k, dtype=str(dt[k]))
+        ptr = lambda k: res[k].data_ptr() if k in res else None
+        with _bracket(solver):
+            solver._chk(solver._L.altro_batch_get_gain_active_set_dev(solver.h, ptr("codes"), ptr("mu_pass"), ptr("fb")))
+        return res
+    if "codes" not in out and "mu_pass" not in out:
+        raise ValueError(f"{name}: out needs 'codes' or 'mu_pass'")
+    dt = dict(codes=np.uint8, mu_pass=np.float64, fb=np.int32)
+    out.setdefault("fb", None)
+    res = {k: (np.empty(shp[k], dtype=dt[k]) if a is None else a) for k, a in out.items()}
+    for k, a in res.items():
+        _check_np_out(name, k, a, shp[k], dt[k])
+    cp = lambda k, t: res[k].ctypes.data_as(t) if k in res else None
+    solver._chk(solver._L.altro_batch_get_gain_active_set(solver.h, cp("codes", C.POINTER(C.c_uint8)), cp("mu_pass", _DP), cp("fb", _IP)))
+    return res
+
+
 _solution_fn = None
 
 
@@ -1533,6 +1644,120 @@ def solution(solver, x0, Xref, Uref, invalid="raise"):
     if not (_on_gpu(x0) and _on_gpu(Xref) and _on_gpu(Uref)):
         raise ValueError("solution: x0, Xref and Uref must be GPU tensors")
     return _solution_function().apply(solver, x0, Xref, Uref, invalid)
+
+
+_mpc_layer_fn = None
+_LAYER_DATA = ("A", "B", "f", "Q", "R", "Qf", "zmin", "zmax")
+
+
+def _mpc_layer_function():
+    """the torch.autograd.Function behind mpc_layer, made on first use (the package imports without torch)"""
+    global _mpc_layer_fn
+    if _mpc_layer_fn is not None:
+        return _mpc_layer_fn
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class MPCLayer(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, solver, invalid, box, x0, Xref, Uref, A, Bm, f, Q, R, Qf, zmin, zmax):
+            B, n, m, N = solver.B, solver.n, solver.m, solver.N
+            # everything validated before the first setter: a refused tensor leaves the solver as it was
+            check_device_tensor(x0, (B, n), solver.device, "x0")
+            check_device_tensor(Xref, (B, N, n), solver.device, "Xref")
+            check_device_tensor(Uref, (B, N - 1, m), solver.device, "Uref")
+            per_knot = A is not None and A.dim() == 4
+            if A is not None:
+                kn = (N - 1,) if per_knot else ()
+                check_device_tensor(A, (B,) + kn + (n, n), solver.device, "A", colmajor=True)
+                check_device_tensor(Bm, (B,) + kn + (n, m), solver.device, "B", colmajor=True)
+                check_device_tensor(f, (B,) + kn + (n,), solver.device, "f")
+            if Q is not None:
+                for nm, t, k in (("Q", Q, n), ("R", R, m), ("Qf", Qf, n)):
+                    check_device_tensor(t, (B, k), solver.device, nm)
+            if zmin is not None:
+                check_device_tensor(zmin, (B, n + m), solver.device, "zmin")
+                check_device_tensor(zmax, (B, n + m), solver.device, "zmax")
+            if Q is not None:   # (the host setter: it synchronises)
+                set_tracking_cost(solver, Q.detach().cpu().numpy(), R.detach().cpu().numpy(), Qf.detach().cpu().numpy())
+            X = torch.empty((B, N, n), dtype=torch.float64, device=x0.device)
+            U = torch.empty((B, N - 1, m), dtype=torch.float64, device=x0.device)
+            with _bracket(solver):
+                if A is not None:
+                    solver._chk(solver._L.altro_batch_set_dynamics_dev(solver.h, _addr(A.detach()), _addr(Bm.detach()), _addr(f.detach()),
+                                                                       int(per_knot), 1))
+                if zmin is not None:
+                    _set_bounds_dev(solver, box, zmin.detach(), zmax.detach())
+                _set_initial_state_dev(solver, x0.detach())
+                _update_trajectory_dev(solver, Xref.detach(), Uref.detach())
+                solver._chk(solver._L.altro_batch_solve_async(solver.h))
+                solver._chk(solver._L.altro_batch_get_states_dev(solver.h, _addr(X)))
+                solver._chk(solver._L.altro_batch_get_controls_dev(solver.h, _addr(U)))
+            # the validity of what the backward will go through, read once
+            data = any(t is not None for t in (A, Q, zmin))
+            if data:
+                fb = solution_vjp_data(solver, gX=torch.zeros_like(X), out=("gQf",))["fb"]
+            else:
+                fb = solution_jvp(solver, vx0=torch.zeros_like(x0), out=("dU",))["fb"]
+            bad = (fb == 0).nonzero().flatten().tolist()
+            if bad and invalid != "zero":
+                raise AltroError(_lib.ERR_STATE, f"mpc_layer: instances {bad} hold no valid gains of an unregularised backward pass at the "
+                                 "penalty they hold: the solution is not differentiable through them (invalid='zero' zeroes their gradients)")
+            ctx.solver, ctx.per_knot = solver, per_knot
+            ctx.bad = (fb == 0) if bad else None
+            return X, U
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, gX, gU):
+            solver, need = ctx.solver, ctx.needs_input_grad[3:]
+            gX, gU = gX.contiguous(), gU.contiguous()
+            grads = {}
+            names = tuple(k for k, nd in zip(("gx0", "gXref", "gUref"), need[:3]) if nd)
+            if names:
+                grads.update(solution_vjp(solver, gX, gU, out=names))
+            names = tuple("g" + k for k, nd in zip(_LAYER_DATA, need[3:]) if nd)
+            if names:
+                grads.update(solution_vjp_data(solver, gX, gU, per_knot=ctx.per_knot, out=names))
+            grads.pop("fb", None)
+            if ctx.bad is not None:
+                for t in grads.values():
+                    t[ctx.bad] = 0.0
+            return (None, None, None) + tuple(grads.get(k) for k in ("gx0", "gXref", "gUref") + tuple("g" + k for k in _LAYER_DATA))
+
+    _mpc_layer_fn = MPCLayer
+    return MPCLayer
+
+
+def mpc_layer(solver, x0, Xref, Uref, *, A=None, B=None, f=None, Q=None, R=None, Qf=None, zmin=None, zmax=None, invalid="raise"):
+    """solution() with the problem data as further differentiable inputs: the solution (X, U) of a solve as tensors torch can
+    differentiate once with respect to x0 (B, n), Xref (B, N, n), Uref (B, N-1, m) and whichever of these are given as tensors --
+    the dynamics A (B, n, n), B (B, n, m), f (B, n) per instance, or (B, N-1, ..) per knot (all three together; A and B stored
+    column-major, the transpose(-1, -2) of contiguous tensors, as set_dynamics takes them); the cost weights Q (B, n), R (B, m),
+    Qf (B, n) (all three together); the bounds zmin, zmax (B, n+m) of the problem's BOX constraint (both together; infinite sides
+    stay infinite).  None means what the solver holds.  GPU tensors on the solver's device, float64; one that is not as
+    described is refused with ValueError before anything is installed.  Forward CHANGES THE SOLVER: it installs what is given
+    -- dynamics and bounds through the device setters, per instance; the weights through
+    altro_batch_set_tracking_cost_per_instance, a host call that copies them to the host and SYNCHRONISES -- solves, and returns
+    the trajectory the solver holds.  Backward is one solution_vjp call and one solution_vjp_data call through the gains the
+    solve stored: the exact derivative of the minimiser of the augmented Lagrangian at the multipliers, penalty and active set
+    of the last backward pass, so the solver must not be changed between forward and backward.  Derivatives
+    with respect to the dynamics and the bounds need a box-only problem.  The forward reads the validity of the stored gains
+    once (it synchronises): invalid means what it means in solution()."""
+    if invalid not in ("raise", "zero"):
+        raise ValueError("mpc_layer: invalid must be 'raise' or 'zero'")
+    data = dict(A=A, B=B, f=f, Q=Q, R=R, Qf=Qf, zmin=zmin, zmax=zmax)
+    if not all(_on_gpu(t) for t in (x0, Xref, Uref)) or not all(t is None or _on_gpu(t) for t in data.values()):
+        raise ValueError("mpc_layer: x0, Xref, Uref and the data given must be GPU tensors")
+    for group in (("A", "B", "f"), ("Q", "R", "Qf"), ("zmin", "zmax")):
+        if len({data[k] is None for k in group}) != 1:
+            raise ValueError(f"mpc_layer: {', '.join(group)} go together: all or none")
+    box = None
+    if zmin is not None:
+        box = next((i for i, (con, _, _) in enumerate(solver.prob.constraints.items) if isinstance(con, BoundConstraint)), None)
+        if box is None:
+            raise ValueError("mpc_layer: zmin / zmax need a BOX constraint on the problem")
+    return _mpc_layer_function().apply(solver, invalid, box, x0, Xref, Uref, A, B, f, Q, R, Qf, zmin, zmax)
 
 
 def rollout(solver, U, x0=None, out=None):

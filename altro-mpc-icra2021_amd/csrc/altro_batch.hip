@@ -19,6 +19,7 @@
 #include "evaluate.h"
 #include "evaluate_grad.h"
 #include "evaluate_al.h"
+#include "sensitivity_data.h"
 #include "launch_ring.h"
 #include "pn_polish.h"
 #include "policy.h"
@@ -2217,6 +2218,7 @@ struct TwinArgs : altro::StageLayout {
   void* dev(int i) const { return !host ? const_cast<void*>(slot[i].arg()) : slot[i].dev ? base + slot[i].off : nullptr; }
   double* f64(int i) const { return static_cast<double*>(dev(i)); }
   int32_t* i32(int i) const { return static_cast<int32_t*>(dev(i)); }
+  uint8_t* u8(int i) const { return static_cast<uint8_t*>(dev(i)); }
   int close() {
     for (int i = 0; i < nslots; ++i)
       if (slot[i].out) HIPCHK(h, hipMemcpyAsync(slot[i].out, base + slot[i].off, slot[i].bytes, hipMemcpyDeviceToHost, st));
@@ -2784,6 +2786,112 @@ int32_t altro_batch_get_gain_factors_dev(altro_handle* h, double* F) {
     HIPCHK(h, hipGetLastError());
     return ALTRO_OK;
   });
+}
+
+// ---- sensitivity of the solution with respect to cost weights, box bounds and dynamics; the active set of the stored pass
+// (kernels in sensitivity_data.h).  What the active-set outputs (gzmin, gzmax, gA, gB, gf) and the getter need: a
+// box-only problem, and on the 16-lane backend a horizon the exact sets cover.
+static int active_set_rules(altro_handle* h, const std::string& f) {
+  const bool rows = h->wide ? h->wide->Pn > 0 : h->ncrows > 0;
+  if (rows)
+    FAIL(h, ALTRO_ERR_UNSUPPORTED, f + ": the active set of the stored pass is kept for box-only problems: with LINEAR or SOC rows the Hessian "
+                                       "inside it is not diagonal (gQ, gQf, gR are available)");
+  if (!h->wide && h->d.N > altro::ASET_MAXN)
+    FAIL(h, ALTRO_ERR_UNSUPPORTED, f + ": the 16-lane kernels keep the exact active set for N <= 128 (gQ, gQf, gR are available)");
+  return ALTRO_OK;
+}
+// the argument rules both forms share, checked before anything else
+static int sens_data_rules(altro_handle* h, const char* fn, int32_t nseed, const double* gX, const double* gU, int32_t per_knot,
+                           const altro_sens_data_out* out) {
+  const std::string f(fn);
+  if (nseed < 1) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": nseed must be at least 1");
+  if (!gX && !gU) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": gX and gU are both null");
+  if (!out) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": out is required");
+  const bool want_set = out->gzmin || out->gzmax || out->gA || out->gB || out->gf;
+  if (!want_set && !out->gQ && !out->gQf && !out->gR) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": every member of out is null");
+  if (per_knot != 0 && per_knot != 1) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": per_knot must be 0 or 1");
+  if (h->wide && h->d.m > 16)
+    FAIL(h, ALTRO_ERR_UNSUPPORTED, f + ": the one-wave-per-instance kernels keep no factors of Quu for m > 16: no data sensitivity is available");
+  if (want_set)
+    if (int rc = active_set_rules(h, f)) return rc;
+  return ALTRO_OK;
+}
+
+// io: device arrays (the caller's, validated; or the staged copies of the host twin).  Enqueues one kernel; allocates only when
+// the workspace that carries d_k and dz_k between the sweeps has to grow.
+static int sens_data_launch(altro_handle* h, int32_t nseed, altro::SensDataIO io) {
+  if (h->wide) return fwd(h, h->wide->solution_vjp_data_dev(nseed, io));
+  if (int rc = score_ready(h)) return rc;
+  const size_t B = h->d.batch, N = h->d.N, n = h->d.n, m = h->d.m;
+  const size_t R = B * (size_t)nseed, ld = (N - 1) * m, lz = N * (n + m);
+  const bool want3 = io.gA || io.gB || io.gf;
+  HIPCHK(h, h->pool.reserve(&h->eval_ws, &h->eval_ws_elems, R * (ld + (want3 ? lz : 0))));
+  io.dws = h->eval_ws;
+  io.zws = want3 ? h->eval_ws + R * ld : nullptr;
+  io.Lb = h->Lb; io.mu = h->mu; io.bslot = h->bslot; io.nbp = h->nbp; io.dt = h->dt;
+  const size_t rows = (R + 3) & ~(size_t)3;   // whole waves of four rows
+  hipLaunchKernelGGL(altro::k_sens_data16, grid_for(rows * LW), dim3(256), 0, h->stream, io, h->Z, h->cur, N * (size_t)LW, h->KD, h->kmu,
+                     h->ahash, eval16_params(h), (int)nseed, R, rows);
+  HIPCHK(h, hipGetLastError());
+  return ALTRO_OK;
+}
+
+static int32_t sens_data_call(altro_handle* h, const char* fn, bool host, int32_t nseed, const double* gX, const double* gU, int32_t per_knot,
+                              const altro_sens_data_out* out, int32_t* fb) {
+  return twin_call(
+      h, fn, host, true, [&] { return sens_data_rules(h, fn, nseed, gX, gU, per_knot, out); },
+      [&](TwinArgs& a) {
+        double* const po[8] = {out->gQ, out->gQf, out->gR, out->gzmin, out->gzmax, out->gA, out->gB, out->gf};
+        altro::stage_solution_vjp_data(a, h->d.batch, h->d.N, h->d.n, h->d.m, nseed, per_knot, gX, gU, po, fb);
+      },
+      [&](const TwinArgs& a) {
+        altro::SensDataIO io{};
+        io.gX = a.f64(altro::SD_GX); io.gU = a.f64(altro::SD_GU);
+        io.gQ = a.f64(altro::SD_GQ); io.gQf = a.f64(altro::SD_GQF); io.gR = a.f64(altro::SD_GR);
+        io.gzmin = a.f64(altro::SD_GZMIN); io.gzmax = a.f64(altro::SD_GZMAX);
+        io.gA = a.f64(altro::SD_GA); io.gB = a.f64(altro::SD_GB); io.gf = a.f64(altro::SD_GF);
+        io.fb = a.i32(altro::SD_FB);
+        io.per_knot = per_knot;
+        return sens_data_launch(h, nseed, io);
+      });
+}
+int32_t altro_batch_solution_vjp_data_dev(altro_handle* h, int32_t nseed, const double* gX, const double* gU, int32_t per_knot,
+                                          const altro_sens_data_out* out, int32_t* fb) {
+  return sens_data_call(h, "altro_batch_solution_vjp_data_dev", false, nseed, gX, gU, per_knot, out, fb);
+}
+int32_t altro_batch_solution_vjp_data(altro_handle* h, int32_t nseed, const double* gX, const double* gU, int32_t per_knot,
+                                      const altro_sens_data_out* out, int32_t* fb) {
+  return sens_data_call(h, "altro_batch_solution_vjp_data", true, nseed, gX, gU, per_knot, out, fb);
+}
+
+// codes, mu_pass, fb: device arrays (the caller's, validated; or the staged copies of the host twin).  Enqueues one kernel.
+static int gain_active_set_launch(altro_handle* h, uint8_t* codes, double* mu_pass, int32_t* fb) {
+  if (h->wide) return fwd(h, h->wide->get_gain_active_set_dev(codes, mu_pass, fb));
+  const size_t B = h->d.batch, N = h->d.N, n = h->d.n, m = h->d.m;
+  hipLaunchKernelGGL(altro::k_gain_aset16, grid_for(B * N * (n + m)), dim3(256), 0, h->stream, codes, mu_pass, fb, h->ahash, h->kmu, h->mu, (int)B,
+                     (int)N, (int)n, (int)m);
+  HIPCHK(h, hipGetLastError());
+  return ALTRO_OK;
+}
+static int32_t gain_active_set_call(altro_handle* h, const char* fn, bool host, uint8_t* codes, double* mu_pass, int32_t* fb) {
+  return twin_call(
+      h, fn, host, true,
+      [&]() -> int {
+        if (!codes && !mu_pass) FAIL(h, ALTRO_ERR_INVALID_ARG, std::string(fn) + ": codes and mu_pass are both null");
+        return active_set_rules(h, fn);
+      },
+      [&](TwinArgs& a) { altro::stage_gain_active_set(a, h->d.batch, h->d.N, h->d.n, h->d.m, codes, mu_pass, fb); },
+      [&](const TwinArgs& a) -> int {
+        if (!host)
+          if (int rc = h->wide ? fwd(h, h->wide->eval_ready()) : score_ready(h)) return rc;
+        return gain_active_set_launch(h, a.u8(altro::GA_CODES), a.f64(altro::GA_MU), a.i32(altro::GA_FB));
+      });
+}
+int32_t altro_batch_get_gain_active_set_dev(altro_handle* h, uint8_t* codes, double* mu_pass, int32_t* fb) {
+  return gain_active_set_call(h, "altro_batch_get_gain_active_set_dev", false, codes, mu_pass, fb);
+}
+int32_t altro_batch_get_gain_active_set(altro_handle* h, uint8_t* codes, double* mu_pass, int32_t* fb) {
+  return gain_active_set_call(h, "altro_batch_get_gain_active_set", true, codes, mu_pass, fb);
 }
 
 // ---- per-instance active mask and cold restart

@@ -1,6 +1,7 @@
 // stage_layout.h -- the argument table of each host/device twin pair (altro_batch_eval_policy, altro_batch_evaluate,
 // altro_batch_evaluate_grad, altro_batch_evaluate_al, altro_batch_warm_start, altro_batch_simulate_policy,
-// altro_batch_propagate_covariance, altro_batch_solution_vjp, altro_batch_solution_jvp and their `_dev` forms): one function per
+// altro_batch_propagate_covariance, altro_batch_solution_vjp, altro_batch_solution_jvp, altro_batch_solution_vjp_data,
+// altro_batch_get_gain_active_set and their `_dev` forms): one function per
 // pair names every array argument once, with its element count, type, direction and mode.  The `_dev` form validates the caller's
 // pointers against the extents written here; the host twin puts the same arrays, in the same order, into the handle's staging buffer.
 // Plain host arithmetic, no HIP: altro_batch.hip's TwinArgs adds the validation and the copies, and tools/stage_layout_check.cpp runs
@@ -151,6 +152,29 @@ inline void stage_solution_sens(StageLayout& L, size_t B, size_t N, size_t n, si
   L.add<double>(jvp ? "dX" : "gXref", R * N * n, nullptr, ox, StageLayout::OPTIONAL);
   L.add<double>(jvp ? "dU" : "gUref", R * (N - 1) * m, nullptr, ou, StageLayout::OPTIONAL);
   L.add<int32_t>("fb", B, nullptr, fb, StageLayout::RESERVED);
+}
+
+// out[0 .. 7]: the eight pointers of altro_sens_data_out in the order of the struct; every sub-array only when given.  K1 = N - 1
+// blocks of gA, gB, gf per row with per_knot, else one.
+enum { SD_GX, SD_GU, SD_GQ, SD_GQF, SD_GR, SD_GZMIN, SD_GZMAX, SD_GA, SD_GB, SD_GF, SD_FB };
+inline void stage_solution_vjp_data(StageLayout& L, size_t B, size_t N, size_t n, size_t m, size_t nseed, size_t per_knot, const double* gX,
+                                    const double* gU, double* const (&out)[8], int32_t* fb) {
+  const size_t R = B * nseed, K1 = per_knot ? N - 1 : 1;
+  const char* const name[8] = {"gQ", "gQf", "gR", "gzmin", "gzmax", "gA", "gB", "gf"};
+  const size_t count[8] = {R * n, R * n, R * m, R * (n + m), R * (n + m), R * K1 * n * n, R * K1 * n * m, R * K1 * n};
+  L.add<double>("gX", R * N * n, gX, nullptr, StageLayout::OPTIONAL);
+  L.add<double>("gU", R * (N - 1) * m, gU, nullptr, StageLayout::OPTIONAL);
+  for (int i = 0; i < 8; ++i) L.add<double>(name[i], count[i], nullptr, out[i], StageLayout::OPTIONAL);
+  L.add<int32_t>("fb", B, nullptr, fb, StageLayout::RESERVED);
+}
+
+// codes last: the doubles and the ints stay aligned whatever its byte count
+enum { GA_MU, GA_FB, GA_CODES };
+inline void stage_gain_active_set(StageLayout& L, size_t B, size_t N, size_t n, size_t m, uint8_t* codes, double* mu_pass, int32_t* fb) {
+  const size_t nc = B * N * (n + m);
+  L.add<double>("mu_pass", B, nullptr, mu_pass, StageLayout::OPTIONAL);
+  L.add<int32_t>("fb", B, nullptr, fb, StageLayout::RESERVED);
+  L.add<uint8_t>("codes", nc, nullptr, codes, StageLayout::OPTIONAL);
 }
 
 }  // namespace altro

@@ -15,6 +15,7 @@
 #include "evaluate.h"
 #include "evaluate_grad.h"
 #include "sensitivity.h"
+#include "sensitivity_data.h"
 #include "evaluate_al.h"
 #include "warm_start.h"
 #include "simulate.h"
@@ -874,6 +875,44 @@ struct WideBackend : altro::BackendCommon {   // (what both backends hold and do
     const size_t thr = (size_t)d.batch * (d.N - 1) * d.m * d.m;
     hipLaunchKernelGGL(altro::k_unpack_factors_wide, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, stream, Fd, fac, wide_fac_size(d.m), d.batch,
                        d.N, d.m);
+    WCHK(hipGetLastError());
+    return ALTRO_OK;
+  }
+  // altro_batch_solution_vjp_data_dev (sensitivity_data.h; pointers and argument rules checked by the caller, the host twin
+  // passes staged copies): one kernel over batch * nseed waves.  Reads what solution_sens_dev reads, the planes the handle holds
+  // and -- only when an output needs them -- the active set of the last backward pass, the duals and the penalty; writes the
+  // caller's outputs and eval_ws (d_k, dz_k between the sweeps) only.  Every output needs d_k: m > 16 is refused.  The active-set
+  // outputs need a diagonal Hessian: generic rows are refused.
+  int solution_vjp_data_dev(int nseed, altro::SensDataIO io) {
+    WCHK(hipSetDevice(device));
+    const bool want_set = io.gzmin || io.gzmax || io.gA || io.gB || io.gf, want3 = io.gA || io.gB || io.gf;
+    if (d.m > 16) WFAIL(ALTRO_ERR_UNSUPPORTED, "the one-wave-per-instance kernels keep no factors of Quu for m > 16: no data sensitivity is available");
+    if (want_set && Pn > 0)
+      WFAIL(ALTRO_ERR_UNSUPPORTED, "gzmin, gzmax, gA, gB and gf need a box-only problem: with LINEAR or SOC rows the Hessian inside the active set is not diagonal");
+    if (int rc = eval_ready()) return rc;
+    const size_t R = (size_t)d.batch * nseed, ld = (size_t)(d.N - 1) * d.m, lz = (size_t)d.N * nz();
+    WCHK(pool.reserve(&eval_ws, &eval_ws_elems, R * (ld + (want3 ? lz : 0))));
+    io.dws = eval_ws;
+    io.zws = want3 ? eval_ws + R * ld : nullptr;
+    io.Lb = Lb; io.mu = mu; io.bslot = nullptr; io.nbp = 0; io.dt = cost_dt;
+    // the accumulators of gA, gB in LDS (per_knot = 0): four waves a block while they fit the 64 KB a kernel gets unasked, else
+    // one (n <= 64, m <= 16: a wave's accumulators take 65 * 80 * 8 = 41600 bytes at the most)
+    const size_t acc = (!io.per_knot && (io.gA || io.gB)) ? (size_t)(d.n | 1) * nz() * sizeof(double) : 0;
+    const int wpb = 4 * acc <= 65536 ? 4 : 1;
+    const size_t lds = acc * wpb;
+    if (lds > 65536) WFAIL(ALTRO_ERR_INTERNAL, "solution_vjp_data: the accumulators of one wave exceed 64 KB");
+    hipLaunchKernelGGL(altro::k_sens_data_wide, dim3((unsigned)((R + wpb - 1) / wpb)), dim3(64 * wpb), lds, stream, io, X, U, cur, Kg, fac,
+                       wide_fac_size(d.m), bwst, aset, (gains_valid || debug_keep_gains) ? 1 : 0, eval_params(), nseed, R);
+    WCHK(hipGetLastError());
+    return ALTRO_OK;
+  }
+  // altro_batch_get_gain_active_set_dev: the plane of the last backward pass of aset, unpacked to one code per knot and element
+  int get_gain_active_set_dev(unsigned char* codes, double* mu_pass, int32_t* fb) {
+    WCHK(hipSetDevice(device));
+    if (Pn > 0) WFAIL(ALTRO_ERR_UNSUPPORTED, "the active set of the stored pass is available for box-only problems");
+    const size_t thr = (size_t)d.batch * d.N * nz();
+    hipLaunchKernelGGL(altro::k_gain_aset_wide, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, stream, codes, mu_pass, fb, aset, bwst,
+                       (gains_valid || debug_keep_gains) ? 1 : 0, mu, d.batch, d.N, d.n, d.m);
     WCHK(hipGetLastError());
     return ALTRO_OK;
   }

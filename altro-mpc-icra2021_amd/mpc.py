@@ -362,6 +362,12 @@ class ExternalMPC:
         gains (api.solution_vjp): a pass-through, GPU tensors or numpy."""
         return api.solution_vjp(self.solver, gX=gX, gU=gU, out=out)
 
+    def solution_vjp_data(self, gX=None, gU=None, per_knot=False, out=None):
+        """the gradients of a loss on the solution the solver holds with respect to the cost weights, the box bounds and the
+        dynamics, through the stored gains and the active set of their pass (api.solution_vjp_data): a pass-through, GPU
+        tensors or numpy."""
+        return api.solution_vjp_data(self.solver, gX=gX, gU=gU, per_knot=per_knot, out=out)
+
     def solution_jvp(self, vx0=None, vXref=None, vUref=None, out=None):
         """the directional derivatives of the solution the solver holds along tangents of x0 and the reference, through the
         stored gains (api.solution_jvp): a pass-through, GPU tensors or numpy."""

@@ -734,6 +734,64 @@ int32_t altro_batch_solution_jvp(altro_handle* h, int32_t nseed, const double* v
                                  double* dX, double* dU, int32_t* fb);
 int32_t altro_batch_get_gain_factors_dev(altro_handle* h, double* F);
 
+/* ---- sensitivity of the SOLUTION of the last solve with respect to the cost weights, the box bounds and the dynamics, and the
+ * active set of the stored pass, on the device: what training a cost or a model through the solver needs.  With
+ * box terms only, the Hessian of the augmented Lagrangian inside the active set of the stored backward pass is diagonal,
+ *   hz_{k,j} = w_{k,j} + mu_p [upper side of element j in the set at knot k] + mu_p [lower side],   mu_p the penalty of that pass,
+ * so next to the two sweeps of altro_batch_solution_vjp_dev, (s_0, xi, nu) = Lin((gX, gU), 0), one more backward sweep gives the
+ * costate of the sensitivity problem, and no value Hessian is needed.  With (x_k, u_k) the trajectory the handle holds,
+ * e = z - zref, dz = (xi, nu), and lam_k the costate of altro_batch_evaluate_al_dev at U == NULL on that trajectory
+ * (lam_{N-1} = Qf e_x + c_x, lam_k = dt Q e_x + c_x + A_k' lam_{k+1}):
+ *   dlam_{N-1} = gX_{N-1} + hz_{N-1} xi_{N-1};   dlam_k = gX_k + hz_k xi_k + A_k' dlam_{k+1},  k = N-2 .. 0
+ *   gQ_j  = dt sum_{k<N-1} xi_k[j] e_k[j]      gQf_j = xi_{N-1}[j] e_{N-1}[j]      gR_a = dt sum_k nu_k[a] e_{u,k}[a]
+ *   gzmax_e = -mu_p sum_k [upper side of e in the set at k] dz_k[e]      gzmin_e = -mu_p sum_k [lower side ..] dz_k[e]
+ *   gA_k = lam_{k+1} xi_k' + dlam_{k+1} x_k'      gB_k = lam_{k+1} nu_k' + dlam_{k+1} u_k'      gf_k = dlam_{k+1}
+ * gQ, gQf, gR are derivatives with respect to the ARGUMENTS of altro_batch_set_tracking_cost (they carry dt, as those of
+ * altro_al_out); gzmin, gzmax are +0 on sides that are not in the set (infinite sides never are).  As for
+ * altro_batch_solution_vjp_dev the result is the exact derivative of the minimiser of the augmented Lagrangian at the
+ * multipliers, the penalty and the active set of the stored pass; its distance to the derivative of the constrained optimum
+ * has not been measured.  There is no forward mode: the response of the solution to a tangent of the dynamics needs the
+ * value Hessians S_k, which no kernel keeps.
+ * altro_batch_solution_vjp_data_dev: nseed >= 1 seeds per instance, gX [batch][nseed][N][n], gU [batch][nseed][N-1][m] (a NULL
+ * one is zero, not both); out a struct of output pointers, each may be NULL, not all:
+ *     gQ, gQf       [batch][nseed][n]            gR   [batch][nseed][m]            gzmin, gzmax   [batch][nseed][n+m]
+ *     per_knot = 0: gA [batch][nseed][n x n], gB [batch][nseed][n x m], gf [batch][nseed][n]: the blocks summed over the knots --
+ *       the derivative with respect to a time-invariant block; on a handle with per-knot dynamics, with respect to a
+ *       perturbation common to all blocks of the window
+ *     per_knot = 1: the same blocks per knot, [batch][nseed][N-1][..]
+ *   Matrices are column-major, as altro_batch_set_dynamics takes them.  Derivatives are per (instance, seed), also where the
+ *   handle shares the datum across the batch (the derivative with respect to a shared datum is their sum).  The window, the
+ *   dynamics blocks, the weights, the bounds and the duals are those altro_batch_evaluate_al_dev sees at that point of the stream.
+ * altro_batch_get_gain_active_set_dev: codes [batch][N][n+m] bytes: bit 0 = the upper side of the element entered the Hessian of
+ * the stored pass at that knot, bit 1 = the lower side (control columns at knot N-1: 0); mu_pass [batch]: the penalty of that
+ * pass.  Either may be NULL, not both; fb [batch] may be NULL.  codes is the region of the piecewise-affine solution map the
+ * instance is in.
+ * fb[b] = 1 iff altro_batch_solution_vjp_dev would report 1 AND the penalty the instance holds (altro_batch_get_penalty) equals
+ * the penalty of the stored pass; otherwise fb[b] = 0 and every output row of the instance is a quiet NaN (the getter: codes 0,
+ * mu_pass NaN).  Which outputs are NULL changes no other output and not fb.  No masking, no status; a NaN stays a NaN.  Nothing
+ * the library owns changes: the stored gains stay, and the next solve is that of a handle that never made the call.  Row (b, s)
+ * gets the bytes it would get alone (nseed = 1) or on a batch-1 handle holding instance b's data.  Summation orders:
+ * csrc/sensitivity_data.h.  The _dev forms follow the rules of the device-pointer block (validated before anything is
+ * enqueued, stream-ordered, no host synchronisation, no caller pointer kept); the only allocation is the grow-only workspace
+ * of altro_batch_evaluate_dev, batch * nseed * ((N-1) m [+ N (n+m) with gA, gB or gf]) doubles.  The host twins go through the
+ * staging buffer, synchronise and write the same bytes.
+ * ALTRO_ERR_INVALID_ARG (nothing enqueued, the handle unchanged and usable): NULL handle; nseed < 1; gX and gU both NULL; out
+ * NULL or all eight members NULL; per_knot not 0 or 1; the getter: codes and mu_pass both NULL; _dev: what the device-pointer
+ * block refuses.  ALTRO_ERR_STATE: as altro_batch_evaluate_dev.  ALTRO_ERR_UNSUPPORTED (nothing enqueued): gzmin, gzmax, gA, gB,
+ * gf and the getter on a handle that holds a LINEAR or SOC constraint (the Hessian inside the set is not diagonal, and the
+ * conic 16-lane kernels keep no exact set) or on the 16-lane kernels with N > 128 (the exact set covers 128 knots); every
+ * output on the one-wave-per-instance kernels with m > 16 (all need d_k, no factors of Quu are kept there).  gQ, gQf, gR work
+ * wherever the full altro_batch_solution_vjp_dev works, conic handles included. */
+typedef struct altro_sens_data_out {
+  double *gQ, *gQf, *gR, *gzmin, *gzmax, *gA, *gB, *gf;
+} altro_sens_data_out;
+int32_t altro_batch_solution_vjp_data_dev(altro_handle* h, int32_t nseed, const double* gX, const double* gU, int32_t per_knot,
+                                          const altro_sens_data_out* out, int32_t* fb);
+int32_t altro_batch_solution_vjp_data(altro_handle* h, int32_t nseed, const double* gX, const double* gU, int32_t per_knot,
+                                      const altro_sens_data_out* out, int32_t* fb);
+int32_t altro_batch_get_gain_active_set_dev(altro_handle* h, uint8_t* codes, double* mu_pass, int32_t* fb);
+int32_t altro_batch_get_gain_active_set(altro_handle* h, uint8_t* codes, double* mu_pass, int32_t* fb);
+
 /* ---- warm start from the best of several candidates, chosen on the device.  The closed loops of the reference start every
  * solve from ONE guess (the shifted previous solution: random_linear_problem.jl:136, simple_rocket.jl:160); a loop that also
  * holds the reference controls and a learned or sampled guess wants the best of them, and the 20-step launch lasts as long as

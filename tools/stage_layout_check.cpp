@@ -266,6 +266,56 @@ int main() {
       arg_is(L, altro::SS_OU, jvp ? "dU" : "gUref", false, B * nc * (N - 1) * m * D, "solution sens: arg gUref / dU", c);
       arg_is(L, altro::SS_FB, "fb", false, B * I, "solution sens: arg fb", c);
     }
+    // altro_batch_solution_vjp_data: two seeds and eight outputs only when given, fb has room either way; fb last (ints);
+    // gA, gB, gf hold N - 1 blocks per row with per_knot
+    for (int c = 0; c < 4096; ++c) {
+      const double *gX = c & 1 ? d : nullptr, *gU = c & 2 ? d : nullptr;
+      double* out[8];
+      for (int q = 0; q < 8; ++q) out[q] = c & (4 << q) ? d : nullptr;
+      int32_t* fb = c & 1024 ? i32 : nullptr;
+      const size_t pk = (c >> 11) & 1, R = B * nc, K1 = pk ? N - 1 : 1;
+      const size_t cnt[8] = {R * n, R * n, R * m, R * (n + m), R * (n + m), R * K1 * n * n, R * K1 * n * m, R * K1 * n};
+      const char* const name[8] = {"gQ", "gQf", "gR", "gzmin", "gzmax", "gA", "gB", "gf"};
+      StageLayout L;
+      altro::stage_solution_vjp_data(L, B, N, n, m, nc, pk, gX, gU, out, fb);
+      expect(L.nslots == 11 && L.nslots <= StageLayout::MAX_SLOTS, "solution data: slots", c);
+      size_t s = 0;
+      slot_is(L, altro::SD_GX, s, gX ? R * N * n * D : 0, gX, D, "solution data: gX", c); s += gX ? R * N * n * D : 0;
+      slot_is(L, altro::SD_GU, s, gU ? R * (N - 1) * m * D : 0, gU, D, "solution data: gU", c); s += gU ? R * (N - 1) * m * D : 0;
+      for (int q = 0; q < 8; ++q) {
+        slot_is(L, altro::SD_GQ + q, s, out[q] ? cnt[q] * D : 0, out[q], D, "solution data: output", c); s += out[q] ? cnt[q] * D : 0;
+        arg_is(L, altro::SD_GQ + q, name[q], false, cnt[q] * D, "solution data: arg output", c);
+        expect(L.slot[altro::SD_GQ + q].out == out[q] && L.slot[altro::SD_GQ + q].in == nullptr, "solution data: copies out", c);
+      }
+      slot_is(L, altro::SD_FB, s, B * I, fb, I, "solution data: fb", c); s += B * I;
+      expect(L.bytes == s, "solution data: size", c);
+      expect(altro::SD_GF == altro::SD_GQ + 7 && L.slot[altro::SD_GX].in == gX && L.slot[altro::SD_GU].in == gU && L.slot[altro::SD_FB].out == fb,
+             "solution data: copies", c);
+      arg_is(L, altro::SD_GX, "gX", false, B * nc * N * n * D, "solution data: arg gX", c);
+      arg_is(L, altro::SD_GU, "gU", false, B * nc * (N - 1) * m * D, "solution data: arg gU", c);
+      arg_is(L, altro::SD_FB, "fb", false, B * I, "solution data: arg fb", c);
+    }
+    // altro_batch_get_gain_active_set: mu_pass and codes only when given, fb has room either way; the bytes of codes last, so that
+    // the doubles and the ints before them stay aligned
+    for (int c = 0; c < 8; ++c) {
+      static uint8_t u8[1];
+      uint8_t* codes = c & 1 ? u8 : nullptr;
+      double* mu = c & 2 ? d : nullptr;
+      int32_t* fb = c & 4 ? i32 : nullptr;
+      const size_t nc8 = B * N * (n + m);
+      StageLayout L;
+      altro::stage_gain_active_set(L, B, N, n, m, codes, mu, fb);
+      expect(L.nslots == 3, "gain active set: slots", c);
+      size_t s = 0;
+      slot_is(L, altro::GA_MU, s, mu ? B * D : 0, mu, D, "gain active set: mu_pass", c); s += mu ? B * D : 0;
+      slot_is(L, altro::GA_FB, s, B * I, fb, I, "gain active set: fb", c); s += B * I;
+      slot_is(L, altro::GA_CODES, s, codes ? nc8 : 0, codes, 1, "gain active set: codes", c); s += codes ? nc8 : 0;
+      expect(L.bytes == s, "gain active set: size", c);
+      expect(L.slot[altro::GA_MU].out == mu && L.slot[altro::GA_FB].out == fb && L.slot[altro::GA_CODES].out == codes, "gain active set: copies", c);
+      arg_is(L, altro::GA_MU, "mu_pass", false, B * D, "gain active set: arg mu_pass", c);
+      arg_is(L, altro::GA_FB, "fb", false, B * I, "gain active set: arg fb", c);
+      arg_is(L, altro::GA_CODES, "codes", false, B * N * (n + m), "gain active set: arg codes", c);
+    }
   }
   std::printf("stage_layout_check: %ld checks passed\n", checks);
   return 0;
