@@ -55,6 +55,18 @@ __device__ __forceinline__ double sens_negw(double w, double v) {
   return -p;
 }
 
+// ------------------------------------------------------------------ the sweep core
+// The per-knot bodies of the two sweeps, written once per backend and called by the kernels below and by sensitivity_data.h's
+// (DESIGN.md 7w); the loops over the knots stay in the kernels.  Everything is inlined by force, so a member of SensRow that a
+// kernel fills with a constant (k_sens_data*: negw = false, need_d = true) folds and that kernel keeps its own code.
+// One row's view of a call: its seed arrays (null: zero) and whether they are weighted (the JVP: g = -(w v)), its slice of the
+// workspace for d_k and whether d_k is needed (both sweeps run).
+struct SensRow {
+  const double *gx, *gu;   // [N][n], [N-1][m]
+  double* d;               // [N-1][m]
+  bool negw, need_d;
+};
+
 // ------------------------------------------------------------------ 16-lane backend
 // One 16-lane row per (instance, seed), four per wave; rows = R padded to whole waves, rows >= R compute on row 0 and store
 // nothing (eval16_row), so EXEC is all ones at every DPP move.  Lane j < n holds element j of s / xi / q_x, lane n + a element
@@ -63,6 +75,77 @@ __device__ __forceinline__ double sens_negw(double w, double v) {
 // kd_dcol of solve_dpp16.h), which is masked out.  Per knot a lane loads KA[C] = element `lane` of gain row C - n for the
 // control lanes C (a state lane: column `lane` of K; control lane n + a: column a of the factors, L[c][a]) and, a control lane
 // only, FR[C] = element C of its own gain row (row a of the factors, L[a][C - n]).
+// the gains are valid and the stored pass ran without regularisation
+__device__ __forceinline__ bool sens16_valid(const double* __restrict__ kmu, size_t b) { return !(kmu[b] < 0.0); }
+
+// gt[i] = [A B][i][lane]: the lane's column, Grow[b][lane][0..n-1], contiguous (k_eval_grad16)
+__device__ __forceinline__ void sens16_col(const Eval16& P, size_t b, int lane, double (&gt)[16]) {
+  const double* G = P.Grow + b * 256 + (size_t)lane * 16;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) gt[i] = (i < P.n && lane < P.n + P.m) ? G[i] : 0.0;
+}
+
+// the lane's element of g_k
+__device__ __forceinline__ double sens16_seed(const SensRow& g, const Ctx16& c, int k, int N, int n, int m) {
+  const bool term = k == N - 1;
+  double v = 0.0;
+  bool have = false;
+  if (c.isx && g.gx != nullptr) { v = g.gx[(size_t)k * n + c.lane]; have = true; }
+  if (c.isu && !term && g.gu != nullptr) { v = g.gu[(size_t)k * m + (c.lane - n)]; have = true; }
+  return (have && g.negw) ? sens_negw(term ? c.wf : c.wd, v) : v;
+}
+
+// q_u -> d = -Quu^-1 q_u through the factors in the control lanes of the knot's gain rows kk; KA: the lane's column of them
+__device__ __forceinline__ double sens16_solve(const double* kk, const double (&KA)[16], double qu, int lane, int ua, bool isu, int n, int m) {
+#pragma clang fp contract(off)
+  double FR[16];
+#pragma unroll
+  for (int C = 0; C < 16; ++C) FR[C] = (isu && C >= n && C < lane) ? kk[(size_t)ua * 16 + C] : 0.0;
+  const double dinv = isu ? kk[(size_t)ua * 16 + lane] : 0.0;
+  double y = qu;
+  sfor<0, 16>([&](auto cc) {   // L y = q_u: y_C is final when its turn comes
+    constexpr int C = decltype(cc)::value;
+    const double yc = bcast<C>(y);
+    y = (isu && C >= n && C < lane) ? __builtin_fma(-FR[C], yc, y) : y;
+  });
+  double w = y * dinv;
+  sfor<0, 16>([&](auto cc) {   // L' w = z, C = 15 .. 0
+    constexpr int C = 15 - decltype(cc)::value;
+    const double wc = bcast<C>(w);
+    w = (isu && C > lane && C < n + m) ? __builtin_fma(-KA[C], wc, w) : w;
+  });
+  return 0.0 - w;
+}
+
+// knot k of the backward sweep: s_{k+1} (on the state lanes, 0 elsewhere) -> s_k; d_k into the workspace when it is needed
+__device__ __forceinline__ double sens16_back_knot(const SensRow& g, const Ctx16& c, const double (&gt)[16], const double* kdp, int k, int N, int n,
+                                                   int m, bool live, double s) {
+#pragma clang fp contract(off)
+  const int lane = c.lane, ua = c.isu ? lane - n : 0;   // ua: the control a control lane holds
+  const bool isu = c.isu;
+  const double* kk = kdp + (size_t)k * m * 16;
+  double KA[16];
+#pragma unroll
+  for (int C = 0; C < 16; ++C) KA[C] = (C >= n && C < n + m && lane < n + m) ? kk[(size_t)(C - n) * 16 + lane] : 0.0;
+  const double q = row_affine(gt, sens16_seed(g, c, k, N, n, m), s);   // q_x on the state lanes, q_u on the control lanes, 0 beyond
+  const double qu = isu ? q : 0.0;
+  if (g.need_d) {
+    const double d = sens16_solve(kk, KA, qu, lane, ua, isu, n, m);
+    if (live && isu) g.d[(size_t)k * m + ua] = d;
+  }
+  const double acc = row_affine(KA, q, qu);   // (on a control lane KA holds factors: the sum is dropped there)
+  return c.isx ? acc : 0.0;
+}
+
+// the control step of knot k of the forward sweep: the row's z = [xi; nu; 0] from xi on the state lanes
+__device__ __forceinline__ double sens16_control(const SensRow& g, const Ctx16& c, const double* kdp, int k, int n, int m, double xi) {
+  const double* kd = kdp + (size_t)k * m * 16 + c.lane;
+  const double d = (g.need_d && c.isu) ? g.d[(size_t)k * m + (c.lane - n)] : 0.0;   // (the lane's own store of the backward sweep)
+  double z = xi;
+  for (int a = 0; a < m; ++a) z = policy16_control(z, c.isx ? kd[(size_t)a * 16] : 0.0, xi, c.isx, c.lane == n + a, d);
+  return z;
+}
+
 __global__ void __launch_bounds__(256)
 k_sens16(SensIO io, const double* __restrict__ KD, const double* __restrict__ kmu, Eval16 P, int nseed, size_t R, size_t rows) {
 #pragma clang fp contract(off)
@@ -72,70 +155,25 @@ k_sens16(SensIO io, const double* __restrict__ KD, const double* __restrict__ km
   const size_t r = row.r, b = row.b;
   const int lane = row.lane;
   const bool live = row.live, isx = row.isx, isu = row.isu;
-  const bool valid = !(kmu[b] < 0.0);
+  const bool valid = sens16_valid(kmu, b);
   const Ctx16 c(P, b, lane);
   const int ua = isu ? lane - n : 0;   // the control a control lane holds
-  const bool need_d = io.bwd != 0 && io.fwd != 0;
   const double* kdp = KD + b * (size_t)N * m * 16;
-  const double* gxr = io.inx != nullptr ? io.inx + r * (size_t)N * n : nullptr;
-  const double* gur = io.inu != nullptr ? io.inu + r * (size_t)(N - 1) * m : nullptr;
-  double* dr = io.dws != nullptr ? io.dws + r * (size_t)(N - 1) * m : nullptr;
-  // the lane's element of g_k
-  auto seed = [&](int k) -> double {
-    const bool term = k == N - 1;
-    double v = 0.0;
-    bool have = false;
-    if (isx && gxr != nullptr) { v = gxr[(size_t)k * n + lane]; have = true; }
-    if (isu && !term && gur != nullptr) { v = gur[(size_t)k * m + ua]; have = true; }
-    return (have && io.jvp) ? sens_negw(term ? c.wf : c.wd, v) : v;
-  };
+  const SensRow g{io.inx != nullptr ? io.inx + r * (size_t)N * n : nullptr, io.inu != nullptr ? io.inu + r * (size_t)(N - 1) * m : nullptr,
+                  io.dws != nullptr ? io.dws + r * (size_t)(N - 1) * m : nullptr, io.jvp != 0, io.bwd != 0 && io.fwd != 0};
   double s = 0.0;   // s_{k+1} on the state lanes, 0 elsewhere
   if (io.bwd) {
-    // gt[i] = [A B][i][lane]: the lane's column, Grow[b][lane][0..n-1], contiguous (k_eval_grad16)
     double gt[16];
-    {
-      const double* G = P.Grow + b * 256 + (size_t)lane * 16;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) gt[i] = (i < n && lane < n + m) ? G[i] : 0.0;
-    }
-    s = isx ? seed(N - 1) : 0.0;
-    for (int k = N - 2; k >= 0; --k) {
-      const double* kk = kdp + (size_t)k * m * 16;
-      double KA[16];
-#pragma unroll
-      for (int C = 0; C < 16; ++C) KA[C] = (C >= n && C < n + m && lane < n + m) ? kk[(size_t)(C - n) * 16 + lane] : 0.0;
-      const double q = row_affine(gt, seed(k), s);   // q_x on the state lanes, q_u on the control lanes, 0 beyond
-      const double qu = isu ? q : 0.0;
-      if (need_d) {
-        double FR[16];
-#pragma unroll
-        for (int C = 0; C < 16; ++C) FR[C] = (isu && C >= n && C < lane) ? kk[(size_t)ua * 16 + C] : 0.0;
-        const double dinv = isu ? kk[(size_t)ua * 16 + lane] : 0.0;
-        double y = qu;
-        sfor<0, 16>([&](auto cc) {   // L y = q_u: y_C is final when its turn comes
-          constexpr int C = decltype(cc)::value;
-          const double yc = bcast<C>(y);
-          y = (isu && C >= n && C < lane) ? __builtin_fma(-FR[C], yc, y) : y;
-        });
-        double w = y * dinv;
-        sfor<0, 16>([&](auto cc) {   // L' w = z, C = 15 .. 0
-          constexpr int C = 15 - decltype(cc)::value;
-          const double wc = bcast<C>(w);
-          w = (isu && C > lane && C < n + m) ? __builtin_fma(-KA[C], wc, w) : w;
-        });
-        const double d = 0.0 - w;
-        if (live && isu) dr[(size_t)k * m + ua] = d;
-      }
-      const double acc = row_affine(KA, q, qu);   // (on a control lane KA holds factors: the sum is dropped there)
-      s = isx ? acc : 0.0;
-    }
+    sens16_col(P, b, lane, gt);
+    s = isx ? sens16_seed(g, c, N - 1, N, n, m) : 0.0;
+    for (int k = N - 2; k >= 0; --k) s = sens16_back_knot(g, c, gt, kdp, k, N, n, m, live, s);
   }
   const double nan = sens_nan();
   if (live && isx && io.o0 != nullptr) io.o0[r * (size_t)n + lane] = valid ? s : nan;
   if (live && lane == 0 && io.fb != nullptr && r == b * (size_t)nseed) io.fb[b] = valid ? 1 : 0;
   if (!io.fwd) return;
-  double g[16], fv;
-  eval16_dyn(P, b, lane, g, fv);
+  double gd[16], fv;
+  eval16_dyn(P, b, lane, gd, fv);
   double* oxr = io.ox != nullptr ? io.ox + r * (size_t)N * n : nullptr;
   double* our = io.ou != nullptr ? io.ou + r * (size_t)(N - 1) * m : nullptr;
   double xi = (isx && io.in0 != nullptr) ? io.in0[r * (size_t)n + lane] : 0.0;
@@ -146,15 +184,12 @@ k_sens16(SensIO io, const double* __restrict__ KD, const double* __restrict__ km
       oxr[(size_t)k * n + lane] = valid ? v : nan;
     }
     if (term) break;
-    const double* kd = kdp + (size_t)k * m * 16 + lane;
-    const double d = (need_d && isu) ? dr[(size_t)k * m + ua] : 0.0;   // (the lane's own store of the backward sweep)
-    double z = xi;
-    for (int a = 0; a < m; ++a) z = policy16_control(z, isx ? kd[(size_t)a * 16] : 0.0, xi, isx, lane == n + a, d);
+    const double z = sens16_control(g, c, kdp, k, n, m, xi);
     if (live && isu && our != nullptr) {
       const double v = io.jvp ? z : sens_negw(c.wd, z);
       our[(size_t)k * m + ua] = valid ? v : nan;
     }
-    xi = eval16_step(g, 0.0, z, isx);
+    xi = eval16_step(gd, 0.0, z, isx);
   }
 }
 
@@ -182,6 +217,74 @@ __device__ __forceinline__ double sensw_step(const EvalWDynT<PAD>& dyn, int k, d
   return evalw_step(dyn.P.A + blk * n * n + dyn.Tn, dyn.P.Bm + blk * n * m + dyn.Tn, n, 0.0, n, m, xs, us);
 }
 
+// The reuse state of the instance's last backward pass as the solve kernels leave it (solve_wide.h: 136 words per instance).
+struct SensWReuse {
+  const unsigned* st;
+  int reuse_ok;
+  __device__ __forceinline__ SensWReuse(const unsigned* __restrict__ bwst, size_t b, int reuse_ok_) : st(bwst + b * 136), reuse_ok(reuse_ok_) {}
+  // the gains are valid (word 128) and the stored pass ran without regularisation (word 129)
+  __device__ __forceinline__ bool valid() const { return reuse_ok != 0 && st[128] != 0u && st[129] != 0u; }
+  // the penalty of the stored pass (words 130-131)
+  __device__ __forceinline__ double mu_pass() const { return __hiloint2double((int)st[131], (int)st[130]); }
+  // the plane of the active set of the last backward pass (bits 0-1 of word 132; a zeroed state: the default roles, plane 0)
+  __device__ __forceinline__ int plane() const {
+    const unsigned roles = st[132];
+    const int b_ = (int)(roles & 3u), q_ = (int)((roles >> 2) & 3u), a_ = (int)((roles >> 4) & 3u);
+    return ((1 << b_) | (1 << q_) | (1 << a_)) == 7 ? b_ : 0;
+  }
+};
+
+// the lane's element of gx_k / gu_k
+__device__ __forceinline__ double sensw_seedx(const SensRow& g, const CtxW& c, int k, int N, int n) {
+  if (!c.isx || g.gx == nullptr) return 0.0;
+  const double v = g.gx[(size_t)k * n + c.T];
+  return g.negw ? sens_negw(k == N - 1 ? c.wfx : c.wx, v) : v;
+}
+__device__ __forceinline__ double sensw_seedu(const SensRow& g, const CtxW& c, int k, int m) {
+  if (!c.isu || g.gu == nullptr) return 0.0;
+  const double v = g.gu[(size_t)k * m + c.T];
+  return g.negw ? sens_negw(c.wu, v) : v;
+}
+
+// q_u -> d = -Quu^-1 q_u through the packed factors Fk of the knot (m <= 16); qu is 0 off the control lanes
+__device__ __forceinline__ double sensw_solve(const double* Fk, const CtxW& c, int m, double qu) {
+#pragma clang fp contract(off)
+  const int T = c.T, Tm = c.Tm;
+  const bool isu = c.isu;
+  const int rowT = Tm * (Tm + 1) / 2;
+  double fr[16], fc[16];
+#pragma unroll
+  for (int cc = 0; cc < 16; ++cc) {
+    fr[cc] = (isu && cc < T) ? Fk[rowT + cc] : 0.0;                          // L[T][cc]
+    fc[cc] = (isu && cc > T && cc < m) ? Fk[cc * (cc + 1) / 2 + Tm] : 0.0;   // L[cc][T]
+  }
+  const double dinv = isu ? Fk[rowT + Tm] : 0.0;
+  double y = qu;
+#pragma unroll
+  for (int cc = 0; cc < 16; ++cc) {
+    if (cc < m) {   // (uniform)
+      const double yc = eval_readlane(y, cc);
+      y = (isu && cc < T) ? __builtin_fma(-fr[cc], yc, y) : y;
+    }
+  }
+  double w = y * dinv;
+#pragma unroll
+  for (int cc = 15; cc >= 0; --cc) {
+    if (cc < m) {
+      const double wc = eval_readlane(w, cc);
+      w = (isu && cc > T) ? __builtin_fma(-fc[cc], wc, w) : w;
+    }
+  }
+  return 0.0 - w;
+}
+
+// nu_k = K_k xi_k + d_k on the control lanes, 0 elsewhere
+__device__ __forceinline__ double sensw_control(const SensRow& g, const CtxW& c, const double* Kb, int k, int n, int m, double xi) {
+  const double d = (g.need_d && c.isu) ? g.d[(size_t)k * m + c.T] : 0.0;   // (the lane's own store of the backward sweep)
+  const double nu = evalw_dot(Kb + (size_t)k * n * m + c.Tm, (size_t)m, xi, n, d, c.isu);   // row Tm of K: stride m
+  return c.isu ? nu : 0.0;
+}
+
 __global__ void k_sens_wide(SensIO io, const double* __restrict__ Kg, const double* __restrict__ fac, int fs, const unsigned* __restrict__ bwst,
                             int reuse_ok, EvalW P, int nseed, size_t R, int use_lds) {
 #pragma clang fp contract(off)
@@ -190,64 +293,27 @@ __global__ void k_sens_wide(SensIO io, const double* __restrict__ Kg, const doub
   if (r >= R) return;   // (whole waves)
   const size_t b = r / (size_t)nseed;
   const int n = P.n, m = P.m, N = P.N;
-  const bool valid = reuse_ok != 0 && bwst[b * 136 + 128] != 0u && bwst[b * 136 + 129] != 0u;
+  const bool valid = SensWReuse(bwst, b, reuse_ok).valid();
   const CtxW c(P, b, T, false);
   const EvalWDynT<true> dyn(P, b, c.kref, T, use_lds != 0);   // (padded: tstep reads the slice transposed)
   const bool isx = c.isx, isu = c.isu;
-  const int Tn = c.Tn, Tm = c.Tm;
-  const bool need_d = io.bwd != 0 && io.fwd != 0;
   const double* Kb = Kg + b * (size_t)(N - 1) * n * m;
-  const double* gxr = io.inx != nullptr ? io.inx + r * (size_t)N * n : nullptr;
-  const double* gur = io.inu != nullptr ? io.inu + r * (size_t)(N - 1) * m : nullptr;
-  double* dr = io.dws != nullptr ? io.dws + r * (size_t)(N - 1) * m : nullptr;
-  auto seedx = [&](int k) -> double {
-    if (!isx || gxr == nullptr) return 0.0;
-    const double v = gxr[(size_t)k * n + T];
-    return io.jvp ? sens_negw(k == N - 1 ? c.wfx : c.wx, v) : v;
-  };
-  auto seedu = [&](int k) -> double {
-    if (!isu || gur == nullptr) return 0.0;
-    const double v = gur[(size_t)k * m + T];
-    return io.jvp ? sens_negw(c.wu, v) : v;
-  };
+  const SensRow g{io.inx != nullptr ? io.inx + r * (size_t)N * n : nullptr, io.inu != nullptr ? io.inu + r * (size_t)(N - 1) * m : nullptr,
+                  io.dws != nullptr ? io.dws + r * (size_t)(N - 1) * m : nullptr, io.jvp != 0, io.bwd != 0 && io.fwd != 0};
   double s = 0.0;
   if (io.bwd) {
-    s = seedx(N - 1);
+    s = sensw_seedx(g, c, N - 1, N, n);
+    // (the knot stands here and in k_sens_data_wide: as one function the same lines give the same loops there, 854, 209 and 223
+    // instructions, but 133 or more VGPRs against the parent's 131 under every signature that returns s: DESIGN.md 7w)
     for (int k = N - 2; k >= 0; --k) {
-      const double* Kk = Kb + (size_t)k * n * m;
-      double qu = dyn.tstep(k, true, s, seedu(k), isu);
-      const double qx = dyn.tstep(k, false, s, seedx(k), isx);
+      double qu = dyn.tstep(k, true, s, sensw_seedu(g, c, k, m), isu);
+      const double qx = dyn.tstep(k, false, s, sensw_seedx(g, c, k, N, n), isx);
       qu = isu ? qu : 0.0;
-      if (need_d) {   // (m <= 16)
-        const double* Fk = fac + (b * (size_t)N + k) * fs;
-        const int rowT = Tm * (Tm + 1) / 2;
-        double fr[16], fc[16];
-#pragma unroll
-        for (int cc = 0; cc < 16; ++cc) {
-          fr[cc] = (isu && cc < T) ? Fk[rowT + cc] : 0.0;                      // L[T][cc]
-          fc[cc] = (isu && cc > T && cc < m) ? Fk[cc * (cc + 1) / 2 + Tm] : 0.0;   // L[cc][T]
-        }
-        const double dinv = isu ? Fk[rowT + Tm] : 0.0;
-        double y = qu;
-#pragma unroll
-        for (int cc = 0; cc < 16; ++cc) {
-          if (cc < m) {   // (uniform)
-            const double yc = eval_readlane(y, cc);
-            y = (isu && cc < T) ? __builtin_fma(-fr[cc], yc, y) : y;
-          }
-        }
-        double w = y * dinv;
-#pragma unroll
-        for (int cc = 15; cc >= 0; --cc) {
-          if (cc < m) {
-            const double wc = eval_readlane(w, cc);
-            w = (isu && cc > T) ? __builtin_fma(-fc[cc], wc, w) : w;
-          }
-        }
-        const double d = 0.0 - w;
-        if (isu) dr[(size_t)k * m + T] = d;
+      if (g.need_d) {   // (m <= 16)
+        const double d = sensw_solve(fac + (b * (size_t)N + k) * fs, c, m, qu);
+        if (isu) g.d[(size_t)k * m + T] = d;
       }
-      const double acc = evalw_dot(Kk + (size_t)Tn * m, 1, qu, m, qx, isx);   // column Tn of K: m consecutive doubles
+      const double acc = evalw_dot(Kb + (size_t)k * n * m + (size_t)c.Tn * m, 1, qu, m, qx, isx);   // column Tn of K: m consecutive doubles
       s = isx ? acc : 0.0;
     }
   }
@@ -265,10 +331,7 @@ __global__ void k_sens_wide(SensIO io, const double* __restrict__ Kg, const doub
       oxr[(size_t)k * n + T] = valid ? v : nan;
     }
     if (term) break;
-    const double* Kk = Kb + (size_t)k * n * m;
-    const double d = (need_d && isu) ? dr[(size_t)k * m + T] : 0.0;   // (the lane's own store of the backward sweep)
-    double nu = evalw_dot(Kk + Tm, (size_t)m, xi, n, d, isu);         // row Tm of K: stride m
-    nu = isu ? nu : 0.0;
+    const double nu = sensw_control(g, c, Kb, k, n, m, xi);
     if (isu && our != nullptr) {
       const double v = io.jvp ? nu : sens_negw(c.wu, nu);
       our[(size_t)k * m + T] = valid ? v : nan;

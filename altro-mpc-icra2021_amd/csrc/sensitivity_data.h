@@ -22,10 +22,11 @@
 // valid = sensitivity.h's rule AND the penalty the instance holds equals the penalty of the stored pass (16-lane backend:
 // mu[b] == kmu[b]; one-wave-per-instance backend: mu[b] == words 130-131 of the reuse state): without it every output of the
 // instance is a quiet NaN.  No masking, no clamp; a NaN stays a NaN.
-// RESTATED, NOT SHARED: sweeps 1 and 2 are the lines of k_sens16 / k_sens_wide and the local term of sweep 3 those of
-// k_eval_al16 / k_eval_al_wide; those four kernels must keep the parent's device code, so nothing was moved out of them.
-// Contraction is off and every fused multiply-add is written out.  SUMMATION ORDERS (both backends unless said); what sensitivity.h
-// states for its two sweeps holds here unchanged (seed, transposed product, the triangular solves, s, nu, xi')
+// Sweep 1 and the control step of sweep 2 are sensitivity.h's per-knot functions, the ones k_sens16 / k_sens_wide call, with an
+// unweighted seed; the local term of sweep 3 restates k_eval_al16 / k_eval_al_wide (evaluate_al.h: 7r measured
+// what sharing costs there).
+// Contraction is off and every fused multiply-add is written out.  SUMMATION ORDERS of what this file adds (both backends unless
+// said; the orders of the two sweeps are stated in sensitivity.h)
 //   e                  z - zref, rounded first
 //   gQ, gR             acc = +0; acc = fma(dz_k, e_k, acc) for k = 0, 1, .., N - 2 in turn; then dt * acc
 //   gQf                xi_{N-1} * e_{N-1}: one product
@@ -81,6 +82,11 @@ __device__ __forceinline__ double sensd_bound(double mu, double acc) {
 }
 
 // ------------------------------------------------------------------ 16-lane backend
+// sensitivity.h's rule AND the penalty the instance holds is the penalty of the stored pass
+__device__ __forceinline__ bool sensd16_valid(const double* __restrict__ kmu, const double* __restrict__ mu, size_t b) {
+  return sens16_valid(kmu, b) && kmu[b] == mu[b];
+}
+
 // One 16-lane row per (instance, seed), four per wave, in the layout of k_sens16: lane j < n holds element j of s / xi / lam /
 // dlam, lane n + a element a of q_u / d / nu; lane c < n + m owns column c of [A B] and with it z_k[c], dz_k[c] and the
 // accumulators G[i] of column c of gA (c < n) or column c - n of gB.  Zp: the planes the handle holds (simulate.h).  ahash [Bp][16]:
@@ -96,81 +102,37 @@ k_sens_data16(SensDataIO io, const double* __restrict__ Zp, const int* __restric
   const int lane = row.lane;
   const bool live = row.live, isx = row.isx, isu = row.isu;
   const double mup = kmu[b];
-  const bool valid = !(mup < 0.0) && mup == io.mu[b];
+  const bool valid = sensd16_valid(kmu, io.mu, b);
   const Ctx16 c(P, b, lane);
   const int ua = isu ? lane - n : 0;   // the control a control lane holds
   const bool want_box = io.gzmin != nullptr || io.gzmax != nullptr;
   const bool want3 = io.gA != nullptr || io.gB != nullptr || io.gf != nullptr;
   const double* kdp = KD + b * (size_t)N * m * 16;
   const double* Zn = Zp + b * (2 * (size_t)N + 1) * 16 + (size_t)cur[b] * plane + lane;
-  const double* gxr = io.gX != nullptr ? io.gX + r * (size_t)N * n : nullptr;
-  const double* gur = io.gU != nullptr ? io.gU + r * (size_t)(N - 1) * m : nullptr;
-  double* dr = io.dws + r * (size_t)(N - 1) * m;
+  const SensRow g{io.gX != nullptr ? io.gX + r * (size_t)N * n : nullptr, io.gU != nullptr ? io.gU + r * (size_t)(N - 1) * m : nullptr,
+                  io.dws + r * (size_t)(N - 1) * m, false, true};
   double* zw = io.zws != nullptr ? io.zws + r * (size_t)N * nz : nullptr;
   const unsigned* aw = (want_box || want3) ? ahash[b * 16 + lane].w : nullptr;
-  // the lane's element of g_k
-  auto seed = [&](int k) -> double {
-    double v = 0.0;
-    if (isx && gxr != nullptr) v = gxr[(size_t)k * n + lane];
-    if (isu && k != N - 1 && gur != nullptr) v = gur[(size_t)k * m + ua];
-    return v;
-  };
   auto code = [&](int k) -> unsigned { return (aw[k >> 4] >> ((k & 15) * 2)) & 3u; };
-  // gt[i] = [A B][i][lane]: the lane's column, Grow[b][lane][0..n-1], contiguous (k_eval_grad16)
   double gt[16];
+  sens16_col(P, b, lane, gt);
+  // ---- sweep 1
   {
-    const double* G = P.Grow + b * 256 + (size_t)lane * 16;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) gt[i] = (i < n && lane < nz) ? G[i] : 0.0;
-  }
-  // ---- sweep 1 (k_sens16's backward sweep, restated)
-  {
-    double s = isx ? seed(N - 1) : 0.0;   // s_{k+1} on the state lanes, 0 elsewhere
-    for (int k = N - 2; k >= 0; --k) {
-      const double* kk = kdp + (size_t)k * m * 16;
-      double KA[16], FR[16];
-#pragma unroll
-      for (int C = 0; C < 16; ++C) KA[C] = (C >= n && C < nz && lane < nz) ? kk[(size_t)(C - n) * 16 + lane] : 0.0;
-      const double q = row_affine(gt, seed(k), s);   // q_x on the state lanes, q_u on the control lanes, 0 beyond
-      const double qu = isu ? q : 0.0;
-#pragma unroll
-      for (int C = 0; C < 16; ++C) FR[C] = (isu && C >= n && C < lane) ? kk[(size_t)ua * 16 + C] : 0.0;
-      const double dinv = isu ? kk[(size_t)ua * 16 + lane] : 0.0;
-      double y = qu;
-      sfor<0, 16>([&](auto cc) {   // L y = q_u: y_C is final when its turn comes
-        constexpr int C = decltype(cc)::value;
-        const double yc = bcast<C>(y);
-        y = (isu && C >= n && C < lane) ? __builtin_fma(-FR[C], yc, y) : y;
-      });
-      double w = y * dinv;
-      sfor<0, 16>([&](auto cc) {   // L' w = z, C = 15 .. 0
-        constexpr int C = 15 - decltype(cc)::value;
-        const double wc = bcast<C>(w);
-        w = (isu && C > lane && C < nz) ? __builtin_fma(-KA[C], wc, w) : w;
-      });
-      const double d = 0.0 - w;
-      if (live && isu) dr[(size_t)k * m + ua] = d;
-      const double acc = row_affine(KA, q, qu);   // (on a control lane KA holds factors: the sum is dropped there)
-      s = isx ? acc : 0.0;
-    }
+    double s = isx ? sens16_seed(g, c, N - 1, N, n, m) : 0.0;   // s_{k+1} on the state lanes, 0 elsewhere
+    for (int k = N - 2; k >= 0; --k) s = sens16_back_knot(g, c, gt, kdp, k, N, n, m, live, s);
   }
   const double nan = sens_nan();
   if (live && lane == 0 && io.fb != nullptr && r == b * (size_t)nseed) io.fb[b] = valid ? 1 : 0;
-  // ---- sweep 2 (k_sens16's forward sweep, restated, with the lane-local sums)
+  // ---- sweep 2, with the lane-local sums
   {
-    double g[16], fv;
-    eval16_dyn(P, b, lane, g, fv);
+    double gd[16], fv;
+    eval16_dyn(P, b, lane, gd, fv);
     double xi = 0.0, sq = 0.0, qf = 0.0, shi = 0.0, slo = 0.0;
     for (int k = 0;; ++k) {
       const bool term = k == N - 1;
       const bool on = isx || (isu && !term);
       const double zl = Zn[(size_t)k * 16], zr = c.Zr[(size_t)k * 16];
-      double z = xi;
-      if (!term) {
-        const double* kd = kdp + (size_t)k * m * 16 + lane;
-        const double d = isu ? dr[(size_t)k * m + ua] : 0.0;   // (the lane's own store of sweep 1)
-        for (int a = 0; a < m; ++a) z = policy16_control(z, isx ? kd[(size_t)a * 16] : 0.0, xi, isx, lane == n + a, d);
-      }
+      const double z = term ? xi : sens16_control(g, c, kdp, k, n, m, xi);
       const double dz = on ? z : 0.0;   // dz_k of the lane's element
       const double e = on ? zl - zr : 0.0;
       if (term) qf = dz * e;
@@ -182,7 +144,7 @@ k_sens_data16(SensDataIO io, const double* __restrict__ Zp, const int* __restric
       }
       if (live && on && zw != nullptr) zw[(size_t)k * nz + lane] = dz;
       if (term) break;
-      xi = eval16_step(g, 0.0, z, isx);
+      xi = eval16_step(gd, 0.0, z, isx);
     }
     if (live && isx) {
       if (io.gQ != nullptr) io.gQ[r * (size_t)n + lane] = valid ? io.dt * sq : nan;
@@ -217,7 +179,7 @@ k_sens_data16(SensDataIO io, const double* __restrict__ Zp, const int* __restric
     const double gl = ge + cz;
     l = on ? gl : 0.0;
     const double hz = sensd_hz(w, mup, on ? code(k) : 0u);
-    const double gd = __builtin_fma(hz, dz, seed(k));
+    const double gd = __builtin_fma(hz, dz, sens16_seed(g, c, k, N, n, m));
     dl = on ? gd : 0.0;
   };
   const size_t K1 = io.per_knot ? (size_t)(N - 1) : 1;
@@ -280,7 +242,7 @@ __global__ void k_gain_aset16(unsigned char* __restrict__ codes, double* __restr
   const int e = (int)(t % nz), k = (int)((t / nz) % N);
   const size_t b = t / nz / N;
   const double mup = kmu[b];
-  const bool valid = !(mup < 0.0) && mup == mu[b];
+  const bool valid = sensd16_valid(kmu, mu, b);
   if (codes != nullptr) {
     const unsigned cd = (ahash[b * 16 + e].w[k >> 4] >> ((k & 15) * 2)) & 3u;
     codes[t] = (unsigned char)((valid && !(k == N - 1 && e >= n)) ? cd : 0u);
@@ -292,6 +254,9 @@ __global__ void k_gain_aset16(unsigned char* __restrict__ codes, double* __restr
 }
 
 // ------------------------------------------------------------------ one-wave-per-instance backend
+// sensitivity.h's rule AND the penalty the instance holds is the penalty of the stored pass
+__device__ __forceinline__ bool sensdw_valid(const SensWReuse& st, const double* __restrict__ mu, size_t b) { return st.valid() && st.mu_pass() == mu[b]; }
+
 // One wave per (instance, seed) in the layout of k_sens_wide: lane T < n owns element T of s / xi / lam / dlam, x_k[T] and column
 // T of gA; lane T < m owns element T of q_u / d / nu, u_k[T] and column T of gB.  Xp, Up: the planes the handle holds
 // (simulate.h).  aset [B][3][N][64]: the plane of the last backward pass (bits 0-1 of word 132 of the reuse state), one byte
@@ -310,16 +275,10 @@ k_sens_data_wide(SensDataIO io, const double* __restrict__ Xp, const double* __r
   if (r >= R) return;   // (whole waves)
   const size_t b = r / (size_t)nseed;
   const int n = P.n, m = P.m, N = P.N, nz = P.n + P.m;
-  const unsigned* st = bwst + b * 136;
-  const double mup = __hiloint2double((int)st[131], (int)st[130]);
-  const bool valid = reuse_ok != 0 && st[128] != 0u && st[129] != 0u && mup == io.mu[b];
-  int bwp = 0;
-  {
-    const unsigned roles = st[132];
-    const int b_ = (int)(roles & 3u), q_ = (int)((roles >> 2) & 3u), a_ = (int)((roles >> 4) & 3u);
-    if (((1 << b_) | (1 << q_) | (1 << a_)) == 7) bwp = b_;   // (zeroed state: the default roles)
-  }
-  const unsigned char* ap = aset + ((b * 3 + (size_t)bwp) * (size_t)N) * 64 + T;   // the lane's byte of knot 0
+  const SensWReuse st(bwst, b, reuse_ok);
+  const double mup = st.mu_pass();
+  const bool valid = sensdw_valid(st, io.mu, b);
+  const unsigned char* ap = aset + ((b * 3 + (size_t)st.plane()) * (size_t)N) * 64 + T;   // the lane's byte of knot 0
   const CtxW c(P, b, T, false);
   const EvalWDynT<true> dyn(P, b, c.kref, T, false);
   const bool isx = c.isx, isu = c.isu;
@@ -330,54 +289,25 @@ k_sens_data_wide(SensDataIO io, const double* __restrict__ Xp, const double* __r
   const double* Xn = Xp + pl * (size_t)N * n + Tn;
   const double* Un = Up + pl * (size_t)(N - 1) * m + Tm;
   const double* Kb = Kg + b * (size_t)(N - 1) * n * m;
-  const double* gxr = io.gX != nullptr ? io.gX + r * (size_t)N * n : nullptr;
-  const double* gur = io.gU != nullptr ? io.gU + r * (size_t)(N - 1) * m : nullptr;
-  double* dr = io.dws + r * (size_t)(N - 1) * m;
+  const SensRow g{io.gX != nullptr ? io.gX + r * (size_t)N * n : nullptr, io.gU != nullptr ? io.gU + r * (size_t)(N - 1) * m : nullptr,
+                  io.dws + r * (size_t)(N - 1) * m, false, true};
   double* zw = io.zws != nullptr ? io.zws + r * (size_t)N * nz : nullptr;
-  auto seedx = [&](int k) -> double { return (isx && gxr != nullptr) ? gxr[(size_t)k * n + T] : 0.0; };
-  auto seedu = [&](int k) -> double { return (isu && gur != nullptr) ? gur[(size_t)k * m + T] : 0.0; };
-  // ---- sweep 1 (k_sens_wide's backward sweep, restated; m <= 16)
+  // ---- sweep 1 (m <= 16)
   {
-    double s = seedx(N - 1);
-    for (int k = N - 2; k >= 0; --k) {
-      const double* Kk = Kb + (size_t)k * n * m;
-      double qu = dyn.tstep(k, true, s, seedu(k), isu);
-      const double qx = dyn.tstep(k, false, s, seedx(k), isx);
+    double s = sensw_seedx(g, c, N - 1, N, n);
+    for (int k = N - 2; k >= 0; --k) {   // (k_sens_wide's knot: the note there says why it is not one function)
+      double qu = dyn.tstep(k, true, s, sensw_seedu(g, c, k, m), isu);
+      const double qx = dyn.tstep(k, false, s, sensw_seedx(g, c, k, N, n), isx);
       qu = isu ? qu : 0.0;
-      const double* Fk = fac + (b * (size_t)N + k) * fs;
-      const int rowT = Tm * (Tm + 1) / 2;
-      double fr[16], fc[16];
-#pragma unroll
-      for (int cc = 0; cc < 16; ++cc) {
-        fr[cc] = (isu && cc < T) ? Fk[rowT + cc] : 0.0;                          // L[T][cc]
-        fc[cc] = (isu && cc > T && cc < m) ? Fk[cc * (cc + 1) / 2 + Tm] : 0.0;   // L[cc][T]
-      }
-      const double dinv = isu ? Fk[rowT + Tm] : 0.0;
-      double y = qu;
-#pragma unroll
-      for (int cc = 0; cc < 16; ++cc) {
-        if (cc < m) {   // (uniform)
-          const double yc = eval_readlane(y, cc);
-          y = (isu && cc < T) ? __builtin_fma(-fr[cc], yc, y) : y;
-        }
-      }
-      double w = y * dinv;
-#pragma unroll
-      for (int cc = 15; cc >= 0; --cc) {
-        if (cc < m) {
-          const double wc = eval_readlane(w, cc);
-          w = (isu && cc > T) ? __builtin_fma(-fc[cc], wc, w) : w;
-        }
-      }
-      const double d = 0.0 - w;
-      if (isu) dr[(size_t)k * m + T] = d;
-      const double acc = evalw_dot(Kk + (size_t)Tn * m, 1, qu, m, qx, isx);   // column Tn of K: m consecutive doubles
+      const double d = sensw_solve(fac + (b * (size_t)N + k) * fs, c, m, qu);
+      if (isu) g.d[(size_t)k * m + T] = d;
+      const double acc = evalw_dot(Kb + (size_t)k * n * m + (size_t)Tn * m, 1, qu, m, qx, isx);   // column Tn of K: m consecutive doubles
       s = isx ? acc : 0.0;
     }
   }
   const double nan = sens_nan();
   if (T == 0 && io.fb != nullptr && r == b * (size_t)nseed) io.fb[b] = valid ? 1 : 0;
-  // ---- sweep 2 (k_sens_wide's forward sweep, restated, with the lane-local sums)
+  // ---- sweep 2, with the lane-local sums
   {
     double xi = 0.0, sqx = 0.0, squ = 0.0, qf = 0.0, sxhi = 0.0, sxlo = 0.0, suhi = 0.0, sulo = 0.0;
     for (int k = 0;; ++k) {
@@ -385,13 +315,7 @@ k_sens_data_wide(SensDataIO io, const double* __restrict__ Xp, const double* __r
       const bool uon = isu && !term;
       const double xl = isx ? Xn[(size_t)k * n] : 0.0;
       const double ul = uon ? Un[(size_t)k * m] : 0.0;
-      double nu = 0.0;
-      if (!term) {
-        const double* Kk = Kb + (size_t)k * n * m;
-        const double d = isu ? dr[(size_t)k * m + T] : 0.0;   // (the lane's own store of sweep 1)
-        nu = evalw_dot(Kk + Tm, (size_t)m, xi, n, d, isu);    // row Tm of K: stride m
-        nu = isu ? nu : 0.0;
-      }
+      const double nu = term ? 0.0 : sensw_control(g, c, Kb, k, n, m, xi);
       const double ex = isx ? xl - c.Xf[(size_t)k * n + Tn] : 0.0;
       const double eu = uon ? ul - c.Uf[(size_t)k * m + Tm] : 0.0;
       if (term) {
@@ -453,7 +377,7 @@ k_sens_data_wide(SensDataIO io, const double* __restrict__ Xp, const double* __r
     const double gl = ge + cx;
     lx = isx ? gl : 0.0;
     const double hz = sensd_hz(wx, mup, isx ? (cd & 3u) : 0u);
-    const double gd = __builtin_fma(hz, dxi, seedx(k));
+    const double gd = __builtin_fma(hz, dxi, sensw_seedx(g, c, k, N, n));
     dlx = isx ? gd : 0.0;
   };
   const size_t K1 = io.per_knot ? (size_t)(N - 1) : 1;
@@ -519,15 +443,11 @@ __global__ void k_gain_aset_wide(unsigned char* __restrict__ codes, double* __re
   if (t >= (size_t)B * N * nz) return;
   const int e = (int)(t % nz), k = (int)((t / nz) % N);
   const size_t b = t / nz / N;
-  const unsigned* st = bwst + b * 136;
-  const double mup = __hiloint2double((int)st[131], (int)st[130]);
-  const bool valid = reuse_ok != 0 && st[128] != 0u && st[129] != 0u && mup == mu[b];
+  const SensWReuse st(bwst, b, reuse_ok);
+  const double mup = st.mu_pass();
+  const bool valid = sensdw_valid(st, mu, b);
   if (codes != nullptr) {
-    int bwp = 0;
-    const unsigned roles = st[132];
-    const int b_ = (int)(roles & 3u), q_ = (int)((roles >> 2) & 3u), a_ = (int)((roles >> 4) & 3u);
-    if (((1 << b_) | (1 << q_) | (1 << a_)) == 7) bwp = b_;
-    const unsigned byte = aset[((b * 3 + (size_t)bwp) * (size_t)N + k) * 64 + (e < n ? e : e - n)];
+    const unsigned byte = aset[((b * 3 + (size_t)st.plane()) * (size_t)N + k) * 64 + (e < n ? e : e - n)];
     const unsigned cd = e < n ? (byte & 3u) : ((byte >> 2) & 3u);
     codes[t] = (unsigned char)((valid && !(k == N - 1 && e >= n)) ? cd : 0u);
   }

@@ -1,5 +1,5 @@
-"""Do two builds of the library score, differentiate, warm-start, simulate and evaluate the policy to the same bytes (DESIGN.md
-7l, 7q)?
+"""Do two builds of the library score, differentiate, warm-start, simulate, evaluate the policy and differentiate the solution to
+the same bytes?
 For each of the two libraries -- the parent's first, then this build's -- one fresh child process (ALTRO_HIP_LIB selects the
 library, as in the other A/B tools) builds the seven cases of tests/evaluate_ref.py plus (12, 4) forced onto the
 one-wave-per-instance backend, solves each once and records SHA-256 of the raw bytes of
@@ -10,6 +10,9 @@ one-wave-per-instance backend, solves each once and records SHA-256 of the raw b
   simulate_policy_dev   nsamp 3, with and without w, clamp 0 and 1: J, c_max, dx_max, fb, Xout, Uout
   eval_policy_dev       at every knot: u, fb
   propagate_covariance_dev   W = 0.01 I: sx, su, dJ, fb and, where the case has a box, zmin_t, zmax_t at kappa = 1
+  solution_vjp / _jvp   nseed 3, the seeds of tests/test_solution_sens_gpu.py: all outputs and fb, gx0 alone; vx0 alone, all inputs
+  get_gain_factors_dev, gain_active_set, solution_vjp_data summed, per knot, the weights alone and with gU = None
+                        (7w; where the library refuses a call -- cone rows, m > 16, the unsolved case -- its status code)
 The parent's child ends before the other starts; each has its own time limit; a child that ends abnormally ends the tool and
 nothing more is started.  The result is the table of digests and whether every one is equal; exit status 1 when one differs.
 Usage: gpu_score_bytes_ab.py out.json <parent libaltro_hip.so>"""
@@ -17,7 +20,7 @@ import hashlib, json, os, subprocess, sys
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (R, os.path.join(R, "tests")):
     sys.path.insert(0, p)
-CHILD_LIMIT_S = 240
+CHILD_LIMIT_S = 300
 S = 3
 
 
@@ -26,10 +29,11 @@ def child(path):
     import torch
     import altro_amd_loader  # noqa: F401
     import altro_mpc_icra2021_amd as altro
-    from altro_mpc_icra2021_amd import mpc
+    from altro_mpc_icra2021_amd import api, mpc
     import evaluate_ref as ER
     import evaluate_grad_ref as GR
     import simulate_ref as SR
+    import test_solution_sens_gpu as SS
     import warm_start_ref as WR
     dev = torch.device("cuda", 0)
     T = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
@@ -87,6 +91,27 @@ def child(path):
         Wc = T(0.01 * np.eye(n))
         cov = altro.propagate_covariance(sv, None, Wc, None, 1.0 if any(c.kind == "box" for c in cs.cons) else None)
         rec(case, "propagate_covariance", **cov)
+        # the sensitivity of the solution, nseed 3; a call the library refuses records its status code
+        def sens(call, fn):
+            try:
+                got = fn()
+            except altro.AltroError as e:
+                out["%s | %s | status" % (case, call)] = "status %d" % e.code
+                return
+            rec(case, call, **(got if isinstance(got, dict) else dict(F=got)))
+
+        sd = SS.seeds(cs, 81, ns=S)
+        gX, gU, v0, vX, vU = (T(a) for a in (sd.gX, sd.gU, sd.vx0, sd.vXref, sd.vUref))
+        sens("solution_vjp", lambda: altro.solution_vjp(sv, gX, gU))
+        sens("solution_vjp gx0 alone", lambda: altro.solution_vjp(sv, gX, gU, out=("gx0",)))
+        sens("solution_jvp vx0 alone", lambda: altro.solution_jvp(sv, vx0=v0))
+        sens("solution_jvp", lambda: altro.solution_jvp(sv, v0, vX, vU))
+        sens("get_gain_factors_dev", lambda: api.get_gain_factors_dev(sv))
+        sens("gain_active_set", lambda: altro.gain_active_set(sv))
+        sens("solution_vjp_data summed", lambda: altro.solution_vjp_data(sv, gX, gU))
+        sens("solution_vjp_data per knot", lambda: altro.solution_vjp_data(sv, gX, gU, per_knot=True))
+        sens("solution_vjp_data weights alone", lambda: altro.solution_vjp_data(sv, gX, gU, out=("gQ", "gQf", "gR")))
+        sens("solution_vjp_data gU = None", lambda: altro.solution_vjp_data(sv, gX, None))
         # warm_start_dev (last: it rewrites the plane)
         U6 = T(WR.six_candidates(cs, Ubar))
         for rho in (0.0, 1e3):
