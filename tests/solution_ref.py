@@ -152,7 +152,7 @@ def gauss_solve(M, R):
         W[:, j] = W[:, j] / W[:, j, j, None]
         fac = W[:, :, j].copy()
         fac[:, j] = 0
-        W = W - fac[:, :, None] * W[:, j, None, :]
+        W[:, :, j:] = W[:, :, j:] - fac[:, :, None] * W[:, j, None, j:]      # (row j is zero left of its pivot: those columns do not change)
     return W[:, :, p:]
 
 

@@ -172,6 +172,33 @@ def test_against_the_stored_model_yardstick(name, pi):
         assert r.fac_code == UNSUP and r.refused == [UNSUP] * 10, (r.fac_code, r.refused)
 
 
+def test_against_the_stored_model_yardstick_at_128_knots():
+    """1 at the longest horizon the exact active set holds, (12, 4) at N = 128 with control and state sides in the set in every
+    ASet word (tests/lane16_horizons.py stored_set_case): the (N - 1) m nseed workspace of the sweeps at its largest, 127 * 4 * 3
+    doubles an instance; the same rule"""
+    import lane16_horizons as lh
+    name = lh.stored_set_name((12, 4), 128)
+    sv, cs = make_solver(name, True, lh.stored_set_case(name), dict(shared=()))
+    try:
+        assert sv.N == 128 and altro.wave_cycles(sv).size != 0
+        Xbar, _ = plane(sv)
+        r = NS(cs=cs, kw=None, pi=True, nofac=False, K=altro.gains(sv)[0], valid=policy_fb(sv, Xbar[:, 0]), sd=seeds(cs, 62), F=H(api.get_gain_factors_dev(sv)))
+        sd = r.sd
+        got = dict(vjp=call(sv, "vjp", dict(gX=sd.gX, gU=sd.gU), VJP_OUT), jvp=call(sv, "jvp", dict(vx0=sd.vx0, vXref=sd.vXref, vUref=sd.vUref), JVP_OUT),
+                   vjp_gx=call(sv, "vjp", dict(gX=sd.gX), VJP_OUT), jvp_u=call(sv, "jvp", dict(vUref=sd.vUref), JVP_OUT))
+    finally:
+        sv.close()
+    assert (r.valid == 1).all(), r.valid
+    ref, r64 = refs(r, LD), refs(r, np.float64)
+    w = []
+    for g, out in got.items():
+        assert same(out["fb"], r.valid), g
+        for k in out:
+            if k != "fb":
+                w.append(within(out[k], getattr(ref, g)[k], getattr(r64, g)[k], r.valid, "%s %s %s" % (name, g, k)))
+    print(name, "largest err / bound", max(w))
+
+
 @pytest.mark.parametrize("name,pi", [q for q in RUNS if q[0] != NOFAC], ids=[i for q, i in zip(RUNS, IDS) if q[0] != NOFAC])
 def test_adjoint_identity(name, pi):
     """2: <gX, dX> + <gU, dU> against <gx0, vx0> + <gXref, vXref> + <gUref, vUref> per (instance, seed); the gap relative to the
