@@ -12,7 +12,7 @@ from .api import first_knot, initial_state, signal_stream, solve_async, synchron
 from .api import evaluate, evaluate_grad, merit, propagate_covariance, rollout, simulate_policy, warm_start  # noqa: F401
 from .api import evaluate_al, optimal_cost, penalty  # noqa: F401
 from .api import get_gain_factors_dev, solution, solution_jvp, solution_vjp  # noqa: F401
-from .api import gain_active_set, mpc_layer, solution_vjp_data  # noqa: F401
+from .api import cost_to_go, gain_active_set, mpc_layer, solution_vjp_data  # noqa: F401
 from .api import alpha_trace, dev_refusals, eval_policy, gain_factors, gains, get_gains_dev, set_bounds, set_dynamics, set_dynamics_track  # noqa: F401
 from .api import (ALTROSolver, AltroError, BoundConstraint, ConstraintList, GoalConstraint, LinearConstraint,
                   LinearModel, NormConstraint, Problem,  # noqa: F401

@@ -57,6 +57,7 @@ EXPORTS = [
     "altro_batch_get_gain_factors_dev",
     "altro_batch_solution_vjp_data_dev", "altro_batch_solution_vjp_data",
     "altro_batch_get_gain_active_set_dev", "altro_batch_get_gain_active_set",
+    "altro_batch_cost_to_go_dev", "altro_batch_cost_to_go",
 ]
 """every symbol include/altro_batch.h declares"""
 
@@ -103,6 +104,14 @@ class SensDataOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in SENS_DATA_OUT_FIELDS]
 
 
+CTG_OUT_FIELDS = ("P0", "p0", "v0", "P", "p", "v")
+
+
+class CtgOut(C.Structure):
+    """altro_ctg_out: six nullable pointers (device addresses for the _dev call, host addresses for the host twin)"""
+    _fields_ = [(k, C.c_void_p) for k in CTG_OUT_FIELDS]
+
+
 class AltroError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libaltro_hip error {code}: {msg}")
@@ -113,7 +122,7 @@ def build(force=False, verbose=False):
     """Generate the DPP block include and compile the HIP library for gfx950, in tree.  The library is several translation
     units (altro_batch.hip: the C-ABI, the 16-lane kernels, the polish; wide_inst.hip once per group of one-wave-per-instance
     kernels, solve_wide.h ALTRO_WIDE_KERNELS) compiled side by side -- one after the other they take ~6 minutes."""
-    srcs = [os.path.join(CSRC, f) for f in ("altro_batch.hip", "wide_inst.hip", "solve_dpp16.h", "solve_wide.h", "wide_backend.h", "backend_common.h", "launch_ring.h", "pn_core.h", "pn_polish.h", "pn_wide.h", "mpc_log.h", "device_io.h", "device_pool.h", "episode_clock.h", "policy.h", "evaluate.h", "evaluate_grad.h", "evaluate_al.h", "warm_start.h", "simulate.h", "covariance.h", "sensitivity.h", "sensitivity_data.h", "stage_layout.h", "gen_dpp_blocks.py")]
+    srcs = [os.path.join(CSRC, f) for f in ("altro_batch.hip", "wide_inst.hip", "solve_dpp16.h", "solve_wide.h", "wide_backend.h", "backend_common.h", "launch_ring.h", "pn_core.h", "pn_polish.h", "pn_wide.h", "mpc_log.h", "device_io.h", "device_pool.h", "episode_clock.h", "policy.h", "evaluate.h", "evaluate_grad.h", "evaluate_al.h", "warm_start.h", "simulate.h", "covariance.h", "cost_to_go.h", "sensitivity.h", "sensitivity_data.h", "stage_layout.h", "gen_dpp_blocks.py")]
     srcs.append(os.path.join(os.path.dirname(_HERE), "include", "altro_batch.h"))
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):
         return LIB_PATH
@@ -235,6 +244,9 @@ def lib():
         L.altro_batch_solution_vjp_data.argtypes = [H, C.c_int32, dp, dp, C.c_int32, C.POINTER(SensDataOut), ip]
         L.altro_batch_get_gain_active_set_dev.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p]
         L.altro_batch_get_gain_active_set.argtypes = [H, C.POINTER(C.c_uint8), dp, ip]
+    if hasattr(L, "altro_batch_cost_to_go_dev"):   # the quadratic cost-to-go of the stored policy
+        L.altro_batch_cost_to_go_dev.argtypes = [H, C.c_int32, C.POINTER(CtgOut), C.c_void_p]
+        L.altro_batch_cost_to_go.argtypes = [H, C.c_int32, C.POINTER(CtgOut), ip]
     L.altro_batch_add_constraint.argtypes = [H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                              dp, dp, dp, dp, C.c_int32, ip]
     L.altro_batch_update_constraint_data.argtypes = [H, C.c_int32, dp, dp]

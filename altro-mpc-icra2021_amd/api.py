@@ -1577,6 +1577,75 @@ def gain_active_set(solver, out=None):
     return res
 
 
+CTG_OUTPUTS = _lib.CTG_OUT_FIELDS + ("fb",)
+
+
+def _cost_to_go_args(solver, out):
+    """({name: array or None} in the order of CTG_OUTPUTS, {name: shape}); refuses here what the library would refuse"""
+    B, N, n = solver.B, solver.N, solver.n
+    shp = dict(P0=(B, n, n), p0=(B, n), v0=(B,), P=(B, N, n, n), p=(B, N, n), v=(B, N), fb=(B,))
+    if out is None:
+        out = ("P0", "p0", "v0", "fb")
+    if not isinstance(out, dict):
+        if isinstance(out, str) or not all(isinstance(k, str) for k in out):
+            raise ValueError(f"cost_to_go: out is a sequence of names or a dict name -> array; the outputs are {CTG_OUTPUTS}")
+        out = {k: None for k in out}
+    unknown = [k for k in out if k not in shp]
+    if unknown:
+        raise ValueError(f"cost_to_go: out: unknown output {unknown[0]!r}; the outputs are {CTG_OUTPUTS}")
+    if not any(k in out for k in _lib.CTG_OUT_FIELDS):
+        raise ValueError(f"cost_to_go: out needs at least one of {_lib.CTG_OUT_FIELDS}")
+    return {k: out[k] for k in CTG_OUTPUTS if k in out}, shp
+
+
+def _cost_to_go_dev(solver, penalty=False, out=None):
+    """device form of cost_to_go: every tensor is validated (shape, dtype, strides, device) before the library is called; an
+    output named without an array gets a new tensor"""
+    out, shp = _cost_to_go_args(solver, out)
+    dt = lambda k: "torch.int32" if k == "fb" else "torch.float64"
+    if any(a is None for a in out.values()):
+        import torch
+        dev = torch.device("cuda", solver.device)
+        out = {k: (torch.empty(shp[k], dtype=torch.int32 if k == "fb" else torch.float64, device=dev) if a is None else a) for k, a in out.items()}
+    for k, t in out.items():
+        check_device_tensor(t, shp[k], solver.device, k, dtype=dt(k))
+    st = _lib.CtgOut()
+    for k in _lib.CTG_OUT_FIELDS:
+        if k in out:
+            setattr(st, k, out[k].data_ptr())
+    solver._chk(solver._L.altro_batch_cost_to_go_dev(solver.h, 1 if penalty else 0, C.byref(st), _addr(out.get("fb"))))
+    return out
+
+
+def cost_to_go(solver, penalty=False, out=None):
+    """The quadratic cost-to-go of the stored policy around the trajectory the solver holds (altro_batch_cost_to_go / _dev,
+    DESIGN.md 7x):  V_k(x) = v_k + p_k'(x - xbar_k) + 1/2 (x - xbar_k)' P_k (x - xbar_k), by the backward recursion
+    P_k = Hx + K_k' Hu K_k + M_k' P_{k+1} M_k, M_k = A_k + B_k K_k -- the transpose of propagate_covariance's.  Returns a dict:
+    P0 (B, n, n), p0 (B, n), v0 (B,) and fb (B,) int32; out may name any subset of those plus the tracks P (B, N, n, n), p (B, N, n)
+    and v (B, N): a sequence of names (new numpy arrays) or a dict name -> array to write into.  penalty=False, the plain cost:
+    the model is exact, J of simulate_policy (clamp off, no disturbance) from xbar_0 + d is v0 + p0'd + d'P0 d / 2, and
+    tr(P0 Sigma0) / 2 + sum_{k>=1} tr(P_k W) / 2 is propagate_covariance's dJ; fb = 0: no valid gains, the loop is open.
+    penalty=True, the augmented Lagrangian inside the active set of the stored pass (box-only problems, AltroError UNSUPPORTED
+    otherwise): P_k is the value Hessian of the LQ problem the stored gains solve, P0 the Hessian of the optimal L_A with respect
+    to x0; fb = 0 (gain_active_set's): every row of the instance is NaN.  Matrices are as computed, not re-symmetrised.  GPU
+    tensors (float64, contiguous; fb int32): stream-ordered, nothing synchronises; numpy: the host twin, the same bytes.  Nothing
+    is converted, a mix is refused, and nothing the solver holds changes."""
+    if _gpu_form("cost_to_go: the arrays of out", tuple(a for a in out.values() if a is not None) if isinstance(out, dict) else ()):
+        with _bracket(solver):
+            return _cost_to_go_dev(solver, penalty, out)
+    out, shp = _cost_to_go_args(solver, out)
+    dt = lambda k: np.int32 if k == "fb" else np.float64
+    out = {k: (np.empty(shp[k], dtype=dt(k)) if a is None else a) for k, a in out.items()}
+    for k, a in out.items():
+        _check_np_out("cost_to_go", k, a, shp[k], dt(k))
+    st = _lib.CtgOut()
+    for k in _lib.CTG_OUT_FIELDS:
+        if k in out:
+            setattr(st, k, out[k].ctypes.data)
+    solver._chk(solver._L.altro_batch_cost_to_go(solver.h, 1 if penalty else 0, C.byref(st), out["fb"].ctypes.data_as(_IP) if "fb" in out else None))
+    return out
+
+
 _solution_fn = None
 
 

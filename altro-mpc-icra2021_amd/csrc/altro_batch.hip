@@ -20,6 +20,7 @@
 #include "evaluate_grad.h"
 #include "evaluate_al.h"
 #include "sensitivity_data.h"
+#include "cost_to_go.h"
 #include "launch_ring.h"
 #include "pn_polish.h"
 #include "policy.h"
@@ -2892,6 +2893,51 @@ int32_t altro_batch_get_gain_active_set_dev(altro_handle* h, uint8_t* codes, dou
 }
 int32_t altro_batch_get_gain_active_set(altro_handle* h, uint8_t* codes, double* mu_pass, int32_t* fb) {
   return gain_active_set_call(h, "altro_batch_get_gain_active_set", true, codes, mu_pass, fb);
+}
+
+// ---- the quadratic cost-to-go of the stored policy (kernels in cost_to_go.h)
+// io: device arrays (the caller's, validated; or the staged copies of the host twin).  Enqueues one kernel, allocates nothing:
+// P lives in registers (16-lane backend) or LDS (one-wave-per-instance backend).
+static int cost_to_go_launch(altro_handle* h, altro::CtgIO io) {
+  if (h->wide) return fwd(h, h->wide->cost_to_go_dev(io));
+  if (int rc = score_ready(h)) return rc;
+  io.Lb = h->Lb; io.mu = h->mu; io.bslot = h->bslot; io.nbp = h->nbp;
+  const size_t B = h->d.batch;
+  const size_t rows = (B + 3) & ~(size_t)3;   // whole waves of four rows
+  hipLaunchKernelGGL(altro::k_ctg16, grid_for(rows * LW), dim3(256), 0, h->stream, io, h->Z, h->cur, (size_t)h->d.N * LW, h->KD, h->kmu, h->ahash,
+                     eval16_params(h), B, rows);
+  HIPCHK(h, hipGetLastError());
+  return ALTRO_OK;
+}
+
+static int32_t cost_to_go_call(altro_handle* h, const char* fn, bool host, int32_t mode, const altro_ctg_out* out, int32_t* fb) {
+  return twin_call(
+      h, fn, host, true,
+      [&]() -> int {
+        const std::string f(fn);
+        if (!out) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": out is required");
+        if (!out->P0 && !out->p0 && !out->v0 && !out->P && !out->p && !out->v) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": every member of out is null");
+        if (mode != 0 && mode != 1) FAIL(h, ALTRO_ERR_INVALID_ARG, f + ": mode must be 0 or 1");
+        return mode ? active_set_rules(h, f) : ALTRO_OK;
+      },
+      [&](TwinArgs& a) {
+        double* const po[6] = {out->P0, out->p0, out->v0, out->P, out->p, out->v};
+        altro::stage_cost_to_go(a, h->d.batch, h->d.N, h->d.n, po, fb);
+      },
+      [&](const TwinArgs& a) {
+        altro::CtgIO io{};
+        io.P0 = a.f64(altro::CTG_P0); io.p0 = a.f64(altro::CTG_SP0); io.v0 = a.f64(altro::CTG_V0);
+        io.P = a.f64(altro::CTG_P); io.p = a.f64(altro::CTG_SP); io.v = a.f64(altro::CTG_V);
+        io.fb = a.i32(altro::CTG_FB);
+        io.mode = mode;
+        return cost_to_go_launch(h, io);
+      });
+}
+int32_t altro_batch_cost_to_go_dev(altro_handle* h, int32_t mode, const altro_ctg_out* out, int32_t* fb) {
+  return cost_to_go_call(h, "altro_batch_cost_to_go_dev", false, mode, out, fb);
+}
+int32_t altro_batch_cost_to_go(altro_handle* h, int32_t mode, const altro_ctg_out* out, int32_t* fb) {
+  return cost_to_go_call(h, "altro_batch_cost_to_go", true, mode, out, fb);
 }
 
 // ---- per-instance active mask and cold restart

@@ -60,7 +60,9 @@ struct SensDataIO {
   int per_knot;
 };
 
-// g = dL_A / dc of a BOX side of value c with dual l (evaluate_al.h's al_lin without the sum)
+// g = dL_A / dc of a BOX side of value c with dual l (evaluate_al.h's al_lin without the sum).  The two must keep ONE rule for
+// `active` and one form of g: cost_to_go.h takes its g from al_lin, next to this file's hz and validity, and relies on the two
+// returning the same bits.
 __device__ __forceinline__ double sensd_side(double c, double l, double mu) {
 #pragma clang fp contract(off)
   const bool active = !(c < 0.0) || l > 0.0;

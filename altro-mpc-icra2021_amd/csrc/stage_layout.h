@@ -1,7 +1,7 @@
 // stage_layout.h -- the argument table of each host/device twin pair (altro_batch_eval_policy, altro_batch_evaluate,
 // altro_batch_evaluate_grad, altro_batch_evaluate_al, altro_batch_warm_start, altro_batch_simulate_policy,
 // altro_batch_propagate_covariance, altro_batch_solution_vjp, altro_batch_solution_jvp, altro_batch_solution_vjp_data,
-// altro_batch_get_gain_active_set and their `_dev` forms): one function per
+// altro_batch_get_gain_active_set, altro_batch_cost_to_go and their `_dev` forms): one function per
 // pair names every array argument once, with its element count, type, direction and mode.  The `_dev` form validates the caller's
 // pointers against the extents written here; the host twin puts the same arrays, in the same order, into the handle's staging buffer.
 // Plain host arithmetic, no HIP: altro_batch.hip's TwinArgs adds the validation and the copies, and tools/stage_layout_check.cpp runs
@@ -175,6 +175,15 @@ inline void stage_gain_active_set(StageLayout& L, size_t B, size_t N, size_t n, 
   L.add<double>("mu_pass", B, nullptr, mu_pass, StageLayout::OPTIONAL);
   L.add<int32_t>("fb", B, nullptr, fb, StageLayout::RESERVED);
   L.add<uint8_t>("codes", nc, nullptr, codes, StageLayout::OPTIONAL);
+}
+
+// out[0 .. 5]: the six pointers of altro_ctg_out in the order of the struct; every sub-array only when given
+enum { CTG_P0, CTG_SP0, CTG_V0, CTG_P, CTG_SP, CTG_V, CTG_FB };
+inline void stage_cost_to_go(StageLayout& L, size_t B, size_t N, size_t n, double* const (&out)[6], int32_t* fb) {
+  const char* const name[6] = {"P0", "p0", "v0", "P", "p", "v"};
+  const size_t count[6] = {B * n * n, B * n, B, B * N * n * n, B * N * n, B * N};
+  for (int i = 0; i < 6; ++i) L.add<double>(name[i], count[i], nullptr, out[i], StageLayout::OPTIONAL);
+  L.add<int32_t>("fb", B, nullptr, fb, StageLayout::RESERVED);
 }
 
 }  // namespace altro

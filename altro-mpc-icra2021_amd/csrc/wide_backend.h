@@ -23,6 +23,7 @@
 #include "policy.h"
 #include "solve_wide.h"
 #include "covariance.h"
+#include "cost_to_go.h"
 #include "pn_wide.h"
 #include "backend_common.h"
 
@@ -145,6 +146,7 @@ struct WideBackend : altro::BackendCommon {   // (what both backends hold and do
   std::vector<hipEvent_t> bench_ev;
   int *cur = nullptr, *ctype = nullptr, *rowk0 = nullptr, *rowk1 = nullptr, *rowc0 = nullptr, *rowcp = nullptr;
   size_t cov_lds_set = 0;      // altro_batch_propagate_covariance(_dev): the LDS bytes its kernel has been allowed (above the 64 KB a kernel gets unasked)
+  size_t ctg_lds_set = 0;      // altro_batch_cost_to_go(_dev): likewise
   int dyn_blocks = 1, dyn_step_stride = 0;
   size_t dyn_table_blocks = 0;   // blocks the tables A, Bm, f have room for (set_dynamics_dev reuses them while it is unchanged)
   bool ltv = false;
@@ -842,6 +844,26 @@ struct WideBackend : altro::BackendCommon {   // (what both backends hold and do
       cov_lds_set = lds;
     }
     hipLaunchKernelGGL(altro::k_cov_wide, dim3((unsigned)d.batch), dim3(64), lds, stream, io, cr, Kg, bwst,
+                       (gains_valid || debug_keep_gains) ? 1 : 0, eval_params());
+    WCHK(hipGetLastError());
+    return ALTRO_OK;
+  }
+  // altro_batch_cost_to_go_dev (cost_to_go.h; pointers and argument rules checked by the caller, the host twin passes staged
+  // copies): one kernel, one wave per instance.  Reads what propagate_covariance_dev reads, the planes the handle holds and --
+  // mode 1 only -- the active set of the last backward pass, the duals and the penalty; writes the caller's outputs only and
+  // allocates nothing.  Mode 1 needs a diagonal Hessian: generic rows are refused.
+  int cost_to_go_dev(altro::CtgIO io) {
+    WCHK(hipSetDevice(device));
+    if (io.mode != 0 && Pn > 0)
+      WFAIL(ALTRO_ERR_UNSUPPORTED, "cost_to_go: mode 1 needs a box-only problem: with LINEAR or SOC rows the Hessian inside the active set is not diagonal");
+    if (int rc = eval_ready()) return rc;
+    io.Lb = Lb; io.mu = mu; io.bslot = nullptr; io.nbp = 0;
+    const size_t lds = altro::ctgw_lds_doubles(d.n, d.m) * sizeof(double);
+    if (lds > 65536 && lds > ctg_lds_set) {
+      WCHK(hipFuncSetAttribute((const void*)altro::k_ctg_wide, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      ctg_lds_set = lds;
+    }
+    hipLaunchKernelGGL(altro::k_ctg_wide, dim3((unsigned)d.batch), dim3(64), lds, stream, io, X, U, cur, Kg, bwst, aset,
                        (gains_valid || debug_keep_gains) ? 1 : 0, eval_params());
     WCHK(hipGetLastError());
     return ALTRO_OK;

@@ -392,6 +392,12 @@ class ExternalMPC:
         in by kappa deviations that set_bounds takes as it is: a pass-through, GPU tensors or numpy."""
         return api.propagate_covariance(self.solver, Sigma0=Sigma0, W=W, con_id=con_id, kappa=kappa, out=out)
 
+    def cost_to_go(self, penalty=False, out=None):
+        """The dict of api.cost_to_go: the quadratic cost-to-go (P, p, v) of the policy the solver holds once its stream reaches
+        this point, around the trajectory it holds -- the second order of the optimal cost in x0, the expected cost increase
+        for every (Sigma0, W) at once: a pass-through, GPU tensors or numpy."""
+        return api.cost_to_go(self.solver, penalty=penalty, out=out)
+
     def _constraints_dev(self, constraint_data, bounds):
         s = self.solver
         for con, (A, b) in (constraint_data or {}).items():

@@ -751,7 +751,7 @@ int32_t altro_batch_get_gain_factors_dev(altro_handle* h, double* F);
  * altro_batch_solution_vjp_dev the result is the exact derivative of the minimiser of the augmented Lagrangian at the
  * multipliers, the penalty and the active set of the stored pass; its distance to the derivative of the constrained optimum
  * has not been measured.  There is no forward mode: the response of the solution to a tangent of the dynamics needs the
- * value Hessians S_k, which no kernel keeps.
+ * value Hessians S_k; altro_batch_cost_to_go_dev (mode 1) now computes them, the forward mode itself is still not built.
  * altro_batch_solution_vjp_data_dev: nseed >= 1 seeds per instance, gX [batch][nseed][N][n], gU [batch][nseed][N-1][m] (a NULL
  * one is zero, not both); out a struct of output pointers, each may be NULL, not all:
  *     gQ, gQf       [batch][nseed][n]            gR   [batch][nseed][m]            gzmin, gzmax   [batch][nseed][n+m]
@@ -791,6 +791,45 @@ int32_t altro_batch_solution_vjp_data(altro_handle* h, int32_t nseed, const doub
                                       const altro_sens_data_out* out, int32_t* fb);
 int32_t altro_batch_get_gain_active_set_dev(altro_handle* h, uint8_t* codes, double* mu_pass, int32_t* fb);
 int32_t altro_batch_get_gain_active_set(altro_handle* h, uint8_t* codes, double* mu_pass, int32_t* fb);
+
+/* ---- the quadratic cost-to-go of the stored policy: value Hessians, gradients and values, on the device.  Around the
+ * trajectory (xbar, ubar) the handle holds, with K_k the matrix altro_batch_get_gains returns and M_k = A_k + B_k K_k,
+ *   V_k(x) = v_k + p_k' (x - xbar_k) + 1/2 (x - xbar_k)' P_k (x - xbar_k)
+ *   P_{N-1} = Hx_{N-1}                 P_k = Hx_k + K_k' Hu_k K_k + M_k' P_{k+1} M_k
+ *   p_{N-1} = lx_{N-1}                 p_k = lx_k + K_k' lu_k + M_k' p_{k+1}
+ *   v_{N-1} = the value of knot N-1    v_k = the value of knot k + v_{k+1},      k = N-2 .. 0
+ * the transpose of the recursion of altro_batch_propagate_covariance_dev.  e = z - zref, w the weights as
+ * altro_batch_evaluate_dev applies them (dt Q, dt R; Qf at knot N-1).
+ * mode = 0, the plain cost: H = diag(w), l = w e, the value of a knot its term of J of altro_batch_evaluate_dev.  The model is
+ *   exact: for the unclamped loop of altro_batch_simulate_policy_dev started at xbar_0 + d with w = NULL,
+ *   J = v_0 + p_0' d + 1/2 d' P_0 d, and v_0 is J of the held trajectory.  1/2 tr(P_0 Sigma0) + 1/2 sum_{k=1..N-1} tr(P_k W) is
+ *   the dJ of altro_batch_propagate_covariance_dev, for every (Sigma0, W) at once.  fb as altro_batch_eval_policy_dev; with 0
+ *   the loop is open, K = 0.  Works on every handle: conic, m > 16, any N.
+ * mode = 1, the augmented Lagrangian inside the active set of the stored pass, box terms only: H = diag(hz),
+ *   hz = w + mu_p [upper side in the set] + mu_p [lower side] (the codes and mu_pass of altro_batch_get_gain_active_set_dev);
+ *   l the local term of altro_batch_evaluate_al_dev at U == NULL, w e + g_hi - g_lo with the duals and the penalty the handle
+ *   holds; the value of a knot its terms of L_A as that call values them.  P_k is the value Hessian of the LQ problem the stored
+ *   gains solve, P_0 the Hessian of the optimal L_A with respect to x0 inside that set.  fb as
+ *   altro_batch_get_gain_active_set_dev; with 0 every output row of the instance is a quiet NaN.
+ * out: a struct of output pointers, each may be NULL, not all:
+ *     P0 [batch][n][n]   p0 [batch][n]   v0 [batch]   P [batch][N][n][n]   p [batch][N][n]   v [batch][N]
+ *   Matrices are row-major, as computed and not re-symmetrised (as Sout).  fb [batch] may be NULL.  Which outputs are NULL
+ *   changes no other output and not fb.
+ * The call sees the window, the dynamics blocks, the weights, the bounds and the duals altro_batch_evaluate_al_dev sees at that
+ * point of the stream (episode clock included).  No masking, no clamp; a NaN stays in its instance.  Instance b gets the bytes it
+ * would get on a batch-1 handle.  Nothing the library owns changes, and the next solve is that of a handle that never made the
+ * call.  The call allocates nothing: P lives in registers or LDS.  Constraint tables a host edit left unpacked are packed first,
+ * as by the sibling calls.  Summation orders: csrc/cost_to_go.h.  The _dev form follows the rules of the device-pointer block;
+ * the host twin goes through the staging buffer, synchronises and writes the same bytes.
+ * ALTRO_ERR_INVALID_ARG (nothing enqueued, the handle usable): NULL handle; out NULL or all six members NULL; mode not 0 or 1;
+ * _dev: what the device-pointer block refuses.  ALTRO_ERR_STATE: as altro_batch_propagate_covariance_dev.
+ * ALTRO_ERR_UNSUPPORTED (nothing enqueued): mode 1 exactly where altro_batch_get_gain_active_set_dev answers so -- a handle with
+ * a LINEAR or SOC constraint, and the 16-lane kernels with N > 128. */
+typedef struct altro_ctg_out {
+  double *P0, *p0, *v0, *P, *p, *v;
+} altro_ctg_out;
+int32_t altro_batch_cost_to_go_dev(altro_handle* h, int32_t mode, const altro_ctg_out* out, int32_t* fb);
+int32_t altro_batch_cost_to_go(altro_handle* h, int32_t mode, const altro_ctg_out* out, int32_t* fb);
 
 /* ---- warm start from the best of several candidates, chosen on the device.  The closed loops of the reference start every
  * solve from ONE guess (the shifted previous solution: random_linear_problem.jl:136, simple_rocket.jl:160); a loop that also

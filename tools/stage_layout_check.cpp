@@ -316,6 +316,42 @@ int main() {
       arg_is(L, altro::GA_FB, "fb", false, B * I, "gain active set: arg fb", c);
       arg_is(L, altro::GA_CODES, "codes", false, B * N * (n + m), "gain active set: arg codes", c);
     }
+    // altro_batch_cost_to_go: P0 [B][n][n], p0 [B][n], v0 [B], P [B][N][n][n], p [B][N][n], v [B][N], each only when given, in the
+    // order of altro_ctg_out; fb has room either way and comes last (ints)
+    for (int c = 0; c < 128; ++c) {
+      double* P0 = c & 1 ? d : nullptr;
+      double* p0 = c & 2 ? d : nullptr;
+      double* v0 = c & 4 ? d : nullptr;
+      double* P = c & 8 ? d : nullptr;
+      double* p = c & 16 ? d : nullptr;
+      double* v = c & 32 ? d : nullptr;
+      int32_t* fb = c & 64 ? i32 : nullptr;
+      double* const out[6] = {P0, p0, v0, P, p, v};
+      StageLayout L;
+      altro::stage_cost_to_go(L, B, N, n, out, fb);
+      expect(L.nslots == 7, "cost to go: slots", c);
+      size_t s = 0;
+      slot_is(L, altro::CTG_P0, s, P0 ? B * n * n * D : 0, P0, D, "cost to go: P0", c); s += P0 ? B * n * n * D : 0;
+      slot_is(L, altro::CTG_SP0, s, p0 ? B * n * D : 0, p0, D, "cost to go: p0", c); s += p0 ? B * n * D : 0;
+      slot_is(L, altro::CTG_V0, s, v0 ? B * D : 0, v0, D, "cost to go: v0", c); s += v0 ? B * D : 0;
+      slot_is(L, altro::CTG_P, s, P ? B * N * n * n * D : 0, P, D, "cost to go: P", c); s += P ? B * N * n * n * D : 0;
+      slot_is(L, altro::CTG_SP, s, p ? B * N * n * D : 0, p, D, "cost to go: p", c); s += p ? B * N * n * D : 0;
+      slot_is(L, altro::CTG_V, s, v ? B * N * D : 0, v, D, "cost to go: v", c); s += v ? B * N * D : 0;
+      slot_is(L, altro::CTG_FB, s, B * I, fb, I, "cost to go: fb", c); s += B * I;
+      expect(L.bytes == s, "cost to go: size", c);
+      expect(L.slot[altro::CTG_P0].out == P0 && L.slot[altro::CTG_SP0].out == p0 && L.slot[altro::CTG_V0].out == v0 &&
+                 L.slot[altro::CTG_P].out == P && L.slot[altro::CTG_SP].out == p && L.slot[altro::CTG_V].out == v &&
+                 L.slot[altro::CTG_FB].out == fb,
+             "cost to go: copies out", c);
+      for (int q = 0; q < 7; ++q) expect(L.slot[q].in == nullptr, "cost to go: no input", c);
+      arg_is(L, altro::CTG_P0, "P0", false, B * n * n * D, "cost to go: arg P0", c);
+      arg_is(L, altro::CTG_SP0, "p0", false, B * n * D, "cost to go: arg p0", c);
+      arg_is(L, altro::CTG_V0, "v0", false, B * D, "cost to go: arg v0", c);
+      arg_is(L, altro::CTG_P, "P", false, B * N * n * n * D, "cost to go: arg P", c);
+      arg_is(L, altro::CTG_SP, "p", false, B * N * n * D, "cost to go: arg p", c);
+      arg_is(L, altro::CTG_V, "v", false, B * N * D, "cost to go: arg v", c);
+      arg_is(L, altro::CTG_FB, "fb", false, B * I, "cost to go: arg fb", c);
+    }
   }
   std::printf("stage_layout_check: %ld checks passed\n", checks);
   return 0;
