@@ -145,8 +145,6 @@ struct WideBackend : altro::BackendCommon {   // (what both backends hold and do
   double *Xsave = nullptr, *Usave = nullptr;  // Z0 of benchmark_solve
   std::vector<hipEvent_t> bench_ev;
   int *cur = nullptr, *ctype = nullptr, *rowk0 = nullptr, *rowk1 = nullptr, *rowc0 = nullptr, *rowcp = nullptr;
-  size_t cov_lds_set = 0;      // altro_batch_propagate_covariance(_dev): the LDS bytes its kernel has been allowed (above the 64 KB a kernel gets unasked)
-  size_t ctg_lds_set = 0;      // altro_batch_cost_to_go(_dev): likewise
   int dyn_blocks = 1, dyn_step_stride = 0;
   size_t dyn_table_blocks = 0;   // blocks the tables A, Bm, f have room for (set_dynamics_dev reuses them while it is unchanged)
   bool ltv = false;
@@ -839,10 +837,9 @@ struct WideBackend : altro::BackendCommon {   // (what both backends hold and do
       cr.p = bl->p; cr.k0 = bl->k0; cr.k1 = bl->k1; cr.r0 = bl->r0;
     }
     const size_t lds = altro::covw_lds_doubles(d.n, d.m) * sizeof(double);
-    if (lds > 65536 && lds > cov_lds_set) {
-      WCHK(hipFuncSetAttribute((const void*)altro::k_cov_wide, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      cov_lds_set = lds;
-    }
+    // the allowance belongs to the kernel, for the whole process, and another handle may have set it since: asked for at
+    // every launch above the 64 KB a kernel gets unasked, as prepare_launch does for the solve kernels
+    if (lds > 65536) WCHK(hipFuncSetAttribute((const void*)altro::k_cov_wide, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(altro::k_cov_wide, dim3((unsigned)d.batch), dim3(64), lds, stream, io, cr, Kg, bwst,
                        (gains_valid || debug_keep_gains) ? 1 : 0, eval_params());
     WCHK(hipGetLastError());
@@ -859,10 +856,7 @@ struct WideBackend : altro::BackendCommon {   // (what both backends hold and do
     if (int rc = eval_ready()) return rc;
     io.Lb = Lb; io.mu = mu; io.bslot = nullptr; io.nbp = 0;
     const size_t lds = altro::ctgw_lds_doubles(d.n, d.m) * sizeof(double);
-    if (lds > 65536 && lds > ctg_lds_set) {
-      WCHK(hipFuncSetAttribute((const void*)altro::k_ctg_wide, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      ctg_lds_set = lds;
-    }
+    if (lds > 65536) WCHK(hipFuncSetAttribute((const void*)altro::k_ctg_wide, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));   // (at every launch: propagate_covariance_dev)
     hipLaunchKernelGGL(altro::k_ctg_wide, dim3((unsigned)d.batch), dim3(64), lds, stream, io, X, U, cur, Kg, bwst, aset,
                        (gains_valid || debug_keep_gains) ? 1 : 0, eval_params());
     WCHK(hipGetLastError());

@@ -5,6 +5,13 @@ penalty.
 Shapes: the eight cases and solved handles of tests/test_covariance_gpu.py (build, make_solver; N = 5 .. 8, batch 9 / 5 / 3), each
 "shared" and "pi"; box-only copies of its wide-ltv(12,12) and wide(17,5), whose LINEAR rows make mode 1 unsupported there; and
 (12, 4) at N = 3 and batch 5, the shortest recursion.  Mode 0 runs on all of them, mode 1 on the box-only ones.
+The horizon axis of the 16-lane backend: the stored-set cases of tests/lane16_horizons.py, (12, 4) and (6, 6) at N = 17, 33 and
+128, batch 2, "pi" (k_ctg16 reads the lane's two bits a knot as ASet word k >> 4, and at N <= 16 word 0 is the only one there is),
+both modes, guarded by sides in the set at knots >= 16 and, at N = 128, >= 112; and (12, 4) at N = 130, where mode 1 is refused
+and mode 0 is held to the rule.
+The one-wave-per-instance backend at a padded state of 48 ((40, 6), (48, 13), (48, 32): the three-tile strip of gemm_rows under
+k_ctg_wide's leading dimensions, just under and over 64 KB of LDS) and at m > n (12, 20) lives in tests/stored_policy_matrix.py
+and tests/test_stored_policy_matrix_gpu.py, which import the checks of this file.
 
 The accuracy bound of an output array, per instance: err = max |out - ref| / max |ref| against the long-double yardstick must
 not exceed 16 x max(err of the float64 yardstick against the same ref, 2^-52).  The bound is computed here from the two numpy
@@ -33,6 +40,7 @@ from altro_mpc_icra2021_amd import api
 import cost_to_go_ref as CT
 import covariance_ref as CR
 import evaluate_ref as ER
+import lane16_horizons as lh
 import solution_data_ref as SD
 import test_covariance_gpu as TC
 from test_covariance_gpu import OPTS, make_solver
@@ -45,9 +53,12 @@ EPS = 2.0 ** -52
 SENT = -12345.5
 NAMES = altro._lib.CTG_OUT_FIELDS
 LTVBOX, W17BOX, SHORT = "wide-ltv(12,12)-box", "wide(17,5)-box", "16(12,4)N3"
-MODE1 = ("16-box(12,4)", "16(6,6)", "16(8,4)", "wide(64,16)", "wide(30,25)", LTVBOX, W17BOX, SHORT)
+LONG = list(lh.STORED_SET_CASES)       # the stored set beyond ASet word 0: (12, 4) and (6, 6) at N = 17, 33, 128, batch 2, "pi"
+MODE1 = ("16-box(12,4)", "16(6,6)", "16(8,4)", "wide(64,16)", "wide(30,25)", LTVBOX, W17BOX, SHORT) + tuple(LONG)
 SHAPES = TC.SHAPES + [LTVBOX, W17BOX, SHORT]
-RUNS = [(s, pi) for s in SHAPES for pi in (False, True)]
+RUNS_SHORT = [(s, pi) for s in SHAPES for pi in (False, True)]
+IDS_SHORT = [s + ("-pi" if pi else "-shared") for s, pi in RUNS_SHORT]
+RUNS = RUNS_SHORT + [(s, True) for s in LONG]
 IDS = [s + ("-pi" if pi else "-shared") for s, pi in RUNS]
 RUNS1 = [(s, pi) for s, pi in RUNS if s in MODE1]
 IDS1 = [s + ("-pi" if pi else "-shared") for s, pi in RUNS1]
@@ -59,6 +70,8 @@ def build(name, pi):
         cs, kw, _, _ = TC.build(name[:-len("-box")], pi)
         cs.cons = cs.cons[:1]
         return cs, dict(kw, shared=tuple(s for s in kw["shared"] if s != 1))
+    if name in LONG:
+        return lh.stored_set_case(name), dict(shared=())
     if name == SHORT:
         ub = 0.5 + np.random.default_rng(32).random((5, 4)) if pi else 0.9
         return ER.add_box(ER.make_case(5, 12, 4, 3, 31, per_instance_cost=pi), ub), dict(shared=() if pi else ("cost", "box"))
@@ -227,6 +240,19 @@ def ran(name, pi):
     return r
 
 
+def assert_late_words_are_read(name, cs, g):
+    """the guard of the long cases, from the getter alone: an instance with fb = 1 holds a nonzero code at a knot >= 16 (ASet word
+    1 or later), at N = 128 at a knot >= 112 (the last word); and, over the instances with fb = 1, sides of every kind there
+    (lane16_horizons.assert_late_sides).  Mode 1 of an instance with fb = 0 is NaN rows and reads no word at all"""
+    N, ok = cs.N, g["fb"] == 1
+    assert ok.any(), (name, "fb = 0 in every instance: the penalty held is not that of the stored pass (mu %s, mu_pass %s), mode 1 reads no "
+                      "set here; pick another seed for lane16_horizons.STORED_SET_SEED on the oracle" % (g.get("mu"), g["mu_pass"]))
+    first = 112 if N == lh.ASET_MAXN else lh.ASET_KNOTS
+    late = (g["codes"][:, first:] != 0).reshape(cs.B, -1).any(axis=1)
+    assert (ok & late).any(), (name, "no instance with valid gains and a side in the set at a knot >= %d" % first, g["fb"], late)
+    lh.assert_late_sides(g["codes"][ok], cs.n, N)
+
+
 @pytest.mark.parametrize("name,pi", RUNS, ids=IDS)
 def test_mode_0_against_the_long_double_yardstick(name, pi):
     """every output of the plain-cost call within the rule; fb is eval_policy_dev's; P0, p0, v0 are knot 0 of the tracks"""
@@ -248,6 +274,8 @@ def test_mode_1_against_the_long_double_yardstick(name, pi):
     r = ran(name, pi)
     g = r.g
     assert ((g["fb"] == 1) & (g["codes"].reshape(r.cs.B, -1) != 0).any(axis=1)).any(), "no instance with valid gains and a side in the set"
+    if name in LONG:
+        assert_late_words_are_read(name, r.cs, g)
     assert same(r.m1.fb, g["fb"])
     y, y64 = yardsticks(r, 1, r.Kraw)
     w = check_accuracy(r.m1, y, y64, g["fb"], name + " mode 1")
@@ -259,7 +287,7 @@ def test_mode_1_against_the_long_double_yardstick(name, pi):
     assert not same(r.m1.P0, r.m0.P0)                # (a side in the set: the Hessians differ)
 
 
-@pytest.mark.parametrize("name,pi", RUNS, ids=IDS)
+@pytest.mark.parametrize("name,pi", RUNS_SHORT, ids=IDS_SHORT)
 def test_mode_0_cross_checks_simulation_and_covariance(name, pi):
     """J of simulate_policy_dev (clamp 0, w NULL) from xbar_0 + d, |d| ~ 0.3, equals v_0 + p_0'd + d'P_0 d / 2, and dJ of
     propagate_covariance_dev equals <P_0, Sigma0> / 2 + sum_{k >= 1} <P_k, W> / 2, each within the sum of the bounds of the arrays
@@ -581,6 +609,37 @@ def test_refusals_at_the_c_abi():
         assert rc == 0 and all(torch.isfinite(t).all() for k, t in o.items() if k != "fb") and (o["fb"] != -77).all()
     finally:
         sv.close()
+
+
+def test_mode_0_beyond_the_stored_set_meets_the_rule():
+    """a 16-lane handle at N = 130, two knots beyond the 128 the exact active set holds: mode 1 answers UNSUPPORTED and writes
+    nothing, mode 0 reads no set and is within the rule on every output, on both forms.  (12, 4) at batch 2, "pi", the dynamics
+    of evaluate_ref.make_case scaled by 0.75 as in lane16_horizons.stored_set_case (their eigenvalues reach 1.3 in modulus: 1e14
+    over 129 knots), control bounds 0.5 and 0.6; seed 0: both instances SOLVE_SUCCEEDED on the oracle in 32 and 18 iterations"""
+    cs = ER.make_case(2, 12, 4, 130, 0, per_instance_cost=True)
+    cs.A = 0.75 * cs.A
+    cs = ER.add_box(cs, lh.STORED_SET_UB + 0.1 * np.arange(2)[:, None] * np.ones((2, 4)))
+    sv, cs = make_solver("16-box(12,4)-N130", True, cs, dict(shared=()))
+    try:
+        assert sv.N == 130 > lh.ASET_MAXN and altro.wave_cycles(sv).size != 0      # (the 16-lane backend)
+        status = altro.stats(sv).status.copy()
+        Xbar, Ubar = plane(sv)
+        Kraw = altro.gains(sv)[0]
+        before = everything(sv, cs.x0, 1)
+        rc, o = raw(sv, 1)
+        m0, host = ctg(sv, 0), ctg(sv, 0, host=True)
+        after = everything(sv, cs.x0, 1)
+    finally:
+        sv.close()
+    assert rc == UNSUP and untouched(o)
+    assert (status == 1).all() and (m0.fb == 1).all(), (status, m0.fb)
+    y, y64 = yardsticks(NS(cs=cs, Xbar=Xbar, Ubar=Ubar), 0, Kraw)
+    w = check_accuracy(m0, y, y64, np.ones(cs.B, dtype=np.int32), "16-box(12,4)-N130 mode 0")
+    print("16-box(12,4)-N130 mode 0 largest err / bound", w)
+    for k in NAMES + ("fb",):
+        assert same(getattr(host, k), getattr(m0, k)), k
+    for k in before:
+        assert np.array_equal(before[k], after[k], equal_nan=True), k
 
 
 @pytest.mark.parametrize("n,m", [(12, 4), (17, 5)])

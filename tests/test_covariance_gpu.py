@@ -8,6 +8,10 @@ Shapes, the smallest at which each code path can go wrong (N = 5 .. 8, one solve
   one MPC step so that the window is 1; (17, 5), padded to 32, with LINEAR rows up to the terminal knot; (64, 16); (30, 25) with
   state bounds up to the terminal knot.
 Every shape runs twice: "shared" (one Sigma0 / W, one row of weights and bounds for the batch) and "pi" (one per instance).
+Not in this list, and run by tests/test_stored_policy_matrix_gpu.py with the checks of this file (the table:
+tests/stored_policy_matrix.py): a padded state of 48 -- (40, 6) with LINEAR rows, (48, 13), (48, 32): the three-tile strip of
+gemm_rows under k_cov_wide's leading dimensions -- and mp > np, (12, 20), where Tt is sized by mp; there too, two live handles
+above 64 KB of LDS called alternately.
 
 The accuracy bound of an output array, per instance: err = max |out - ref| / max |ref| against the long-double yardstick must
 not exceed 16 x max(err of the float64 yardstick against the same ref, 2^-52).  The bound is computed here from the two numpy
