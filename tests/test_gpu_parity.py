@@ -1506,7 +1506,10 @@ def test_wide_kernel_generic_rows_on_large_states(oracle, n):
 def test_wide_kernel_shortest_horizons(oracle, monkeypatch, N):
     """Horizons of 3..6 knots (3 is the ABI's minimum) on the one-wave-per-instance kernel, time-invariant and per-knot dynamics: the row
     rollouts request their operands up to three knots ahead and the dynamics / gain blocks two knots ahead, so every
-    clamp at the end of the horizon is exercised (sizes (3,2), (12,4) via ALTRO_FORCE_WIDE, and (16,4))."""
+    clamp at the end of the horizon is exercised (sizes (3,2), (12,4) via ALTRO_FORCE_WIDE, and (16,4)).
+    The horizon axis of this kernel as a table -- every knot loop with its period and lookahead, N = 3 to 33, one class per
+    rollout and sweep, with guards that bounds bind and that the sweeps ran -- is tests/wide_horizons.py, run by
+    tests/test_wide_horizons.py and tests/test_wide_horizons_gpu.py."""
     monkeypatch.setenv("ALTRO_FORCE_WIDE", "1")
     for n, m in ((3, 2), (12, 4), (16, 4)):
         B, S = 4, 3
