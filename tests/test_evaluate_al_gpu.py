@@ -9,7 +9,9 @@ own branch counts say that every branch of the definition is reached.
 Tolerances are the derived bounds of tests/evaluate_al_ref.py (its docstring has the derivations), none of them measured; the
 measure is error over bound <= 1 against the numpy yardstick evaluated on the device's own Xout.  Everything else is an
 equality of bytes, except the envelope identity, which is held instance by instance to 16 times the error the CPU oracle's
-identical procedure shows."""
+identical procedure shows.
+
+The row tables, LDS sizes and shapes these cases do not reach are in tests/scoring_matrix.py."""
 import ctypes as C
 import functools
 from types import SimpleNamespace as NS

@@ -13,7 +13,9 @@ T = N nz), none of them measured:
  4. c_max against numpy: E = 2 (nz + 2) u (|A_r||z| + |b_r|) for rows, 2 u (|z| + |bound|) for BOX sides,
     sqrt(p) E + 16 u |v|_2 for a cone of dimension p.
  5. oracle: a fresh OracleSolver with zero duals per (instance, candidate) takes the controls; (X_orc, U) scored in the given
-    form gives its c_max within bound 4 and, where the oracle finds the candidate feasible, its cost within bound 3."""
+    form gives its c_max within bound 4 and, where the oracle finds the candidate feasible, its cost within bound 3.
+
+The row tables, LDS sizes and shapes these cases do not reach are in tests/scoring_matrix.py."""
 import ctypes as C
 import functools
 from types import SimpleNamespace as NS

@@ -6,7 +6,9 @@ tests/test_evaluate_grad_api.py shows to be clear of every kink (seed 101; (7, 3
 
 Tolerances are the derived bounds of tests/evaluate_grad_ref.py (its docstring has the derivations), none of them measured:
 P within bound 5, gU and gx0 within twice bound 6, both against the numpy yardstick evaluated on the device's own Xout; finite
-differences of the device's own J + rho P within bounds 3, 5, 6, 7 and 8.  Everything else is an equality of bytes."""
+differences of the device's own J + rho P within bounds 3, 5, 6, 7 and 8.  Everything else is an equality of bytes.
+
+The row tables, LDS sizes and shapes these cases do not reach are in tests/scoring_matrix.py."""
 import ctypes as C
 import functools
 import itertools

@@ -11,7 +11,9 @@ that the clamp bites.
 
 The ALTRO_ERR_STATE case "the window runs past the stored reference" is not exercised: every call that advances the window
 checks it first, so no sequence of public calls leaves a handle in that state (the tests of evaluate and warm_start, which
-share the check, do not reach it either)."""
+share the check, do not reach it either).
+
+The row tables, LDS sizes and shapes these cases do not reach are in tests/scoring_matrix.py."""
 import ctypes as C
 import functools
 from types import SimpleNamespace as NS

@@ -7,7 +7,9 @@ reference controls; six candidates per instance -- the three of ER.candidates, a
 controls, one holding a NaN -- and the incumbent: 35 rows, a partial wave, instances straddling waves and 16-row blocks.  On
 16-box also ncand = 1 and ncand = 17 (more rows per instance than a 256-thread block holds), and the (12, 4) case on both
 backends.  The yardstick of every plane is the composition a caller had to write before: evaluate_dev with Xout, a gather by
-`chosen`, set_initial_trajectory_dev -- on a twin handle."""
+`chosen`, set_initial_trajectory_dev -- on a twin handle.
+
+The row tables, LDS sizes and shapes these cases do not reach are in tests/scoring_matrix.py."""
 import ctypes as C
 import functools
 import os
